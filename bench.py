@@ -8,11 +8,17 @@
 A step = one pass of the hot path over one synthetic batch already resident in HBM: forward (conv+BN+ReLU blocks,
 GAP, FC), label-smoothed CE, backward, gradient all-reduce (N > 1), SGD-momentum update — nothing skipped.
 Workload = BASELINE.json metric config: ResNet-50, bs 256 per GPU, 224 px (configs[1] fp32 with --dtype fp32,
-configs[2] bf16 by default), weak scaling.  Rank 0 prints ONE JSON line; besides the contract fields it carries
+configs[2] bf16 by default), weak scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly K steps and prints the line; `roofline` / `roofline_hbm` are null there.
+With --full the line also carries (each measured in runs of its own, after the timed steps, or inside the last timed step)
   roofline     — the dominant conv kernel (by HIP-event time inside the timed region, on the launch stream):
                  algorithmic FLOPs / measured time against the dense MFMA peak of the dtype
+  secondary*   — fp32 (configs[1]), fp8 at bs 512 (configs[4]), BResNet-50 (configs[3]) and the Runner loop, bf16 N=1 only
   cpu_baseline — the torch-CPU oracle (oracle/resnet50_ref.py) timed on this host's cores on a bounded sample
                  (BASELINE.json configs[0]: bs 32, fp32, 224 px), rank 0, N=1 only.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy: loss, logits, a fixed seeded sample of
+the updated parameters and of the gradients, the BN buffers (and, for bresnet50, the EMA parameters' sample).
 """
 import argparse
 import json
@@ -32,7 +38,7 @@ SUSTAINED_TFLOPS = {"bf16": 2016.0, "fp8": 4061.0}
 FP8_KIND = 9  # profile_read kind: the conv launches that ran on e4m3 operands
 PEAK_HBM_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 EVENT_STEPS = 1  # timed steps whose conv / BN launches carry HIP-event pairs for `roofline` (each pair is a barrier on its stream: such a
-                 # step is ~1.8 ms slower, and that is part of `value` — 1 step = 90 timed launches of the dominant class, 53 of the HBM kernel)
+                 # step is ~1.8 ms slower, and with --full that is part of `value` — 1 step = 90 timed launches of the dominant class, 53 of the HBM kernel)
 HBM_CLASS = 7  # executor profile class of bn_bwd_apply_kernel, the largest HBM-bound kernel of the step
 # profile class -> kernel symbols (template instances of one source; names as tools/pmc_traffic.py writes them)
 KERNEL_NAMES = {0: ["igemm_kernel<{T},128,128>", "igemm_kernel<{T},256,256>", "igemm_kernel<{T},256,128>", "igemm8_kernel<224,256>", "igemm8_kernel<256,128>",
@@ -185,6 +191,30 @@ def cpu_baseline():
                       f"oracle; forward_only_value: the same for the forward + loss alone"}
 
 
+DUMP_SAMPLE = 1 << 21  # elements of each flat array sample in --dump-outputs (8 MiB in fp32)
+
+
+def dump_outputs(out_dir, model, loss, logits, ema_par=None):
+    """what the last timed step handed its caller, as float32 .npy files: the loss, the logits, the BN buffers, and a fixed seeded
+    sample (the same indices from run to run) of the updated parameters, their gradients and, when kept, the EMA parameters"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = model.flat_params.numel()
+    idx = torch.randint(0, n, (min(n, DUMP_SAMPLE),), generator=torch.Generator().manual_seed(0)).sort().values
+    arrays = {"loss": loss.detach().reshape(1), "logits": logits.detach(), "buffers": model._flat_buffers,
+              "params_sample": model.flat_params.detach()[idx.to(model.flat_params.device)],
+              "grads_sample": model.flat_grads[idx.to(model.flat_grads.device)]}
+    if ema_par is not None:
+        arrays["ema_params_sample"] = ema_par[idx.to(ema_par.device)]
+    total = 0
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def spawn_ranks(n):
     """the driver's own launch form (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>) as
     a child process; its stdout (rank 0's one JSON line) and stderr pass straight through.  Returns the child's exit code."""
@@ -215,6 +245,10 @@ def main():
     ap.add_argument("--model", default="resnet50", choices=["resnet50", "bresnet50"],
                     help="bresnet50: BASELINE configs[3] (variant graph, CutmixMixup on) — reported with its own workload name, no roofline")
     ap.add_argument("--spawn", action="store_true", help="launch the ranks from this process even for --gpus 1 (test hook)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the secondary configurations and the CPU baseline (off: the headline line alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, logits, parameter / gradient samples, BN buffers) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
@@ -249,8 +283,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(dtype, steps, warmup, want_roof, N=N, S=S, variant=None, extra_mask=0):
-        """W untimed + exactly K timed training steps in `dtype`; returns (seconds, final loss, model)."""
+    last = {}  # the headline run's last timed step: what --dump-outputs writes
+
+    def run(dtype, steps, warmup, want_roof, N=N, S=S, variant=None, extra_mask=0, keep=False):
+        """W untimed + exactly K timed training steps in `dtype`; returns (seconds, final loss, model).
+        keep: the last step's loss / logits / EMA parameters stay in `last`."""
         variant = args.model == "bresnet50" if variant is None else variant
         kw = dict(stem_type="deep", antialias=True, attn_type="eca", norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2,
                   drop_connect_rate=0.2, weight_standardization=True) if variant else {}
@@ -282,13 +319,14 @@ def main():
             lr = 0.001 + 0.0001 * (i % 8)  # the scheduler writes a new LR every batch (train.py:131)
             for g in opt.param_groups:
                 g["lr"] = lr
-            loss = criterion(net(data), target)
+            logits = net(data)
+            loss = criterion(logits, target)
             opt.zero_grad()
             loss.backward()
             opt.step()
             if ema_buf is not None:
                 ema_buf.lerp_(model._flat_buffers, 1.0 - 0.9999)
-            return loss
+            return loss, logits
 
         dom = None
         for i in range(warmup):
@@ -306,7 +344,7 @@ def main():
             if want_roof and i == steps - nprof:
                 # HIP events around the dominant conv class and the largest HBM-bound kernel, inside the timed region
                 model.profile((N, S, S), (1 << dom) | 0b11 | (1 << HBM_CLASS) | extra_mask)  # 0b11: both igemm classes (the 3x3 convs)
-            loss = step(warmup + i)
+            loss, logits = step(warmup + i)
         fence()
         dt = time.perf_counter() - t0
         if use_ddp:
@@ -315,13 +353,18 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = t.item()
+        if keep:
+            last.update(loss=loss, logits=logits, ema_par=ema_par if variant else None)
         return dt, loss.item(), model, dom
 
     shape = (N, S, S)
     if args.model == "bresnet50":
         args.no_roofline = args.no_secondary = True
-    want_roof = (not args.no_roofline) and rank == 0
-    dt, final_loss, model, dom = run(args.dtype, args.steps, args.warmup, want_roof)
+    want_roof = args.full and (not args.no_roofline) and rank == 0
+    dt, final_loss, model, dom = run(args.dtype, args.steps, args.warmup, want_roof, keep=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last["loss"], last["logits"], last["ema_par"])
+    last.clear()
 
     def roof_of(model, dom, dtype, shape=shape):
         """(roofline, roofline_hbm) dicts from the HIP events recorded in the last timed steps of `model`"""
@@ -448,7 +491,7 @@ def main():
             torch.cuda.empty_cache()
             add_serial(roof, roof_class, args.dtype, max(3, args.steps // 4))
             model = None
-        if world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary:
+        if args.full and world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary:
             # BASELINE.json configs[1] (fp32, single MI355X) measured in the same process, with its own roofline
             model = None
             torch.cuda.empty_cache()
@@ -467,7 +510,7 @@ def main():
                 out["secondary"]["roofline_hbm"] = h2
             else:
                 del m2
-        if world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary:
+        if args.full and world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary:
             # BASELINE.json configs[4] on one GPU: bs 512, 224 px, fp8 (e4m3) convolutions — the step of §4.6 of DESIGN.md, with the
             # bf16 step at the SAME shape measured right beside it (same process, same box)
             model = None
@@ -490,7 +533,7 @@ def main():
                     out["secondary_fp8"]["roofline"] = r8
             except Exception as e:  # the headline line must not depend on the extra measurement
                 out["secondary_fp8"] = {"error": str(e)[:200]}
-        if world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary:
+        if args.full and world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary:
             # BASELINE.json configs[3] on one GPU: the BResNet-50 variant graph with CutmixMixup on (bench.py --model bresnet50)
             model = None
             torch.cuda.empty_cache()
@@ -507,7 +550,7 @@ def main():
                                               "step_hbm": bresnet_step_hbm(256, S, dtb / kb * 1e3)}
             except Exception as e:
                 out["secondary_bresnet50"] = {"error": str(e)[:200]}
-        if world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary and args.model != "bresnet50":
+        if args.full and world == 1 and not use_ddp and args.dtype == "bf16" and not args.no_secondary and args.model != "bresnet50":
             # the reference's entry point is pytorch_tools' Runner (/root/reference/train.py:145-173): the same step driven by
             # fit_wrapper.Runner with BatchMetrics + PhasesScheduler, on the same batch pool — what the loop around the step costs
             model = None
@@ -517,7 +560,7 @@ def main():
                 out["secondary_runner"]["vs_value"] = round(out["secondary_runner"]["value"] / out["value"], 4)
             except Exception as e:
                 out["secondary_runner"] = {"error": str(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_ddp:

@@ -81,7 +81,7 @@ def test_bench_with_rccl_ddp_single_rank(dev):
     env = dict(os.environ, BENCH_FORCE_DDP="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29517")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                           "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
-                          "--warmup", "1", "--batch", "16", "--size", "64", "--dtype", "bf16", "--no-cpu-baseline"],
+                          "--warmup", "1", "--batch", "16", "--size", "64", "--dtype", "bf16", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -94,10 +94,28 @@ def test_bench_launches_its_own_ranks(dev):
     relays rank 0's line — here N = 1 through the spawner (--spawn), the one-GPU rehearsal of the driver's 8-GPU command form."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1", "--batch", "16",
-                          "--size", "64", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, env=env, timeout=600)
+                          "--size", "64", "--no-cpu-baseline", "--no-secondary", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and rec["config"]["parallelism"] == "dp1"
+
+
+def test_bench_plain_line_and_dump_outputs(dev, tmp_path):
+    """a plain `bench.py` run (no --full): exactly --steps timed steps, the headline fields only, and --dump-outputs writes the last
+    timed step's outputs as float32 .npy files within 64 MB"""
+    import numpy as np
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16",
+                          "--size", "64", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["dtype"] == "bf16" and rec["higher_is_better"] is True
+    assert rec["roofline"] is None and "cpu_baseline" not in rec and not any(k.startswith("secondary") for k in rec)
+    arrays = {os.path.basename(f)[:-4]: np.load(f) for f in glob.glob(os.path.join(str(tmp_path), "*.npy"))}
+    assert set(arrays) == {"loss", "logits", "params_sample", "grads_sample", "buffers"}
+    assert arrays["logits"].shape == (16, 1000) and abs(float(arrays["loss"][0]) - rec["config"]["final_loss"]) < 1e-3
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
 
 
 def test_bench_bresnet50_line_with_rccl_single_rank(dev):

@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for S in 160 224 320; do
   for dt in bf16 fp8; do
-    python3 bench.py --batch 512 --size $S --dtype $dt --steps 10 --warmup 4 --no-cpu-baseline --no-secondary > $OUT/bench_${dt}_$S.json 2>> $OUT/err.log
+    python3 bench.py --full --batch 512 --size $S --dtype $dt --steps 10 --warmup 4 --no-cpu-baseline --no-secondary > $OUT/bench_${dt}_$S.json 2>> $OUT/err.log
     MI355_WGRAD_STREAM=0 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_${dt}_$S -- python3 bench.py --batch 512 --size $S --dtype $dt --steps 5 --warmup 3 --no-cpu-baseline --no-secondary --no-roofline > /dev/null 2>> $OUT/err.log
     python3 tools/trace_layers.py $OUT/trace_${dt}_$S/* 512 $S > $OUT/conv_per_layer_${dt}_$S.txt 2>> $OUT/err.log
     rm -rf $OUT/trace_${dt}_$S
