@@ -239,6 +239,23 @@ int mi355_sgd_step(float* p, const float* g, float* m, size_t n, float lr, float
 int mi355_sgd_step_ema(float* p, const float* g, float* m, float* ema, size_t n, float lr, float momentum,
                        float weight_decay, float grad_scale, float ema_decay, void* stream);
 
+/* fused Adam / AdamW on a flat fp32 range (torch.optim.Adam / AdamW semantics, amsgrad and maximize off), in the operation
+ * order of torch's _single_tensor_adam; p, m (exp_avg), v (exp_avg_sq) in place, g read-only:
+ *   g = g*grad_scale;  decoupled (AdamW): p *= 1 - lr*wd  |  else (Adam): g += wd*p      (both skipped when wd == 0)
+ *   m = m + (1-beta1)*(g - m);  v = v*beta2 + (1-beta2)*g*g;  p -= step_size*m / (sqrt(v)/bc2_sqrt + eps)
+ * step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) for the range's step count t (t >= 1) are computed by the
+ * caller in double, as torch does; beta1, beta2, lr and wd are doubles so that 1-beta and 1-lr*wd round as in torch.
+ * Fails (-1) on a null or non-16-byte-aligned pointer, beta outside [0, 1), eps negative or not finite.
+ * replaces torch.optim._multi_tensor.AdamW.step — train.py:92, configs/hydra_exp/5.r50_base_adamw_high-aug.yaml:17-20 */
+int mi355_adam_step(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps,
+                    float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled, float grad_scale,
+                    void* stream);
+/* the same step + the moving average of the updated parameters in the same pass (ema_decay in [0, 1]):
+ *   ema += (1 - ema_decay) * (p_new - ema)       replaces the ModelEma callback's lerp (train.py:111-112) under AdamW */
+int mi355_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, double beta1, double beta2,
+                        float eps, float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled,
+                        float grad_scale, float ema_decay, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

@@ -24,6 +24,10 @@ TARGET_ALIASES = {
     "pytorch_tools.losses.CrossEntropyLoss": "sota_imagenet_amd.losses.CrossEntropyLoss",
     "torch.optim._multi_tensor.SGD": "sota_imagenet_amd.optim.SGD",
     "torch.optim.SGD": "sota_imagenet_amd.optim.SGD",
+    "torch.optim._multi_tensor.AdamW": "sota_imagenet_amd.optim.AdamW",
+    "torch.optim.AdamW": "sota_imagenet_amd.optim.AdamW",
+    "torch.optim._multi_tensor.Adam": "sota_imagenet_amd.optim.Adam",
+    "torch.optim.Adam": "sota_imagenet_amd.optim.Adam",
     "pytorch_tools.fit_wrapper.callbacks.Callback": "sota_imagenet_amd.fit_wrapper.Callback",
     "pytorch_tools.fit_wrapper.callbacks.Cutmix": "sota_imagenet_amd.callbacks.Cutmix",
     "pytorch_tools.fit_wrapper.callbacks.Mixup": "sota_imagenet_amd.callbacks.Mixup",

@@ -334,6 +334,10 @@ int launch_ce(const float* logits, const float* target, float smoothing, float g
               float* row_loss, float* dlogits, int N, int C, hipStream_t s);
 int launch_sgd(float* p, const float* g, float* m, size_t n, float lr, float mom, float wd, float gscale,
                hipStream_t s, float* ema = nullptr, float ema_decay = 0.f);
+// optim.hip: fused Adam (decoupled = 0) / AdamW (decoupled = 1) step, + the parameter average when ema != nullptr
+int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps, float step_size,
+                float bc2_sqrt, double lr, double wd, int decoupled, float gscale, hipStream_t s, float* ema = nullptr,
+                float ema_decay = 0.f);
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

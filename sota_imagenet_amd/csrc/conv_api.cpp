@@ -530,5 +530,18 @@ int mi355_sgd_step_ema(float* p, const float* g, float* m, float* ema, size_t n,
   MI355_ARG(ema, "sgd_step_ema: null ema");
   return launch_sgd(p, g, m, n, lr, momentum, weight_decay, grad_scale, (hipStream_t)stream, ema, ema_decay);
 }
+int mi355_adam_step(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps,
+                    float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled, float grad_scale,
+                    void* stream) {
+  return launch_adam(p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lr, weight_decay, decoupled, grad_scale,
+                     (hipStream_t)stream);
+}
+int mi355_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, double beta1, double beta2,
+                        float eps, float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled,
+                        float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "adam_step_ema: null ema");
+  return launch_adam(p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lr, weight_decay, decoupled, grad_scale,
+                     (hipStream_t)stream, ema, ema_decay);
+}
 
 }  // extern "C"

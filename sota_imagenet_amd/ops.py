@@ -336,6 +336,24 @@ def sgd_step(p, g, m, lr, momentum=0.0, weight_decay=0.0, grad_scale=1.0, ema=No
     check(_L().mi355_sgd_step_ema(ptr(p), ptr(g), ptr(m), ptr(ema), p.numel(), lr, momentum, weight_decay, grad_scale, ema_decay, cur_stream()))
 
 
+def adam_step(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, grad_scale=1.0, ema=None, ema_decay=0.0):
+    """one Adam (decoupled=False) / AdamW (decoupled=True) step of a flat range whose parameters have all taken `step` steps before
+    this one (torch's state['step'] after its increment is step + 1).  The bias corrections are computed here in double, as torch
+    does; ema (optional): the moving average of the updated parameters, advanced in the same kernel (mi355_adam_step_ema)"""
+    _need_cuda(p, g, m, v)
+    b1, b2 = float(betas[0]), float(betas[1])
+    t = float(step + 1)
+    step_size = lr / (1.0 - b1 ** t)
+    bc2_sqrt = (1.0 - b2 ** t) ** 0.5
+    args = (p.numel(), b1, b2, eps, step_size, bc2_sqrt, lr, weight_decay, int(bool(decoupled)), grad_scale)
+    if ema is None:
+        check(_L().mi355_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), *args, cur_stream()))
+        return
+    _need_cuda(ema)
+    assert ema.numel() == p.numel() and ema.dtype == torch.float32 and ema.is_contiguous()
+    check(_L().mi355_adam_step_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), *args, ema_decay, cur_stream()))
+
+
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
 def blurpool_fwd(x):
     _need_cuda(x)

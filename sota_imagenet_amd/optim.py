@@ -1,4 +1,4 @@
-"""`SGD` plugin: torch.optim-compatible SGD with momentum whose step is ONE fused HIP kernel over the flat buffer.
+"""`SGD`, `Adam` and `AdamW` plugins: torch.optim-compatible optimizers whose step is ONE fused HIP kernel per flat range.
 
 Drop-in for `_target_: torch.optim._multi_tensor.SGD` (sota_imagenet/arg_parser.py:136-138; r50 recipe adds
 momentum 0.9 / weight_decay 3e-5, configs/hydra_exp/1.r50_baseline.yaml:29-31; built at train.py:92 from
@@ -7,6 +7,8 @@ momentum 0.9 / weight_decay 3e-5, configs/hydra_exp/1.r50_baseline.yaml:29-31; b
     g += wd * p ;  m = mu * m + g  (first step m = g) ;  p -= lr * m
 Parameters that are views of a model's flat fp32 array (models.ResNet50) are updated range-wise in place;
 adjacent ranges of one param group collapse into a single launch (the default recipe = 1 launch / step).
+Adam / AdamW (csrc/optim.hip) share that range planner and the rest of the contract (attach_model, attach_ema, grad_scale,
+zero_grad, re-planning after load_state_dict); their per-parameter state is laid out as torch lays it out.
 """
 import torch
 from torch.optim import Optimizer
@@ -29,11 +31,13 @@ def _dense_range(t):
     return base, (t.data_ptr() - base) // t.element_size(), n
 
 
-class SGD(Optimizer):
-    def __init__(self, params, lr=0.0, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, **ignored):
-        if dampening != 0.0 or nesterov:
-            raise NotImplementedError("dampening / nesterov are not on the hot path")
-        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay)
+class _FlatOptimizer(Optimizer):
+    """what the native optimizers share: the flat-range planner (merged launch ranges, barriers, 16-byte alignment), the
+    fused parameter average (attach_ema), grad_scale, zero_grad that only marks the model's flat gradients clean, and
+    re-planning after add_param_group / load_state_dict.  Subclasses build their plans from _merged_ranges() in
+    _build_plans() and launch them in step()."""
+
+    def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._plans = None
         self._models = []
@@ -59,18 +63,21 @@ class SGD(Optimizer):
         self._ema = None
         self._plans = None
 
-    # one plan per param group: list of (p_flat_slice, g_flat_slice, m_flat_slice, ema_flat_slice or None)
-    def _build_plans(self):
+    def _merged_ranges(self, split_key=None, bridge_padding=True):
+        """[[param base, grad base, first elem, end elem, [params], group index]]: one entry per launch.  Parameters whose
+        split_key differs (Adam: their step counts) never share a range; bridge_padding=False when the update would not keep
+        zeros zero (Adam with eps = 0: 0/0)."""
+        name = type(self).__name__
         entries = []  # (param base, grad base, first elem, numel, group index, param)
         for gi, group in enumerate(self.param_groups):
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 if not (p.is_cuda and p.dtype == torch.float32):
-                    raise RuntimeError("SGD: parameters must be CUDA fp32 tensors (no CPU fallback on the hot path)")
+                    raise RuntimeError(f"{name}: parameters must be CUDA fp32 tensors (no CPU fallback on the hot path)")
                 rp, rg = _dense_range(p.data), _dense_range(p.grad)
                 if rp is None or rg is None or rp[1:] != rg[1:]:
-                    raise RuntimeError("SGD: parameter and gradient must be dense and share their flat offset")
+                    raise RuntimeError(f"{name}: parameter and gradient must be dense and share their flat offset")
                 entries.append((rp[0], rg[0], rp[1], rp[2], gi, p))
         # Neighbours of one group merge into one launch only when the gap between them is PROVABLY padding (zeros stay
         # zeros under the update): every tensor of the attached models that this optimizer does not update in the same
@@ -86,7 +93,7 @@ class SGD(Optimizer):
                 r = _dense_range(q.data)
                 if r is not None:
                     barriers.setdefault(r[0], []).append((r[1], r[1] + r[2]))
-        max_gap = 64 * 2048 if self._models else 64
+        max_gap = (64 * 2048 if self._models else 64) if bridge_padding else 1
 
         def gap_is_padding(pb, lo, hi):
             return 0 <= hi - lo < max_gap and not any(b < hi and e > lo for b, e in barriers.get(pb, ()))
@@ -94,34 +101,82 @@ class SGD(Optimizer):
         merged = []
         for pb, gb, off, n, gi, p in entries:
             m = merged[-1] if merged else None
-            if m and m[0] == pb and m[1] == gb and m[5] == gi and gap_is_padding(pb, m[3], off):
+            if (m and m[0] == pb and m[1] == gb and m[5] == gi and gap_is_padding(pb, m[3], off)
+                    and (split_key is None or split_key(m[4][-1]) == split_key(p))):
                 m[3] = off + n
                 m[4].append(p)
             else:
                 merged.append([pb, gb, off, off + n, [p], gi])
-        plans = [[] for _ in self.param_groups]
-        for pb, gb, b, e, ps, gi in merged:
+        for _, _, b, _, _, _ in merged:
             if b * 4 % 16:
-                raise RuntimeError("SGD: flat range not 16-byte aligned")
-            dev = ps[0].device
-            fp = torch.empty(0, dtype=torch.float32, device=dev).set_(ps[0].data.untyped_storage(), b, (e - b,))
-            fg = torch.empty(0, dtype=torch.float32, device=dev).set_(ps[0].grad.untyped_storage(), b, (e - b,))
-            fm = torch.zeros(e - b, dtype=torch.float32, device=dev)
+                raise RuntimeError(f"{name}: flat range not 16-byte aligned")
+        return merged
+
+    @staticmethod
+    def _flat_views(ps, b, e):
+        """the (parameter, gradient) slices [b, e) of the flat arrays the parameters ps live in"""
+        dev = ps[0].device
+        fp = torch.empty(0, dtype=torch.float32, device=dev).set_(ps[0].data.untyped_storage(), b, (e - b,))
+        fg = torch.empty(0, dtype=torch.float32, device=dev).set_(ps[0].grad.untyped_storage(), b, (e - b,))
+        return fp, fg
+
+    def _state_view(self, flat, p, b, key):
+        """state[p][key] := the view of the flat state array `flat` (starting at element b) that covers p; a tensor already there
+        (loaded from a checkpoint, train.py:144, or kept across a re-plan) is carried over into it"""
+        r = _dense_range(p.data)
+        view = torch.as_strided(flat, p.shape, p.stride(), r[1] - b)
+        old = self.state[p].get(key)
+        if old is not None:
+            view.copy_(old.to(device=flat.device, dtype=torch.float32))
+        self.state[p][key] = view
+
+    def _ema_slice(self, pb, b, e):
+        if self._ema is not None:
+            r = _dense_range(self._ema[0])
+            if r is not None and r[0] == pb and r[1] <= b and e <= r[1] + r[2]:
+                return self._ema[1][b - r[1]: e - r[1]]
+        return None
+
+    def _check_ema(self, slices):
+        if self._ema is not None and not any(fe is not None for fe in slices):
+            raise RuntimeError(f"{type(self).__name__}.attach_ema: none of the updated ranges lies in the attached flat array")
+
+    def zero_grad(self, set_to_none=False):
+        # gradients live in the model's flat array and are overwritten by the next backward: no memset needed
+        if self._models:
+            for m in self._models:
+                m.mark_grads_clean()
+        else:
+            super().zero_grad(set_to_none=False)
+
+    def add_param_group(self, group):
+        super().add_param_group(group)
+        self._plans = None
+
+    def load_state_dict(self, state_dict):
+        """torch's loader replaces the per-parameter state by fresh tensors: re-plan at the next step, which copies them into
+        the flat state arrays the kernel reads (resume path, train.py:140-146)."""
+        super().load_state_dict(state_dict)
+        self._plans = None
+
+
+class SGD(_FlatOptimizer):
+    def __init__(self, params, lr=0.0, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, **ignored):
+        if dampening != 0.0 or nesterov:
+            raise NotImplementedError("dampening / nesterov are not on the hot path")
+        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay)
+        super().__init__(params, defaults)
+
+    # one plan per param group: list of (p_flat_slice, g_flat_slice, m_flat_slice, ema_flat_slice or None)
+    def _build_plans(self):
+        plans = [[] for _ in self.param_groups]
+        for pb, gb, b, e, ps, gi in self._merged_ranges():
+            fp, fg = self._flat_views(ps, b, e)
+            fm = torch.zeros(e - b, dtype=torch.float32, device=fp.device)
             for p in ps:  # expose momentum buffers per parameter (state_dict compatibility)
-                r = _dense_range(p.data)
-                view = torch.as_strided(fm, p.shape, p.stride(), r[1] - b)
-                old = self.state[p].get("momentum_buffer")
-                if old is not None:  # loaded from a checkpoint (train.py:144) or kept across a re-plan: carry it over
-                    view.copy_(old.to(device=dev, dtype=torch.float32))
-                self.state[p]["momentum_buffer"] = view
-            fe = None
-            if self._ema is not None:
-                r = _dense_range(self._ema[0])
-                if r is not None and r[0] == pb and r[1] <= b and e <= r[1] + r[2]:
-                    fe = self._ema[1][b - r[1]: e - r[1]]
-            plans[gi].append((fp, fg, fm, fe))
-        if self._ema is not None and not any(fe is not None for segs in plans for *_, fe in segs):
-            raise RuntimeError("SGD.attach_ema: none of the updated ranges lies in the attached flat array")
+                self._state_view(fm, p, b, "momentum_buffer")
+            plans[gi].append((fp, fg, fm, self._ema_slice(pb, b, e)))
+        self._check_ema([fe for segs in plans for *_, fe in segs])
         self._plans = plans
 
     @torch.no_grad()
@@ -138,20 +193,107 @@ class SGD(Optimizer):
                              ema=fe, ema_decay=self._ema[2] if fe is not None else 0.0)
         return loss
 
-    def zero_grad(self, set_to_none=False):
-        # gradients live in the model's flat array and are overwritten by the next backward: no memset needed
-        if self._models:
-            for m in self._models:
-                m.mark_grads_clean()
-        else:
-            super().zero_grad(set_to_none=False)
 
-    def add_param_group(self, group):
-        super().add_param_group(group)
-        self._plans = None
+class Adam(_FlatOptimizer):
+    """torch.optim.Adam (decoupled_weight_decay=False: L2 term g += wd*p) whose step is one mi355_adam_step launch per flat range
+    (csrc/optim.hip).  Per-parameter state as torch lays it out — state[p] = {step: 0-dim fp32 CPU tensor, exp_avg, exp_avg_sq} —
+    so checkpoints move both ways between this class and torch's; exp_avg / exp_avg_sq are views of the flat m / v arrays and the
+    step tensors are views of one CPU array that a single add_(1) advances.  A launch range holds parameters of one group with equal
+    step counts only (after loading a state whose counts differ, the ranges split there).
+    amsgrad, maximize and a tensor lr are not on the hot path; foreach / fused / capturable / differentiable are accepted and ignored."""
 
-    def load_state_dict(self, state_dict):
-        """torch's loader replaces self.state[p]['momentum_buffer'] by fresh tensors: re-plan at the next step, which
-        copies them into the flat momentum array the kernel reads (resume path, train.py:140-146)."""
-        super().load_state_dict(state_dict)
-        self._plans = None
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        if amsgrad or maximize:
+            raise NotImplementedError("amsgrad / maximize are not on the hot path")
+        if isinstance(lr, torch.Tensor):
+            raise NotImplementedError("a tensor lr is not on the hot path")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        for i, b in enumerate(betas):
+            if not 0.0 <= float(b) < 1.0:
+                raise ValueError(f"Invalid beta parameter at index {i}: {b}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        # the group keys of torch's Adam (with its defaults for the ignored switches): state dicts load into torch as they are
+        defaults = dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay, amsgrad=False,
+                        maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                        decoupled_weight_decay=bool(decoupled_weight_decay))
+        super().__init__(params, defaults)
+        self._steps = None  # CPU fp32 array behind every state[p]['step'] of the planned parameters
+
+    def __setstate__(self, state):
+        # (load_state_dict ends here) groups of older or capturable / fused torch checkpoints: the switches this class ignores
+        # take torch's defaults again, which describe the layout it keeps (CPU step counts)
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault("amsgrad", False)
+            group.setdefault("maximize", False)
+            group.setdefault("decoupled_weight_decay", False)
+            group.update(foreach=None, capturable=False, differentiable=False, fused=None)
+
+    def _step_count(self, p):
+        t = self.state[p].get("step")
+        return 0 if t is None else int(float(t))
+
+    # one plan per param group: list of [p, g, m, v, ema or None, step count of the range]
+    def _build_plans(self):
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise NotImplementedError("amsgrad / maximize are not on the hot path")
+        plans = [[] for _ in self.param_groups]
+        planned = []
+        bridge = all(float(g["eps"]) > 0.0 for g in self.param_groups)
+        for pb, gb, b, e, ps, gi in self._merged_ranges(split_key=self._step_count, bridge_padding=bridge):
+            fp, fg = self._flat_views(ps, b, e)
+            fm = torch.zeros(e - b, dtype=torch.float32, device=fp.device)
+            fv = torch.zeros(e - b, dtype=torch.float32, device=fp.device)
+            t = self._step_count(ps[0])
+            for p in ps:
+                self._state_view(fm, p, b, "exp_avg")
+                self._state_view(fv, p, b, "exp_avg_sq")
+                planned.append((p, t))
+            plans[gi].append([fp, fg, fm, fv, self._ema_slice(pb, b, e), t])
+        self._check_ema([seg[4] for segs in plans for seg in segs])
+        self._steps = torch.tensor([float(t) for _, t in planned], dtype=torch.float32)
+        for i, (p, _) in enumerate(planned):
+            self.state[p]["step"] = self._steps[i]
+        self._plans = plans
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._plans is None:
+            self._build_plans()
+        for group, segs in zip(self.param_groups, self._plans):
+            lr = group["lr"]
+            if isinstance(lr, torch.Tensor):
+                raise NotImplementedError("a tensor lr is not on the hot path")
+            decoupled = bool(group.get("decoupled_weight_decay", False))
+            for seg in segs:
+                fp, fg, fm, fv, fe, t = seg
+                ops.adam_step(fp, fg, fm, fv, t, float(lr), group["betas"], float(group["eps"]), float(group["weight_decay"]),
+                              decoupled=decoupled, grad_scale=float(self.grad_scale), ema=fe,
+                              ema_decay=self._ema[2] if fe is not None else 0.0)
+                seg[5] = t + 1
+        self._steps.add_(1.0)
+        return loss
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: Adam with decoupled weight decay, p *= 1 - lr*wd before the update (weight_decay default 1e-2)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group["decoupled_weight_decay"] = True
