@@ -332,7 +332,10 @@ int mi355_resnet50_destroy(mi355_ctx* ctx);
  * first, stem last) so that gradient buckets complete front-to-back during backward.
  *   kind: 0 = parameter (offset into flat params/grads), 1 = buffer (offset into flat buffers:
  *         running_mean / running_var; num_batches_tracked is kept host-side by the caller).
- *   shape: torch logical shape (conv: [Cout,Cin,KH,KW], stored channels_last = KRSC).               */
+ *   shape: torch logical shape (conv: [Cout,Cin,KH,KW], stored channels_last = KRSC), zero beyond ndim.
+ *   name: a buffer of name_cap > 0 bytes is required; kind / offset / ndim / shape may be NULL.
+ * The table queries, bind, segment_range, bucket_plan, set_comm and set_grad_sync of both executors (ResNet-50 here,
+ * BResNet-50 below) share one implementation and one contract.                                      */
 int mi355_resnet50_num_tensors(const mi355_ctx* ctx);
 int mi355_resnet50_tensor_info(const mi355_ctx* ctx, int idx, char* name, int name_cap, int* kind,
                                size_t* offset, int* ndim, int shape[4]);
@@ -340,7 +343,8 @@ size_t mi355_resnet50_flat_param_elems(const mi355_ctx* ctx);  /* incl. alignmen
 size_t mi355_resnet50_flat_buffer_elems(const mi355_ctx* ctx);
 size_t mi355_resnet50_workspace_bytes(const mi355_ctx* ctx);
 
-/* caller-owned flat fp32 device arrays; must outlive the ctx.  Padding elements must be zero. */
+/* caller-owned flat fp32 device arrays; must outlive the ctx.  Padding elements must be zero.  All three are required and
+ * 256-byte aligned (MI355_E_ARG otherwise); a layout-only ctx refuses to bind (MI355_E_STATE). */
 int mi355_resnet50_bind(mi355_ctx* ctx, float* params, float* grads, float* buffers);
 
 /* logits[N,num_classes] fp32 = model(x_nchw[N,3,H,W] fp32).  training!=0: batch statistics, running
@@ -401,7 +405,7 @@ int mi355_bresnet50_flops(const mi355_bctx* ctx, double* fwd_flops, double* trai
  * the backward call runs mi355_bresnet50_num_segments() segments — 0 = the head, then the bottlenecks last to first, then the stem;
  * the flat gradient array is laid out in FORWARD (pytorch_tools registration) order, so the segments descend through it — and, with a
  * communicator attached, issues ONE mean all-reduce per bucket of consecutive segments (>= bucket_cap_mb MiB, the last bucket cut once
- * more: the rule of mi355_resnet50_set_comm) on the communicator's stream as soon as the bucket's last segment has been enqueued on
+ * more: the rule of mi355_resnet50_set_comm, which both executors share) on the communicator's stream as soon as the bucket's last segment has been enqueued on
  * both streams; the caller's stream waits for the last one before the call returns.  set_grad_sync(0): no collective (DDP.no_sync()). */
 typedef struct mi355_comm mi355_comm;
 int mi355_bresnet50_num_segments(const mi355_bctx* ctx);

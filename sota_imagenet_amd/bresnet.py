@@ -18,7 +18,6 @@ Channel counts below 64 (the 3 / 32-channel stem) run zero-padded to 64, the gra
 path: a CPU tensor raises.
 """
 import ctypes
-from collections import OrderedDict
 
 import torch
 import torch.nn as nn
@@ -357,34 +356,13 @@ _DT = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "torch.bfloat16": tor
        "torch.float32": torch.float32, "None": torch.float32}  # (keys are str(dtype): None = fp32, as models.resnet50)
 
 
-def _layout(dtype_code, num_classes, wstd):
-    """tensor table of the native BResNet-50 executor: [(name, kind, offset, shape)] + flat sizes (layout-only ctx: no GPU needed)"""
-    from . import native
-
-    L = native.lib()
-    ctx = ctypes.c_void_p()
-    native.check(L.mi355_bresnet50_create(ctypes.byref(ctx), -1, dtype_code, 1, 32, 32, num_classes, int(wstd)))
-    try:
-        table = []
-        for i in range(L.mi355_bresnet50_num_tensors(ctx)):
-            name = ctypes.create_string_buffer(128)
-            kind, off, nd, sh = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_int * 4)()
-            native.check(L.mi355_bresnet50_tensor_info(ctx, i, name, 128, ctypes.byref(kind), ctypes.byref(off), ctypes.byref(nd), sh))
-            table.append((name.value.decode(), kind.value, off.value, tuple(sh[j] for j in range(nd.value))))
-        segs = []
-        for i in range(L.mi355_bresnet50_num_segments(ctx)):
-            b, e = ctypes.c_size_t(), ctypes.c_size_t()
-            native.check(L.mi355_bresnet50_segment_range(ctx, i, ctypes.byref(b), ctypes.byref(e)))
-            segs.append((b.value, e.value))
-        return table, L.mi355_bresnet50_flat_param_elems(ctx), L.mi355_bresnet50_flat_buffer_elems(ctx), segs
-    finally:
-        L.mi355_bresnet50_destroy(ctx)
-
-
 class BResNet50(_DropStream, _FlatModel):
     """BResNet-50 on the static executor (csrc/bresnet_exec.cpp): forward and backward are ONE C-ABI call each; every parameter
     (pytorch_tools names / shapes, see the module docstring) is a view into one flat fp32 array, so the native SGD and the flat
     gradient all-reduce apply as they do to models.ResNet50.  No CPU path: a CPU tensor raises."""
+
+    _prefix = "bresnet50"
+    _max_ctxs = 2  # train + val batch shapes (each holds every activation AND every gradient: 50 GB at 256 x 224 px)
 
     def __init__(self, num_classes=1000, dtype="bf16", drop_rate=0.0, drop_connect_rate=0.0, weight_standardization=False, seed=None, **kw):
         super().__init__()
@@ -400,24 +378,17 @@ class BResNet50(_DropStream, _FlatModel):
         self.num_classes, self.drop_rate, self.drop_connect_rate, self.seed = int(num_classes), float(drop_rate), float(drop_connect_rate), int(seed or 0)
         self._seed_given = seed is not None
         self.weight_standardization = bool(weight_standardization)
-        self._table, self._nparam, self._nbuf, self._segments = _layout(self._dt, self.num_classes, self.weight_standardization)
-        # (backward segments of the ONE native backward call: head, bottlenecks last to first, stem — descending through the flat array)
-        self._comm = None  # (mi355_comm*, bucket cap in MiB) once a native communicator is attached: the all-reduces run inside the call
-        self._flat_params = torch.zeros(self._nparam, dtype=torch.float32)
-        self._flat_grads = torch.zeros(self._nparam, dtype=torch.float32)
-        self._flat_buffers = torch.zeros(self._nbuf, dtype=torch.float32)
-        self._hook = torch.zeros(1, requires_grad=True)
-        self._ctxs = OrderedDict()
-        self._grads_dirty = False
-        self._grad_sync = None  # parallel.FlatBucketDDP: callable(segment, begin, end), run after the backward call
-        self._grad_sync_points = None
-        self._sync_grads = True
-        self._bn_leaves = []
         self._step = 0
         self.masks = None  # test hook: {"dc": [per block [N] fp32 or None], "do": [N, 2048] fp32 or None} overrides the sampler
-        self._build_modules()
-        self._rebind_views()
+        # (backward segments of the ONE native backward call: head, bottlenecks last to first, stem — descending through the flat array;
+        # with a native communicator attached the all-reduces run inside that call)
+        self._init_flat_state()
         self.reset_parameters()
+
+    def _create(self, out, device, N, H, W):
+        from . import native
+
+        return native.lib().mi355_bresnet50_create(out, device, self._dt, N, H, W, self.num_classes, int(self.weight_standardization))
 
     def _canonical_order(self):
         return list(self._table)  # the executor registers in pytorch_tools' module order
@@ -443,44 +414,6 @@ class BResNet50(_DropStream, _FlatModel):
                     p.copy_(((torch.rand(shape, generator=g) * 2 - 1) / 2048 ** 0.5).to(p.device))
                 else:
                     p.fill_(1.0 if (attr == "weight" and isinstance(leaf, _BNLeaf)) else 0.0)
-
-    # ---- native contexts ---------------------------------------------------------------------------------------------
-    def _destroy_ctxs(self):
-        if self._ctxs:
-            from . import native
-
-            L = native.lib()
-            for c in self._ctxs.values():
-                L.mi355_bresnet50_destroy(c)
-            self._ctxs.clear()
-
-    def _ctx(self, N, H, W):
-        from . import native
-
-        key = (N, H, W)
-        c = self._ctxs.get(key)
-        if c is None:
-            if not self._flat_params.is_cuda:
-                raise RuntimeError("bresnet50: the MI355X hot path has no CPU fallback — call .cuda() first")
-            if len(self._ctxs) >= 2:  # train + val batch shapes (each holds every activation AND every gradient: 50 GB at 256 x 224 px)
-                pending = getattr(self, "_last", None)
-                for k in list(self._ctxs):  # oldest first; the context a pending backward will use is never the one to go
-                    if pending is None or self._ctxs[k] is not pending[0]:
-                        native.lib().mi355_bresnet50_destroy(self._ctxs.pop(k))
-                        break
-            L = native.lib()
-            c = ctypes.c_void_p()
-            dev = self._flat_params.device.index or 0
-            native.check(L.mi355_bresnet50_create(ctypes.byref(c), dev, self._dt, N, H, W, self.num_classes, int(self.weight_standardization)))
-            native.check(L.mi355_bresnet50_bind(c, native.ptr(self._flat_params), native.ptr(self._flat_grads), native.ptr(self._flat_buffers)))
-            if self._comm is not None:
-                native.check(L.mi355_bresnet50_set_comm(c, self._comm[0], float(self._comm[1])))
-            if not self._sync_grads:
-                native.check(L.mi355_bresnet50_set_grad_sync(c, 0))
-            self._ctxs[key] = c
-        else:
-            self._ctxs.move_to_end(key)
-        return c
 
     def _native_forward(self, x, training):
         from . import native
@@ -556,71 +489,10 @@ class BResNet50(_DropStream, _FlatModel):
         self._hook_alive = (record, replay)
         native.check(native.lib().mi355_bresnet50_grad_hooks(self._last[0], arrs[0], arrs[1], 16))
 
-    def debug_tensor(self, shape, name):
-        """copy of an internal tensor of the last forward at batch shape (N,H,W) — test hook (mi355_bresnet50_debug_tensor)."""
-        from . import native
-
-        L = native.lib()
-        p, dt, nd, sh = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), (ctypes.c_int * 4)()
-        native.check(L.mi355_bresnet50_debug_tensor(self._ctx(*shape), name.encode(), ctypes.byref(p), ctypes.byref(dt), ctypes.byref(nd), sh))
-        dims = [sh[i] for i in range(nd.value)]
-        out = torch.empty(dims, dtype={native.F32: torch.float32, native.BF16: torch.bfloat16}[dt.value], device=self._flat_params.device)
-        torch.cuda.synchronize()
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), p, out.numel() * out.element_size(), 3)
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpy failed ({rc})")
-        return out
-
-    def set_comm(self, comm, bucket_cap_mb=32.0):
-        """attaches a native RCCL communicator (parallel.FlatBucketDDP owns it): the backward call then reduces the flat gradient array
-        bucket by bucket behind the segments that complete it (mi355_bresnet50_set_comm)"""
-        from . import native
-
-        self._comm = None if comm is None else (comm, float(bucket_cap_mb))
-        for c in self._ctxs.values():
-            native.check(native.lib().mi355_bresnet50_set_comm(c, comm, float(bucket_cap_mb)))
-
-    def set_grad_sync(self, on):
-        """DDP.no_sync(): off -> backward leaves the gradients rank-local (mi355_bresnet50_set_grad_sync)"""
-        from . import native
-
-        self._sync_grads = bool(on)
-        for c in self._ctxs.values():
-            native.check(native.lib().mi355_bresnet50_set_grad_sync(c, int(self._sync_grads)))
-
-    def bucket_plan(self, bucket_cap_mb):
-        """[(begin, end, last_segment)] the native executor would reduce at this cap (layout-only: works on the CPU)"""
-        from . import native
-
-        L = native.lib()
-        ctx = ctypes.c_void_p()
-        native.check(L.mi355_bresnet50_create(ctypes.byref(ctx), -1, self._dt, 1, 32, 32, self.num_classes, int(self.weight_standardization)))
-        try:
-            n = ctypes.c_int()
-            B, E, S = (ctypes.c_size_t * 32)(), (ctypes.c_size_t * 32)(), (ctypes.c_int * 32)()
-            native.check(L.mi355_bresnet50_bucket_plan(ctx, float(bucket_cap_mb), 32, ctypes.byref(n), B, E, S))
-            return [(B[i], E[i], S[i]) for i in range(n.value)]
-        finally:
-            L.mi355_bresnet50_destroy(ctx)
-
     def forward(self, x):
         if self.training and torch.is_grad_enabled():
             return _ResNetFn.apply(x, self._hook, self)
         return self._native_forward(x, training=False)  # eval, or train mode under no_grad: batch statistics as the mode says, no drops
-
-    def flops(self, N, H, W):
-        """(forward, training) algorithmic FLOPs of one step at this shape (2 FLOP/MAC, conv + FC)"""
-        from . import native
-
-        L = native.lib()
-        ctx = ctypes.c_void_p()
-        native.check(L.mi355_bresnet50_create(ctypes.byref(ctx), -1, self._dt, N, H, W, self.num_classes, int(self.weight_standardization)))
-        f, t = ctypes.c_double(), ctypes.c_double()
-        native.check(L.mi355_bresnet50_flops(ctx, ctypes.byref(f), ctypes.byref(t)))
-        L.mi355_bresnet50_destroy(ctx)
-        return f.value, t.value
 
 
 def bresnet50(**kwargs):

@@ -30,22 +30,13 @@
 #include <vector>
 
 #include "../../include/mi355rn.h"
-#include "comm.h"
-#include "common.h"
+#include "flat_model.h"
 
 namespace mi355 {
 namespace {
 
 constexpr int ACT_NONE = 0, ACT_LEAKY = 2;
 constexpr float BN_EPS = 1e-5f, WS_EPS = 1e-5f;
-
-struct TInfo {
-  std::string name;
-  int kind;  // 0 parameter, 1 buffer
-  size_t off;
-  int ndim;
-  int shape[4];
-};
 
 struct VConv {
   std::string name;
@@ -95,37 +86,22 @@ struct VBlock {
   bool scaled = false;            // the last forward scaled the branch by `keep` (drop-connect)
 };
 
-struct Arena {
-  size_t size = 0;
-  std::vector<std::pair<void**, size_t>> slots;
-  template <typename P>
-  void add(P** p, size_t bytes) {
-    slots.push_back({reinterpret_cast<void**>(p), size});
-    size += align_up(bytes, 256);
-  }
-};
-
 }  // namespace
 }  // namespace mi355
 
 using namespace mi355;
 
-struct mi355_bctx {
-  int device = 0, dtype = 0, N = 0, H = 0, W = 0, num_classes = 0, fc_pad = 0;
+struct mi355_bctx : FlatModel {
+  int fc_pad = 0;
   size_t es = 4;
   bool wstd = false;
   float drop_rate = 0.f, drop_connect = 0.f;
   unsigned long long seed = 0;
-  std::vector<TInfo> tensors;
-  size_t param_elems = 0, buffer_elems = 0;
-  float *params = nullptr, *grads = nullptr, *buffers = nullptr;
   VConv s0, s1, s2;
   VBN sb0, sb1, sb2;
   std::vector<VBlock> blocks;
   size_t fc_w_off = 0, fc_b_off = 0;
   // workspace
-  char* arena = nullptr;
-  size_t arena_bytes = 0;
   void *h0 = nullptr, *m = nullptr, *dm = nullptr, *p = nullptr;
   uint8_t* pool_idx = nullptr;
   float *pooled = nullptr, *pooled_d = nullptr, *do_mask = nullptr, *fc_tmp = nullptr, *dlogits_pad = nullptr, *dpooled = nullptr, *fc_wtr = nullptr;
@@ -138,19 +114,8 @@ struct mi355_bctx {
   size_t wg_ws_bytes = 0;
   float* dw_tmp = nullptr; // padded / pre-standardisation weight gradient (side stream)
   float* eca_ws = nullptr;
-  // streams
-  hipStream_t wstream = nullptr;
-  std::vector<hipEvent_t> ev;
-  size_t ev_next = 0;
-  bool overlap = true, w_dirty = false;
-  // gradient collective inside the boundary (comm.cpp), as in resnet_exec.cpp: backward segments (0 = head, then the bottlenecks last
-  // to first, then the stem; the flat array is laid out in FORWARD order, so segments descend through it) form buckets, each reduced by
-  // one mean all-reduce on the communicator's stream as soon as its last segment has been enqueued on both streams
-  struct Bucket { size_t begin, end; int last_seg; };
-  std::vector<std::pair<size_t, size_t>> segs;
-  std::vector<Bucket> buckets;
-  mi355_comm* comm = nullptr;
-  bool grad_sync = true, comm_dirty = false;
+  // (FlatModel: side stream; backward segments — 0 = head, then the bottlenecks last to first, then the stem; the flat array is laid
+  // out in FORWARD order, so segments descend through it — and the buckets reduced behind them)
   // test hooks of the NEXT backward call (mi355_bresnet50_grad_hooks): per block, where to copy the gradient wrt its output before its backward runs,
   // and what to overwrite it with (teacher forcing between backward segments)
   std::vector<void*> hook_record;
@@ -175,21 +140,20 @@ struct mi355_bctx {
 namespace {
 
 size_t reg(mi355_bctx* c, const std::string& name, int kind, std::initializer_list<int> shape) {
-  TInfo t;
+  TensorInfo t;
   t.name = name;
   t.kind = kind;
   size_t n = 1;
-  t.ndim = 0;
   for (int s : shape) {
     t.shape[t.ndim++] = s;
     n *= (size_t)s;
   }
   size_t& cur = kind == 0 ? c->param_elems : c->buffer_elems;
   cur = align_up(cur, 64);  // 256-byte aligned tensors: the kernels load per-channel constants as 16-byte vectors
-  t.off = cur;
+  t.offset = cur;
   cur += n;
   c->tensors.push_back(t);
-  return t.off;
+  return t.offset;
 }
 
 int up64(int v) { return (v + 63) / 64 * 64; }
@@ -236,27 +200,6 @@ void plan_bn(mi355_bctx* c, Arena& ar, VBN& b, int H, int W, bool want_dout = tr
   ar.add(&b.out, o);
   if (want_dout) ar.add(&b.dout, o);
   if (b.act != ACT_NONE) ar.add(&b.bits, o / 16);
-}
-
-int fork(mi355_bctx* c, hipStream_t s, hipStream_t* w) {
-  if (!c->overlap) {
-    *w = s;
-    return 0;
-  }
-  hipEvent_t e = c->ev[c->ev_next++ % c->ev.size()];
-  MI355_HIP(hipEventRecord(e, s));
-  MI355_HIP(hipStreamWaitEvent(c->wstream, e, 0));
-  c->w_dirty = true;
-  *w = c->wstream;
-  return 0;
-}
-int join(mi355_bctx* c, hipStream_t s) {
-  if (!c->overlap || !c->w_dirty) return 0;
-  hipEvent_t e = c->ev[c->ev_next++ % c->ev.size()];
-  MI355_HIP(hipEventRecord(e, c->wstream));
-  MI355_HIP(hipStreamWaitEvent(s, e, 0));
-  c->w_dirty = false;
-  return 0;
 }
 
 // ---- BN parameter views: the flat arrays directly, or the zero / one padded staging rows of the 32-channel stem BNs ---------------
@@ -362,7 +305,7 @@ int bn_back(mi355_bctx* c, VConv& v, VBN& b, const void* dout, float beta, hipSt
 // weight gradient of v from v.dy and its input, on the side stream: wgrad -> [un-pad] -> [standardisation backward] -> flat gradients
 int conv_wgrad(mi355_bctx* c, VConv& v, const void* in, float beta, hipStream_t s) {
   hipStream_t w;
-  MI355_TRY(fork(c, s, &w));
+  MI355_TRY(c->fork(s, &w));
   float* g = c->grads + v.w_off;
   const bool direct = !v.padded() && !c->wstd;
   float* dwp = direct ? g : c->dw_tmp;
@@ -414,59 +357,6 @@ void for_each_conv(mi355_bctx* c, F f) {
 }
 
 }  // namespace
-
-// consecutive backward segments form buckets of >= cap_elems gradient elements; a bucket is the contiguous span of its segments.  The
-// LAST bucket (nothing left to overlap its all-reduce with) is cut once more: its trailing segments up to cap_elems / 8 form a bucket
-// of their own (the rule of resnet_exec.cpp plan_buckets and parallel.plan_buckets, stated for any segment order).
-static std::vector<mi355_bctx::Bucket> plan_bbuckets(const mi355_bctx* c, size_t cap_elems) {
-  std::vector<mi355_bctx::Bucket> out;
-  std::vector<int> firsts;
-  const int nseg = (int)c->segs.size();
-  auto span = [&](int f, int l) {
-    size_t lo = c->segs[f].first, hi = c->segs[f].second;
-    for (int i = f; i <= l; ++i) { lo = std::min(lo, c->segs[i].first); hi = std::max(hi, c->segs[i].second); }
-    return mi355_bctx::Bucket{lo, hi, l};
-  };
-  int first = -1;
-  size_t size = 0;
-  for (int i = 0; i < nseg; ++i) {
-    if (first < 0) { first = i; size = 0; }
-    size += c->segs[i].second - c->segs[i].first;
-    if (size >= cap_elems || i == nseg - 1) {
-      out.push_back(span(first, i));
-      firsts.push_back(first);
-      first = -1;
-    }
-  }
-  const size_t tail_cap = cap_elems / 8;
-  if (!out.empty() && out.back().end - out.back().begin > tail_cap) {
-    const int f = firsts.back(), l = out.back().last_seg;
-    int cut = l + 1;
-    size_t tail = 0;
-    for (int i = l; i > f; --i) {
-      const size_t n = c->segs[i].second - c->segs[i].first;
-      if (tail + n > tail_cap) break;
-      tail += n;
-      cut = i;
-    }
-    if (cut > f && cut <= l) {
-      out.back() = span(f, cut - 1);
-      out.push_back(span(cut, l));
-    }
-  }
-  return out;
-}
-
-// segment `seg` of this backward call is enqueued on both streams: reduce the buckets it completes
-static int after_segment(mi355_bctx* c, int seg, hipStream_t s) {
-  if (!c->comm || !c->grad_sync) return 0;
-  for (const auto& bk : c->buckets)
-    if (bk.last_seg == seg) {
-      MI355_TRY(comm_allreduce_bucket(c->comm, c->grads, bk.begin, bk.end, s, c->overlap && c->w_dirty ? c->wstream : nullptr));
-      c->comm_dirty = true;
-    }
-  return 0;
-}
 
 extern "C" {
 
@@ -634,13 +524,7 @@ int mi355_bresnet50_create(mi355_bctx** out, int device, int dtype, int N, int H
     *out = nullptr;
     return MI355_E_ARG;
   }
-  bool ok = true;
-  if (c->overlap) {
-    ok = hipStreamCreateWithFlags(&c->wstream, hipStreamNonBlocking) == hipSuccess;
-    c->ev.resize(64);
-    for (auto& e : c->ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-  }
-  if (!ok) {
+  if (c->overlap && !c->create_side_stream(false, 64)) {
     set_error("bresnet50_create: stream / event creation failed");
     mi355_bresnet50_destroy(c);
     *out = nullptr;
@@ -650,41 +534,19 @@ int mi355_bresnet50_create(mi355_bctx** out, int device, int dtype, int N, int H
 }
 
 int mi355_bresnet50_destroy(mi355_bctx* c) {
-  if (!c) return 0;
-  if (c->wstream) {
-    (void)hipStreamSynchronize(c->wstream);
-    (void)hipStreamDestroy(c->wstream);
-  }
-  for (auto& e : c->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->arena) (void)hipFree(c->arena);
-  delete c;
+  delete c;  // (FlatModel: side stream, its events, the arena)
   return 0;
 }
 
-int mi355_bresnet50_num_tensors(const mi355_bctx* c) { return c ? (int)c->tensors.size() : 0; }
+int mi355_bresnet50_num_tensors(const mi355_bctx* c) { return flat_num_tensors(c); }
 
 int mi355_bresnet50_tensor_info(const mi355_bctx* c, int idx, char* name, int name_cap, int* kind, size_t* offset, int* ndim, int* shape) {
-  MI355_ARG(c && idx >= 0 && idx < (int)c->tensors.size() && name && name_cap > 0, "bresnet50_tensor_info: bad index %d", idx);
-  const TInfo& t = c->tensors[idx];
-  snprintf(name, (size_t)name_cap, "%s", t.name.c_str());
-  if (kind) *kind = t.kind;
-  if (offset) *offset = t.off;
-  if (ndim) *ndim = t.ndim;
-  if (shape)
-    for (int i = 0; i < t.ndim; ++i) shape[i] = t.shape[i];
-  return 0;
+  return flat_tensor_info(c, "bresnet50", idx, name, name_cap, kind, offset, ndim, shape);
 }
-
-size_t mi355_bresnet50_flat_param_elems(const mi355_bctx* c) { return c ? c->param_elems : 0; }
-size_t mi355_bresnet50_flat_buffer_elems(const mi355_bctx* c) { return c ? c->buffer_elems : 0; }
-size_t mi355_bresnet50_workspace_bytes(const mi355_bctx* c) { return c ? c->arena_bytes : 0; }
-
-int mi355_bresnet50_bind(mi355_bctx* c, float* params, float* grads, float* buffers) {
-  MI355_ARG(c && params && grads && buffers, "bresnet50_bind: null pointer");
-  c->params = params; c->grads = grads; c->buffers = buffers;
-  return 0;
-}
+size_t mi355_bresnet50_flat_param_elems(const mi355_bctx* c) { return flat_param_elems(c); }
+size_t mi355_bresnet50_flat_buffer_elems(const mi355_bctx* c) { return flat_buffer_elems(c); }
+size_t mi355_bresnet50_workspace_bytes(const mi355_bctx* c) { return flat_workspace_bytes(c); }
+int mi355_bresnet50_bind(mi355_bctx* c, float* params, float* grads, float* buffers) { return flat_bind(c, "bresnet50", params, grads, buffers); }
 
 int mi355_bresnet50_set_drop(mi355_bctx* c, float drop_rate, float drop_connect_rate, unsigned long long seed) {
   MI355_ARG(c && drop_rate >= 0.f && drop_rate < 1.f && drop_connect_rate >= 0.f && drop_connect_rate < 1.f, "bresnet50_set_drop: rates in [0, 1)");
@@ -709,14 +571,14 @@ int mi355_bresnet50_forward(mi355_bctx* c, const float* x_nchw, float* logits, i
   const int N = c->N, dt = c->dtype;
   const bool tr = training != 0;
   c->have_fwd = false;  // (until this pass has completed: a failed forward must not be differentiated)
-  MI355_TRY(join(c, s));  // (a previous backward's side-stream work reads the tensors this pass overwrites)
+  MI355_TRY(c->join(s));  // (a previous backward's side-stream work reads the tensors this pass overwrites)
   // ---- weight preparation: [standardise] -> pad -> cast; FC weights transposed for the input gradient ------------------------------
   // The first conv's weights on the caller's stream; everything else on the side stream, beside the input conversion and the first conv, which only
   // have to wait for their own: two launches over a table of every layer (variant.hip launch_bres_weight_prep) — as 106 + 54 small launches their
   // dispatch chain outlasted the first conv and held the second one up.
   MI355_TRY(prep_weight(c, c->s0, s));
   hipStream_t ps;
-  MI355_TRY(fork(c, s, &ps));
+  MI355_TRY(c->fork(s, &ps));
   int rc = 0;
   if (c->batch_prep) {
     if (c->prep_params != c->params) {   // (once per bound parameter array: the table holds pointers into it)
@@ -764,7 +626,7 @@ int mi355_bresnet50_forward(mi355_bctx* c, const float* x_nchw, float* logits, i
   if (c->stem_im2col) MI355_TRY(launch_nchw_im2col3s2(dt, x_nchw, c->h0, N, c->H, c->W, s));
   else MI355_TRY(launch_nchw_pad64(dt, x_nchw, c->h0, N, c->H * c->W, s));
   MI355_TRY(conv_bn(c, c->s0, c->sb0, c->h0, tr, bn_momentum, s));
-  MI355_TRY(join(c, s));  // the prepared weights of every later layer
+  MI355_TRY(c->join(s));  // the prepared weights of every later layer
   MI355_TRY(conv_bn(c, c->s1, c->sb1, c->sb0.out, tr, bn_momentum, s));
   MI355_TRY(conv_bn(c, c->s2, c->sb2, c->sb1.out, tr, bn_momentum, s));
   MI355_TRY(mi355_maxpool3s1_fwd(dt, c->sb2.out, c->m, c->pool_idx, N, c->H / 2, c->W / 2, 64, s));
@@ -855,7 +717,7 @@ int mi355_bresnet50_backward(mi355_bctx* c, const float* dlogits, int accumulate
     w.dy = c->dlogits_pad; w.x = c->dropped ? c->pooled_d : c->pooled; w.partial = (float*)c->wg_ws;
     const int splits = plan_wgrad_splits(MI355_F32, N, P, 1, 2048);
     hipStream_t ws;
-    MI355_TRY(fork(c, s, &ws));
+    MI355_TRY(c->fork(s, &ws));
     MI355_TRY(launch_wgrad(MI355_F32, w, splits, ws));
     MI355_TRY(launch_splitk_reduce((const float*)c->wg_ws, splits, (size_t)P * 2048, c->grads + c->fc_w_off, (size_t)O * 2048, beta, ws));
   }
@@ -863,7 +725,7 @@ int mi355_bresnet50_backward(mi355_bctx* c, const float* dlogits, int accumulate
   if (c->dropped) MI355_TRY(mi355_mul_f32(c->dpooled, c->do_mask, c->dpooled, (size_t)N * 2048, s));
   const VBlock& last = c->blocks.back();
   MI355_TRY(mi355_gap_bwd(dt, c->dpooled, c->dlast, N, last.Ho * last.Wo, 2048, s));
-  MI355_TRY(after_segment(c, 0, s));
+  MI355_TRY(c->after_segment(0, s));
   // ---- bottlenecks, last to first ------------------------------------------------------------------------------------------------
   const void* g = c->dlast;  // gradient wrt the block output
   for (int i = (int)c->blocks.size() - 1; i >= 0; --i) {
@@ -933,7 +795,7 @@ int mi355_bresnet50_backward(mi355_bctx* c, const float* dlogits, int accumulate
       MI355_TRY(mi355_residual_act_fwd(dt, b.dxb, nullptr, gs, b.dx, N, (size_t)b.H * b.W * b.cin, ACT_NONE, s));  // (the autograd sum of the per-op graph)
     }
     g = b.dx;
-    MI355_TRY(after_segment(c, (int)c->blocks.size() - i, s));
+    MI355_TRY(c->after_segment((int)c->blocks.size() - i, s));
   }
   // ---- stem ------------------------------------------------------------------------------------------------------------------------
   MI355_TRY(mi355_blurpool_bwd(dt, g, c->dm, N, c->H / 2, c->W / 2, 64, s));
@@ -947,12 +809,8 @@ int mi355_bresnet50_backward(mi355_bctx* c, const float* dlogits, int accumulate
   MI355_TRY(conv_dgrad(c, c->s1, c->sb0.dout, nullptr, s, &c->s0, &c->sb0, &srows));
   MI355_TRY(bn_back(c, c->s0, c->sb0, c->sb0.dout, beta, s, nullptr, srows));
   MI355_TRY(conv_wgrad(c, c->s0, c->h0, beta, s));
-  MI355_TRY(after_segment(c, (int)c->blocks.size() + 1, s));
-  MI355_TRY(join(c, s));
-  if (c->comm && c->comm_dirty) {
-    MI355_TRY(comm_join(c->comm, s));
-    c->comm_dirty = false;
-  }
+  MI355_TRY(c->after_segment((int)c->blocks.size() + 1, s));
+  MI355_TRY(c->finish(s));
   c->hook_record.clear();
   c->hook_replay.clear();
   return 0;
@@ -1008,42 +866,12 @@ int mi355_bresnet50_debug_tensor(const mi355_bctx* c, const char* name, void** p
   return MI355_E_ARG;
 }
 
-int mi355_bresnet50_num_segments(const mi355_bctx* c) { return c ? (int)c->segs.size() : 0; }
-
-int mi355_bresnet50_segment_range(const mi355_bctx* c, int seg, size_t* grad_begin, size_t* grad_end) {
-  MI355_ARG(c && grad_begin && grad_end && seg >= 0 && seg < (int)c->segs.size(), "bresnet50_segment_range: bad arguments");
-  *grad_begin = c->segs[seg].first;
-  *grad_end = c->segs[seg].second;
-  return 0;
-}
-
+int mi355_bresnet50_num_segments(const mi355_bctx* c) { return flat_num_segments(c); }
+int mi355_bresnet50_segment_range(const mi355_bctx* c, int seg, size_t* gb, size_t* ge) { return flat_segment_range(c, "bresnet50", seg, gb, ge); }
 int mi355_bresnet50_bucket_plan(const mi355_bctx* c, double bucket_cap_mb, int cap, int* n_out, size_t* begins, size_t* ends, int* last_segs) {
-  MI355_ARG(c && n_out && bucket_cap_mb > 0, "bresnet50_bucket_plan: bad arguments");
-  const auto bk = plan_bbuckets(c, (size_t)(bucket_cap_mb * (1 << 20) / 4));
-  *n_out = (int)bk.size();
-  for (int i = 0; i < (int)bk.size() && i < cap; ++i) {
-    if (begins) begins[i] = bk[i].begin;
-    if (ends) ends[i] = bk[i].end;
-    if (last_segs) last_segs[i] = bk[i].last_seg;
-  }
-  return 0;
+  return flat_bucket_plan(c, "bresnet50", bucket_cap_mb, cap, n_out, begins, ends, last_segs);
 }
-
-int mi355_bresnet50_set_comm(mi355_bctx* c, mi355_comm* comm, double bucket_cap_mb) {
-  MI355_ARG(c && (comm == nullptr || bucket_cap_mb > 0), "bresnet50_set_comm: bad arguments");
-  if (c->device < 0) {
-    set_error("bresnet50_set_comm: layout-only ctx (created with device < 0)");
-    return MI355_E_STATE;
-  }
-  c->comm = comm;
-  c->buckets = comm ? plan_bbuckets(c, (size_t)(bucket_cap_mb * (1 << 20) / 4)) : std::vector<mi355_bctx::Bucket>();
-  return 0;
-}
-
-int mi355_bresnet50_set_grad_sync(mi355_bctx* c, int on) {
-  MI355_ARG(c, "bresnet50_set_grad_sync: null ctx");
-  c->grad_sync = on != 0;
-  return 0;
-}
+int mi355_bresnet50_set_comm(mi355_bctx* c, mi355_comm* comm, double bucket_cap_mb) { return flat_set_comm(c, "bresnet50", comm, bucket_cap_mb); }
+int mi355_bresnet50_set_grad_sync(mi355_bctx* c, int on) { return flat_set_grad_sync(c, "bresnet50", on); }
 
 }  // extern "C"

@@ -13,8 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "comm.h"
-#include "common.h"
+#include "flat_model.h"
 
 namespace mi355 {
 
@@ -27,14 +26,6 @@ constexpr float BN_EPS = 1e-5f;
 constexpr float FP8_HEADROOM = 2.f;  // scale = 448 / (FP8_HEADROOM * amax of the previous step): one binade of the e4m3 range
 constexpr size_t PARAM_ALIGN = 64;  // floats (256 B)
 constexpr int MAX_EVENTS = 8192;
-
-struct TensorInfo {
-  std::string name;
-  int kind;  // 0 param, 1 buffer
-  size_t offset;
-  int ndim;
-  int shape[4];
-};
 
 struct ConvBN {
   std::string conv_name, bn_name;
@@ -73,16 +64,6 @@ struct Block {
   uint8_t *a1_q = nullptr, *a2_q = nullptr, *out_q = nullptr;           // e4m3 twins (fp8 step; null where no fp8 conv reads them)
   int qid_a1 = -1, qid_a2 = -1, qid_out = -1;
   int Hin, Win, Hout, Wout, Cin, Cout;
-  size_t grad_begin = 0, grad_end = 0;
-};
-
-struct Arena {
-  size_t size = 0;
-  std::vector<std::pair<void**, size_t>> slots;
-  void add(void** p, size_t bytes) {
-    slots.push_back({p, size});
-    size += align_up(bytes, 256);
-  }
 };
 
 }  // namespace
@@ -92,20 +73,14 @@ using namespace mi355;
 
 constexpr int MAX_GSETS = 4;
 
-struct mi355_ctx {
-  int device = 0, dtype = 0, N = 0, H = 0, W = 0, num_classes = 0, fc_pad = 0;
+struct mi355_ctx : FlatModel {
+  int fc_pad = 0;
   size_t es = 4;
   ConvBN stem;
   std::vector<Block> blocks;
-  std::vector<TensorInfo> tensors;
-  size_t param_elems = 0, buffer_elems = 0;
   size_t fc_w_off = 0, fc_b_off = 0;
-  size_t fc_grad_begin = 0, fc_grad_end = 0, stem_grad_begin = 0, stem_grad_end = 0;
-  float *params = nullptr, *grads = nullptr, *buffers = nullptr;
 
   // workspace
-  char* arena = nullptr;
-  size_t arena_bytes = 0;
   void *xpad = nullptr, *stem_pack = nullptr, *p0 = nullptr;
   uint8_t* pool_idx = nullptr;
   uint8_t* a0_bits = nullptr;
@@ -114,14 +89,6 @@ struct mi355_ctx {
   float *bn_partial2 = nullptr, *bn_coef2 = nullptr;  // the same for BN work issued to the side stream
   void* sk_ws[2] = {nullptr, nullptr};                // stream-K scratch of the conv kernel, main / side stream
   bool stream_k = true;
-  // gradient collective inside the boundary (comm.cpp): buckets of consecutive backward segments, each reduced by one
-  // mean all-reduce on the communicator's stream as soon as its last segment has been enqueued
-  mi355_comm* comm = nullptr;
-  struct Bucket {
-    size_t begin, end;
-    int last_seg;
-  };
-  std::vector<Bucket> buckets;
   // fp8 training step: bf16 tensors everywhere + e4m3 twins of the conv operands; delayed per-tensor scaling (a tensor's amax of
   // step k sets its scale of step k + 1); the first training step of a ctx runs bf16 operands and only records the amaxes
   bool fp8 = false;
@@ -136,8 +103,6 @@ struct mi355_ctx {
   bool fp8_keep_bf16 = false;                     // MI355_FP8_KEEP_BF16=1: write the bf16 tensors even where every consumer reads the twin
                                                   // (tests compare the twins with them)
   bool fp8_lean = false;                          // this step: bf16 tensors whose consumers all read twins are not written
-  bool grad_sync = true;    // false: backward skips the bucket all-reduces (DDP.no_sync(): non-final accumulation micro-steps)
-  bool comm_dirty = false;  // an all-reduce of this backward call is in flight on the communicator's stream
   unsigned* sk_err_host = nullptr;  // pinned copy of the two scratch blocks' error words, refreshed by an async copy at the
                                     // end of every forward / backward call and looked at (no wait) at the start of the next
   PrepDesc* prep_table[2] = {nullptr, nullptr};  // [0]: cast only (inference), [1]: cast + transposed (training)
@@ -153,18 +118,13 @@ struct mi355_ctx {
   size_t max_c = 64;  // widest BatchNorm of the network (sizes bn_partial)
   int nsets = 2;  // gradient buffer sets in rotation (MI355_GSETS, read at ctx creation): the main stream waits for the weight gradients of
                   // the block that used a set nsets blocks ago
-  // weight-gradient side stream (wgrad + split-K reduce run beside the BN-backward / dgrad chain of the main stream)
-  bool overlap = false;
+  // weight-gradient side stream (FlatModel: wgrad + split-K reduce run beside the BN-backward / dgrad chain of the main stream)
   bool fuse_bn_bwd = false;  // BN-backward sums in the dgrad epilogues (MI355_FUSE_BN_BWD=0/1 overrides the default)
   bool fuse_bn_in = true;    // bn1 + ReLU in conv2's operand path where a generated kernel has that form (library switch MI355_DCONV_BN)
   bool stem_fused_bwd = true;  // stem BN backward gathers the pool gradient on the fly (MI355_STEM_FUSED=0: pool-backward kernel + plain BN backward)
-  hipStream_t wstream = nullptr;
-  std::vector<hipEvent_t> fork_ev;
-  size_t fork_next = 0;
   hipEvent_t w_done[MAX_GSETS] = {};
   hipEvent_t ds_done = nullptr;  // the downsample branch issued to the side stream has finished
   bool w_pending[MAX_GSETS] = {};
-  bool w_dirty = false;
   int bwd_parity = 0;
   bool fwd_training_done = false;
   int next_seg = 0;
@@ -628,20 +588,7 @@ int weight_prep_all(mi355_ctx* c, bool need_tr, hipStream_t s) {
   return 0;
 }
 
-// ---- weight-gradient side stream ----------------------------------------------------------------------------------
-// fork(): the stream the next wgrad goes to, ordered after everything issued to `s` so far.
-int fork(mi355_ctx* c, hipStream_t s, hipStream_t* w) {
-  if (!c->overlap) {
-    *w = s;
-    return 0;
-  }
-  hipEvent_t e = c->fork_ev[c->fork_next++ % c->fork_ev.size()];
-  MI355_HIP(hipEventRecord(e, s));
-  MI355_HIP(hipStreamWaitEvent(c->wstream, e, 0));
-  c->w_dirty = true;
-  *w = c->wstream;
-  return 0;
-}
+// ---- gradient-set rotation on the weight-gradient side stream -----------------------------------------------------
 // before the main stream overwrites gradient set p: the wgrads of the block that used it last must have read it
 int acquire_set(mi355_ctx* c, int p, hipStream_t s) {
   if (c->overlap && c->w_pending[p]) {
@@ -657,17 +604,6 @@ int release_set(mi355_ctx* c, int p) {
   }
   return 0;
 }
-// join(): everything on the side stream becomes visible to `s` (end of a backward call: the caller reads the gradients)
-int join(mi355_ctx* c, hipStream_t s) {
-  if (!c->overlap || !c->w_dirty) return 0;
-  hipEvent_t e = c->fork_ev[c->fork_next++ % c->fork_ev.size()];
-  MI355_HIP(hipEventRecord(e, c->wstream));
-  MI355_HIP(hipStreamWaitEvent(s, e, 0));
-  c->w_dirty = false;
-  for (int p = 0; p < MAX_GSETS; ++p) c->w_pending[p] = false;
-  return 0;
-}
-
 // stream-K (fp32 conv): a hand-off that timed out leaves a wrong tile behind; the kernel raises an error word, which is
 // copied to pinned host memory behind the kernels of a call and checked at the start of the following calls
 int sk_check(mi355_ctx* c) {
@@ -687,65 +623,6 @@ int sk_snapshot(mi355_ctx* c, hipStream_t s) {
   return 0;
 }
 
-void seg_range(const mi355_ctx* c, int seg, size_t* b, size_t* e) {
-  const int nb = (int)c->blocks.size();
-  if (seg == 0) {
-    *b = c->fc_grad_begin; *e = c->fc_grad_end;
-  } else if (seg == nb + 1) {
-    *b = c->stem_grad_begin; *e = c->stem_grad_end;
-  } else {
-    const Block& blk = c->blocks[nb - seg];
-    *b = blk.grad_begin; *e = blk.grad_end;
-  }
-}
-// consecutive segments (backward completion order = ascending offsets) form buckets of >= cap_elems gradient elements.
-// The LAST bucket has nothing left to hide behind (its all-reduce starts when backward ends), so it is cut once more: its trailing
-// segments up to cap_elems / 8 (stem + layer 1 + the end of layer 2: ~4 MB at the default cap) become a bucket of their own and the
-// part before them is reduced while those last, activation-heavy blocks are still computing.
-std::vector<mi355_ctx::Bucket> plan_buckets(const mi355_ctx* c, size_t cap_elems) {
-  std::vector<mi355_ctx::Bucket> out;
-  const int nseg = (int)c->blocks.size() + 2;
-  bool open = false;
-  size_t start = 0;
-  int first_seg = 0;
-  std::vector<int> firsts;
-  for (int i = 0; i < nseg; ++i) {
-    size_t b, e;
-    seg_range(c, i, &b, &e);
-    if (!open) {
-      start = b;
-      first_seg = i;
-      open = true;
-    }
-    if (e - start >= cap_elems || i == nseg - 1) {
-      out.push_back({start, e, i});
-      firsts.push_back(first_seg);
-      open = false;
-    }
-  }
-  const size_t tail_cap = cap_elems / 8;
-  if (!out.empty() && out.back().end - out.back().begin > tail_cap) {
-    const int f = firsts.back(), l = out.back().last_seg;
-    int cut = l + 1;  // first segment of the tail bucket (l + 1: no tail — the last segment alone exceeds the tail cap)
-    size_t tail = 0;
-    for (int i = l; i > f; --i) {
-      size_t b, e;
-      seg_range(c, i, &b, &e);
-      if (tail + (e - b) > tail_cap) break;
-      tail += e - b;
-      cut = i;
-    }
-    if (cut > f && cut <= l) {
-      size_t b, e;
-      seg_range(c, cut, &b, &e);
-      const mi355_ctx::Bucket last = out.back();
-      out.back() = {last.begin, b, cut - 1};
-      out.push_back({b, last.end, l});
-    }
-  }
-  return out;
-}
-
 int backward_fc(mi355_ctx* c, const float* dlogits, float beta_acc, hipStream_t s) {
   const int N = c->N, O = c->num_classes, P = c->fc_pad;
   MI355_TRY(launch_pad_dlogits(dlogits, c->dlogits_pad, P, c->grads + c->fc_b_off, beta_acc, N, O, s));
@@ -755,7 +632,7 @@ int backward_fc(mi355_ctx* c, const float* dlogits, float beta_acc, hipStream_t 
   w.dy = c->dlogits_pad; w.x = c->pooled; w.partial = c->wg_partial;
   const int splits = plan_wgrad_splits(MI355_F32, N, P, 1, 2048);
   hipStream_t ws;
-  MI355_TRY(fork(c, s, &ws));
+  MI355_TRY(c->fork(s, &ws));
   MI355_TRY(launch_wgrad(MI355_F32, w, splits, ws));
   MI355_TRY(launch_splitk_reduce(c->wg_partial, splits, (size_t)P * 2048, c->grads + c->fc_w_off, (size_t)O * 2048,
                                  beta_acc, ws));
@@ -779,7 +656,7 @@ int backward_block(mi355_ctx* c, Block& b, Block* prev, float beta_acc, hipStrea
   const bool sub2 = sub2_ok(c, b, prev);
   MI355_TRY(acquire_set(c, par, s));
   MI355_TRY(bn_backward(c, b.c3, G, b.out_bits, nullptr, B1, beta_acc, s));  // B1 = dy3
-  MI355_TRY(fork(c, s, &ws));
+  MI355_TRY(c->fork(s, &ws));
   MI355_TRY(conv_wgrad(c, b.c3, B1, b.a2, beta_acc, ws));
   if (b.has_ds) {
     // the whole downsample branch runs beside the conv3 -> conv1 chain (same fork: it only needs G)
@@ -791,11 +668,11 @@ int backward_block(mi355_ctx* c, Block& b, Block* prev, float beta_acc, hipStrea
   }
   MI355_TRY(conv_dgrad(c, b.c3, B1, B3, nullptr, s, nullptr, &b.c2, b.a2_bits, beta_acc));  // B3 = da2 (+ bn2's sums)
   MI355_TRY(bn_backward(c, b.c2, B3, b.a2_bits, nullptr, B3, beta_acc, s));  // B3 = dy2
-  MI355_TRY(fork(c, s, &ws));
+  MI355_TRY(c->fork(s, &ws));
   MI355_TRY(conv_wgrad(c, b.c2, B3, b.a1, beta_acc, ws));
   MI355_TRY(conv_dgrad(c, b.c2, B3, B4, nullptr, s, nullptr, &b.c1, b.a1_bits, beta_acc));  // B4 = da1 (+ bn1's sums)
   MI355_TRY(bn_backward(c, b.c1, B4, b.a1_bits, nullptr, B4, beta_acc, s));  // B4 = dy1
-  MI355_TRY(fork(c, s, &ws));
+  MI355_TRY(c->fork(s, &ws));
   MI355_TRY(conv_wgrad(c, b.c1, B4, b.in, beta_acc, ws));
   if (b.has_ds) {
     if (c->overlap) MI355_HIP(hipStreamWaitEvent(s, c->ds_done, 0));
@@ -842,7 +719,7 @@ int backward_stem(mi355_ctx* c, float beta_acc, hipStream_t s) {
   build_stem_wgrad_args(a, c->N, c->H, c->W);
   a.dy = B1; a.x = c->xpad; a.partial = c->wg_partial;
   hipStream_t ws;
-  MI355_TRY(fork(c, s, &ws));
+  MI355_TRY(c->fork(s, &ws));
   {
     Prof p(c, PC_WGRAD64, conv_flops(c, l), 0, ws);
     MI355_TRY(launch_wgrad(c->dtype, a, l.splits, ws));
@@ -894,25 +771,28 @@ int mi355_resnet50_create(mi355_ctx** out, int device, int dtype, int N, int H, 
       c->blocks.push_back(b);
     }
   }
-  // ---- flat parameter layout, reverse execution order ----
+  // ---- flat parameter layout, reverse execution order: backward segment k (0 = fc, then the blocks last to first, then the
+  // stem) is the k-th range registered ----
   std::vector<TensorInfo> rev;
-  c->fc_grad_begin = c->param_elems;
+  size_t seg_begin = c->param_elems;
+  auto end_segment = [&] {
+    c->segs.push_back({seg_begin, c->param_elems});
+    seg_begin = c->param_elems;
+  };
   add_param(c, rev, "fc.bias", &c->fc_b_off, 1, num_classes);
   add_param(c, rev, "fc.weight", &c->fc_w_off, 2, num_classes, 2048, 0, 0,
             (size_t)(c->fc_pad - num_classes) * 2048);
-  c->fc_grad_end = c->param_elems;
+  end_segment();
   for (int i = (int)c->blocks.size() - 1; i >= 0; --i) {
     Block& b = c->blocks[i];
-    b.grad_begin = c->param_elems;
     if (b.has_ds) register_convbn(c, rev, b.ds);
     register_convbn(c, rev, b.c3);
     register_convbn(c, rev, b.c2);
     register_convbn(c, rev, b.c1);
-    b.grad_end = c->param_elems;
+    end_segment();
   }
-  c->stem_grad_begin = c->param_elems;
   register_convbn(c, rev, c->stem);
-  c->stem_grad_end = c->param_elems;
+  end_segment();
   // expose tensors in torchvision (forward) order
   c->tensors.assign(rev.rbegin(), rev.rend());
 
@@ -965,7 +845,6 @@ int mi355_resnet50_create(mi355_ctx** out, int device, int dtype, int N, int H, 
   e = hipMemset(c->arena, 0, ar.size);
   if (e != hipSuccess) {
     set_error("create: hipMemset -> %s", hipGetErrorString(e));
-    (void)hipFree(c->arena);
     delete c;
     return MI355_E_HIP;
   }
@@ -1028,14 +907,7 @@ int mi355_resnet50_create(mi355_ctx** out, int device, int dtype, int N, int H, 
   if (c->overlap) {
     // the weight-gradient stream runs at the highest priority: it is the busier of the two during backward and the main stream ends
     // up waiting for it (profiles/r04_ab_side_stream_priority.txt: -0.07..-0.13 ms per step on three boxes)
-    bool ok;
-    {
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-      ok = hipStreamCreateWithPriority(&c->wstream, hipStreamNonBlocking, hi) == hipSuccess;
-    }
-    c->fork_ev.resize(16);
-    for (auto& ev : c->fork_ev) ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+    bool ok = c->create_side_stream(true, 16);
     for (auto& ev : c->w_done) ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ds_done, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
@@ -1058,51 +930,23 @@ int mi355_resnet50_destroy(mi355_ctx* c) {
   if (!c) return 0;
   if (c->device >= 0) (void)hipSetDevice(c->device);
   for (auto e : c->ev) (void)hipEventDestroy(e);
-  for (auto e : c->fork_ev)
-    if (e) (void)hipEventDestroy(e);
   for (auto e : c->w_done)
     if (e) (void)hipEventDestroy(e);
   if (c->ds_done) (void)hipEventDestroy(c->ds_done);
-  if (c->wstream) (void)hipStreamDestroy(c->wstream);
   if (c->sk_err_host) (void)hipHostFree(c->sk_err_host);
-  if (c->arena) (void)hipFree(c->arena);
-  delete c;
+  delete c;  // (FlatModel: side stream, its events, the arena)
   return 0;
 }
 
-int mi355_resnet50_num_tensors(const mi355_ctx* c) { return c ? (int)c->tensors.size() : 0; }
-
-int mi355_resnet50_tensor_info(const mi355_ctx* c, int idx, char* name, int name_cap, int* kind, size_t* offset,
-                               int* ndim, int shape[4]) {
-  MI355_ARG(c && idx >= 0 && idx < (int)c->tensors.size(), "tensor_info: bad index %d", idx);
-  const TensorInfo& t = c->tensors[idx];
-  if (name && name_cap > 0) {
-    strncpy(name, t.name.c_str(), name_cap - 1);
-    name[name_cap - 1] = 0;
-  }
-  if (kind) *kind = t.kind;
-  if (offset) *offset = t.offset;
-  if (ndim) *ndim = t.ndim;
-  if (shape)
-    for (int i = 0; i < 4; ++i) shape[i] = t.shape[i];
-  return 0;
+int mi355_resnet50_num_tensors(const mi355_ctx* c) { return flat_num_tensors(c); }
+int mi355_resnet50_tensor_info(const mi355_ctx* c, int idx, char* name, int name_cap, int* kind, size_t* offset, int* ndim,
+                               int shape[4]) {
+  return flat_tensor_info(c, "resnet50", idx, name, name_cap, kind, offset, ndim, shape);
 }
-
-size_t mi355_resnet50_flat_param_elems(const mi355_ctx* c) { return c ? c->param_elems : 0; }
-size_t mi355_resnet50_flat_buffer_elems(const mi355_ctx* c) { return c ? c->buffer_elems : 0; }
-size_t mi355_resnet50_workspace_bytes(const mi355_ctx* c) { return c ? c->arena_bytes : 0; }
-
-int mi355_resnet50_bind(mi355_ctx* c, float* params, float* grads, float* buffers) {
-  MI355_ARG(c && params && buffers, "bind: null pointer");
-  if (c->device < 0) {
-    set_error("bind: layout-only ctx (created with device < 0)");
-    return MI355_E_STATE;
-  }
-  MI355_ARG(((uintptr_t)params % 256 == 0) && ((uintptr_t)buffers % 256 == 0) && ((uintptr_t)grads % 256 == 0),
-            "bind: flat arrays must be 256-byte aligned");
-  c->params = params; c->grads = grads; c->buffers = buffers;
-  return 0;
-}
+size_t mi355_resnet50_flat_param_elems(const mi355_ctx* c) { return flat_param_elems(c); }
+size_t mi355_resnet50_flat_buffer_elems(const mi355_ctx* c) { return flat_buffer_elems(c); }
+size_t mi355_resnet50_workspace_bytes(const mi355_ctx* c) { return flat_workspace_bytes(c); }
+int mi355_resnet50_bind(mi355_ctx* c, float* params, float* grads, float* buffers) { return flat_bind(c, "resnet50", params, grads, buffers); }
 
 int mi355_resnet50_forward(mi355_ctx* c, const float* x_nchw, float* logits, int training, float bn_momentum,
                            void* stream) {
@@ -1150,7 +994,7 @@ int mi355_resnet50_forward(mi355_ctx* c, const float* x_nchw, float* logits, int
   for (auto& b : c->blocks) {
     if (b.has_ds) {  // the downsample conv + its statistics run beside conv1..conv3
       hipStream_t ws;
-      MI355_TRY(fork(c, s, &ws));
+      MI355_TRY(c->fork(s, &ws));
       MI355_TRY(conv_forward(c, b.ds, b.in, training, bn_momentum, ws));
       MI355_TRY(bn_prepare(c, b.ds, training, bn_momentum, ws));
       if (c->overlap) MI355_HIP(hipEventRecord(c->ds_done, ws));
@@ -1195,51 +1039,19 @@ int mi355_resnet50_forward(mi355_ctx* c, const float* x_nchw, float* logits, int
   return sk_snapshot(c, s);
 }
 
-int mi355_resnet50_num_segments(const mi355_ctx* c) { return c ? (int)c->blocks.size() + 2 : 0; }
-
-int mi355_resnet50_segment_range(const mi355_ctx* c, int seg, size_t* gb, size_t* ge) {
-  MI355_ARG(c && seg >= 0 && seg < (int)c->blocks.size() + 2, "segment_range: bad segment %d", seg);
-  size_t b, e;
-  seg_range(c, seg, &b, &e);
-  if (gb) *gb = b;
-  if (ge) *ge = e;
-  return 0;
-}
-
+int mi355_resnet50_num_segments(const mi355_ctx* c) { return flat_num_segments(c); }
+int mi355_resnet50_segment_range(const mi355_ctx* c, int seg, size_t* gb, size_t* ge) { return flat_segment_range(c, "resnet50", seg, gb, ge); }
 int mi355_resnet50_bucket_plan(const mi355_ctx* c, double bucket_cap_mb, int cap, int* n_out, size_t* begins, size_t* ends,
                                int* last_segs) {
-  MI355_ARG(c && n_out && bucket_cap_mb > 0, "bucket_plan: bad arguments");
-  const auto bk = plan_buckets(c, (size_t)(bucket_cap_mb * (1 << 20) / 4));
-  *n_out = (int)bk.size();
-  for (int i = 0; i < (int)bk.size() && i < cap; ++i) {
-    if (begins) begins[i] = bk[i].begin;
-    if (ends) ends[i] = bk[i].end;
-    if (last_segs) last_segs[i] = bk[i].last_seg;
-  }
-  return 0;
+  return flat_bucket_plan(c, "resnet50", bucket_cap_mb, cap, n_out, begins, ends, last_segs);
 }
-
-int mi355_resnet50_set_comm(mi355_ctx* c, mi355_comm* comm, double bucket_cap_mb) {
-  MI355_ARG(c && (comm == nullptr || bucket_cap_mb > 0), "set_comm: bad arguments");
-  if (c->device < 0) {
-    set_error("set_comm: layout-only ctx (created with device < 0)");
-    return MI355_E_STATE;
-  }
-  c->comm = comm;
-  c->buckets = comm ? plan_buckets(c, (size_t)(bucket_cap_mb * (1 << 20) / 4)) : std::vector<mi355_ctx::Bucket>();
-  return 0;
-}
-
-int mi355_resnet50_set_grad_sync(mi355_ctx* c, int on) {
-  MI355_ARG(c, "set_grad_sync: null ctx");
-  c->grad_sync = on != 0;
-  return 0;
-}
+int mi355_resnet50_set_comm(mi355_ctx* c, mi355_comm* comm, double bucket_cap_mb) { return flat_set_comm(c, "resnet50", comm, bucket_cap_mb); }
+int mi355_resnet50_set_grad_sync(mi355_ctx* c, int on) { return flat_set_grad_sync(c, "resnet50", on); }
 
 int mi355_resnet50_backward(mi355_ctx* c, const float* dlogits, int seg_begin, int seg_end, int accumulate,
                             void* stream) {
   MI355_ARG(c, "backward: null ctx");
-  const int nseg = (int)c->blocks.size() + 2;
+  const int nseg = (int)c->segs.size();
   MI355_ARG(seg_begin >= 0 && seg_end <= nseg && seg_begin < seg_end, "backward: bad segment range [%d,%d)", seg_begin,
             seg_end);
   if (!c->fwd_training_done || !c->grads) {
@@ -1264,18 +1076,10 @@ int mi355_resnet50_backward(mi355_ctx* c, const float* dlogits, int seg_begin, i
       MI355_TRY(backward_block(c, c->blocks[nb - seg], nb - seg > 0 ? &c->blocks[nb - seg - 1] : nullptr, beta_acc, s));
     }
     c->next_seg = seg + 1;
-    if (c->comm && c->grad_sync)
-      for (const auto& bk : c->buckets)
-        if (bk.last_seg == seg) {  // the bucket's producers are all enqueued (main + weight-gradient stream): reduce it
-          MI355_TRY(comm_allreduce_bucket(c->comm, c->grads, bk.begin, bk.end, s, c->overlap && c->w_dirty ? c->wstream : nullptr));
-          c->comm_dirty = true;
-        }
+    MI355_TRY(c->after_segment(seg, s));
   }
-  MI355_TRY(join(c, s));
-  if (c->comm && c->comm_dirty) {
-    MI355_TRY(comm_join(c->comm, s));
-    c->comm_dirty = false;
-  }
+  MI355_TRY(c->finish(s));
+  for (bool& p : c->w_pending) p = false;  // (the join waited for every set's readers)
   if (c->next_seg == nseg) {
     c->fwd_training_done = false;
     c->fp8_bwd_cal = true;

@@ -11,6 +11,7 @@ in reverse execution order so DDP buckets complete front to back; conv weights a
 tensors in channels_last memory (= the KRSC layout the kernels read).  Nothing here computes: forward and
 backward are single C-ABI calls; without the HIP library / a GPU they raise.
 """
+import contextlib
 import ctypes
 from collections import OrderedDict
 
@@ -43,28 +44,6 @@ class _BNLeaf(_Leaf):
         self.eps = 1e-5
 
 
-def _layout(dtype_code, N, H, W, num_classes):
-    """tensor table of the native executor: [(name, kind, offset, shape)], sizes, segment ranges (no GPU needed)."""
-    L = native.lib()
-    ctx = ctypes.c_void_p()
-    check(L.mi355_resnet50_create(ctypes.byref(ctx), -1, dtype_code, N, H, W, num_classes))
-    try:
-        table = []
-        for i in range(L.mi355_resnet50_num_tensors(ctx)):
-            name = ctypes.create_string_buffer(128)
-            kind, off, nd, sh = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_int * 4)()
-            check(L.mi355_resnet50_tensor_info(ctx, i, name, 128, ctypes.byref(kind), ctypes.byref(off), ctypes.byref(nd), sh))
-            table.append((name.value.decode(), kind.value, off.value, tuple(sh[j] for j in range(nd.value))))
-        segs = []
-        for s in range(L.mi355_resnet50_num_segments(ctx)):
-            b, e = ctypes.c_size_t(), ctypes.c_size_t()
-            check(L.mi355_resnet50_segment_range(ctx, s, ctypes.byref(b), ctypes.byref(e)))
-            segs.append((b.value, e.value))
-        return table, L.mi355_resnet50_flat_param_elems(ctx), L.mi355_resnet50_flat_buffer_elems(ctx), segs
-    finally:
-        L.mi355_resnet50_destroy(ctx)
-
-
 class _ResNetFn(torch.autograd.Function):
     """autograd bridge so reference-style `loss.backward()` (callbacks.py:317) drives the native backward."""
 
@@ -81,8 +60,62 @@ class _ResNetFn(torch.autograd.Function):
 
 class _FlatModel(nn.Module):
     """What the facades over the two static executors (ResNet-50 here, BResNet-50 in bresnet.py) share: every parameter / buffer is
-    a view into ONE flat fp32 array (gradients likewise) laid out by the native library; subclasses provide `_table`
-    [(name, kind, offset, shape)], `_canonical_order()`, the flat arrays, `_segments`, and `_destroy_ctxs()`."""
+    a view into ONE flat fp32 array (gradients likewise) laid out by the native library, native contexts per batch shape, and the
+    gradient-collective switches.  A subclass provides `_prefix` (its C-ABI symbols are mi355_<prefix>_*), `_create()` (its create
+    call with its own arguments), `_max_ctxs`, `_canonical_order()`, `_native_forward()` and `_native_backward()`."""
+
+    _prefix = None
+    _max_ctxs = None
+
+    def _create(self, out, device, N, H, W):
+        """mi355_<prefix>_create(out, device, dtype, N, H, W, num_classes, ...) -> status"""
+        raise NotImplementedError
+
+    def _fn(self, name):
+        return getattr(native.lib(), f"mi355_{self._prefix}_{name}")
+
+    @contextlib.contextmanager
+    def _layout_ctx(self, N=1, H=32, W=32):
+        """a layout-only context (device -1: no GPU needed) for tables, sizes, bucket plans and FLOP counts"""
+        ctx = ctypes.c_void_p()
+        check(self._create(ctypes.byref(ctx), -1, N, H, W))
+        try:
+            yield ctx
+        finally:
+            self._fn("destroy")(ctx)
+
+    def _layout(self):
+        """tensor table of the native executor: [(name, kind, offset, shape)], flat sizes, segment ranges"""
+        with self._layout_ctx() as ctx:
+            table = []
+            for i in range(self._fn("num_tensors")(ctx)):
+                name = ctypes.create_string_buffer(128)
+                kind, off, nd, sh = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_int * 4)()
+                check(self._fn("tensor_info")(ctx, i, name, 128, ctypes.byref(kind), ctypes.byref(off), ctypes.byref(nd), sh))
+                table.append((name.value.decode(), kind.value, off.value, tuple(sh[j] for j in range(nd.value))))
+            segs = []
+            for i in range(self._fn("num_segments")(ctx)):
+                b, e = ctypes.c_size_t(), ctypes.c_size_t()
+                check(self._fn("segment_range")(ctx, i, ctypes.byref(b), ctypes.byref(e)))
+                segs.append((b.value, e.value))
+            return table, self._fn("flat_param_elems")(ctx), self._fn("flat_buffer_elems")(ctx), segs
+
+    def _init_flat_state(self):
+        """the executor's layout, the flat arrays, the module tree over them, and the state kept around the native contexts"""
+        self._table, self._nparam, self._nbuf, self._segments = self._layout()
+        self._flat_params = torch.zeros(self._nparam, dtype=torch.float32)
+        self._flat_grads = torch.zeros(self._nparam, dtype=torch.float32)
+        self._flat_buffers = torch.zeros(self._nbuf, dtype=torch.float32)
+        self._hook = torch.zeros(1, requires_grad=True)  # gives autograd an edge into _ResNetFn
+        self._ctxs = OrderedDict()  # (N,H,W) -> native ctx
+        self._grads_dirty = False
+        self._grad_sync = None  # set by parallel.FlatBucketDDP: callable(segment, begin, end)
+        self._grad_sync_points = None  # optional set of segments the hook acts on (None: after every segment)
+        self._comm = None  # (mi355_comm*, bucket cap in MiB) once a native communicator is attached
+        self._sync_grads = True  # False inside FlatBucketDDP.no_sync(): backward keeps the gradients rank-local
+        self._bn_leaves = []
+        self._build_modules()
+        self._rebind_views()
 
     def _leaf(self, dotted, bn=False):
         node = self
@@ -203,8 +236,87 @@ class _FlatModel(nn.Module):
     def bn_momentum(self):
         return float(self._bn_leaves[0].momentum) if self._bn_leaves else 0.1
 
+    def set_comm(self, comm, bucket_cap_mb=32.0):
+        """attaches a native RCCL communicator (mi355_comm*, parallel.FlatBucketDDP owns it): every backward then reduces the flat
+        gradient array bucket by bucket inside the native backward call, behind the segments that complete each bucket
+        (mi355_<prefix>_set_comm)."""
+        self._comm = None if comm is None else (comm, float(bucket_cap_mb))
+        for c in self._ctxs.values():
+            check(self._fn("set_comm")(c, comm, float(bucket_cap_mb)))
+
+    def set_grad_sync(self, on):
+        """DDP.no_sync() for the native collective: off -> the following backwards skip the bucket all-reduces
+        (mi355_<prefix>_set_grad_sync); the torch.distributed stand-in path honours the same flag."""
+        self._sync_grads = bool(on)
+        for c in self._ctxs.values():
+            check(self._fn("set_grad_sync")(c, int(self._sync_grads)))
+
+    def bucket_plan(self, bucket_cap_mb):
+        """[(begin, end, last_segment)] the native executor would reduce at this cap (layout-only: works on the CPU)."""
+        with self._layout_ctx() as ctx:
+            n = ctypes.c_int()
+            B, E, S = (ctypes.c_size_t * 32)(), (ctypes.c_size_t * 32)(), (ctypes.c_int * 32)()
+            check(self._fn("bucket_plan")(ctx, float(bucket_cap_mb), 32, ctypes.byref(n), B, E, S))
+            return [(B[i], E[i], S[i]) for i in range(n.value)]
+
+    def flops(self, N, H, W):
+        """(forward, training) algorithmic FLOPs of one step at this shape (2 FLOP/MAC, conv + FC)."""
+        with self._layout_ctx(N, H, W) as ctx:
+            f, t = ctypes.c_double(), ctypes.c_double()
+            check(self._fn("flops")(ctx, ctypes.byref(f), ctypes.byref(t)))
+            return f.value, t.value
+
+    # ---- native contexts -------------------------------------------------------------------------------------
+    def _destroy_ctxs(self):
+        if self._ctxs:
+            for c in self._ctxs.values():
+                self._fn("destroy")(c)
+            self._ctxs.clear()
+
+    def _ctx(self, N, H, W):
+        key = (N, H, W)
+        c = self._ctxs.get(key)
+        if c is not None:
+            self._ctxs.move_to_end(key)
+            return c
+        if not self._flat_params.is_cuda:
+            raise RuntimeError(f"{self._prefix}: the MI355X hot path has no CPU fallback — call .cuda() first")
+        if len(self._ctxs) >= self._max_ctxs:
+            pending = getattr(self, "_last", None)
+            for k in list(self._ctxs):  # oldest first; the context a pending training forward's backward will use is never the one to go
+                if pending is None or self._ctxs[k] is not pending[0]:
+                    self._fn("destroy")(self._ctxs.pop(k))
+                    break
+        c = ctypes.c_void_p()
+        check(self._create(ctypes.byref(c), self._flat_params.device.index or 0, N, H, W))
+        check(self._fn("bind")(c, ptr(self._flat_params), ptr(self._flat_grads), ptr(self._flat_buffers)))
+        if self._comm is not None:
+            check(self._fn("set_comm")(c, self._comm[0], float(self._comm[1])))
+        if not self._sync_grads:
+            check(self._fn("set_grad_sync")(c, 0))
+        self._ctxs[key] = c
+        return c
+
+    def debug_tensor(self, shape, name):
+        """copy of an internal tensor of the last step at batch shape (N,H,W) — test hook (mi355_<prefix>_debug_tensor)."""
+        p, dt, nd, sh = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), (ctypes.c_int * 4)()
+        check(self._fn("debug_tensor")(self._ctx(*shape), name.encode(), ctypes.byref(p), ctypes.byref(dt), ctypes.byref(nd), sh))
+        dims = [sh[i] for i in range(nd.value)]
+        tdt = {native.F32: torch.float32, native.BF16: torch.bfloat16, native.FP8: torch.uint8}[dt.value]  # FP8: raw e4m3 bytes
+        out = torch.empty(dims, dtype=tdt, device=self._flat_params.device)
+        torch.cuda.synchronize()
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), p, out.numel() * out.element_size(), 3)
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy failed ({rc})")
+        return out
+
 
 class ResNet50(_FlatModel):
+    _prefix = "resnet50"
+    _max_ctxs = 3  # progressive resize / val batch: keep the 3 most recent shapes
+
     def __init__(self, num_classes=1000, dtype=None, pretrained=None, **unsupported):
         super().__init__()
         if pretrained:
@@ -217,22 +329,11 @@ class ResNet50(_FlatModel):
         self.compute_dtype = _DTYPES[dtype]
         self.fp8 = isinstance(dtype, str) and dtype in _FP8_NAMES
         self._dt = native.FP8 if self.fp8 else native.dtype_code(self.compute_dtype)
-        table, self._nparam, self._nbuf, self._segments = _layout(self._dt, 1, 32, 32, self.num_classes)
-        self._table = table
-        self._flat_params = torch.zeros(self._nparam, dtype=torch.float32)
-        self._flat_grads = torch.zeros(self._nparam, dtype=torch.float32)
-        self._flat_buffers = torch.zeros(self._nbuf, dtype=torch.float32)
-        self._hook = torch.zeros(1, requires_grad=True)  # gives autograd an edge into _ResNetFn
-        self._ctxs = OrderedDict()  # (N,H,W) -> native ctx
-        self._grads_dirty = False
-        self._grad_sync = None  # set by parallel.FlatBucketDDP: callable(segment, begin, end)
-        self._grad_sync_points = None  # optional set of segments the hook acts on (None: after every segment)
-        self._comm = None  # (mi355_comm*, bucket cap in MiB) once a native communicator is attached
-        self._sync_grads = True  # False inside FlatBucketDDP.no_sync(): backward keeps the gradients rank-local
-        self._bn_leaves = []
-        self._build_modules()
-        self._rebind_views()
+        self._init_flat_state()
         self.reset_parameters()
+
+    def _create(self, out, device, N, H, W):
+        return native.lib().mi355_resnet50_create(out, device, self._dt, N, H, W, self.num_classes)
 
     # ---- module tree with torchvision names --------------------------------------------------------------
     def _canonical_order(self):
@@ -269,66 +370,6 @@ class ResNet50(_FlatModel):
                 tgt = leaf._parameters[attr] if kind == 0 else leaf._buffers[attr]
                 tgt.copy_(sd[name].to(tgt.device))
 
-    def set_comm(self, comm, bucket_cap_mb=32.0):
-        """attaches a native RCCL communicator (mi355_comm*, parallel.FlatBucketDDP owns it): every backward then reduces
-        the flat gradient array bucket by bucket inside the ONE native backward call (mi355_resnet50_set_comm)."""
-        self._comm = None if comm is None else (comm, float(bucket_cap_mb))
-        L = native.lib()
-        for c in self._ctxs.values():
-            check(L.mi355_resnet50_set_comm(c, comm, float(bucket_cap_mb)))
-
-    def set_grad_sync(self, on):
-        """DDP.no_sync() for the native collective: off -> the following backwards skip the bucket all-reduces
-        (mi355_resnet50_set_grad_sync); the torch.distributed stand-in path honours the same flag."""
-        self._sync_grads = bool(on)
-        L = native.lib()
-        for c in self._ctxs.values():
-            check(L.mi355_resnet50_set_grad_sync(c, int(self._sync_grads)))
-
-    def bucket_plan(self, bucket_cap_mb):
-        """[(begin, end, last_segment)] the native executor would reduce at this cap (layout-only: works on the CPU)."""
-        L = native.lib()
-        ctx = ctypes.c_void_p()
-        check(L.mi355_resnet50_create(ctypes.byref(ctx), -1, self._dt, 1, 32, 32, self.num_classes))
-        try:
-            n = ctypes.c_int()
-            B, E, S = (ctypes.c_size_t * 32)(), (ctypes.c_size_t * 32)(), (ctypes.c_int * 32)()
-            check(L.mi355_resnet50_bucket_plan(ctx, float(bucket_cap_mb), 32, ctypes.byref(n), B, E, S))
-            return [(B[i], E[i], S[i]) for i in range(n.value)]
-        finally:
-            L.mi355_resnet50_destroy(ctx)
-
-    # ---- native contexts -------------------------------------------------------------------------------------
-    def _destroy_ctxs(self):
-        if self._ctxs:
-            L = native.lib()
-            for c in self._ctxs.values():
-                L.mi355_resnet50_destroy(c)
-            self._ctxs.clear()
-
-    def _ctx(self, N, H, W):
-        key = (N, H, W)
-        c = self._ctxs.get(key)
-        if c is None:
-            if not self._flat_params.is_cuda:
-                raise RuntimeError("resnet50: the MI355X hot path has no CPU fallback — call .cuda() first")
-            if len(self._ctxs) >= 3:  # progressive resize / val batch: keep the 3 most recent shapes
-                _, old = self._ctxs.popitem(last=False)
-                native.lib().mi355_resnet50_destroy(old)
-            L = native.lib()
-            c = ctypes.c_void_p()
-            dev = self._flat_params.device.index or 0
-            check(L.mi355_resnet50_create(ctypes.byref(c), dev, self._dt, N, H, W, self.num_classes))
-            check(L.mi355_resnet50_bind(c, ptr(self._flat_params), ptr(self._flat_grads), ptr(self._flat_buffers)))
-            if self._comm is not None:
-                check(L.mi355_resnet50_set_comm(c, self._comm[0], float(self._comm[1])))
-            if not self._sync_grads:
-                check(L.mi355_resnet50_set_grad_sync(c, 0))
-            self._ctxs[key] = c
-        else:
-            self._ctxs.move_to_end(key)
-        return c
-
     def _native_forward(self, x, training):
         if not x.is_cuda:
             raise RuntimeError("resnet50: the MI355X hot path has no CPU fallback — move the model and the batch to CUDA")
@@ -339,7 +380,10 @@ class ResNet50(_FlatModel):
         c = self._ctx(N, H, W)
         logits = torch.empty((N, self.num_classes), dtype=torch.float32, device=x.device)
         check(native.lib().mi355_resnet50_forward(c, ptr(x), ptr(logits), int(training), self.bn_momentum(), native.cur_stream()))
-        self._last = (c, x)  # keep the input alive until backward
+        if training:
+            self._last = (c, x)  # keep the input alive until backward
+        else:
+            self._eval_alive = x  # (an eval forward between a training forward and its backward leaves that pair alone)
         if training:
             self._nbt += 1
         return logits
@@ -371,16 +415,6 @@ class ResNet50(_FlatModel):
             return _ResNetFn.apply(x, self._hook, self)
         return self._native_forward(x, training=self.training)
 
-    def flops(self, N, H, W):
-        """(forward, training) algorithmic FLOPs of one step at this shape (2 FLOP/MAC, conv + FC)."""
-        L = native.lib()
-        ctx = ctypes.c_void_p()
-        check(L.mi355_resnet50_create(ctypes.byref(ctx), -1, self._dt, N, H, W, self.num_classes))
-        f, t = ctypes.c_double(), ctypes.c_double()
-        check(L.mi355_resnet50_flops(ctx, ctypes.byref(f), ctypes.byref(t)))
-        L.mi355_resnet50_destroy(ctx)
-        return f.value, t.value
-
     def kernel_table(self, shape):
         """{conv name: {"fwd": kernel, "dgrad": kernel, "wgrad": kernel}} of the last step at batch shape (N,H,W) — which kernel each
         convolution's launches went to (mi355_resnet50_kernel_table; '-' = not launched)."""
@@ -393,22 +427,6 @@ class ResNet50(_FlatModel):
         for ln in buf.value.decode().splitlines():
             name, *kv = ln.split()
             out[name] = dict(x.split("=", 1) for x in kv)
-        return out
-
-    def debug_tensor(self, shape, name):
-        """copy of an internal tensor of the last step at batch shape (N,H,W) — test hook (mi355_resnet50_debug_tensor)."""
-        L = native.lib()
-        p, dt, nd, sh = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), (ctypes.c_int * 4)()
-        check(L.mi355_resnet50_debug_tensor(self._ctx(*shape), name.encode(), ctypes.byref(p), ctypes.byref(dt), ctypes.byref(nd), sh))
-        dims = [sh[i] for i in range(nd.value)]
-        tdt = {native.F32: torch.float32, native.BF16: torch.bfloat16, native.FP8: torch.uint8}[dt.value]  # FP8: raw e4m3 bytes
-        out = torch.empty(dims, dtype=tdt, device=self._flat_params.device)
-        torch.cuda.synchronize()
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), p, out.numel() * out.element_size(), 3)
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpy failed ({rc})")
         return out
 
     def force_grad(self, shape, g):

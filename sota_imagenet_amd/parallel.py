@@ -32,7 +32,7 @@ def plan_buckets(segments, cap_elems):
     contiguous span of its segments (ascending for the ResNet-50 executor, whose flat array is laid out in backward order; descending for
     the BResNet-50 executor, laid out in forward order).  The last bucket (nothing left to overlap its all-reduce with) is cut once more:
     its trailing segments up to cap_elems // 8 form a bucket of their own, the part before them is reduced while those last blocks still
-    compute (same rule as csrc/resnet_exec.cpp plan_buckets and csrc/bresnet_exec.cpp plan_bbuckets)."""
+    compute (same rule as csrc/flat_model.cpp FlatModel::plan_buckets, which both executors share)."""
     def span(f, l):
         return (min(b for b, _ in segments[f:l + 1]), max(e for _, e in segments[f:l + 1]), l)
 

@@ -6,9 +6,11 @@ dependencies — hydra, loguru, pytorch_tools, nvidia.dali — are not installed
 SURVEY.md §8c), so these vectors pin the ORACLE (torch 2.10 CPU kernels), not the reference: "parity unpinned".
 Inputs are regenerated from seeds by sota_imagenet_amd.synth on both sides; only expected outputs are stored.
 
-    python tests/golden/make_golden.py           # rewrites ops_small.npz, resnet50_small.npz and curve20.npz
+    python tests/golden/make_golden.py           # rewrites ops_small.npz, resnet50_small.npz, curve20.npz and flat_layouts.json
     python tests/golden/make_golden.py curve20   # only the 20-step bs 32 / 224 px loss curve
+    python tests/golden/make_golden.py flat_layouts   # only flat_layouts.json, from the built library (layout-only contexts)
 """
+import json
 import os
 import sys
 
@@ -145,13 +147,92 @@ def make_curve20():
     print("curve20 fp32", np.round(l32, 4), "\n        fp64", np.round(l64, 4))
 
 
+# flat_layouts.json: what the two executors' layout-only contexts (device -1, no GPU) report through the C-ABI — tensor tables,
+# flat sizes, backward segments, bucket plans, FLOPs and workspace sizes.  Pins the offsets nothing else does.
+LAYOUT_CONFIGS = [("resnet50", "fp32", None), ("resnet50", "bf16", None), ("resnet50", "fp8", None),
+                  ("bresnet50", "fp32", 0), ("bresnet50", "fp32", 1), ("bresnet50", "bf16", 0), ("bresnet50", "bf16", 1)]
+LAYOUT_CAPS_MB = (0.5, 2, 8, 25, 32, 500)
+LAYOUT_SHAPES = ((256, 224, 224), (512, 160, 160))
+
+
+def flat_layouts():
+    """{"tables": {key: table}, "configs": {"model/dtype[/ws]": record}}; configs that share a tensor table point at one copy"""
+    import ctypes
+
+    from sota_imagenet_amd import native
+
+    L = native.lib()
+    codes = {"fp32": native.F32, "bf16": native.BF16, "fp8": native.FP8}
+
+    def create(model, dt, ws, N, H, W):
+        ctx = ctypes.c_void_p()
+        fn = getattr(L, f"mi355_{model}_create")
+        native.check(fn(ctypes.byref(ctx), -1, codes[dt], N, H, W, 1000, *([] if ws is None else [ws])))
+        return ctx
+
+    tables, configs = {}, {}
+    for model, dt, ws in LAYOUT_CONFIGS:
+        f = lambda name: getattr(L, f"mi355_{model}_{name}")  # noqa: E731
+        rec = {}
+        ctx = create(model, dt, ws, 1, 32, 32)
+        try:
+            table = []
+            for i in range(f("num_tensors")(ctx)):
+                name = ctypes.create_string_buffer(128)
+                kind, off, nd, sh = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_int(), (ctypes.c_int * 4)()
+                native.check(f("tensor_info")(ctx, i, name, 128, ctypes.byref(kind), ctypes.byref(off), ctypes.byref(nd), sh))
+                table.append([name.value.decode(), kind.value, off.value, nd.value, [sh[j] for j in range(nd.value)]])
+            key = next((k for k, t in tables.items() if t == table), f"{model}#{sum(k.startswith(model + '#') for k in tables)}")
+            tables[key] = table
+            rec["table"] = key
+            rec["flat_param_elems"] = f("flat_param_elems")(ctx)
+            rec["flat_buffer_elems"] = f("flat_buffer_elems")(ctx)
+            segs = []
+            for i in range(f("num_segments")(ctx)):
+                b, e = ctypes.c_size_t(), ctypes.c_size_t()
+                native.check(f("segment_range")(ctx, i, ctypes.byref(b), ctypes.byref(e)))
+                segs.append([b.value, e.value])
+            rec["segments"] = segs
+            rec["bucket_plan"] = {}
+            for cap in LAYOUT_CAPS_MB:
+                n = ctypes.c_int()
+                B, E, S = (ctypes.c_size_t * 64)(), (ctypes.c_size_t * 64)(), (ctypes.c_int * 64)()
+                native.check(f("bucket_plan")(ctx, float(cap), 64, ctypes.byref(n), B, E, S))
+                assert n.value <= 64
+                rec["bucket_plan"][str(cap)] = [[B[i], E[i], S[i]] for i in range(n.value)]
+        finally:
+            f("destroy")(ctx)
+        rec["flops"], rec["workspace_bytes"] = {}, {}
+        for N, H, W in LAYOUT_SHAPES:
+            ctx = create(model, dt, ws, N, H, W)
+            try:
+                fw, tr = ctypes.c_double(), ctypes.c_double()
+                native.check(f("flops")(ctx, ctypes.byref(fw), ctypes.byref(tr)))
+                rec["flops"][f"{N}x{H}x{W}"] = [fw.value, tr.value]
+                rec["workspace_bytes"][f"{N}x{H}x{W}"] = f("workspace_bytes")(ctx)
+            finally:
+                f("destroy")(ctx)
+        configs[f"{model}/{dt}" + ("" if ws is None else f"/ws{ws}")] = rec
+    return {"tables": tables, "configs": configs}
+
+
+def make_flat_layouts():
+    with open(os.path.join(HERE, "flat_layouts.json"), "w") as fh:
+        json.dump(flat_layouts(), fh, separators=(",", ":"))
+        fh.write("\n")
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     if sys.argv[1:] == ["curve20"]:
         make_curve20()
         sys.exit(0)
+    if sys.argv[1:] == ["flat_layouts"]:
+        make_flat_layouts()
+        sys.exit(0)
     make_ops()
     make_net()
     make_curve20()
-    for f in ("ops_small.npz", "resnet50_small.npz", "curve20.npz"):
+    make_flat_layouts()
+    for f in ("ops_small.npz", "resnet50_small.npz", "curve20.npz", "flat_layouts.json"):
         print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")

@@ -31,26 +31,32 @@ def test_library_is_built_for_gfx950():
     assert "gfx950" in out
 
 
-def test_layout_only_context_and_param_table():
+# (model, extra create arguments, forward / training GFLOP per image at 224 px, tensors in the table, a forward's arguments after ctx)
+LAYOUT_ONLY = [("resnet50", (), 8.178, 24.30, 161 + 106, (None, None, 1, 0.1, None)),  # 8.178 / 24.30 GFLOP per image
+               ("bresnet50", (1,), 10.739, 32.02, 183 + 110, (None, None, 1, 0.1, 0, None, None, None))]
+
+
+@pytest.mark.parametrize("model,extra,gf_fwd,gf_train,ntensors,fwd_args", LAYOUT_ONLY, ids=[m[0] for m in LAYOUT_ONLY])
+def test_layout_only_context_and_param_table(model, extra, gf_fwd, gf_train, ntensors, fwd_args):
     L = native.lib()
+    fn = lambda name: getattr(L, f"mi355_{model}_{name}")  # noqa: E731
     assert L.mi355_version() >= 100
     ctx = ctypes.c_void_p()
-    native.check(L.mi355_resnet50_create(ctypes.byref(ctx), -1, native.F32, 256, 224, 224, 1000))
+    native.check(fn("create")(ctypes.byref(ctx), -1, native.F32, 256, 224, 224, 1000, *extra))
     try:
         f, t = ctypes.c_double(), ctypes.c_double()
-        native.check(L.mi355_resnet50_flops(ctx, ctypes.byref(f), ctypes.byref(t)))
-        # 8.178 GFLOP fwd / 24.30 GFLOP train per image
-        assert abs(f.value / 256 / 1e9 - 8.178) < 2e-3 and abs(t.value / 256 / 1e9 - 24.30) < 5e-3
-        assert L.mi355_resnet50_num_segments(ctx) == 18
-        assert L.mi355_resnet50_num_tensors(ctx) == 161 + 106
-        # layout-only contexts refuse to compute
-        rc = L.mi355_resnet50_forward(ctx, None, None, 1, 0.1, None)
+        native.check(fn("flops")(ctx, ctypes.byref(f), ctypes.byref(t)))
+        assert abs(f.value / 256 / 1e9 - gf_fwd) < 2e-3 and abs(t.value / 256 / 1e9 - gf_train) < 5e-3
+        assert fn("num_segments")(ctx) == 18
+        assert fn("num_tensors")(ctx) == ntensors
+        # layout-only contexts refuse to compute, and to be bound (MI355_E_STATE)
+        rc = fn("forward")(ctx, *fwd_args)
         assert rc != 0 and native.last_error()
         buf = (ctypes.c_float * 64)()
-        rc = L.mi355_resnet50_bind(ctx, ctypes.cast(buf, ctypes.c_void_p), ctypes.cast(buf, ctypes.c_void_p), ctypes.cast(buf, ctypes.c_void_p))
-        assert rc != 0
+        rc = fn("bind")(ctx, ctypes.cast(buf, ctypes.c_void_p), ctypes.cast(buf, ctypes.c_void_p), ctypes.cast(buf, ctypes.c_void_p))
+        assert rc == -3 and "layout-only" in native.last_error()
     finally:
-        L.mi355_resnet50_destroy(ctx)
+        fn("destroy")(ctx)
 
 
 def test_bad_arguments_return_status_not_crash():

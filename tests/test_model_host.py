@@ -101,3 +101,24 @@ def test_bresnet50_executor_facade_layout_matches_the_per_op_graph():
         m(torch.zeros(2, 3, 64, 64))
     with pytest.raises(ValueError):
         BResNet50(dtype="fp8")
+
+
+def test_flat_layouts_match_the_pinned_fixture():
+    """both executors' layout-only contexts (no GPU) report exactly what tests/golden/flat_layouts.json recorded: tensor tables
+    (name, kind, offset, shape), flat sizes, backward segments, bucket plans, FLOPs and workspace sizes (make_golden.py flat_layouts)"""
+    import importlib.util
+    import json
+    import os
+
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(here, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    with open(os.path.join(here, "flat_layouts.json")) as fh:
+        want = json.load(fh)
+    got = mg.flat_layouts()
+    assert sorted(got["configs"]) == sorted(want["configs"])
+    for key, rec in want["configs"].items():
+        g = got["configs"][key]
+        assert got["tables"][g["table"]] == want["tables"][rec["table"]], key
+        assert {k: v for k, v in g.items() if k != "table"} == {k: v for k, v in rec.items() if k != "table"}, key
