@@ -29,10 +29,15 @@ Structure (one workgroup = 4 waves = one wave per SIMD, one tile per workgroup):
               BN-backward sums of the layer whose activation gradient the output is, reduced by DPP row sums, one partial
               row per workgroup.
 """
-import argparse
+import functools
 import os
+import re
 import sys
 from dataclasses import dataclass
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import asm_common  # noqa: E402
+from asm_common import LEAKY_BITS, Emitter, R, merge, resolve_waits  # noqa: E402
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -141,11 +146,11 @@ class Cfg:
     def tile_rows(self):
         return self.ROWS_T if self.ROWS_T else self.IPT * self.H
 
+    @property
+    def LDS(self):    # [A buffer 0][A buffer 1][weight ring NB stages]; the statistics scratch reuses the ring
+        return self.NA * self.ABUF + self.NB * self.BSTAGE
 
-# LDS: [A buffer 0][A buffer 1][weight ring NB stages]; the statistics scratch reuses the ring
 
-
-LEAKY_BITS = 0x3c23d70a   # 0.01f: the slope of the stats == 3 epilogues
 NCLS = 3  # tile classes of a row tile: 0 first of its image (the row above is zero halo), 1 middle, 2 last (the row below is)
 
 
@@ -270,44 +275,7 @@ def ttables(c):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-class Alloc:
-    def __init__(self, prefix, first, limit):
-        self.p, self.n, self.limit = prefix, first, limit
-
-    def get(self, n=1, align=1):
-        self.n = (self.n + align - 1) // align * align
-        r = self.n
-        self.n += n
-        assert self.n <= self.limit, "out of %s registers" % self.p
-        return r
-
-
-def R(p, i, n=1):
-    return "%s%d" % (p, i) if n == 1 else "%s[%d:%d]" % (p, i, i + n - 1)
-
-
-class Gen:
-    def __init__(self, c: Cfg):
-        self.c = c
-        self.out = []
-        self.nlabel = 0
-        self.S = Alloc("s", 4, 100)
-        self.V = Alloc("v", 1, 256)
-
-    def e(self, s, comment=None):
-        self.out.append("\t" + s + ("\t; " + comment if comment else ""))
-
-    def label(self, name):
-        self.out.append(name + ":")
-
-    def newlabel(self, stem):
-        self.nlabel += 1
-        return "L_%s_%d" % (stem, self.nlabel)
-
-    def comment(self, s):
-        self.out.append("\t; " + s)
-
-    # -----------------------------------------------------------------------------------------------------------------
+class Gen(Emitter):
     def gen(self):
         c = self.c
         S, V, e = self.S, self.V, self.e
@@ -381,6 +349,7 @@ class Gen:
         # prologue temporaries live in fragment set 1, which is first written by the main loop (v_t[2] = the kept lane >> 4)
         self.v_t = [self.F[1][0] + i for i in range(10)]
         self.v_t[2] = self.v_kg
+        self.late_pair1 = False
         if c.stats >= 2:
             # BN-backward sums: y / mask of the same (pixel, 8 channels) vectors as the output in two register sets, mean / invstd of
             # this lane's 8 channels per tile pair.  The sets of pairs 0 and 1 are loaded in the PROLOGUE (the main loop does not
@@ -422,13 +391,21 @@ class Gen:
         self.prologue()
         self.mainloop()
         self.epilogue()
-        return self.finish()
+        return self.code_object()
 
     # -----------------------------------------------------------------------------------------------------------------
     # kernel arguments: 9 pointers (the 9th unused: reserved), 9 weight-tap byte offsets, the chunk count, padding to 128 bytes,
     # then the per-wave piece tables (3 tile classes x 4 waves x 64 words)
     KA = dict(in_=0, wt=8, out=16, stat=24, bn_y=32, bn_bits=40, bn_mean=48, bn_invstd=56, rsvd=64, wtap=72, nchunks=108,
               table=128, size=128 + NCLS * 4 * 256)
+
+    @property
+    def ka_size(self):   # (bnin: + the transform tables)
+        return self.KA["size"] + (NCLS * 4 * 256 if self.c.bnin else 0)
+
+    def code_object(self):
+        """the kernel arguments as 9 pointers, 10 words and the rest of the segment in one block (pk_gen.py too)"""
+        return self.finish(self.c.LDS, self.ka_size, 9, [4] * 10 + [self.ka_size - 112], wg_id_y=1)
 
     def never_written_blocks(self):
         """1 KiB blocks (relative to an A buffer's base) that no LDS-DMA piece ever writes: halo rows, right padding, the tail"""
@@ -456,12 +433,7 @@ class Gen:
             e("s_load_dwordx2 %s, s[0:1], 0x40" % R("s", self.s_sci, 2), "scale_in (device scalar) or null")
             e("s_load_dwordx4 %s, s[0:1], 0x70" % R("s", self.s_x4, 4), "-, oscale, scale_wt")
         lane, r, kg = v[0], v[1], v[2]
-        e("v_lshrrev_b32 %s, 6, v0" % R("v", v[3]))
-        e("v_and_b32 %s, 63, v0" % R("v", lane))
-        e("v_readfirstlane_b32 %s, %s" % (R("s", self.s_w), R("v", v[3])))
-        e("v_and_b32 %s, 15, v0" % R("v", r))
-        e("v_bfe_u32 %s, v0, 4, 2" % R("v", kg))
-        e("s_nop 3")
+        self.lane_constants()
         if c.s2d:
             # workgroup id y = class * column tiles + column tile; the class's first output pixel (ph, pw) as a byte offset into the tile's window
             nct = c.NCOLS // c.BN
@@ -533,20 +505,7 @@ class Gen:
             e("v_cmp_gt_u32 vcc, %d, %s" % (c.W, R("v", x)), "0 <= x < W (x = -1 wraps to 2^32 - 1)")
             e("v_mov_b32 %s, 0x80000000" % R("v", x))
             e("v_cndmask_b32 %s, %s, %s, vcc" % (R("v", self.vA_dma[xb]), R("v", x), R("v", off)))
-        # B (variant ib = piece & 1): rr = 8*ib + (lane>>3); channel = (2*ib + (lane>>5))*8 + ((lane>>3)&3);
-        #   chunk = (lane&7) ^ (4*ib + ((lane>>4)&3))
-        l5, l43, ch, x = v[5], v[8], v[7], v[9]
-        e("v_lshrrev_b32 %s, 5, %s" % (R("v", l5), R("v", lane)))
-        e("v_bfe_u32 %s, %s, 4, 2" % (R("v", l43), R("v", lane)))
-        for ib in range(2):
-            e("v_lshl_add_u32 %s, %s, 3, %d" % (R("v", ch), R("v", l5), 16 * ib))
-            e("v_and_b32 %s, 3, %s" % (R("v", x), R("v", l3)))
-            e("v_add_u32 %s, %s, %s" % (R("v", ch), R("v", ch), R("v", x)))
-            e("v_mov_b32 %s, %d" % (R("v", x), c.w_row))
-            e("v_mul_lo_u32 %s, %s, %s" % (R("v", ch), R("v", ch), R("v", x)))
-            e("v_or_b32 %s, %d, %s" % (R("v", x), 4 * ib, R("v", l43)))
-            e("v_xor_b32 %s, %s, %s" % (R("v", x), R("v", l7), R("v", x)))
-            e("v_lshl_add_u32 %s, %s, 4, %s" % (R("v", self.vB_dma[ib]), R("v", x), R("v", ch)))
+        self.b_dma_lanes()
 
         # ---- descriptors ------------------------------------------------------------------------------------------
         e("s_waitcnt lgkmcnt(0)")
@@ -613,13 +572,7 @@ class Gen:
             e("s_mov_b32 %s, 0x00020000" % R("s", self.srdSS + 3))
             e("s_mov_b32 %s, 0" % R("s", self.s_last))
             e("s_mov_b32 %s, 0x00010001" % R("s", self.s_k1))
-        # B: rows nt*BN .. + BN
-        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * c.w_row))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdB), R("s", ka + 2), R("s", t0)))
-        e("s_addc_u32 %s, %s, 0" % (R("s", self.srdB + 1), R("s", ka + 3)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdB + 1), R("s", self.srdB + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdB + 2), c.BN * c.w_row))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdB + 3))
+        self.b_descriptor()
         e("s_mov_b32 %s, %s" % (R("s", self.s_nch), R("s", kb + 3)))
         e("s_mov_b32 %s, %s" % (R("s", self.s_wt + 8), R("s", kb + 2)))
         # the table (24 words) to its place: [NPA lds][NPA src][8 B consts]
@@ -645,49 +598,6 @@ class Gen:
                 self.first_stage_issue(st)
 
 
-        def descriptors_out():
-            # ---- the rest of the set-up runs under the latency of those loads
-            # O: + tile*tile_out + nt*512 bytes
-            e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_tile), tile_out))
-            e("s_mul_hi_u32 %s, %s, %d" % (R("s", t1), R("s", self.s_tile), tile_out))
-            e("s_mul_i32 %s, %s, %d" % (R("s", self.s_stg), R("s", self.s_nt), c.BN * 2))
-            e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
-            e("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
-            e("s_add_u32 %s, %s, %s" % (R("s", self.srdO), R("s", ka + 4), R("s", t0)))
-            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdO + 1), R("s", ka + 5), R("s", t1)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdO + 1), R("s", self.srdO + 1)))
-            e("s_mov_b32 %s, %d" % (R("s", self.srdO + 2), tile_out))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdO + 3))
-            # (the O window starts at this tile's column offset: num_records covers exactly what may be stored)
-            e("s_sub_u32 %s, %s, %s" % (R("s", self.srdO + 2), R("s", self.srdO + 2), R("s", self.s_stg)))
-            e("s_mov_b32 %s, %s" % (R("s", self.srdX), R("s", ka + 6)), "statistics rows")
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdX + 1), R("s", ka + 7)))
-            e("s_mov_b32 %s, 0x7fffffff" % R("s", self.srdX + 2))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdX + 3))
-            if c.stats >= 2:
-                # y: laid out like the output (same window); mask bytes: 1/16 of it; mean / invstd: this column tile's 256 floats
-                e("s_add_u32 %s, %s, %s" % (R("s", self.srdY), R("s", ka + 8), R("s", t0)))
-                e("s_addc_u32 %s, %s, %s" % (R("s", self.srdY + 1), R("s", ka + 9), R("s", t1)))
-                e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdY + 1), R("s", self.srdY + 1)))
-                e("s_mov_b32 %s, %s" % (R("s", self.srdY + 2), R("s", self.srdO + 2)))
-                e("s_mov_b32 %s, 0x00020000" % R("s", self.srdY + 3))
-                e("s_lshr_b32 %s, %s, 4" % (R("s", t0), R("s", t0)))
-                e("s_lshl_b32 %s, %s, 28" % (R("s", self.s_stg), R("s", t1)))
-                e("s_or_b32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
-                e("s_lshr_b32 %s, %s, 4" % (R("s", t1), R("s", t1)))
-                e("s_add_u32 %s, %s, %s" % (R("s", self.srdM), R("s", ka + 10), R("s", t0)))
-                e("s_addc_u32 %s, %s, %s" % (R("s", self.srdM + 1), R("s", ka + 11), R("s", t1)))
-                e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdM + 1), R("s", self.srdM + 1)))
-                e("s_lshr_b32 %s, %s, 4" % (R("s", self.srdM + 2), R("s", self.srdO + 2)))
-                e("s_mov_b32 %s, 0x00020000" % R("s", self.srdM + 3))
-                e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * 4))
-                for srd, k0 in ((self.srdMu, 12), (self.srdIs, 14)):
-                    e("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", ka + k0), R("s", t0)))
-                    e("s_addc_u32 %s, %s, 0" % (R("s", srd + 1), R("s", ka + k0 + 1)))
-                    e("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
-                    e("s_mov_b32 %s, %d" % (R("s", srd + 2), c.BN * 4))
-                    e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
-
         def lane_out():
             # ---- output lane offset: pixel part * NCOLS*2 + (wn*NT*16 + kg*8)*2
             x, off = v[6], v[7]
@@ -708,20 +618,13 @@ class Gen:
 
 
         if c.stats >= 2:
-            # the BN-backward inputs of tile pairs 0 and 1 are requested FIRST (oldest vector-memory operations: every counted wait
-            # of the main loop is unaffected), so the epilogue finds them in registers
-            descriptors_out()
+            self.out_descriptors(tile_out)
             lane_out()
-            self.tile_mask_loads()
-            e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_wn), c.NT * 16 * 4))
-            e("v_lshl_add_u32 %s, %s, 5, %s" % (R("v", self.v_chan), R("v", self.v_kg), R("s", t0)), "this lane's 8 floats of mean / invstd")
-            self.epi_issue_loads(0)
-            if not getattr(self, "late_pair1", False):
-                self.epi_issue_loads(1)
+            self.bn_backward_first_loads()
             first_loads()
         else:
             first_loads()
-            descriptors_out()
+            self.out_descriptors(tile_out)
             lane_out()
         # ---- A read bases: pos0 = wm*MFR*16 + r + kx ; chunk = (kg + 4kk + (pos0 & 6)) & 7
         e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_wm), c.MFR * 16 * 128))
@@ -736,19 +639,7 @@ class Gen:
             e("v_add_u32 %s, %s, %s" % (R("v", cc), R("s", t0), R("v", cc)))
             e("v_add_u32 %s, %d, %s" % (R("v", self.vA_rd[kx][0]), c.ABASE, R("v", cc)))
             e("v_xor_b32 %s, 64, %s" % (R("v", self.vA_rd[kx][1]), R("v", self.vA_rd[kx][0])))
-        # ---- B read bases: row = wn*NT*16 + r ; chunk = (kg + 4kk) ^ ((r >> 1) & 7)
-        sw, cc = v[3], v[4]
-        e("v_bfe_u32 %s, %s, 1, 3" % (R("v", sw), R("v", r)))
-        e("v_xor_b32 %s, %s, %s" % (R("v", cc), R("v", kg), R("v", sw)))
-        e("v_lshlrev_b32 %s, 4, %s" % (R("v", cc), R("v", cc)))
-        e("v_lshl_add_u32 %s, %s, 7, %s" % (R("v", cc), R("v", r), R("v", cc)))
-        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_wn), c.NT * 16 * 128))
-        e("s_add_u32 %s, %s, %d" % (R("s", t0), R("s", t0), c.BBASE))
-        e("v_add_u32 %s, %s, %s" % (R("v", self.vB_rd[0][0]), R("s", t0), R("v", cc)))
-        e("v_xor_b32 %s, 64, %s" % (R("v", self.vB_rd[0][1]), R("v", self.vB_rd[0][0])))
-        for st in range(1, c.NB):
-            for kk in range(2):
-                e("v_add_u32 %s, %d, %s" % (R("v", self.vB_rd[st][kk]), st * c.BSTAGE, R("v", self.vB_rd[0][kk])))
+        self.b_read_bases(self.row_chunk())
         # ---- zero the LDS blocks of both A buffers that no DMA piece writes (halo rows, padding): wave w takes blocks w, w+4, ...
         self.comment("zero the never-written blocks of both A buffers")
         self.zero_blocks([c.ABASE + b * c.ASTRIDE + o for b in range(c.NA) for o in self.never_written_blocks()])
@@ -785,6 +676,124 @@ class Gen:
             for ins in self.frag_reads(0, rt0.pop(), 0, 0):
                 e(ins)
         e("s_mov_b32 %s, %s" % (R("s", self.s_cnt), R("s", self.s_nch)))
+
+    # ---- set-up blocks the prologue of pk_gen.py shares --------------------------------------------------------------
+    def lane_constants(self):
+        """v_t[0] = lane, v_t[1] = r = lane & 15 (row of a fragment), v_t[2] = kg = (lane >> 4) & 3, s_w = wave"""
+        e, v = self.e, self.v_t
+        e("v_lshrrev_b32 %s, 6, v0" % R("v", v[3]))
+        e("v_and_b32 %s, 63, v0" % R("v", v[0]))
+        e("v_readfirstlane_b32 %s, %s" % (R("s", self.s_w), R("v", v[3])))
+        e("v_and_b32 %s, 15, v0" % R("v", v[1]))
+        e("v_bfe_u32 %s, v0, 4, 2" % R("v", v[2]))
+        e("s_nop 3")
+
+    def b_dma_lanes(self):
+        """lane parts of the weight pieces (variant ib = piece & 1): rr = 8*ib + (lane>>3); channel = (2*ib + (lane>>5))*8 + ((lane>>3)&3);
+        chunk = (lane&7) ^ (4*ib + ((lane>>4)&3)).  v_t[3] / v_t[4] hold lane >> 3 / lane & 7"""
+        c, e, v = self.c, self.e, self.v_t
+        lane, l3, l7 = v[0], v[3], v[4]
+        l5, l43, ch, x = v[5], v[8], v[7], v[9]
+        e("v_lshrrev_b32 %s, 5, %s" % (R("v", l5), R("v", lane)))
+        e("v_bfe_u32 %s, %s, 4, 2" % (R("v", l43), R("v", lane)))
+        for ib in range(2):
+            e("v_lshl_add_u32 %s, %s, 3, %d" % (R("v", ch), R("v", l5), 16 * ib))
+            e("v_and_b32 %s, 3, %s" % (R("v", x), R("v", l3)))
+            e("v_add_u32 %s, %s, %s" % (R("v", ch), R("v", ch), R("v", x)))
+            e("v_mov_b32 %s, %d" % (R("v", x), c.w_row))
+            e("v_mul_lo_u32 %s, %s, %s" % (R("v", ch), R("v", ch), R("v", x)))
+            e("v_or_b32 %s, %d, %s" % (R("v", x), 4 * ib, R("v", l43)))
+            e("v_xor_b32 %s, %s, %s" % (R("v", x), R("v", l7), R("v", x)))
+            e("v_lshl_add_u32 %s, %s, 4, %s" % (R("v", self.vB_dma[ib]), R("v", x), R("v", ch)))
+
+    def b_descriptor(self):
+        """srdB = weight rows nt*BN .. + BN"""
+        c, e, ka, t0 = self.c, self.e, self.s_ka, self.s_t0
+        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * c.w_row))
+        e("s_add_u32 %s, %s, %s" % (R("s", self.srdB), R("s", ka + 2), R("s", t0)))
+        e("s_addc_u32 %s, %s, 0" % (R("s", self.srdB + 1), R("s", ka + 3)))
+        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdB + 1), R("s", self.srdB + 1)))
+        e("s_mov_b32 %s, %d" % (R("s", self.srdB + 2), c.BN * c.w_row))
+        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdB + 3))
+
+    def out_descriptors(self, tile_out):
+        """the output window of this tile and column tile (tile_out bytes per tile), the statistics rows; stats >= 2: the y and ReLU-mask
+        windows of the same pixels and this column tile's mean / invstd.  Runs under the latency of the first loads."""
+        c, e, ka, t0, t1 = self.c, self.e, self.s_ka, self.s_t0, self.s_t1
+        # O: + tile*tile_out + nt*512 bytes
+        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_tile), tile_out))
+        e("s_mul_hi_u32 %s, %s, %d" % (R("s", t1), R("s", self.s_tile), tile_out))
+        e("s_mul_i32 %s, %s, %d" % (R("s", self.s_stg), R("s", self.s_nt), c.BN * 2))
+        e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
+        e("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
+        e("s_add_u32 %s, %s, %s" % (R("s", self.srdO), R("s", ka + 4), R("s", t0)))
+        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdO + 1), R("s", ka + 5), R("s", t1)))
+        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdO + 1), R("s", self.srdO + 1)))
+        e("s_mov_b32 %s, %d" % (R("s", self.srdO + 2), tile_out))
+        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdO + 3))
+        # (the O window starts at this tile's column offset: num_records covers exactly what may be stored)
+        e("s_sub_u32 %s, %s, %s" % (R("s", self.srdO + 2), R("s", self.srdO + 2), R("s", self.s_stg)))
+        e("s_mov_b32 %s, %s" % (R("s", self.srdX), R("s", ka + 6)), "statistics rows")
+        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdX + 1), R("s", ka + 7)))
+        e("s_mov_b32 %s, 0x7fffffff" % R("s", self.srdX + 2))
+        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdX + 3))
+        if c.stats >= 2:
+            # y: laid out like the output (same window); mask bytes: 1/16 of it; mean / invstd: this column tile's 256 floats
+            e("s_add_u32 %s, %s, %s" % (R("s", self.srdY), R("s", ka + 8), R("s", t0)))
+            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdY + 1), R("s", ka + 9), R("s", t1)))
+            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdY + 1), R("s", self.srdY + 1)))
+            e("s_mov_b32 %s, %s" % (R("s", self.srdY + 2), R("s", self.srdO + 2)))
+            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdY + 3))
+            e("s_lshr_b32 %s, %s, 4" % (R("s", t0), R("s", t0)))
+            e("s_lshl_b32 %s, %s, 28" % (R("s", self.s_stg), R("s", t1)))
+            e("s_or_b32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
+            e("s_lshr_b32 %s, %s, 4" % (R("s", t1), R("s", t1)))
+            e("s_add_u32 %s, %s, %s" % (R("s", self.srdM), R("s", ka + 10), R("s", t0)))
+            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdM + 1), R("s", ka + 11), R("s", t1)))
+            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdM + 1), R("s", self.srdM + 1)))
+            e("s_lshr_b32 %s, %s, 4" % (R("s", self.srdM + 2), R("s", self.srdO + 2)))
+            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdM + 3))
+            e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * 4))
+            for srd, k0 in ((self.srdMu, 12), (self.srdIs, 14)):
+                e("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", ka + k0), R("s", t0)))
+                e("s_addc_u32 %s, %s, 0" % (R("s", srd + 1), R("s", ka + k0 + 1)))
+                e("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
+                e("s_mov_b32 %s, %d" % (R("s", srd + 2), c.BN * 4))
+                e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
+
+    def bn_backward_first_loads(self):
+        """stats >= 2: the BN-backward inputs of tile pairs 0 and 1, requested before the first loads of the main loop (the oldest vector-memory
+        operations: every counted wait of the main loop is unaffected), so the epilogue finds them in registers (late_pair1: pair 1's set is
+        loaded at the start of the epilogue)"""
+        c, e, t0 = self.c, self.e, self.s_t0
+        self.tile_mask_loads()
+        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_wn), c.NT * 16 * 4))
+        e("v_lshl_add_u32 %s, %s, 5, %s" % (R("v", self.v_chan), R("v", self.v_kg), R("s", t0)), "this lane's 8 floats of mean / invstd")
+        self.epi_issue_loads(0)
+        if c.NT >= 4 and not self.late_pair1:
+            self.epi_issue_loads(1)
+
+    def row_chunk(self):
+        """v_t[4] = r*128 + ((kg ^ ((r >> 1) & 7)) * 16): this lane's row and swizzled 16-byte chunk in a fragment read"""
+        e, v = self.e, self.v_t
+        r, kg = v[1], v[2]
+        sw, cc = v[3], v[4]
+        e("v_bfe_u32 %s, %s, 1, 3" % (R("v", sw), R("v", r)))
+        e("v_xor_b32 %s, %s, %s" % (R("v", cc), R("v", kg), R("v", sw)))
+        e("v_lshlrev_b32 %s, 4, %s" % (R("v", cc), R("v", cc)))
+        e("v_lshl_add_u32 %s, %s, 7, %s" % (R("v", cc), R("v", r), R("v", cc)))
+        return cc
+
+    def b_read_bases(self, cc):
+        """weight fragment read bases of every ring stage: row wn*NT*16 + r, chunk (kg + 4kk) ^ ((r >> 1) & 7) (cc: row_chunk())"""
+        c, e, t0 = self.c, self.e, self.s_t0
+        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_wn), c.NT * 16 * 128))
+        e("s_add_u32 %s, %s, %d" % (R("s", t0), R("s", t0), c.BBASE))
+        e("v_add_u32 %s, %s, %s" % (R("v", self.vB_rd[0][0]), R("s", t0), R("v", cc)))
+        e("v_xor_b32 %s, 64, %s" % (R("v", self.vB_rd[0][1]), R("v", self.vB_rd[0][0])))
+        for st in range(1, c.NB):
+            for kk in range(2):
+                e("v_add_u32 %s, %d, %s" % (R("v", self.vB_rd[st][kk]), st * c.BSTAGE, R("v", self.vB_rd[0][kk])))
 
     def zero_blocks(self, blocks):
         """ds_write zeros over the listed 1 KiB LDS blocks: the four waves take blocks[4k + w]"""
@@ -840,34 +849,20 @@ class Gen:
                 "buffer_load_dwordx4 %s, %s, %s offen lds" % (R("v", self.vB_dma[i & 1]), R("s", self.srdB, 4), R("s", self.s_t0)) + tag]
 
     def patch_waits(self, start):
-        """the stage-barrier waits of the main-loop trip emitted since self.out[start]: a wait line carries `@need:<tags>@`; its count = vector-memory
-        operations issued after the youngest operation it names (the most recent one of each tag, looking back cyclically through the trip: steady
-        state; the first trip only has MORE younger operations in flight, from the prologue, which makes a counted wait stronger, never weaker)"""
-        import re
-        ops = []      # (line index, tag) of the tagged operations, in issue order; every other buffer_ instruction of the trip must be tagged
-        waits = []    # (line index, number of operations issued before it, needed tags)
+        """the stage-barrier waits of the main-loop trip emitted since self.out[start]: a wait line carries `@need:<tags>@`, a vector-memory
+        operation its tag; the counts are resolve_waits' (every buffer_ instruction of the trip must be tagged)"""
+        events = []
         for i in range(start, len(self.out)):
             line = self.out[i]
             m = re.search(r";vm:(\S+)", line)
             if m:
-                ops.append((i, m.group(1)))
+                events.append(("op", m.group(1), False))
             elif re.match(r"\tbuffer_", line):
                 raise AssertionError("untagged vector-memory operation in the main loop: " + line)
             w = re.search(r"@need:([^@]*)@", line)
             if w:
-                waits.append((i, len(ops), w.group(1).split(",")))
-        n = len(ops)
-        for i, before, need in waits:
-            best = None
-            for tag in need:
-                # distance back to the most recent operation with this tag (cyclic)
-                for d in range(1, n + 1):
-                    if ops[(before - d) % n][1] == tag:
-                        best = d if best is None else min(best, d)
-                        break
-                else:
-                    raise AssertionError("no operation tagged %s in the trip" % tag)
-            cnt = best - 1
+                events.append(("wait", i, w.group(1).split(",")))
+        for i, cnt in resolve_waits(events).items():
             assert 0 <= cnt <= 63
             self.out[i] = re.sub(r"vmcnt\(@need:[^@]*@\)", "vmcnt(%d)" % cnt, self.out[i])
         for i in range(start, len(self.out)):
@@ -1200,7 +1195,7 @@ class Gen:
                         groups += a_next[n * per:(n + 1) * per]
                     if n < pre:
                         per = -(-len(vm) // pre)
-                        groups = self.merge(groups, vm[n * per:(n + 1) * per])
+                        groups = merge(groups, vm[n * per:(n + 1) * per])
                     if c.probe & 2:
                         groups = [g for g in groups if not g[0].startswith("ds_read")]
                     self.interleave(self.mfma8_col(n, aset), groups, first=0)
@@ -1273,7 +1268,7 @@ class Gen:
                     pieces = []
                 if c.probe & 2:
                     groups = []
-                groups = self.merge(groups, pieces)
+                groups = merge(groups, pieces)
                 if bn:
                     groups = self.tr_groups(groups, read_at.get((t, 0), []), work_at.get((t, 0), []), cp ^ 1)
                 self.interleave(mf, groups)
@@ -1309,7 +1304,7 @@ class Gen:
                     pieces = []
                 if c.probe & 2:
                     groups = []
-                groups = self.merge(groups, pieces)
+                groups = merge(groups, pieces)
                 if bn:
                     groups = self.tr_groups(groups, read_at.get((t, 1), []), work_at.get((t, 1), []), cp ^ 1)
                 self.interleave(mf, groups)
@@ -1331,23 +1326,7 @@ class Gen:
         the work on the blocks read in the previous substep spread through the rest, one block after the other (they share scalar temporaries)"""
         rd = [self.tr_read(k, buf, k % len(self.tr)) for k in reads]
         wk = [g for k in works for g in self.tr_work(k, self.s_cN, k % len(self.tr))]
-        return rd + self.merge(groups, wk) if (rd or wk) else groups
-
-    @staticmethod
-    def merge(a, b):
-        """merge two group lists evenly (b spread through a)"""
-        if not b:
-            return a
-        out = []
-        na, nb = len(a), len(b)
-        ib = 0
-        for i, g in enumerate(a):
-            out.append(g)
-            while ib < nb and (ib + 1) * na <= (i + 1) * nb:
-                out.append(b[ib])
-                ib += 1
-        out.extend(b[ib:])
-        return out
+        return rd + merge(groups, wk) if (rd or wk) else groups
 
     # -----------------------------------------------------------------------------------------------------------------
     def frag_out(self, f):
@@ -1528,7 +1507,7 @@ class Gen:
         e("s_barrier", "every LDS-DMA of the (unused) lookahead has landed: the ring is free for the statistics scratch")
         e("s_nop 15")
         e("s_nop 15")
-        late1 = c.stats >= 2 and getattr(self, "late_pair1", False)  # (pk_gen.py: the second register set lives in the fragment registers)
+        late1 = c.stats >= 2 and self.late_pair1  # (pk_gen.py: the second register set lives in the fragment registers)
         if late1:
             issue_loads(1)
         if c.stats:
@@ -1654,77 +1633,6 @@ class Gen:
         e("s_mov_b32 exec_lo, 0x%x" % lo)
         e("s_mov_b32 exec_hi, 0x%x" % hi)
 
-    # -----------------------------------------------------------------------------------------------------------------
-    def finish(self):
-        c = self.c
-        name = c.name
-        lds = c.NA * c.ABUF + c.NB * c.BSTAGE  # the A buffer(s), the weight ring
-        assert lds <= 160 * 1024
-        total_v = self.accum_offset + self.nagpr
-        self.ka_size = self.KA["size"] + (NCLS * 4 * 256 if getattr(c, "bnin", 0) else 0)   # (bnin: + the transform tables)
-        hdr = []
-        hdr.append('\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
-        hdr.append("\t.amdhsa_code_object_version 6")
-        hdr.append("\t.text")
-        hdr.append("\t.protected\t%s" % name)
-        hdr.append("\t.globl\t%s" % name)
-        hdr.append("\t.p2align\t8")
-        hdr.append("\t.type\t%s,@function" % name)
-        hdr.append("%s:" % name)
-        tail = []
-        tail.append("\t.section\t.rodata,\"a\",@progbits")
-        tail.append("\t.p2align\t6, 0x0")
-        tail.append("\t.amdhsa_kernel %s" % name)
-        kd = dict(group_segment_fixed_size=lds, private_segment_fixed_size=0, kernarg_size=self.ka_size,
-                  user_sgpr_count=2, user_sgpr_dispatch_ptr=0, user_sgpr_queue_ptr=0, user_sgpr_kernarg_segment_ptr=1,
-                  user_sgpr_dispatch_id=0, user_sgpr_kernarg_preload_length=0, user_sgpr_kernarg_preload_offset=0,
-                  user_sgpr_private_segment_size=0, uses_dynamic_stack=0, enable_private_segment=0,
-                  system_sgpr_workgroup_id_x=1, system_sgpr_workgroup_id_y=1, system_sgpr_workgroup_id_z=0,
-                  system_sgpr_workgroup_info=0, system_vgpr_workitem_id=0, next_free_vgpr=total_v,
-                  next_free_sgpr=self.S.n, accum_offset=self.accum_offset, reserve_vcc=1, float_round_mode_32=0,
-                  float_round_mode_16_64=0, float_denorm_mode_32=3, float_denorm_mode_16_64=3, dx10_clamp=1, ieee_mode=1,
-                  fp16_overflow=0, tg_split=0)
-        for k, v in kd.items():
-            tail.append("\t\t.amdhsa_%s %d" % (k, v))
-        tail.append("\t.end_amdhsa_kernel")
-        tail.append("\t.text")
-        tail.append("\t.amdgpu_metadata")
-        tail.append("---")
-        tail.append("amdhsa.kernels:")
-        tail.append("  - .agpr_count:     %d" % self.nagpr)
-        tail.append("    .args:")
-        off = 0
-        for i in range(9):
-            tail.append("      - .address_space:  global\n        .offset:         %d\n        .size:           8\n        .value_kind:     global_buffer" % off)
-            off += 8
-        for i in range(10):
-            tail.append("      - .offset:         %d\n        .size:           4\n        .value_kind:     by_value" % off)
-            off += 4
-        tail.append("      - .offset:         %d\n        .size:           %d\n        .value_kind:     by_value" % (off, self.ka_size - off))
-        off = self.ka_size
-        assert off == self.ka_size
-        tail.append("    .group_segment_fixed_size: %d" % lds)
-        tail.append("    .kernarg_segment_align: 8")
-        tail.append("    .kernarg_segment_size: %d" % self.ka_size)
-        tail.append("    .max_flat_workgroup_size: 256")
-        tail.append("    .name:           %s" % name)
-        tail.append("    .private_segment_fixed_size: 0")
-        tail.append("    .sgpr_count:     %d" % (self.S.n + 6))
-        tail.append("    .sgpr_spill_count: 0")
-        tail.append("    .symbol:         %s.kd" % name)
-        tail.append("    .uniform_work_group_size: 1")
-        tail.append("    .uses_dynamic_stack: false")
-        tail.append("    .vgpr_count:     %d" % total_v)
-        tail.append("    .vgpr_spill_count: 0")
-        tail.append("    .wavefront_size: 64")
-        tail.append("amdhsa.target:   amdgcn-amd-amdhsa--gfx950")
-        tail.append("amdhsa.version:\n  - 1\n  - 2")
-        tail.append("...")
-        tail.append("\t.end_amdgpu_metadata")
-        body = self.out + ["\t.p2align 8", ".Lend_%s:" % name, "\t.size\t%s, .Lend_%s-%s" % (name, name, name)]
-        self.lds_bytes = lds
-        return "\n".join(hdr + body + tail) + "\n"
-
 
 # ---------------------------------------------------------------------------------------------------------------------
 VARIANTS = {
@@ -1846,37 +1754,13 @@ def _variant_model_sizes():
 _variant_model_sizes()
 
 
-def generate(base, **over):
-    c = VARIANTS[base]
-    if over:
-        c = Cfg(**{**c.__dict__, **over})
-    g = Gen(c)
-    text = g.gen()
-    return c, g, text
+generate = functools.partial(asm_common.generate, VARIANTS, Gen)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="build")
-    ap.add_argument("--set", action="append", default=[], help="tuning: override a Cfg field (key=int), with --suffix names the kernel")
-    ap.add_argument("--suffix", default="")
-    ap.add_argument("names", nargs="*")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    over = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in a.set}
-    for name in (a.names or VARIANTS):
-        if a.suffix:
-            over["name"] = name + a.suffix
-        c, g, text = generate(name, **over)
-        name = c.name
-        if a.suffix:  # tuning builds: the per-wave table as a raw file for tools/micro/dconv_bench.cpp
-            import struct
-            with open(os.path.join(a.out, name + ".tbl"), "wb") as f:
-                f.write(struct.pack("<768I", *[w for par in tables(c) for row in par for w in row]))
-        with open(os.path.join(a.out, name + ".s"), "w") as f:
-            f.write(text)
-        print("%s: %d lines, %d VGPR + %d AGPR, %d SGPR, LDS %d" % (name, text.count("\n"), g.accum_offset, g.nagpr, g.S.n, g.lds_bytes))
+def table_words(c):
+    """--suffix: the per-wave piece tables as tools/micro/dconv_bench.cpp passes them"""
+    return [w for par in tables(c) for row in par for w in row]
 
 
 if __name__ == "__main__":
-    main()
+    asm_common.main(VARIANTS, generate, table_words)

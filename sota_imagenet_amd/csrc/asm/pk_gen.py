@@ -15,14 +15,15 @@ reused as they are) with the 9-tap loop replaced by a walk over 64-channel chunk
 A tile is W consecutive pixels (196 = one 14 x 14 image; 98 = two 7 x 7 images, or half an image where the BN-backward register sets
 need the shorter tile) x 256 columns; waves 1 (M) x 4 (N).
 """
-import argparse
+import functools
 import os
 import sys
 from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import asm_common  # noqa: E402
 import dconv_gen  # noqa: E402
-from dconv_gen import Alloc, R  # noqa: E402
+from asm_common import R, merge  # noqa: E402
 
 
 @dataclass
@@ -128,7 +129,7 @@ class Gen(dconv_gen.Gen):
         self.prologue()
         self.mainloop()
         self.epilogue()
-        return self.finish()
+        return self.code_object()
 
     # -----------------------------------------------------------------------------------------------------------------
     def a_piece(self, k, buf, s_chunk):
@@ -185,12 +186,7 @@ class Gen(dconv_gen.Gen):
         e("s_load_dwordx16 %s, s[0:1], 0x0" % R("s", ka, 16))
         e("s_load_dword %s, s[0:1], 0x48" % R("s", kb))            # nchunks
         lane, r, kg = v[0], v[1], v[2]
-        e("v_lshrrev_b32 %s, 6, v0" % R("v", v[3]))
-        e("v_and_b32 %s, 63, v0" % R("v", lane))
-        e("v_readfirstlane_b32 %s, %s" % (R("s", self.s_w), R("v", v[3])))
-        e("v_and_b32 %s, 15, v0" % R("v", r))
-        e("v_bfe_u32 %s, v0, 4, 2" % R("v", kg))
-        e("s_nop 3")
+        self.lane_constants()
         e("s_mov_b32 %s, 0" % R("s", self.s_wm))
         e("s_mov_b32 %s, %s" % (R("s", self.s_wn), R("s", self.s_w)))
         e("s_mul_i32 %s, %s, %d" % (R("s", self.s_ldsBw), R("s", self.s_w), c.BSTAGE // 4), "this wave's quarter of a weight stage")
@@ -209,19 +205,7 @@ class Gen(dconv_gen.Gen):
         e("v_lshlrev_b32 %s, 4, %s" % (R("v", j), R("v", j)))
         e("v_mov_b32 %s, %d" % (R("v", off), c.Cin * 2))
         e("v_mad_u32_u24 %s, %s, %s, %s" % (R("v", self.vA_dma), R("v", l3), R("v", off), R("v", j)))
-        # B (variant ib = piece & 1), as dconv_gen.py
-        l5, l43, ch, x = v[5], v[8], v[7], v[9]
-        e("v_lshrrev_b32 %s, 5, %s" % (R("v", l5), R("v", lane)))
-        e("v_bfe_u32 %s, %s, 4, 2" % (R("v", l43), R("v", lane)))
-        for ib in range(2):
-            e("v_lshl_add_u32 %s, %s, 3, %d" % (R("v", ch), R("v", l5), 16 * ib))
-            e("v_and_b32 %s, 3, %s" % (R("v", x), R("v", l3)))
-            e("v_add_u32 %s, %s, %s" % (R("v", ch), R("v", ch), R("v", x)))
-            e("v_mov_b32 %s, %d" % (R("v", x), c.w_row))
-            e("v_mul_lo_u32 %s, %s, %s" % (R("v", ch), R("v", ch), R("v", x)))
-            e("v_or_b32 %s, %d, %s" % (R("v", x), 4 * ib, R("v", l43)))
-            e("v_xor_b32 %s, %s, %s" % (R("v", x), R("v", l7), R("v", x)))
-            e("v_lshl_add_u32 %s, %s, 4, %s" % (R("v", self.vB_dma[ib]), R("v", x), R("v", ch)))
+        self.b_dma_lanes()
         e("s_waitcnt lgkmcnt(0)")
         self.comment("descriptors: A = this tile's pixels, B = this column tile's weight rows, O = this tile's output pixels")
         tile_in = c.W * c.Cin * 2
@@ -233,12 +217,7 @@ class Gen(dconv_gen.Gen):
         e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdA + 1), R("s", self.srdA + 1)))
         e("s_mov_b32 %s, %d" % (R("s", self.srdA + 2), tile_in), "pixels past the tile read zeros")
         e("s_mov_b32 %s, 0x00020000" % R("s", self.srdA + 3))
-        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * c.w_row))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdB), R("s", ka + 2), R("s", t0)))
-        e("s_addc_u32 %s, %s, 0" % (R("s", self.srdB + 1), R("s", ka + 3)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdB + 1), R("s", self.srdB + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdB + 2), c.BN * c.w_row))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdB + 3))
+        self.b_descriptor()
         e("s_mov_b32 %s, %s" % (R("s", self.s_nch), R("s", kb)))
         e("s_sub_u32 %s, %s, 1" % (R("s", self.s_clast), R("s", self.s_nch)))
         e("s_lshl_b32 %s, %s, 7" % (R("s", self.s_clast), R("s", self.s_clast)), "byte offset of the last chunk in a pixel / weight row")
@@ -263,45 +242,6 @@ class Gen(dconv_gen.Gen):
                         e(ins)
                 self.adv_b()
 
-        def descriptors_out():
-            e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_tile), tile_out))
-            e("s_mul_hi_u32 %s, %s, %d" % (R("s", t1), R("s", self.s_tile), tile_out))
-            e("s_mul_i32 %s, %s, %d" % (R("s", self.s_stg), R("s", self.s_nt), c.BN * 2))
-            e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
-            e("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
-            e("s_add_u32 %s, %s, %s" % (R("s", self.srdO), R("s", ka + 4), R("s", t0)))
-            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdO + 1), R("s", ka + 5), R("s", t1)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdO + 1), R("s", self.srdO + 1)))
-            e("s_mov_b32 %s, %d" % (R("s", self.srdO + 2), tile_out))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdO + 3))
-            e("s_sub_u32 %s, %s, %s" % (R("s", self.srdO + 2), R("s", self.srdO + 2), R("s", self.s_stg)))
-            e("s_mov_b32 %s, %s" % (R("s", self.srdX), R("s", ka + 6)), "statistics rows")
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdX + 1), R("s", ka + 7)))
-            e("s_mov_b32 %s, 0x7fffffff" % R("s", self.srdX + 2))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdX + 3))
-            if c.stats >= 2:
-                e("s_add_u32 %s, %s, %s" % (R("s", self.srdY), R("s", ka + 8), R("s", t0)))
-                e("s_addc_u32 %s, %s, %s" % (R("s", self.srdY + 1), R("s", ka + 9), R("s", t1)))
-                e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdY + 1), R("s", self.srdY + 1)))
-                e("s_mov_b32 %s, %s" % (R("s", self.srdY + 2), R("s", self.srdO + 2)))
-                e("s_mov_b32 %s, 0x00020000" % R("s", self.srdY + 3))
-                e("s_lshr_b32 %s, %s, 4" % (R("s", t0), R("s", t0)))
-                e("s_lshl_b32 %s, %s, 28" % (R("s", self.s_stg), R("s", t1)))
-                e("s_or_b32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
-                e("s_lshr_b32 %s, %s, 4" % (R("s", t1), R("s", t1)))
-                e("s_add_u32 %s, %s, %s" % (R("s", self.srdM), R("s", ka + 10), R("s", t0)))
-                e("s_addc_u32 %s, %s, %s" % (R("s", self.srdM + 1), R("s", ka + 11), R("s", t1)))
-                e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdM + 1), R("s", self.srdM + 1)))
-                e("s_lshr_b32 %s, %s, 4" % (R("s", self.srdM + 2), R("s", self.srdO + 2)))
-                e("s_mov_b32 %s, 0x00020000" % R("s", self.srdM + 3))
-                e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * 4))
-                for srd, k0 in ((self.srdMu, 12), (self.srdIs, 14)):
-                    e("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", ka + k0), R("s", t0)))
-                    e("s_addc_u32 %s, %s, 0" % (R("s", srd + 1), R("s", ka + k0 + 1)))
-                    e("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
-                    e("s_mov_b32 %s, %d" % (R("s", srd + 2), c.BN * 4))
-                    e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
-
         def lane_out():
             x, off = v[6], v[7]
             e("v_mov_b32 %s, %d" % (R("v", off), c.NCOLS * 2))
@@ -311,35 +251,20 @@ class Gen(dconv_gen.Gen):
             e("v_add_u32 %s, %s, %s" % (R("v", self.v_out), R("s", t0), R("v", x)))
 
         if c.stats >= 2:
-            descriptors_out()
+            self.out_descriptors(tile_out)
             lane_out()
-            self.tile_mask_loads()
-            e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_wn), c.NT * 16 * 4))
-            e("v_lshl_add_u32 %s, %s, 5, %s" % (R("v", self.v_chan), R("v", self.v_kg), R("s", t0)), "this lane's 8 floats of mean / invstd")
-            self.epi_issue_loads(0)
-            if not self.late_pair1 and c.NT >= 4:
-                self.epi_issue_loads(1)
+            self.bn_backward_first_loads()
             first_loads()
         else:
             first_loads()
-            descriptors_out()
+            self.out_descriptors(tile_out)
             lane_out()
         # ---- read bases.  A: row r of a fragment, chunk (kg + 4kk) ^ ((r >> 1) & 7) (16 rows per fragment: the swizzle repeats);  B as dconv_gen.py
-        sw, cc = v[3], v[4]
-        e("v_bfe_u32 %s, %s, 1, 3" % (R("v", sw), R("v", r)))
-        e("v_xor_b32 %s, %s, %s" % (R("v", cc), R("v", kg), R("v", sw)))
-        e("v_lshlrev_b32 %s, 4, %s" % (R("v", cc), R("v", cc)))
-        e("v_lshl_add_u32 %s, %s, 7, %s" % (R("v", cc), R("v", r), R("v", cc)))
+        cc = self.row_chunk()
         for b in range(c.NA):
             e("v_add_u32 %s, %d, %s" % (R("v", self.vA_rd[b][0]), c.ABASE + b * c.ASTRIDE, R("v", cc)))
             e("v_xor_b32 %s, 64, %s" % (R("v", self.vA_rd[b][1]), R("v", self.vA_rd[b][0])))
-        e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_wn), c.NT * 16 * 128))
-        e("s_add_u32 %s, %s, %d" % (R("s", t0), R("s", t0), c.BBASE))
-        e("v_add_u32 %s, %s, %s" % (R("v", self.vB_rd[0][0]), R("s", t0), R("v", cc)))
-        e("v_xor_b32 %s, 64, %s" % (R("v", self.vB_rd[0][1]), R("v", self.vB_rd[0][0])))
-        for st in range(1, c.NB):
-            for kk in range(2):
-                e("v_add_u32 %s, %d, %s" % (R("v", self.vB_rd[st][kk]), st * c.BSTAGE, R("v", self.vB_rd[0][kk])))
+        self.b_read_bases(cc)
         for i in range(self.nagpr):
             e("v_accvgpr_write_b32 a%d, 0" % i)
         e("s_waitcnt vmcnt(%d)" % (self.NPA + (c.NB - 1) * c.NPB), "weight stage 0 and tile 0 have landed")
@@ -384,7 +309,7 @@ class Gen(dconv_gen.Gen):
             pieces[-1] = pieces[-1] + self.adv_insts(self.s_cA, self.s_srcAw)
             if c.probe & 1:
                 pieces = []
-            self.interleave(self.mfmas(0), self.merge(groups, pieces))
+            self.interleave(self.mfmas(0), merge(groups, pieces))
             # ---- substep 1: the stage barrier (chunk + 1 has landed for every wave; this chunk's fragments are all read), compute on
             # set 1, read (chunk + 1, kk 0), request the weight slab of chunk + NB into the stage just released
             self.comment("chunk %d substep 1" % ch)
@@ -397,7 +322,7 @@ class Gen(dconv_gen.Gen):
             pieces[-1] = pieces[-1] + self.adv_insts(self.s_cB, self.s_srcBw)
             if c.probe & 1:
                 pieces = []
-            self.interleave(self.mfmas(1), self.merge(groups, pieces))
+            self.interleave(self.mfmas(1), merge(groups, pieces))
             e("s_sub_u32 %s, %s, 1" % (R("s", self.s_cnt), R("s", self.s_cnt)))
             e("s_cmp_eq_u32 %s, 0" % R("s", self.s_cnt))
             if ch < trip - 1:
@@ -405,11 +330,6 @@ class Gen(dconv_gen.Gen):
             else:
                 e("s_cbranch_scc0 %s" % top)
         self.label(done)
-
-    def finish(self):
-        c = self.c
-        text = super().finish()
-        return text
 
 
 def _variants():
@@ -442,25 +362,7 @@ def _variants():
 VARIANTS = _variants()
 
 
-def generate(name, **over):
-    c = VARIANTS[name]
-    if over:
-        c = PkCfg(**{**c.__dict__, **over})
-    g = Gen(c)
-    return c, g, g.gen()
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", required=True)
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    for name in VARIANTS:
-        c, g, text = generate(name)
-        with open(os.path.join(a.out, name + ".s"), "w") as f:
-            f.write(text)
-        print("%s: %d vgpr + %d agpr, lds %d, %d lines" % (name, g.accum_offset, g.nagpr, g.lds_bytes, text.count("\n")))
-
+generate = functools.partial(asm_common.generate, VARIANTS, Gen)
 
 if __name__ == "__main__":
-    main()
+    asm_common.main(VARIANTS, generate)

@@ -27,13 +27,14 @@ pipe.  So:
 Tensor extents are enforced by the buffer descriptors (num_records = bytes left from the tile's base, moved tile by tile), so a
 ragged last tile (pixel count not a multiple of 64) reads zeros and drops its stores; no SGPR offset takes part in a range check.
 """
-import argparse
+import functools
 import os
 import sys
 from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from dconv_gen import Alloc, R, LEAKY_BITS  # noqa: E402
+import asm_common  # noqa: E402
+from asm_common import LEAKY_BITS, Emitter, R, merge  # noqa: E402
 
 
 @dataclass
@@ -122,29 +123,12 @@ class PoCfg:
         return self.NT == 4
 
 
-class Gen:
+class Gen(Emitter):
     KA = dict(in_=0, wt=8, out=16, stat=24, bn_y=32, bn_bits=40, bn_mean=48, bn_invstd=56, addend=64, addend_bits=72,
               npix=80, ncols=84, tpg=88, ngroups=92, ntiles=96, lognct=100, W=104, H=108, magic_w=112, magic_h=116, size=128)
 
     def __init__(self, c: PoCfg):
-        self.c = c
-        self.out = []
-        self.nlabel = 0
-        self.S = Alloc("s", 4, 102)
-        self.V = Alloc("v", 1, 256)
-
-    def e(self, s, comment=None):
-        self.out.append("\t" + s + ("\t; " + comment if comment else ""))
-
-    def label(self, name):
-        self.out.append(name + ":")
-
-    def newlabel(self, stem):
-        self.nlabel += 1
-        return "L_%s_%s_%d" % (self.c.name, stem, self.nlabel)
-
-    def comment(self, s):
-        self.out.append("\t; " + s)
+        super().__init__(c, sgpr_limit=102, label_prefix="L_%s_" % c.name)
 
     # -----------------------------------------------------------------------------------------------------------------
     def gen(self):
@@ -234,7 +218,7 @@ class Gen:
         self.prologue()
         self.mainloop()
         self.finale()
-        return self.finish()
+        return self.finish(c.LDS, self.KA["size"], 10, [4] * 6 + [self.KA["size"] - 104])
 
     def acc(self, m, n, aset=None):
         aset = self.accset if aset is None else aset
@@ -747,21 +731,6 @@ class Gen:
                 m, p = divmod(i, c.NT // 2)
                 self.item(i, m, p, CW)
 
-    @staticmethod
-    def weave(primary, secondary):
-        """secondary (the MFMA phase of the next tile, order kept) spread evenly through primary (the epilogue of this tile, order kept).  An
-        s_waitcnt of either list keeps its place relative to its own list: lgkmcnt waits belong to the MFMA phase's fragment reads (the
-        epilogue has no LDS operation), vmcnt waits to the epilogue's loads (the MFMA phase has no vector-memory operation)."""
-        np_, ns = len(primary), len(secondary)
-        out, j = [], 0
-        for i, ins in enumerate(primary):
-            out.append(ins)
-            while j < ns and (j + 1) * np_ <= (i + 1) * ns:
-                out.append(secondary[j])
-                j += 1
-        out.extend(secondary[j:])
-        return out
-
     def mainloop(self):
         c, e = self.c, self.e
         top, done = self.newlabel("loop"), self.newlabel("done")
@@ -810,7 +779,9 @@ class Gen:
                 self.mbuf = b
                 epi = self.capture(self.epilogue_tile, CW)
                 mfm = self.capture(self.mfma_phase, nb, nb)
-                for ins in self.weave(epi, mfm):
+                # the MFMA phase of the next tile spread evenly through the epilogue of this one, both in order: an s_waitcnt keeps its place in
+                # its own list (lgkmcnt waits belong to the MFMA phase's fragment reads, vmcnt waits to the epilogue's loads)
+                for ins in merge(epi, mfm):
                     self.out.append(ins)
             else:
                 e("s_waitcnt vmcnt(%d)" % TOPW, "this tile's A pieces have landed (younger: the last tile's stores and refills)")
@@ -873,7 +844,7 @@ class Gen:
             else:
                 for k in range(8):
                     e("v_bfe_i32 %s, %s, %d, 1" % (R("v", vm), R("v", d["yb"]), k), "0 / -1: ReLU bit of element %d" % k)
-                    if c.stats == 3:   # leaky mask: dz = bit ? dx : dx * 0.01 (dconv_gen.py LEAKY_BITS; tv + k is dead after the conversion)
+                    if c.stats == 3:   # leaky mask: dz = bit ? dx : dx * 0.01 (asm_common.LEAKY_BITS; tv + k is dead after the conversion)
                         e("v_mul_f32 %s, 0x%08x, %s" % (R("v", tv + k), LEAKY_BITS, R("v", xr + k)))
                         e("v_bfi_b32 %s, %s, %s, %s" % (R("v", xr + k), R("v", vm), R("v", xr + k), R("v", tv + k)), "dz")
                     else:
@@ -956,7 +927,7 @@ class Gen:
             else:
                 for k in range(8):
                     e("v_bfe_i32 %s, %s, %d, 1" % (R("v", vm), R("v", d["yb"]), k), "0 / -1: ReLU bit of element %d" % k)
-                    if c.stats == 3:   # leaky mask: dz = bit ? dx : dx * 0.01 (dconv_gen.py LEAKY_BITS; tv + k is dead after the conversion)
+                    if c.stats == 3:   # leaky mask: dz = bit ? dx : dx * 0.01 (asm_common.LEAKY_BITS; tv + k is dead after the conversion)
                         e("v_mul_f32 %s, 0x%08x, %s" % (R("v", tv + k), LEAKY_BITS, R("v", xr + k)))
                         e("v_bfi_b32 %s, %s, %s, %s" % (R("v", xr + k), R("v", vm), R("v", xr + k), R("v", tv + k)), "dz")
                     else:
@@ -1043,44 +1014,6 @@ class Gen:
         e("s_waitcnt vmcnt(0)")
         e("s_endpgm")
 
-    # -----------------------------------------------------------------------------------------------------------------
-    def finish(self):
-        c = self.c
-        name = c.name
-        lds = c.LDS
-        total_v = self.accum_offset + self.nagpr
-        hdr = ['\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"', "\t.amdhsa_code_object_version 6", "\t.text", "\t.protected\t%s" % name, "\t.globl\t%s" % name,
-               "\t.p2align\t8", "\t.type\t%s,@function" % name, "%s:" % name]
-        tail = ["\t.section\t.rodata,\"a\",@progbits", "\t.p2align\t6, 0x0", "\t.amdhsa_kernel %s" % name]
-        kd = dict(group_segment_fixed_size=lds, private_segment_fixed_size=0, kernarg_size=self.KA["size"],
-                  user_sgpr_count=2, user_sgpr_dispatch_ptr=0, user_sgpr_queue_ptr=0, user_sgpr_kernarg_segment_ptr=1,
-                  user_sgpr_dispatch_id=0, user_sgpr_kernarg_preload_length=0, user_sgpr_kernarg_preload_offset=0,
-                  user_sgpr_private_segment_size=0, uses_dynamic_stack=0, enable_private_segment=0,
-                  system_sgpr_workgroup_id_x=1, system_sgpr_workgroup_id_y=0, system_sgpr_workgroup_id_z=0,
-                  system_sgpr_workgroup_info=0, system_vgpr_workitem_id=0, next_free_vgpr=total_v,
-                  next_free_sgpr=self.S.n, accum_offset=self.accum_offset, reserve_vcc=1, float_round_mode_32=0,
-                  float_round_mode_16_64=0, float_denorm_mode_32=3, float_denorm_mode_16_64=3, dx10_clamp=1, ieee_mode=1,
-                  fp16_overflow=0, tg_split=0)
-        for k, v in kd.items():
-            tail.append("\t\t.amdhsa_%s %d" % (k, v))
-        tail += ["\t.end_amdhsa_kernel", "\t.text", "\t.amdgpu_metadata", "---", "amdhsa.kernels:", "  - .agpr_count:     %d" % self.nagpr, "    .args:"]
-        off = 0
-        for i in range(10):
-            tail.append("      - .address_space:  global\n        .offset:         %d\n        .size:           8\n        .value_kind:     global_buffer" % off)
-            off += 8
-        for i in range(6):
-            tail.append("      - .offset:         %d\n        .size:           4\n        .value_kind:     by_value" % off)
-            off += 4
-        tail.append("      - .offset:         %d\n        .size:           %d\n        .value_kind:     by_value" % (off, self.KA["size"] - off))
-        tail += ["    .group_segment_fixed_size: %d" % lds, "    .kernarg_segment_align: 8", "    .kernarg_segment_size: %d" % self.KA["size"],
-                 "    .max_flat_workgroup_size: 256", "    .name:           %s" % name, "    .private_segment_fixed_size: 0",
-                 "    .sgpr_count:     %d" % (self.S.n + 6), "    .sgpr_spill_count: 0", "    .symbol:         %s.kd" % name,
-                 "    .uniform_work_group_size: 1", "    .uses_dynamic_stack: false", "    .vgpr_count:     %d" % total_v, "    .vgpr_spill_count: 0",
-                 "    .wavefront_size: 64", "amdhsa.target:   amdgcn-amd-amdhsa--gfx950", "amdhsa.version:\n  - 1\n  - 2", "...", "\t.end_amdgpu_metadata"]
-        body = self.out + ["\t.p2align 8", ".Lend_%s:" % name, "\t.size\t%s, .Lend_%s-%s" % (name, name, name)]
-        self.lds_bytes = lds
-        return "\n".join(hdr + body + tail) + "\n"
-
 
 def _variants():
     v = {}
@@ -1104,32 +1037,7 @@ def _variants():
 VARIANTS = _variants()
 
 
-def generate(base, **over):
-    c = VARIANTS[base]
-    if over:
-        c = PoCfg(**{**c.__dict__, **over})
-    g = Gen(c)
-    return c, g, g.gen()
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--set", action="append", default=[], help="tuning: override a PoCfg field (key=int), with --suffix names the kernel")
-    ap.add_argument("--suffix", default="")
-    ap.add_argument("names", nargs="*")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    over = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in a.set}
-    for name in (a.names or VARIANTS):
-        if a.suffix:
-            over["name"] = name + a.suffix
-        c, g, text = generate(name, **over)
-        name = c.name
-        with open(os.path.join(a.out, name + ".s"), "w") as f:
-            f.write(text)
-        print("%s: %d vgpr + %d agpr, %d sgpr, lds %d, %d lines" % (name, g.accum_offset, g.nagpr, g.S.n, g.lds_bytes, text.count("\n")))
-
+generate = functools.partial(asm_common.generate, VARIANTS, Gen)
 
 if __name__ == "__main__":
-    main()
+    asm_common.main(VARIANTS, generate)

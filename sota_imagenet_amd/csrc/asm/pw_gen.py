@@ -22,16 +22,16 @@ Structure:
               so the code is unrolled over the two accumulator sets only; rows permuted so that a lane's accumulators of a
               tile pair are 8 consecutive channels.
   waits       one s_barrier per stage behind a counted vmcnt; the count is derived by the generator from the program order of
-              every vector-memory instruction (class Tracker), never by hand.
+              every vector-memory instruction (asm_common.resolve_waits), never by hand.
 """
-import argparse
+import functools
 import os
-import struct
 import sys
 from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from dconv_gen import Alloc, R  # noqa: E402
+import asm_common  # noqa: E402
+from asm_common import Emitter, R, merge, resolve_waits  # noqa: E402
 
 
 @dataclass
@@ -112,69 +112,13 @@ def tables(c):
     return rows
 
 
-class Tracker:
-    """program order of the vector-memory instructions of the steady-state loop; vmcnt for a wait = the number of UNCONDITIONAL
-    instructions issued after the youngest one the wait must retire (conditional ones only make the real count larger)."""
-
-    def __init__(self):
-        self.events = []  # ("op", tag, conditional) | ("wait", placeholder index, [required tags])
-
-    def op(self, tag, conditional=False):
-        self.events.append(("op", tag, conditional))
-
-    def wait(self, slot, required):
-        self.events.append(("wait", slot, required))
-
-    def resolve(self):
-        """events of ONE loop trip; the loop is cyclic: search backwards, wrapping once"""
-        n = len(self.events)
-        res = {}
-        for idx, ev in enumerate(self.events):
-            if ev[0] != "wait":
-                continue
-            _, slot, required = ev
-            best = None
-            for tag in required:
-                cnt, found = 0, False
-                for back in range(1, 2 * n + 1):
-                    e2 = self.events[(idx - back) % n]
-                    if e2[0] != "op":
-                        continue
-                    if e2[1] == tag:
-                        found = True
-                        break
-                    if not e2[2]:
-                        cnt += 1
-                assert found, "tag %r never issued" % (tag,)
-                best = cnt if best is None else min(best, cnt)
-            res[slot] = best if best is not None else 63
-        return res
-
-
-class Gen:
+class Gen(Emitter):
     KA = dict(in_=0, wt=8, out=16, stat=24, units=80, upw=84, mtiles=88, table=128, size=640)
 
     def __init__(self, c: PwCfg):
-        self.c = c
-        self.out = []
-        self.nlabel = 0
-        self.S = Alloc("s", 4, 100)
-        self.V = Alloc("v", 1, 256)
-        self.tr = Tracker()
-        self.wait_slots = {}
-
-    def e(self, s, comment=None):
-        self.out.append("\t" + s + ("\t; " + comment if comment else ""))
-
-    def label(self, name):
-        self.out.append(name + ":")
-
-    def newlabel(self, stem):
-        self.nlabel += 1
-        return "L_%s_%d" % (stem, self.nlabel)
-
-    def comment(self, s):
-        self.out.append("\t; " + s)
+        super().__init__(c)
+        self.events = []   # the vector-memory operations and counted waits of one loop trip, in program order (resolve_waits)
+        self.nwaits = 0
 
     # -----------------------------------------------------------------------------------------------------------------
     def gen(self):
@@ -225,10 +169,9 @@ class Gen:
             self.UB += 2
         self.prologue()
         self.loop()
-        text = self.finish()
+        text = self.finish(c.LDS, self.KA["size"], 10, [self.KA["size"] - 80])
         # resolve the counted waits
-        res = self.tr.resolve()
-        for slot, n in res.items():
+        for slot, n in resolve_waits(self.events).items():
             text = text.replace("@VM%d@" % slot, str(min(n, 63)))
         assert "@VM" not in text
         return text
@@ -527,9 +470,9 @@ class Gen:
         return [entries[i:i + size] for i in range(0, len(entries), size)]
 
     def wait_vm(self, required):
-        slot = len(self.wait_slots)
-        self.wait_slots[slot] = required
-        self.tr.wait(slot, required)
+        slot = self.nwaits
+        self.nwaits += 1
+        self.events.append(("wait", slot, required))
         self.e("s_waitcnt vmcnt(@VM%d@)" % slot)
 
     # -----------------------------------------------------------------------------------------------------------------
@@ -553,7 +496,7 @@ class Gen:
             e("v_add_u32 %s, %s, %s" % (R("v", self.vBcur1), R("s", self.s_bcur), R("v", self.vB0[1])))
             e("s_waitcnt lgkmcnt(0)")
             groups = [[r] for r in self.frag_reads(1, ch, 1)]
-            self.interleave(self.mfmas(0, ap, zero_c=(ch == 0)), self.merge(per[2 * ch], groups))
+            self.interleave(self.mfmas(0, ap, zero_c=(ch == 0)), merge(per[2 * ch], groups))
             # ---- the stage barrier: the next stage's weights have landed for every wave (and, at the last stage, plane 0)
             self.comment("acc set %d stage %d substep 1" % (ap, ch))
             g = (ub * c.NCH + ch)
@@ -592,17 +535,17 @@ class Gen:
             for k in range(len(a_slots(c))):
                 ins = self.a_slot_insts(k, ch)
                 adma.append(ins[:2] + [("vm", ("A", ch, (ub + 1) % self.UB), ins[2], True)])
-            saved = list(self.tr.events)
-            allg = self.merge(self.merge(per[2 * ch + 1], groups), self.merge(dma, adma))
+            saved = list(self.events)
+            allg = merge(merge(per[2 * ch + 1], groups), merge(dma, adma))
             self.interleave(mf, allg)
             e("s_branch %s" % lab_end)
             self.label(lab_no)
             # (the tracker follows the refill path: its extra instructions are flagged conditional; the other path is the same
             # stream without them)
-            ev_refill = self.tr.events
-            self.tr.events = list(saved)
+            ev_refill = self.events
+            self.events = list(saved)
             self.interleave(mf, allg, skip=adma)
-            self.tr.events = ev_refill
+            self.events = ev_refill
             self.label(lab_end)
             e("s_mov_b32 %s, %s" % (R("s", self.s_bcur), R("s", self.s_bnext)))
 
@@ -610,27 +553,10 @@ class Gen:
         for ins in entries:
             if isinstance(ins, tuple):
                 tag, text = ins[1], ins[2]
-                self.tr.op(tag, conditional=len(ins) > 3 and ins[3])
+                self.events.append(("op", tag, len(ins) > 3 and ins[3]))
                 self.e(text)
             else:
                 self.e(ins)
-
-    @staticmethod
-    def merge(a, b):
-        if not b:
-            return list(a)
-        if not a:
-            return list(b)
-        out = []
-        na, nb = len(a), len(b)
-        ib = 0
-        for i, g in enumerate(a):
-            out.append(g)
-            while ib < nb and (ib + 1) * na <= (i + 1) * nb:
-                out.append(b[ib])
-                ib += 1
-        out.extend(b[ib:])
-        return out
 
     def unit_switch(self, ap, lab_exit):
         """the unit that just ran becomes the previous one; advance to the next unit or leave the loop"""
@@ -677,11 +603,11 @@ class Gen:
             self.label(exits[ap])
             e("s_nop 15")
             e("s_nop 15")
-            saved = self.tr.events
-            self.tr.events = []
+            saved = self.events
+            self.events = []
             for kind, g in self.epi_groups(ap):
                 self.emit_group(g)
-            self.tr.events = saved
+            self.events = saved
             if ap == 0:
                 e("s_branch %s" % done)
         self.label(done)
@@ -704,42 +630,6 @@ class Gen:
         e("s_waitcnt vmcnt(0)")
         e("s_endpgm")
 
-    # -----------------------------------------------------------------------------------------------------------------
-    def finish(self):
-        c = self.c
-        name = c.name
-        total_v = self.accum_offset + self.nagpr
-        assert total_v <= 512
-        hdr = ['\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"', "\t.amdhsa_code_object_version 6", "\t.text", "\t.protected\t%s" % name,
-               "\t.globl\t%s" % name, "\t.p2align\t8", "\t.type\t%s,@function" % name, "%s:" % name]
-        tail = ["\t.section\t.rodata,\"a\",@progbits", "\t.p2align\t6, 0x0", "\t.amdhsa_kernel %s" % name]
-        kd = dict(group_segment_fixed_size=c.LDS, private_segment_fixed_size=0, kernarg_size=self.KA["size"],
-                  user_sgpr_count=2, user_sgpr_dispatch_ptr=0, user_sgpr_queue_ptr=0, user_sgpr_kernarg_segment_ptr=1,
-                  user_sgpr_dispatch_id=0, user_sgpr_kernarg_preload_length=0, user_sgpr_kernarg_preload_offset=0,
-                  user_sgpr_private_segment_size=0, uses_dynamic_stack=0, enable_private_segment=0,
-                  system_sgpr_workgroup_id_x=1, system_sgpr_workgroup_id_y=0, system_sgpr_workgroup_id_z=0,
-                  system_sgpr_workgroup_info=0, system_vgpr_workitem_id=0, next_free_vgpr=total_v,
-                  next_free_sgpr=self.S.n, accum_offset=self.accum_offset, reserve_vcc=1, float_round_mode_32=0,
-                  float_round_mode_16_64=0, float_denorm_mode_32=3, float_denorm_mode_16_64=3, dx10_clamp=1, ieee_mode=1,
-                  fp16_overflow=0, tg_split=0)
-        for k, v in kd.items():
-            tail.append("\t\t.amdhsa_%s %d" % (k, v))
-        tail += ["\t.end_amdhsa_kernel", "\t.text", "\t.amdgpu_metadata", "---", "amdhsa.kernels:", "  - .agpr_count:     %d" % self.nagpr,
-                 "    .args:"]
-        off = 0
-        for i in range(10):
-            tail.append("      - .address_space:  global\n        .offset:         %d\n        .size:           8\n        .value_kind:     global_buffer" % off)
-            off += 8
-        tail.append("      - .offset:         %d\n        .size:           %d\n        .value_kind:     by_value" % (off, self.KA["size"] - off))
-        tail += ["    .group_segment_fixed_size: %d" % c.LDS, "    .kernarg_segment_align: 8", "    .kernarg_segment_size: %d" % self.KA["size"],
-                 "    .max_flat_workgroup_size: 256", "    .name:           %s" % name, "    .private_segment_fixed_size: 0",
-                 "    .sgpr_count:     %d" % (self.S.n + 6), "    .sgpr_spill_count: 0", "    .symbol:         %s.kd" % name,
-                 "    .uniform_work_group_size: 1", "    .uses_dynamic_stack: false", "    .vgpr_count:     %d" % total_v,
-                 "    .vgpr_spill_count: 0", "    .wavefront_size: 64", "amdhsa.target:   amdgcn-amd-amdhsa--gfx950",
-                 "amdhsa.version:\n  - 1\n  - 2", "...", "\t.end_amdgpu_metadata"]
-        body = self.out + ["\t.p2align 8", ".Lend_%s:" % name, "\t.size\t%s, .Lend_%s-%s" % (name, name, name)]
-        return "\n".join(hdr + body + tail) + "\n"
-
 
 VARIANTS = {
     "pw_k256_n1024_s1": PwCfg("pw_k256_n1024_s1", K=256, N=1024, stats=1),
@@ -749,35 +639,13 @@ VARIANTS = {
 }
 
 
-def generate(base, **over):
-    c = VARIANTS[base]
-    if over:
-        c = PwCfg(**{**c.__dict__, **over})
-    g = Gen(c)
-    text = g.gen()
-    return c, g, text
+generate = functools.partial(asm_common.generate, VARIANTS, Gen)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="build")
-    ap.add_argument("--set", action="append", default=[])
-    ap.add_argument("--suffix", default="")
-    ap.add_argument("names", nargs="*")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    over = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in a.set}
-    for name in (a.names or VARIANTS):
-        if a.suffix:
-            over["name"] = name + a.suffix
-        c, g, text = generate(name, **over)
-        if a.suffix:
-            with open(os.path.join(a.out, c.name + ".tbl"), "wb") as f:
-                f.write(struct.pack("<128I", *[w for row in tables(c) for w in row]))
-        with open(os.path.join(a.out, c.name + ".s"), "w") as f:
-            f.write(text)
-        print("%s: %d lines, %d VGPR + %d AGPR, %d SGPR, LDS %d" % (c.name, text.count("\n"), g.accum_offset, g.nagpr, g.S.n, c.LDS))
+def table_words(c):
+    """--suffix: the per-wave tables as tools/micro/dconv_bench.cpp passes them"""
+    return [w for row in tables(c) for w in row]
 
 
 if __name__ == "__main__":
-    main()
+    asm_common.main(VARIANTS, generate, table_words)

@@ -20,14 +20,15 @@ keeping bytes in flight, not around the MFMA pipe:
   operands    ds_read_b64_tr_b16 (both operands are k-major in memory), the k permutation and the chunk swizzle of wg_gen.py.
   epilogue    accumulators straight from AGPRs to this split's fp32 slab.
 """
-import argparse
+import functools
 import os
 import sys
 from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from dconv_gen import Alloc, R  # noqa: E402
+import asm_common  # noqa: E402
 import wg_gen  # noqa: E402
+from asm_common import R, merge  # noqa: E402
 
 
 @dataclass
@@ -61,14 +62,6 @@ class W1Cfg:
 class Gen(wg_gen.Gen):
     KA = dict(dy=0, x=8, partial=16, tps=24, ntiles=28, npix=32, size=64)
 
-    def __init__(self, c):
-        self.c = c
-        self.out = []
-        self.nlabel = 0
-        self.S = Alloc("s", 4, 100)
-        self.V = Alloc("v", 1, 256)
-
-
     def gen(self):
         c, S, V = self.c, self.S, self.V
         self.NPC = 2 * (c.XP + c.DP)   # pieces per wave and tile: every plane's two 8-position blocks w and w + 4
@@ -101,7 +94,7 @@ class Gen(wg_gen.Gen):
         self.prologue()
         self.mainloop()
         self.epilogue()
-        return self.finish()
+        return self.finish(c.LDS, self.KA["size"], 3, [4] * 10, wg_id_y=1)
 
     # -----------------------------------------------------------------------------------------------------------------
     def tile_setup(self):
@@ -276,7 +269,7 @@ class Gen(wg_gen.Gen):
             pb = (b + c.NBUF - 1) % c.NBUF     # the buffer the previous tile freed
             ps = self.all_pieces(pb)
             half = len(ps) // 2
-            self.interleave(self.mfmas(0), self.merge(groups, ps[half:]))
+            self.interleave(self.mfmas(0), merge(groups, ps[half:]))
             # ---- k-step 1: barrier (the next tile has landed; this buffer's fragments are all read), compute on set 1, read the next
             # tile's step 0, first half of the pieces of tile + NBUF into this buffer
             self.comment("buffer %d k-step 1" % b)
@@ -288,7 +281,7 @@ class Gen(wg_gen.Gen):
             ps = self.all_pieces(b)
             setup = self.next_tile_insts() + self.tile_setup()
             first = [setup + ps[0]] + ps[1:half]
-            self.interleave(self.mfmas(1), self.merge(groups, first))
+            self.interleave(self.mfmas(1), merge(groups, first))
             e("s_sub_u32 %s, %s, 1" % (R("s", self.s_cnt), R("s", self.s_cnt)))
             e("s_cmp_eq_u32 %s, 0" % R("s", self.s_cnt))
             if b < c.NBUF - 1:
@@ -334,25 +327,7 @@ VARIANTS = {
 EXTRA = {"wg1_c256_o64": W1Cfg("wg1_c256_o64", C=256, CO=64, XP=4, DP=1)}  # test-only tile shape (see above)
 
 
-def generate(name, **over):
-    c = VARIANTS.get(name) or EXTRA[name]
-    if over:
-        c = W1Cfg(**{**c.__dict__, **over})
-    g = Gen(c)
-    return c, g, g.gen()
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", required=True)
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    for name in VARIANTS:
-        c, g, text = generate(name)
-        with open(os.path.join(a.out, name + ".s"), "w") as f:
-            f.write(text)
-        print("%s: %d vgpr + %d agpr, lds %d, %d lines" % (name, g.accum_offset, g.nagpr, g.lds_bytes, text.count("\n")))
-
+generate = functools.partial(asm_common.generate, {**VARIANTS, **EXTRA}, Gen)
 
 if __name__ == "__main__":
-    main()
+    asm_common.main(VARIANTS, generate)

@@ -24,13 +24,14 @@ Structure (one workgroup = 4 waves = one wave per SIMD; grid = splits x (ci tile
               tile; fragment reads of step s + 1 between the MFMAs of step s.
   epilogue    accumulators straight from AGPRs to the fp32 slab of this split.
 """
-import argparse
+import functools
 import os
 import sys
 from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from dconv_gen import Alloc, R  # noqa: E402
+import asm_common  # noqa: E402
+from asm_common import Emitter, R, merge  # noqa: E402
 
 
 @dataclass
@@ -187,28 +188,8 @@ def piece_plan(c, kind):
     return dict(n=n, LJ=LJ, SJ=SJ, LW=LW, SW=SW, var=[variants.index(k) for k in keys], variants=variants)
 
 
-class Gen:
+class Gen(Emitter):
     KA = dict(dy=0, x=8, partial=16, tps=24, ntiles=28, size=64)
-
-    def __init__(self, c: WCfg):
-        self.c = c
-        self.out = []
-        self.nlabel = 0
-        self.S = Alloc("s", 4, 100)
-        self.V = Alloc("v", 1, 256)
-
-    def e(self, s, comment=None):
-        self.out.append("\t" + s + ("\t; " + comment if comment else ""))
-
-    def label(self, name):
-        self.out.append(name + ":")
-
-    def newlabel(self, stem):
-        self.nlabel += 1
-        return "L_%s_%d" % (stem, self.nlabel)
-
-    def comment(self, s):
-        self.out.append("\t; " + s)
 
     def sel_w(self, dst, vals):
         """dst (SGPR) = vals[wave]"""
@@ -261,7 +242,7 @@ class Gen:
         self.prologue()
         self.mainloop()
         self.epilogue()
-        return self.finish()
+        return self.finish(c.LDS, self.KA["size"], 3, [4] * 10, wg_id_y=1)
 
     # -----------------------------------------------------------------------------------------------------------------
     def tile_setup(self):
@@ -538,14 +519,14 @@ class Gen:
                     setup = self.next_tile_insts() + self.tile_setup()
                     first = [setup + ps[0]] + ps[1:half]
                     self._carry_next = ps[half:]
-                    groups = self.merge(groups, first)
+                    groups = merge(groups, first)
                 else:
                     groups = [[r] for r in self.frag_reads(fset ^ 1, s + 1, b)]
                     if s == 0:
                         # second half of the pieces issued behind the previous tile's barrier (static: both buffers emit the same count)
                         ps = self.all_pieces(b ^ 1)
                         half = (len(ps) + 1) // 2
-                        groups = self.merge(groups, ps[half:])
+                        groups = merge(groups, ps[half:])
                 self.interleave(self.mfmas(fset, s, b), groups)
                 fset ^= 1
             e("s_sub_u32 %s, %s, 1" % (R("s", self.s_cnt), R("s", self.s_cnt)))
@@ -556,21 +537,6 @@ class Gen:
                 e("s_cbranch_scc0 %s" % top)
         assert (2 * KS) % 2 == 0  # the fragment set parity is the same at the top of every trip
         self.label(done)
-
-    @staticmethod
-    def merge(a, b):
-        if not b:
-            return a
-        out = []
-        na, nb = len(a), len(b)
-        ib = 0
-        for i, g in enumerate(a):
-            out.append(g)
-            while ib < nb and (ib + 1) * na <= (i + 1) * nb:
-                out.append(b[ib])
-                ib += 1
-        out.extend(b[ib:])
-        return out
 
     def epilogue(self):
         c, e = self.c, self.e
@@ -586,44 +552,6 @@ class Gen:
                 e("buffer_store_dwordx4 %s, %s, %s, %s offen" % (R("a", acc, 4), R("v", self.v_out), R("s", self.srdP, 4), R("s", self.s_t0)))
         e("s_waitcnt vmcnt(0)")
         e("s_endpgm")
-
-    def finish(self):
-        c = self.c
-        name = c.name
-        lds = c.LDS
-        assert lds <= 160 * 1024
-        total_v = self.accum_offset + self.nagpr
-        hdr = ['\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"', "\t.amdhsa_code_object_version 6", "\t.text", "\t.protected\t%s" % name,
-               "\t.globl\t%s" % name, "\t.p2align\t8", "\t.type\t%s,@function" % name, "%s:" % name]
-        tail = ["\t.section\t.rodata,\"a\",@progbits", "\t.p2align\t6, 0x0", "\t.amdhsa_kernel %s" % name]
-        kd = dict(group_segment_fixed_size=lds, private_segment_fixed_size=0, kernarg_size=self.KA["size"],
-                  user_sgpr_count=2, user_sgpr_dispatch_ptr=0, user_sgpr_queue_ptr=0, user_sgpr_kernarg_segment_ptr=1,
-                  user_sgpr_dispatch_id=0, user_sgpr_kernarg_preload_length=0, user_sgpr_kernarg_preload_offset=0,
-                  user_sgpr_private_segment_size=0, uses_dynamic_stack=0, enable_private_segment=0,
-                  system_sgpr_workgroup_id_x=1, system_sgpr_workgroup_id_y=1, system_sgpr_workgroup_id_z=0,
-                  system_sgpr_workgroup_info=0, system_vgpr_workitem_id=0, next_free_vgpr=total_v,
-                  next_free_sgpr=self.S.n, accum_offset=self.accum_offset, reserve_vcc=1, float_round_mode_32=0,
-                  float_round_mode_16_64=0, float_denorm_mode_32=3, float_denorm_mode_16_64=3, dx10_clamp=1, ieee_mode=1,
-                  fp16_overflow=0, tg_split=0)
-        for k, v in kd.items():
-            tail.append("\t\t.amdhsa_%s %d" % (k, v))
-        tail += ["\t.end_amdhsa_kernel", "\t.text", "\t.amdgpu_metadata", "---", "amdhsa.kernels:", "  - .agpr_count:     %d" % self.nagpr, "    .args:"]
-        off = 0
-        for i in range(3):
-            tail.append("      - .address_space:  global\n        .offset:         %d\n        .size:           8\n        .value_kind:     global_buffer" % off)
-            off += 8
-        for i in range((self.KA["size"] - off) // 4):
-            tail.append("      - .offset:         %d\n        .size:           4\n        .value_kind:     by_value" % off)
-            off += 4
-        tail += ["    .group_segment_fixed_size: %d" % lds, "    .kernarg_segment_align: 8", "    .kernarg_segment_size: %d" % self.KA["size"],
-                 "    .max_flat_workgroup_size: 256", "    .name:           %s" % name, "    .private_segment_fixed_size: 0",
-                 "    .sgpr_count:     %d" % (self.S.n + 6), "    .sgpr_spill_count: 0", "    .symbol:         %s.kd" % name,
-                 "    .uniform_work_group_size: 1", "    .uses_dynamic_stack: false", "    .vgpr_count:     %d" % total_v,
-                 "    .vgpr_spill_count: 0", "    .wavefront_size: 64", "amdhsa.target:   amdgcn-amd-amdhsa--gfx950",
-                 "amdhsa.version:\n  - 1\n  - 2", "...", "\t.end_amdgpu_metadata"]
-        body = self.out + ["\t.p2align 8", ".Lend_%s:" % name, "\t.size\t%s, .Lend_%s-%s" % (name, name, name)]
-        self.lds_bytes = lds
-        return "\n".join(hdr + body + tail) + "\n"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -652,25 +580,7 @@ VARIANTS = {
 }
 
 
-def generate(name, **over):
-    c = VARIANTS[name]
-    if over:
-        c = WCfg(**{**c.__dict__, **over})
-    g = Gen(c)
-    return c, g, g.gen()
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", required=True)
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    for name in VARIANTS:
-        c, g, text = generate(name)
-        with open(os.path.join(a.out, name + ".s"), "w") as f:
-            f.write(text)
-        print("%s: %d vgpr + %d agpr, lds %d, %d lines" % (name, g.accum_offset, g.nagpr, g.lds_bytes, text.count("\n")))
-
+generate = functools.partial(asm_common.generate, VARIANTS, Gen)
 
 if __name__ == "__main__":
-    main()
+    asm_common.main(VARIANTS, generate)

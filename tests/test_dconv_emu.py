@@ -324,6 +324,35 @@ def test_the_emulator_rejects_a_read_of_another_waves_dma_without_a_barrier():
     gcn_emu.Emulator(good, mem, lds_bytes=4096).run_workgroup(2, ka)
 
 
+@pytest.mark.parametrize("gen,base,sets,tbl_words", [
+    ("dconv_gen", "dconv_l1_s1", {"ROWS_T": 8}, 768),
+    ("pw_gen", "pw_k256_n1024_s1", {"MT": 6}, 128),
+    ("po_gen", "po_k256_b256_s1_a0", {"nt": 2}, None),
+])
+def test_the_tuning_command_line_writes_the_renamed_kernel_and_its_table(tmp_path, gen, base, sets, tbl_words):
+    """python <gen>.py --out DIR --set k=v --suffix SFX <variant> (tools/dconv_tune.sh, po_tune.sh, dconv_l1_rows.sh): the kernel renamed,
+    the overrides applied, and for dconv / pw the raw per-wave table dconv_bench.cpp passes as kernel arguments"""
+    import struct
+
+    asm = os.path.join(ROOT, "sota_imagenet_amd", "csrc", "asm")
+    sys.path.insert(0, asm)
+    mod = __import__(gen)
+    cmd = [sys.executable, os.path.join(asm, gen + ".py"), "--out", str(tmp_path), "--suffix", "_x", base]
+    for k, v in sets.items():
+        cmd[2:2] = ["--set", "%s=%d" % (k, v)]
+    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
+    c, g, text = mod.generate(base, name=base + "_x", **sets)
+    assert c.name == base + "_x" and all(getattr(c, k) == v for k, v in sets.items())
+    assert (tmp_path / (base + "_x.s")).read_text() == text
+    assert "\n%s_x:\n" % base in text
+    tbl = tmp_path / (base + "_x.tbl")
+    if tbl_words is None:
+        assert not tbl.exists()
+    else:
+        words = mod.table_words(c)
+        assert len(words) == tbl_words and tbl.read_bytes() == struct.pack("<%dI" % tbl_words, *words)
+
+
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="ROCm clang not installed")
 def test_every_shipped_variant_assembles_for_gfx950_within_the_register_and_lds_budget(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "sota_imagenet_amd", "csrc", "asm"))
@@ -338,8 +367,7 @@ def test_every_shipped_variant_assembles_for_gfx950_within_the_register_and_lds_
         for name in mod.VARIANTS:
             c, g, text = mod.generate(name)
             assert g.accum_offset + g.nagpr <= 512
-            lds = g.lds_bytes if hasattr(g, "lds_bytes") else c.LDS
-            assert lds <= 160 * 1024
+            assert g.lds_bytes <= 160 * 1024
             f = tmp_path / (name + ".s")
             f.write_text(text)
             subprocess.run([CLANG, "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", str(f), "-o", str(tmp_path / (name + ".o"))],
