@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""embed.py — the files dconv.cpp embeds.
+"""embed.py — the files gen_kernels.cpp embeds.
   embed.py kernels <out dir>           every shipped kernel of the six generators as <name>.s (each variant generated once) and one
                                        initialiser per kernel: dconv_meta.inc (direct 3x3 kernels), dconv_tt.inc (their transform tables,
                                        Cfg.bnin), pw_meta.inc (pointwise), wg_meta.inc / wg1_meta.inc (3x3 / 1x1 weight gradient),
@@ -20,7 +20,7 @@ INCLUDES = ("dconv_meta.inc", "dconv_tt.inc", "pw_meta.inc", "wg_meta.inc", "wg1
 
 
 def initialisers(mod, c, g):
-    """(include file, initialiser) of one generated kernel: the fields of its variant struct in dconv.cpp"""
+    """(include file, initialiser) of one generated kernel: the fields of its variant struct in gen_kernels.cpp"""
     ka = mod.Gen.KA["size"]
     if mod is dconv_gen:
         words = ",".join("%du" % w for par in dconv_gen.tables(c) for row in par for w in row)

@@ -124,26 +124,28 @@ struct WgradArgs {
 };
 
 // ---- kernel launchers (all enqueue on `stream`, return mi355_status) -------------------------------
+// The convolution (conv_select.cpp picks the kernel; what the conv sources call in one another is in conv_kernels.h).
 // stat_rows (optional): number of partial rows written to a.stat_partial, 0 if the statistics were not produced
+int launch_igemm(int dtype, const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows = nullptr);
 // does a generated kernel with the leaky form of the BN-backward sums (IgemmArgs::bn_slope == 0.01) take this launch?  (no other kernel has that epilogue)
 bool igemm_leaky_sums_legal(int dtype, const IgemmArgs& a, int nclass);
-int launch_igemm(int dtype, const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows = nullptr);
-bool igemm_sub2_legal(int dtype, const IgemmArgs& a, int nclass);
-bool dconv_fp8_legal(const IgemmArgs& a, int nclass);   // launch_igemm_fp8: the generated e4m3 3x3 kernel serves this launch
-int launch_dconv_fp8(const IgemmArgs& a, int nclass, float oscale, hipStream_t stream, int* stat_rows);
-bool igemm_bn_in_legal(int dtype, const IgemmArgs& a, int nclass);  // a launch with a.bn_in has a kernel (else: run bn_apply first)  // a launch with a.addend_sub2 has a kernel (else: materialise the addend)
+bool igemm_sub2_legal(int dtype, const IgemmArgs& a, int nclass);   // a launch with a.addend_sub2 has a kernel (else: materialise the addend)
+bool igemm_bn_in_legal(int dtype, const IgemmArgs& a, int nclass);  // a launch with a.bn_in has a kernel (else: run bn_apply first)
 static constexpr size_t IGEMM_SK_FLAG_BYTES = 4096;  // 512 flags + an error word, padded
 static constexpr int IGEMM_SK_ERR_WORD = 512;        // index of the error word in the flag block: nonzero = a stream-K
                                                      // hand-off timed out in some launch that used this scratch
 size_t igemm_sk_ws_bytes();
-// fp8 (e4m3) operands in `a.in` / `a.wt` (1-byte elements), bf16 output: the 8-wave kernel with 128-channel k-tiles (fp8.hip picks
-// the tile).  igemm_fp8_legal: geometry the kernel can run (Ck % 128, Ncols % 128, ...).
+// fp8 (e4m3) operands in `a.in` / `a.wt` (1-byte elements), bf16 output: the generated e4m3 3x3 kernel, else the 8-wave kernel with
+// 128-channel k-tiles (conv_select.cpp picks the tile).  igemm_fp8_legal: geometry the 8-wave kernel can run (Ck % 128, Ncols % 128, ...).
 bool igemm_fp8_legal(const IgemmArgs& a, int nclass);
 int launch_igemm_fp8(const IgemmArgs& a, int nclass, float oscale, hipStream_t stream, int* stat_rows = nullptr);
-// splits chosen by plan_wgrad_splits(); partial must hold splits*Cout*wtaps*Ck floats
+// The weight gradient (conv_wgrad.hip).  plan_wgrad_splits: the split count of the implicit-GEMM kernels.
+// plan_wgrad: the split count for THIS launch — the generated kernels (asm/wg_gen.py, wg1_gen.py; gen_kernels.cpp) have their own, every
+// other launch plan_wgrad_splits' — and what launch_wgrad must be given for the launch to take the kernel the plan was made for;
+// partial must hold splits*Cout*wtaps*Ck floats
 int plan_wgrad_splits(int dtype, int M, int Cout, int ntaps, int Ck);
-// plan_wgrad: the split count for THIS launch — the generated 3x3 kernels (asm/wg_gen.py, dconv.cpp) have their own, every other
-// launch plan_wgrad_splits' — and what launch_wgrad must be given for the launch to take the kernel the plan was made for
+int plan_wgrad(int dtype, const WgradArgs& a);
+int launch_wgrad(int dtype, const WgradArgs& a, int splits, hipStream_t stream);
 // Per-launch tile knobs of the conv launchers (test hooks and A/B switches: MI355_IGEMM8, MI355_IGEMM_BIG, MI355_STEM_DIRECT, MI355_STEM_TH,
 // MI355_STEM_DBG): read from the environment ONCE and on mi355_reload_knobs() — no getenv on a launch path.
 struct Knobs {
@@ -182,13 +184,9 @@ inline int env_switch(const char* name, int def, int maxv, const char** bad) {
   if (bad && !*bad) *bad = name;
   return def;
 }
-int plan_wgrad(int dtype, const WgradArgs& a);
-int wg3_plan(int dtype, const WgradArgs& a);  // 0: the launch is not served by a generated kernel
 // name of the kernel the last conv / weight-gradient launch of this thread went to (a generated kernel's symbol, or the implicit-GEMM
 // tile family): tests assert the selection rules with it (mi355_last_conv_kernel)
 void note_kernel(const char* fmt, ...);
-int launch_wg3(const WgradArgs& a, int splits, hipStream_t stream);
-int launch_wgrad(int dtype, const WgradArgs& a, int splits, hipStream_t stream);
 // dst[i] = beta*dst[i] + sum_s partial[s][i], i < n  (n multiple of 4); deterministic order
 // sa / sb (optional device scalars, fp8 wgrad): the sum is multiplied by 1 / (*sa * *sb) before beta * dst is added
 int launch_splitk_reduce(const float* partial, int splits, size_t stride, float* dst, size_t n, float beta,

@@ -7,7 +7,7 @@
 #include <set>
 #include <string>
 
-#include "common.h"
+#include "conv_kernels.h"
 
 namespace mi355 {
 
@@ -34,6 +34,16 @@ int probe_env(const char* name) {
       fprintf(stderr, "libmi355rn: %s=%d — timing probe active: kernels skip loads / stores, RESULTS ARE NOT VALID\n", name, x);
   }
   return x;
+}
+
+void lds_opt_in(const void* fn, size_t lds) {
+  if (lds <= 64 * 1024) return;
+  static std::mutex mu;
+  static std::set<const void*> done;
+  std::lock_guard<std::mutex> g(mu);
+  if (done.count(fn)) return;
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  done.insert(fn);
 }
 
 // compute units of the current device (hipDeviceProp), the unit every persistent-grid size in this library is a multiple of;

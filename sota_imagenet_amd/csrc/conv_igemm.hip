@@ -9,7 +9,7 @@
 //   tile        BM pixels x BN channels; K advances in 128-byte slabs of the tap's channel run.  Instantiations (see the
 //               kernel's own comment for why each exists): 128 x 64 and 128 x 128 (4 waves, 2-stage ring, 3 resp. 2
 //               workgroups per CU — the default), 256 x 256 (4 waves, 1 per CU) and 256 x 128 (8 waves, 3-stage ring,
-//               1 per CU) for the bf16 launches the rules in launch_igemm() select.
+//               1 per CU) for the bf16 launches the rules in conv_select.cpp select.
 //   MFMA        waves in a WMW x 2 grid, each BM/WMW x BN/2 from 32x32 tiles: v_mfma_f32_32x32x2_f32 (exact fp32, the
 //               parity path) / v_mfma_f32_32x32x16_bf16 (fp32 accumulate).  Operands are swapped (D^T = W * A^T) so a
 //               lane ends up holding 4 consecutive channels of one pixel.
@@ -32,11 +32,9 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_kernels.h"
 #include "lds_dma.h"
 #include "vec.h"
 
@@ -673,17 +671,6 @@ __global__ __launch_bounds__(128 * WMW, (BM == 256 ? 1 : (BN == 64 && NSTG == 2 
   }
 }
 
-// > 64 KiB of dynamic LDS needs an opt-in per kernel symbol (once)
-void lds_opt_in(const void* fn, size_t lds) {
-  if (lds <= 64 * 1024) return;
-  static std::mutex mu;
-  static std::set<const void*> done;
-  std::lock_guard<std::mutex> g(mu);
-  if (done.count(fn)) return;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  done.insert(fn);
-}
-
 template <typename T, int BM, int BN, int WMW = 2, int NSTG = 2>
 int launch_t(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows) {
   constexpr int NT = 128 * WMW;
@@ -804,135 +791,16 @@ int launch_t(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows)
 
 size_t igemm_sk_ws_bytes() { return IGEMM_SK_FLAG_BYTES + (size_t)512 * 128 * 128 * sizeof(float); }
 
-// stem_direct.hip: the stem as a direct convolution
-bool stem_direct_legal(const IgemmArgs& a, int nclass);
-int launch_stem_direct(const IgemmArgs& a, hipStream_t stream, int* stat_rows);
-
-// dconv.cpp: the generated one-wave-per-SIMD direct 3x3 / stride-1 kernels (asm/dconv_gen.py) for the layer-3 / layer-4 shapes
-bool dconv_legal(const IgemmArgs& a, int nclass);
-int launch_dconv(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows);
-bool pw_legal(const IgemmArgs& a, int nclass);  // the persistent pointwise kernels (asm/pw_gen.py): output-heavy 1x1 forward
-int launch_pw(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows);
-bool pk_legal(const IgemmArgs& a, int nclass);  // the long-reduction pointwise kernels (asm/pk_gen.py): K = 1024 / 2048 -> 256-column tiles
-int launch_pk(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows);
-bool po_legal(const IgemmArgs& a, int nclass);  // the output-heavy pointwise kernels with resident weights (asm/po_gen.py): K <= 512 -> 4K columns, shortcut addend, BN-backward sums
-int launch_po(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows);
-
-// conv_igemm8.hip
-bool igemm8_legal(const IgemmArgs& a, int nclass, int bn);
-int launch_igemm8(const IgemmArgs& a, int nclass, int bm, int bn, int korder, int fat, hipStream_t stream, int* stat_rows);
-
-// Which bf16 launches go to the 8-wave ping-pong kernel, and with which tile.  MI355_IGEMM8 in the environment:
-//   "0" never;  "<BM>x<BN>[k][f]" (e.g. 256x256, 224x128kf) forces that tile wherever it is legal (k: channel chunks
-//   outer, taps inner; f: the fat-phase form);  unset: the measured rule below.
-static bool choose_igemm8(const IgemmArgs& a, int nclass, int* bm, int* bn, int* korder, int* fat) {
-  const char* env = knobs().has_igemm8 ? knobs().igemm8 : nullptr;
-  if (env && env[0] == '0') return false;
-  if (env && env[0]) {
-    int m = 0, n = 0;
-    char k1 = 0, k2 = 0;
-    if (sscanf(env, "%dx%d%c%c", &m, &n, &k1, &k2) >= 2 && (m == 256 || m == 224) && (n == 256 || n == 128) && igemm8_legal(a, nclass, n)) {
-      *bm = m; *bn = n; *korder = k1 == 'k' || k2 == 'k'; *fat = k1 == 'f' || k2 == 'f';
-      return true;
-    }
-    return false;
-  }
-  // Measured per layer shape at batch 256 (tools/conv8_check.py, same-process A/B against the 4-wave tiles):
-  //  - >= 256 output columns and a reduction of >= 256: the 224 x 256 tile wins on every layer-3/4 shape as long as its
-  //    tile count still covers most of the 256 CUs (it is bound by fragment reads + LDS-DMA issue, not by MFMAs, and a
-  //    224-row tile has 1/8 fewer A reads than a 256-row one; 224 divides the 49 * 2^k * N pixel counts);
-  //  - the 512-column layer-4 3x3 (98 tiles of 256 x 256, 112 of 224 x 256): 256 x 128 fat phases, 196 tiles.
-  int max_taps = 0;
-  for (int ci = 0; ci < nclass; ++ci) max_taps = a.cls[ci].ntaps > max_taps ? a.cls[ci].ntaps : max_taps;
-  const long K = (long)max_taps * a.Ck;
-  const long M = (long)a.N * a.Hsub * a.Wsub;
-  //  - NOT the output-heavy launches: one workgroup per CU runs its epilogue with the matrix pipe idle, so a short
-  //    reduction under a long epilogue (conv1's dgrad: K = 256 / 512 into 1024 / 2048 columns, + shortcut addend + the
-  //    BN-backward sums) loses 10-65 us per launch against two independent 4-wave workgroups per CU, and so does a
-  //    multi-round launch of short tap classes (the stride-2 3x3 dgrad of layer 3) — measured in the executor,
-  //    profiles/r02a_conv_per_layer_bf16_serial_{old,rule}.txt.
-  const bool heavy_epilogue = (a.addend != nullptr && K < 1024);
-  // k order of a multi-tap launch: channel chunks outer, taps inner — the 9 taps of a 64-channel chunk re-read the same
-  // A rows back to back, so they are served from the XCD's L2 instead of being fetched again from beyond it (layer-4 3x3:
-  // 373 -> see 77 MB per launch for 25.7 MB of activations, profiles/r02c_pmc_per_conv_launch_bf16_serial.txt; same speed)
-  const int ko = (max_taps > 1 && a.Ck > 64) ? 1 : 0;
-  if (a.Ncols % 256 == 0 && K >= 256 && !heavy_epilogue && igemm8_legal(a, nclass, 256)) {
-    const long tiles = ((M + 223) / 224) * nclass * (a.Ncols / 256);
-    const int cus = device_cus();  // thresholds measured on 256 CUs, kept as fractions of the chip (0.7 of a round; two rounds)
-    if (tiles * 10 >= 7L * cus && !(nclass > 1 && tiles > 2L * cus && max_taps > 1)) {
-      *bm = 224; *bn = 256; *korder = ko; *fat = 0;
-      return true;
-    }
-  }
-  if (a.Ncols % 128 == 0 && K >= 4096 && igemm8_legal(a, nclass, 128)) {
-    const long tiles = ((M + 255) / 256) * nclass * (a.Ncols / 128);
-    if (tiles * 10 >= 7L * device_cus() && tiles <= device_cus()) {
-      *bm = 256; *bn = 128; *korder = ko; *fat = 1;
-      return true;
-    }
-  }
-  return false;
-}
-
-bool igemm_leaky_sums_legal(int dtype, const IgemmArgs& a, int nclass) {
-  if (dtype != MI355_BF16 || !a.bn_y || !a.stat_partial || a.bn_slope != 0.01f || knobs().error[0]) return false;
-  return dconv_legal(a, nclass) || po_legal(a, nclass) || pk_legal(a, nclass);
-}
-
-int launch_igemm(int dtype, const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows) {
-  const int bk = BKB / (int)dtype_size(dtype);
-  MI355_ARG(a.in && a.wt && a.out, "igemm: null pointer");
-  MI355_ARG(a.Ck % bk == 0, "igemm: Ck=%d not a multiple of %d", a.Ck, bk);
-  MI355_ARG(a.Ncols % 64 == 0, "igemm: Ncols=%d not a multiple of 64", a.Ncols);
-  MI355_ARG(nclass >= 1 && nclass <= 4, "igemm: nclass=%d", nclass);
-  MI355_ARG(((size_t)a.pix_stride * dtype_size(dtype)) % 8 == 0, "igemm: pixel stride not 8-byte aligned");
-  MI355_ARG(a.N > 0 && a.Hsub > 0 && a.Wsub > 0, "igemm: empty problem");
-  MI355_ARG(!knobs().error[0], "%s", knobs().error);
-  // BN = 128 unless that leaves most of the 256 CUs without a tile (the FC layer: 256 rows): then 64-wide tiles double
-  // the workgroups
-  const long tiles128 = (long)cdiv(a.N * a.Hsub * a.Wsub, 128) * nclass * (a.Ncols / 128);
-  const bool wide = (a.Ncols % 128 == 0) && tiles128 * 2 >= device_cus();
-  MI355_ARG(dtype == MI355_BF16 || !a.addend_sub2, "igemm: a half-resolution addend needs the generated pointwise kernel (igemm_sub2_legal)");
-  MI355_ARG(a.bn_slope == 0.f || igemm_leaky_sums_legal(dtype, a, nclass), "igemm: BN-backward sums under a leaky mask need a generated kernel with that epilogue and slope 0.01 (igemm_leaky_sums_legal)");
-  MI355_ARG(a.bn_in == nullptr || igemm_bn_in_legal(dtype, a, nclass), "igemm: the input's BatchNorm in the operand path needs a generated kernel with that form (igemm_bn_in_legal)");
-  if (dtype == MI355_F32)
-    return wide ? launch_t<float, 128, 128>(a, nclass, stream, stat_rows) : launch_t<float, 128, 64>(a, nclass, stream, stat_rows);
-  if (dtype == MI355_BF16) {
-    if (dconv_legal(a, nclass)) return launch_dconv(a, nclass, stream, stat_rows);
-    if (po_legal(a, nclass)) return launch_po(a, nclass, stream, stat_rows);
-    MI355_ARG(!a.addend_sub2, "igemm: a half-resolution addend needs the generated pointwise kernel (igemm_sub2_legal)");
-    if (pw_legal(a, nclass)) return launch_pw(a, nclass, stream, stat_rows);
-    if (pk_legal(a, nclass)) return launch_pk(a, nclass, stream, stat_rows);
-    {
-      // the stem as a direct convolution out of raw input rows (stem_direct.hip; MI355_STEM_DIRECT=0: the row-pair implicit GEMM)
-      if (knobs().stem_direct && stem_direct_legal(a, nclass)) return launch_stem_direct(a, stream, stat_rows);
-    }
-    {
-      int bm8 = 0, bn8 = 0, ko8 = 0, fat8 = 0;
-      if (choose_igemm8(a, nclass, &bm8, &bn8, &ko8, &fat8)) return launch_igemm8(a, nclass, bm8, bn8, ko8, fat8, stream, stat_rows);
-    }
-    // 256 x 256 tiles (bf16 only: fp32 MFMAs are slow enough that the LDS port is not the limit).  Measured per layer
-    // shape at batch 256 (tools/one_conv.py): they win when the 256 single-workgroup CUs are still mostly filled
-    // (>= 192 tiles) and the reduction is long enough to amortise the larger epilogue (K >= 256); they lose on the
-    // HBM-bound layer-1/2 shapes and when layer 4's 98 row tiles leave most CUs idle.
-    const int big_mode = knobs().has_igemm_big ? knobs().igemm_big : -1;  // MI355_IGEMM_BIG: 0 never / 1 wherever N % 256 == 0 (tests, A/B); unset: the rule
-    const long items256 = (long)cdiv(a.N * a.Hsub * a.Wsub, 256) * nclass * (a.Ncols / 256);
-    int max_taps = 0;
-    for (int ci = 0; ci < nclass; ++ci) max_taps = a.cls[ci].ntaps > max_taps ? a.cls[ci].ntaps : max_taps;
-    // (not with the BN-backward sums: that epilogue needs more registers than the 256 x 256 tile leaves)
-    const int cus = device_cus();
-    const bool big = a.Ncols % 256 == 0 && (big_mode < 0 ? (items256 * 4 >= 3L * cus && max_taps * a.Ck >= 256 && !a.bn_y) : big_mode == 1);
-    if (big) return launch_t<bf16_t, 256, 256>(a, nclass, stream, stat_rows);
-    // 256 x 128, 8 waves, 3-stage ring: per CU and k-step 8 % faster than two 128 x 128 workgroups (the slab wait drops
-    // from ~700 to ~200 cycles), but a partial round costs it a full one where the 2-workgroup form speeds up when a CU
-    // holds a single workgroup — so only where all its tiles fit into one round, and the reduction is long
-    const long items3 = (long)cdiv(a.N * a.Hsub * a.Wsub, 256) * nclass * (a.Ncols / 128);
-    const bool tall = a.Ncols % 128 == 0 &&
-                      (big_mode < 0 ? ((items3 <= cus && items3 * 2 >= cus && max_taps * a.Ck >= 512) || (items3 <= 2L * cus && max_taps == 1 && a.Ck >= 1024)) : big_mode == 3);
-    if (tall) return launch_t<bf16_t, 256, 128, 4, 3>(a, nclass, stream, stat_rows);
-    return wide ? launch_t<bf16_t, 128, 128>(a, nclass, stream, stat_rows) : launch_t<bf16_t, 128, 64>(a, nclass, stream, stat_rows);
-  }
-  set_error("igemm: bad dtype %d", dtype);
+// the instantiated tiles by their run-time parameters (conv_select.cpp picks them): fp32 128 x 128 and 128 x 64; bf16 256 x 256,
+// 256 x 128 (8 waves, 3-stage ring), 128 x 128 and 128 x 64
+int launch_igemm_tile(int dtype, const IgemmArgs& a, int nclass, int bm, int bn, hipStream_t stream, int* stat_rows) {
+  if (dtype == MI355_F32 && bm == 128 && bn == 128) return launch_t<float, 128, 128>(a, nclass, stream, stat_rows);
+  if (dtype == MI355_F32 && bm == 128 && bn == 64) return launch_t<float, 128, 64>(a, nclass, stream, stat_rows);
+  if (dtype == MI355_BF16 && bm == 256 && bn == 256) return launch_t<bf16_t, 256, 256>(a, nclass, stream, stat_rows);
+  if (dtype == MI355_BF16 && bm == 256 && bn == 128) return launch_t<bf16_t, 256, 128, 4, 3>(a, nclass, stream, stat_rows);
+  if (dtype == MI355_BF16 && bm == 128 && bn == 128) return launch_t<bf16_t, 128, 128>(a, nclass, stream, stat_rows);
+  if (dtype == MI355_BF16 && bm == 128 && bn == 64) return launch_t<bf16_t, 128, 64>(a, nclass, stream, stat_rows);
+  set_error("igemm: no %dx%d tile for dtype %d", bm, bn, dtype);
   return MI355_E_ARG;
 }
 

@@ -32,11 +32,9 @@
 //               pixels.  Statistics: per-lane sums over the wave's pixels, a fixed-order DPP row reduction, ONE lane per
 //               (wave, channel) adds into the workgroup's LDS accumulator, one flush per workgroup — no atomics.
 #include <cstdlib>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_kernels.h"
 #include "lds_dma.h"
 #include "vec.h"
 
@@ -44,17 +42,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 namespace mi355 {
 
 namespace {
-
-// > 64 KiB of dynamic LDS needs an opt-in per kernel symbol (once)
-void lds_opt_in8(const void* fn, size_t lds) {
-  if (lds <= 64 * 1024) return;
-  static std::mutex mu;
-  static std::set<const void*> done;
-  std::lock_guard<std::mutex> g(mu);
-  if (done.count(fn)) return;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  done.insert(fn);
-}
 
 __device__ __attribute__((aligned(256))) unsigned char g8_trash[512 * 16];
 
@@ -803,8 +790,6 @@ __global__ __launch_bounds__(512, 2) void igemm8_kernel(const Igemm8KArgs kp) {
 #endif
 }
 
-unsigned magic32(unsigned d) { return (unsigned)((1ull << 32) / d + 1); }
-
 template <int BM, int BN, int FAT, int EB = 2>
 int launch8_t(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows, int korder, float oscale = 1.f) {
   static_assert(EB == 2 || EB == 1, "EB");
@@ -876,14 +861,14 @@ int launch8_t(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows
   if (stats) {
     lds += (size_t)2 * chan * 2 * sizeof(float);
     if (a.bn_y) {
-      lds_opt_in8((const void*)igemm8_kernel<BM, BN, 2, FAT, EB>, lds);
+      lds_opt_in((const void*)igemm8_kernel<BM, BN, 2, FAT, EB>, lds);
       hipLaunchKernelGGL((igemm8_kernel<BM, BN, 2, FAT, EB>), dim3(grid), dim3(512), lds, stream, k);
     } else {
-      lds_opt_in8((const void*)igemm8_kernel<BM, BN, 1, FAT, EB>, lds);
+      lds_opt_in((const void*)igemm8_kernel<BM, BN, 1, FAT, EB>, lds);
       hipLaunchKernelGGL((igemm8_kernel<BM, BN, 1, FAT, EB>), dim3(grid), dim3(512), lds, stream, k);
     }
   } else {
-    lds_opt_in8((const void*)igemm8_kernel<BM, BN, 0, FAT, EB>, lds);
+    lds_opt_in((const void*)igemm8_kernel<BM, BN, 0, FAT, EB>, lds);
     hipLaunchKernelGGL((igemm8_kernel<BM, BN, 0, FAT, EB>), dim3(grid), dim3(512), lds, stream, k);
   }
   MI355_LAUNCH_CHECK();

@@ -24,7 +24,7 @@
 // splitk_reduce (bitwise reproducible, no float atomics).
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_kernels.h"
 #include "lds_dma.h"
 
 namespace mi355 {

@@ -3,7 +3,8 @@
 // BASELINE.json configs[4] asks for "fp8 MFMA convs".  gfx950 runs the non-scaled fp8 MFMAs at the bf16 matrix rate
 // (MI355X_MICROARCH.md § Matrix cores), so what fp8 operands buy is bytes: half the HBM / L2 / LDS traffic per MAC, and —
 // decisive for the 8-wave kernel, which is bound by its fragment reads — one ds_read_b128 per TWO MFMAs.
-// The convolution itself is conv_igemm8.hip with EB = 1; this file holds the element-wise quantiser and the C-ABI wrappers.
+// The convolution itself is conv_igemm8.hip with EB = 1 (conv_select.cpp picks its tile); this file holds the element-wise quantiser
+// and the C-ABI wrappers.
 // Scaling is per tensor: q = sat_e4m3(x * scale); the conv output is (sum q_x * q_w) / (scale_x * scale_w) in bf16.
 #include <hip/hip_fp8.h>
 
@@ -11,9 +12,6 @@
 #include "vec.h"
 
 namespace mi355 {
-
-int launch_igemm8_fp8(const IgemmArgs& a, int nclass, int bm, int bn, int korder, float oscale, hipStream_t stream, int* stat_rows);
-bool igemm8_fp8_legal(const IgemmArgs& a, int nclass, int bn);
 
 namespace {
 
@@ -34,15 +32,6 @@ __global__ __launch_bounds__(256) void quantize_fp8_kernel(const T* x, unsigned 
   }
 }
 
-int pick_tile(const IgemmArgs& a, int nclass, int* bm, int* bn) {
-  // the wide tile when it alone fills most of the 256 CUs (same threshold as the bf16 rule, conv_igemm.hip::choose_igemm8)
-  const long long M = (long long)a.N * a.Hsub * a.Wsub;
-  if (a.Ncols % 256 == 0 && ((M + 223) / 224) * nclass * (a.Ncols / 256) * 10 >= 7LL * device_cus()) { *bm = 224; *bn = 256; return 0; }
-  if (a.Ncols % 128 == 0) { *bm = 256; *bn = 128; return 0; }
-  set_error("conv fp8: %d output columns (a multiple of 128 is needed)", a.Ncols);
-  return MI355_E_ARG;
-}
-
 // delayed per-tensor scaling: the amax a tensor's producer recorded in the previous step sets this step's scale
 __global__ void fp8_scale_update_kernel(float* scale, unsigned* amax, int n, float headroom) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -53,18 +42,6 @@ __global__ void fp8_scale_update_kernel(float* scale, unsigned* amax, int n, flo
 }
 
 }  // namespace
-
-bool igemm_fp8_legal(const IgemmArgs& a, int nclass) { return igemm8_fp8_legal(a, nclass, 128); }
-
-int launch_igemm_fp8(const IgemmArgs& a, int nclass, float oscale, hipStream_t stream, int* stat_rows) {
-  // the stride-1 3x3 launches of layers 2 - 4: the generated direct kernel on the K = 128 MFMA (asm/dconv_gen.py Cfg.fp8)
-  if (dconv_fp8_legal(a, nclass)) return launch_dconv_fp8(a, nclass, oscale, stream, stat_rows);
-  int bm, bn;
-  MI355_TRY(pick_tile(a, nclass, &bm, &bn));
-  int max_taps = 0;
-  for (int ci = 0; ci < nclass; ++ci) max_taps = a.cls[ci].ntaps > max_taps ? a.cls[ci].ntaps : max_taps;
-  return launch_igemm8_fp8(a, nclass, bm, bn, max_taps > 1 ? 1 : 0, oscale, stream, stat_rows);
-}
 
 int launch_fp8_scale_update(float* scale, unsigned* amax, int n, float headroom, hipStream_t s) {
   hipLaunchKernelGGL(fp8_scale_update_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, scale, amax, n, headroom);

@@ -1,11 +1,11 @@
-// dconv.cpp — host side of the generated direct 3x3 / stride-1 convolution kernels (asm/dconv_gen.py): the code object is
-// embedded in this library, loaded per device with hipModuleLoadData, and launched with the IgemmArgs contract of
-// launch_igemm() (conv forward / data gradient under `model(data)` / `loss.backward()`,
-// /root/reference/sota_imagenet/callbacks.py:316-317).
+// gen_kernels.cpp — host side of the generated gfx950 kernel families (asm/*_gen.py: dconv, pw, pk, po, wg, wg1): the one code object
+// is embedded in this library, loaded per device with hipModuleLoadData, and launched with the IgemmArgs contract of launch_igemm()
+// (conv forward / data gradient under `model(data)` / `loss.backward()`, sota_imagenet/callbacks.py:316-317 of the reference) and the
+// WgradArgs contract of launch_wgrad().
 #include <cstdlib>
 #include <mutex>
 
-#include "common.h"
+#include "conv_kernels.h"
 
 namespace mi355 {
 
@@ -91,22 +91,23 @@ alignas(4096) const unsigned char g_blob[] = {
 #include "build/asm/dconv_blob.inc"
 };
 
+// every kernel of the code object in ONE table per device, family after family: a family's variant i is kernel <its base> + i
+constexpr int B_DCONV = 0, B_PW = B_DCONV + NVAR, B_WG = B_PW + NPW, B_PK = B_WG + NWG, B_WG1 = B_PK + NPK, B_PO = B_WG1 + NWG1, NKERN = B_PO + NPO;
+const char* kernel_name(int k) {
+  return k >= B_PO ? g_po[k - B_PO].name : k >= B_WG1 ? g_wg1[k - B_WG1].name : k >= B_PK ? g_pk[k - B_PK].name : k >= B_WG ? g_wg[k - B_WG].name : k >= B_PW ? g_pw[k - B_PW].name : g_variants[k].name;
+}
+
 struct DevState {
   bool ok = false;
   int attempts = 0;
   hipModule_t mod = nullptr;
-  hipFunction_t fn[NVAR] = {};
-  hipFunction_t pw[NPW] = {};
-  hipFunction_t wg[NWG] = {};
-  hipFunction_t pk[NPK] = {};
-  hipFunction_t wg1[NWG1] = {};
-  hipFunction_t po[NPO] = {};
+  hipFunction_t fn[NKERN] = {};
 };
 DevState g_dev[64];
 std::mutex g_mu;
 
 // loads the module on the current device (once); false with the error set when the runtime refuses it.  A refusal is remembered per
-// device ("failed"): the *_legal() checks below then keep every launch on the implicit-GEMM kernels instead of failing it, and one line
+// device ("failed"): the *_pick() checks below then keep every launch on the implicit-GEMM kernels instead of failing it, and one line
 // on stderr says so.  A transient refusal (out of memory at load time) is retried a few times before it is taken as final.
 bool dev_state(DevState** out) {
   int dev = 0;
@@ -121,17 +122,10 @@ bool dev_state(DevState** out) {
     hipError_t e = hipSuccess;
     const char* what = "hipModuleLoadData";
     if (d.mod == nullptr) e = hipModuleLoadData(&d.mod, g_blob);
-    auto get = [&](hipFunction_t* f, const char* name) {
-      if (e != hipSuccess) return;
-      e = hipModuleGetFunction(f, d.mod, name);
-      if (e != hipSuccess) what = name;
-    };
-    for (int i = 0; i < NVAR; ++i) get(&d.fn[i], g_variants[i].name);
-    for (int i = 0; i < NPW; ++i) get(&d.pw[i], g_pw[i].name);
-    for (int i = 0; i < NWG; ++i) get(&d.wg[i], g_wg[i].name);
-    for (int i = 0; i < NPK; ++i) get(&d.pk[i], g_pk[i].name);
-    for (int i = 0; i < NWG1; ++i) get(&d.wg1[i], g_wg1[i].name);
-    for (int i = 0; i < NPO; ++i) get(&d.po[i], g_po[i].name);
+    for (int k = 0; k < NKERN && e == hipSuccess; ++k) {
+      e = hipModuleGetFunction(&d.fn[k], d.mod, kernel_name(k));
+      if (e != hipSuccess) what = kernel_name(k);
+    }
     if (e != hipSuccess) {
       (void)hipGetLastError();
       set_error("dconv: %s -> %s", what, hipGetErrorString(e));
@@ -152,10 +146,18 @@ bool dev_state(DevState** out) {
   return true;
 }
 
-// the generated kernels can be launched on the current device (loads the module on first use)
-bool module_ok() {
-  DevState* d = nullptr;
-  return dev_state(&d);
+// the launch tail of every family (`tag`: its name in the error text): kernarg buffer, 256-thread workgroups, the statistics rows
+// written (`rows`, reported through stat_rows when given), the kernel's name for mi355_last_conv_kernel
+int launch_kernel(const char* tag, int k, hipFunction_t fn, unsigned gx, unsigned gy, void* kargs, size_t ksize, hipStream_t stream, int* stat_rows = nullptr, int rows = 0) {
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kargs, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksize, HIP_LAUNCH_PARAM_END};
+  const hipError_t e = hipModuleLaunchKernel(fn, gx, gy, 1, 256, 1, 1, 0, stream, nullptr, extra);
+  if (e != hipSuccess) {
+    set_error("%s: hipModuleLaunchKernel(%s) -> %s", tag, kernel_name(k), hipGetErrorString(e));
+    return MI355_E_HIP;
+  }
+  if (stat_rows) *stat_rows = rows;
+  note_kernel("%s", kernel_name(k));
+  return 0;
 }
 
 // the 9 taps of a stride-1 3x3 class as wtap[(dh + 1)*3 + (dw + 1)], false when the class is not that pattern
@@ -197,46 +199,54 @@ bool s2d_tap_table(const IgemmArgs& a, int nclass, int wtap[9]) {
   return slot == 9;
 }
 
-int find_variant_s2d(const IgemmArgs& a, int nclass, int stats) {
-  if (nclass != 4 || a.IS != 1 || a.OS != 2 || a.pair_delta != 0 || a.wtaps != 9) return -1;
-  if (a.Hsub != a.Hin || a.Wsub != a.Win || a.Hout != 2 * a.Hin || a.Wout != 2 * a.Win) return -1;
-  if (a.pix_stride != a.Ck || a.addend != nullptr || a.q_scale_in != nullptr || a.q_scale_wt != nullptr) return -1;
-  if (stats == 1) return -1;
-  int wtap[9];
-  if (!s2d_tap_table(a, nclass, wtap)) return -1;
-  for (int i = 0; i < NVAR; ++i) {
-    const DconvVariant& v = g_variants[i];
-    if (v.s2d && v.H == a.Hin && v.W == a.Win && v.Cin == a.Ck && v.NCOLS == a.Ncols && v.stats == stats && a.N % v.IPT == 0) return i;
-  }
-  return -1;
+// a 3x3 over dense pixels (pix_stride == Ck) without an addend whose sub-grid is the whole input and whose output is `os` times its extent:
+// the stride-1 convolution (os = 1) or the data gradient of a stride-2 one (os = 2)
+bool plain_3x3(const IgemmArgs& a, int os) {
+  if (a.IS != 1 || a.OS != os || a.pair_delta != 0 || a.wtaps != 9) return false;
+  if (a.Hsub != a.Hin || a.Wsub != a.Win || a.Hout != os * a.Hin || a.Wout != os * a.Win) return false;
+  return a.pix_stride == a.Ck && a.addend == nullptr;
 }
 
-int find_variant(const IgemmArgs& a, int nclass, int stats, int fp8 = 0) {
-  if (nclass == 4) return fp8 ? -1 : find_variant_s2d(a, nclass, stats);
-  if (nclass != 1 || a.IS != 1 || a.OS != 1 || a.pair_delta != 0 || a.wtaps != 9) return -1;
-  if (a.Hsub != a.Hin || a.Wsub != a.Win || a.Hout != a.Hin || a.Wout != a.Win) return -1;
-  if (a.pix_stride != a.Ck || a.addend != nullptr) return -1;  // (sk_ws is optional scratch: not needed here)
+// a bf16 1x1 / stride 1 over dense pixels, input and output of the same extent (an addend is the caller's business)
+bool plain_1x1(const IgemmArgs& a, int nclass) {
+  if (nclass != 1 || a.IS != 1 || a.OS != 1 || a.pair_delta != 0 || a.wtaps != 1 || a.cls[0].ntaps != 1) return false;
+  if (a.cls[0].taps[0].dh != 0 || a.cls[0].taps[0].dw != 0 || a.cls[0].taps[0].wtap != 0 || a.cls[0].ph != 0 || a.cls[0].pw != 0) return false;
+  if (a.Hsub != a.Hin || a.Wsub != a.Win || a.Hout != a.Hin || a.Wout != a.Win) return false;
+  return a.pix_stride == a.Ck && a.q_scale_in == nullptr && a.q_scale_wt == nullptr;
+}
+
+// a bf16 weight gradient of a `taps`-tap (9: 3x3, 1: 1x1) stride-1 convolution over dense pixels, taps in row-major order
+bool plain_wgrad(int dtype, const WgradArgs& a, int taps) {
+  if (dtype != MI355_BF16 || a.ntaps != taps || a.wtaps != taps || a.IS != 1 || a.pair_delta != 0) return false;
+  if (a.Ho != a.Hin || a.Wo != a.Win || a.pix_stride != a.Ck) return false;
+  const int r = taps == 9 ? 1 : 0;
+  for (int t = 0; t < taps; ++t)
+    if (a.taps[t].dh != t / 3 - r || a.taps[t].dw != t % 3 - r || a.taps[t].wtap != t) return false;
+  return true;
+}
+
+// the direct 3x3 kernel of this launch, or -1: stride 1 (one class), or the data gradient of a stride-2 3x3 by its four output-parity
+// classes (s2d: bf16 only, no BN statistics of the output, and an input BatchNorm is not its business)
+int find_variant(const IgemmArgs& a, int nclass, int stats, int fp8) {
+  const int s2d = nclass == 4 ? 1 : 0;
+  if ((nclass != 1 && nclass != 4) || !plain_3x3(a, s2d ? 2 : 1) || (s2d && (fp8 || stats == 1))) return -1;  // (sk_ws is optional scratch: not needed here)
   if (!fp8 && (a.q_scale_in != nullptr || a.q_scale_wt != nullptr)) return -1;
   if (fp8 && ((a.q_scale_in == nullptr) != (a.q_scale_wt == nullptr) || a.bn_in != nullptr)) return -1;
   int wtap[9];
-  if (!tap_table(a.cls[0], wtap)) return -1;
-  const int bnin = a.bn_in != nullptr ? 1 : 0;
+  if (!(s2d ? s2d_tap_table(a, nclass, wtap) : tap_table(a.cls[0], wtap))) return -1;
+  const int bnin = !s2d && a.bn_in != nullptr ? 1 : 0;
   if (bnin && (a.bn_in_a == nullptr || a.bn_in_bits == nullptr)) return -1;
   for (int i = 0; i < NVAR; ++i) {
     const DconvVariant& v = g_variants[i];
-    if (v.bnin != bnin || v.fp8 != fp8) continue;
-    if (!v.s2d && v.H == a.Hin && v.W == a.Win && v.Cin == a.Ck && v.NCOLS == a.Ncols && v.stats == stats && a.N % v.IPT == 0) return i;
+    if (v.s2d != s2d || v.bnin != bnin || v.fp8 != fp8) continue;
+    if (v.H == a.Hin && v.W == a.Win && v.Cin == a.Ck && v.NCOLS == a.Ncols && v.stats == stats && a.N % v.IPT == 0) return i;
   }
   return -1;
 }
 
 // the persistent pointwise kernel that can run this launch (1x1, stride 1, no addend, statistics 0 / 1), or -1
 int find_pw(const IgemmArgs& a, int nclass, int stats) {
-  if (nclass != 1 || a.IS != 1 || a.OS != 1 || a.pair_delta != 0 || a.wtaps != 1 || a.cls[0].ntaps != 1) return -1;
-  if (a.cls[0].taps[0].dh != 0 || a.cls[0].taps[0].dw != 0 || a.cls[0].taps[0].wtap != 0 || a.cls[0].ph != 0 || a.cls[0].pw != 0) return -1;
-  if (a.Hsub != a.Hin || a.Wsub != a.Win || a.Hout != a.Hin || a.Wout != a.Win) return -1;
-  if (a.pix_stride != a.Ck || a.addend != nullptr || a.q_scale_in != nullptr || a.q_scale_wt != nullptr) return -1;
-  if (stats >= 2) return -1;
+  if (!plain_1x1(a, nclass) || a.addend != nullptr || stats >= 2) return -1;
   const long M = (long)a.N * a.Hin * a.Win;
   for (int i = 0; i < NPW; ++i) {
     const PwVariant& v = g_pw[i];
@@ -247,10 +257,7 @@ int find_pw(const IgemmArgs& a, int nclass, int stats) {
 
 // the generated 3x3 / stride-1 weight-gradient kernel of this launch, or -1
 int find_wg(int dtype, const WgradArgs& a) {
-  if (dtype != MI355_BF16 || a.ntaps != 9 || a.wtaps != 9 || a.IS != 1 || a.pair_delta != 0) return -1;
-  if (a.Ho != a.Hin || a.Wo != a.Win || a.pix_stride != a.Ck) return -1;
-  for (int t = 0; t < 9; ++t)
-    if (a.taps[t].dh != t / 3 - 1 || a.taps[t].dw != t % 3 - 1 || a.taps[t].wtap != t) return -1;
+  if (!plain_wgrad(dtype, a, 9)) return -1;
   for (int i = 0; i < NWG; ++i) {
     const WgVariant& v = g_wg[i];
     if (v.H == a.Hin && v.W == a.Win && v.C == a.Ck && v.CO == a.Cout && (a.N * v.tn) % v.ti == 0) return i;
@@ -260,8 +267,7 @@ int find_wg(int dtype, const WgradArgs& a) {
 
 // the generated 1x1 / stride-1 weight-gradient kernel of this launch, or -1
 int find_wg1(int dtype, const WgradArgs& a) {
-  if (dtype != MI355_BF16 || a.ntaps != 1 || a.wtaps != 1 || a.IS != 1 || a.pair_delta != 0) return -1;
-  if (a.Ho != a.Hin || a.Wo != a.Win || a.pix_stride != a.Ck || a.taps[0].dh != 0 || a.taps[0].dw != 0 || a.taps[0].wtap != 0) return -1;
+  if (!plain_wgrad(dtype, a, 1)) return -1;
   if ((long)a.N * a.Ho * a.Wo * (long)(a.Ck > a.Cout ? a.Ck : a.Cout) * 2 >= (1L << 32)) return -1;  // 32-bit offsets into the tensors
   for (int i = 0; i < NWG1; ++i)
     if (g_wg1[i].C == a.Ck && g_wg1[i].CO == a.Cout) return i;
@@ -271,12 +277,12 @@ int find_wg1(int dtype, const WgradArgs& a) {
 // 3: the BN-backward sums under a leaky-ReLU mask of slope 0.01 (asm/dconv_gen.py Cfg.stats, LEAKY_BITS)
 int wanted_stats(const IgemmArgs& a) { return a.stat_partial == nullptr ? 0 : (a.bn_y != nullptr ? (a.bn_slope != 0.f ? 3 : 2) : 1); }
 
+// partial statistics rows the caller's buffer holds (bn_finalize adds any number of rows, 512 per pass)
+int stat_rows_cap(const IgemmArgs& a) { return a.stat_rows_cap > 0 ? a.stat_rows_cap : 768; }
+
 // the long-reduction pointwise kernel that can run this launch (1x1, stride 1, no addend), or -1
 int find_pk(const IgemmArgs& a, int nclass, int stats) {
-  if (nclass != 1 || a.IS != 1 || a.OS != 1 || a.pair_delta != 0 || a.wtaps != 1 || a.cls[0].ntaps != 1) return -1;
-  if (a.cls[0].taps[0].dh != 0 || a.cls[0].taps[0].dw != 0 || a.cls[0].taps[0].wtap != 0 || a.cls[0].ph != 0 || a.cls[0].pw != 0) return -1;
-  if (a.Hsub != a.Hin || a.Wsub != a.Win || a.Hout != a.Hin || a.Wout != a.Win) return -1;
-  if (a.pix_stride != a.Ck || a.addend != nullptr || a.q_scale_in != nullptr || a.q_scale_wt != nullptr) return -1;
+  if (!plain_1x1(a, nclass) || a.addend != nullptr) return -1;
   const long M = (long)a.N * a.Hin * a.Win;
   for (int i = 0; i < NPK; ++i) {
     const PkVariant& v = g_pk[i];
@@ -285,52 +291,79 @@ int find_pk(const IgemmArgs& a, int nclass, int stats) {
   return -1;
 }
 
-}  // namespace
+// the first eight kernarg slots of the dconv, pk and po kernels
+struct __attribute__((packed)) KHead {
+  const void* in;
+  const void* wt;
+  void* out;
+  float* stat;
+  const void* bn_y;
+  const void* bn_bits;
+  const float* bn_mean;
+  const float* bn_invstd;
+};
+KHead kernarg_head(const IgemmArgs& a, int bnin) {
+  if (bnin)  // the pointer slots of the BN-backward sums carry the input's BatchNorm: a out, its bits out, [2][Ck] scale / shift
+    return {a.in, a.wt, a.out, a.stat_partial, a.bn_in_a, a.bn_in_bits, a.bn_in, nullptr};
+  return {a.in, a.wt, a.out, a.stat_partial, a.bn_y, a.bn_bits, a.bn_mean, a.bn_invstd};
+}
 
 // MI355_DCONV=0 keeps every launch on the implicit-GEMM kernels (A/B; a switch of struct Knobs: read once and on mi355_reload_knobs()).
 // A launch that FORCES an implicit-GEMM tile (MI355_IGEMM8 / MI355_IGEMM_BIG, the per-launch knobs of the tile tests) is left to those
 // kernels too, and so is every launch on a device whose runtime refused the embedded code object (dev_state()).
-static bool dconv_enabled() {
+bool dconv_enabled() {
   return knobs().dconv && !knobs().has_igemm8 && !knobs().has_igemm_big;
 }
 
 // plans are also made on GPU-less hosts (layout-only contexts): there the kernels count as available
-static bool module_usable() {
+bool module_usable() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
     (void)hipGetLastError();
     return true;
   }
-  return module_ok();
+  DevState* d = nullptr;
+  return dev_state(&d);
 }
+
+// the last step of every *_pick: the kernel's function on this device (loads the module on first use)
+bool pick(ConvFamily family, int base, int vi, ConvPick* p) {
+  DevState* d = nullptr;
+  if (!dev_state(&d)) return false;
+  *p = ConvPick{family, vi, d->fn[base + vi]};
+  return true;
+}
+
+// the generated weight-gradient kernel of a launch: the 3x3 family (wg), else the 1x1 family (wg1: flat 64-pixel tiles)
+struct WgPick {
+  const char* tag;
+  int kern, kernarg, pairs, ntiles, npix;  // pairs: (ci tile, co tile) pairs = workgroups per split; npix: wg1 only
+};
+bool find_wgrad(int dtype, const WgradArgs& a, WgPick* w) {
+  const int vi = find_wg(dtype, a);
+  const int v1 = vi < 0 ? find_wg1(dtype, a) : -1;
+  const int npix = a.N * a.Ho * a.Wo;
+  if (vi >= 0) *w = {"wg3", B_WG + vi, g_wg[vi].kernarg, (g_wg[vi].C / 64) * (g_wg[vi].CO / 64), a.N * g_wg[vi].tn / g_wg[vi].ti, 0};
+  if (v1 >= 0) *w = {"wg1", B_WG1 + v1, g_wg1[v1].kernarg, (g_wg1[v1].C / (64 * g_wg1[v1].XP)) * (g_wg1[v1].CO / (64 * g_wg1[v1].DP)), (npix + 63) / 64, npix};
+  return vi >= 0 || v1 >= 0;
+}
+
+}  // namespace
 
 // split count of the generated weight-gradient kernel for this launch (0: not served).  One workgroup per CU: the (ci tile, co tile)
 // pairs times the splits fill the device once; a split is a run of whole tiles.
 int wg3_plan(int dtype, const WgradArgs& a) {
-  if (!knobs().wg3 || !dconv_enabled()) return 0;
-  const int vi = find_wg(dtype, a);
-  const int v1 = vi < 0 ? find_wg1(dtype, a) : -1;
-  if (vi < 0 && v1 < 0) return 0;
-  if (!module_usable()) return 0;
-  int pairs, ntiles;
-  if (vi >= 0) {
-    const WgVariant& v = g_wg[vi];
-    pairs = (v.C / 64) * (v.CO / 64);
-    ntiles = a.N * v.tn / v.ti;
-  } else {
-    pairs = (g_wg1[v1].C / (64 * g_wg1[v1].XP)) * (g_wg1[v1].CO / (64 * g_wg1[v1].DP));
-    ntiles = (a.N * a.Ho * a.Wo + 63) / 64;
-  }
+  WgPick w;
+  if (!knobs().wg3 || !dconv_enabled() || !find_wgrad(dtype, a, &w) || !module_usable()) return 0;
   const int cus = device_cus();
-  const int max_splits = cus / pairs > 0 ? cus / pairs : 1;
-  const int tps = (ntiles + max_splits - 1) / max_splits;
-  return (ntiles + tps - 1) / tps;
+  const int max_splits = cus / w.pairs > 0 ? cus / w.pairs : 1;
+  const int tps = (w.ntiles + max_splits - 1) / max_splits;
+  return (w.ntiles + tps - 1) / tps;
 }
 
 int launch_wg3(const WgradArgs& a, int splits, hipStream_t stream) {
-  const int vi = find_wg(MI355_BF16, a);
-  const int v1 = vi < 0 ? find_wg1(MI355_BF16, a) : -1;
-  MI355_ARG((vi >= 0 || v1 >= 0) && splits >= 1, "wg3: no kernel variant for this launch");
+  WgPick w;
+  MI355_ARG(find_wgrad(MI355_BF16, a, &w) && splits >= 1, "wg3: no kernel variant for this launch");
   DevState* d = nullptr;
   if (!dev_state(&d)) return MI355_E_HIP;
   struct __attribute__((packed)) KArgs {
@@ -340,59 +373,27 @@ int launch_wg3(const WgradArgs& a, int splits, hipStream_t stream) {
     unsigned tps, ntiles, npix;
     unsigned pad[7];
   } k;
-  if (v1 >= 0) {  // 1x1: flat pixel tiles
-    const Wg1Variant& v = g_wg1[v1];
-    MI355_ARG((int)sizeof(KArgs) == v.kernarg, "wg1: kernarg size mismatch");
-    memset(&k, 0, sizeof(k));
-    k.dy = a.dy;
-    k.x = a.x;
-    k.partial = a.partial;
-    k.npix = (unsigned)(a.N * a.Ho * a.Wo);
-    k.ntiles = (k.npix + 63) / 64;
-    k.tps = (k.ntiles + (unsigned)splits - 1) / (unsigned)splits;
-    MI355_ARG((k.ntiles + k.tps - 1) / k.tps == (unsigned)splits, "wg1: %d splits leave an empty split (%u tiles)", splits, k.ntiles);
-    size_t ksize = sizeof(k);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksize, HIP_LAUNCH_PARAM_END};
-    const hipError_t e = hipModuleLaunchKernel(d->wg1[v1], (unsigned)splits, (unsigned)((v.C / (64 * v.XP)) * (v.CO / (64 * v.DP))), 1, 256, 1, 1, 0, stream, nullptr, extra);
-    if (e != hipSuccess) {
-      set_error("wg1: hipModuleLaunchKernel(%s) -> %s", v.name, hipGetErrorString(e));
-      return MI355_E_HIP;
-    }
-    note_kernel("%s", v.name);
-    return 0;
-  }
-  const WgVariant& v = g_wg[vi];
-  static_assert(sizeof(KArgs) == 64, "kernarg layout of asm/wg_gen.py (Gen.KA)");
-  MI355_ARG((int)sizeof(KArgs) == v.kernarg, "wg3: kernarg size mismatch");
+  static_assert(sizeof(KArgs) == 64, "kernarg layout of asm/wg_gen.py and asm/wg1_gen.py (Gen.KA)");
+  MI355_ARG((int)sizeof(KArgs) == w.kernarg, "%s: kernarg size mismatch", w.tag);
   memset(&k, 0, sizeof(k));
   k.dy = a.dy;
   k.x = a.x;
   k.partial = a.partial;
-  k.ntiles = (unsigned)(a.N * v.tn / v.ti);
+  k.npix = (unsigned)w.npix;
+  k.ntiles = (unsigned)w.ntiles;
   k.tps = (k.ntiles + (unsigned)splits - 1) / (unsigned)splits;
-  MI355_ARG((k.ntiles + k.tps - 1) / k.tps == (unsigned)splits, "wg3: %d splits leave an empty split (%u tiles)", splits, k.ntiles);
-  size_t ksize = sizeof(k);
-  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksize, HIP_LAUNCH_PARAM_END};
-  const hipError_t e = hipModuleLaunchKernel(d->wg[vi], (unsigned)splits, (unsigned)((v.C / 64) * (v.CO / 64)), 1, 256, 1, 1, 0, stream, nullptr, extra);
-  if (e != hipSuccess) {
-    set_error("wg3: hipModuleLaunchKernel(%s) -> %s", v.name, hipGetErrorString(e));
-    return MI355_E_HIP;
-  }
-  note_kernel("%s", v.name);
-  return 0;
+  MI355_ARG((k.ntiles + k.tps - 1) / k.tps == (unsigned)splits, "%s: %d splits leave an empty split (%u tiles)", w.tag, splits, k.ntiles);
+  return launch_kernel(w.tag, w.kern, d->fn[w.kern], (unsigned)splits, (unsigned)w.pairs, &k, sizeof(k), stream);
 }
 
-bool pw_legal(const IgemmArgs& a, int nclass) {
+bool pw_pick(const IgemmArgs& a, int nclass, ConvPick* p) {
   if (!knobs().pw || !dconv_enabled()) return false;
-  return find_pw(a, nclass, wanted_stats(a)) >= 0 && module_ok();
+  const int v = find_pw(a, nclass, wanted_stats(a));
+  return v >= 0 && pick(CONV_PW, B_PW, v, p);
 }
 
-int launch_pw(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows) {
-  const int vi = find_pw(a, nclass, wanted_stats(a));
-  MI355_ARG(vi >= 0, "pw: no kernel variant for this launch");
-  const PwVariant& v = g_pw[vi];
-  DevState* d = nullptr;
-  if (!dev_state(&d)) return MI355_E_HIP;
+static int launch_pw(const ConvPick& p, const IgemmArgs& a, hipStream_t stream, int* stat_rows) {
+  const PwVariant& v = g_pw[p.vi];
   struct __attribute__((packed)) KArgs {
     const void* in;
     const void* wt;
@@ -417,41 +418,21 @@ int launch_pw(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows
   k.upw = (k.units + cus - 1) / cus;
   const unsigned grid = (k.units + k.upw - 1) / k.upw;  // every workgroup has at least one unit (it writes its statistics row)
   memcpy(k.table, v.table, sizeof(k.table));
-  size_t ksize = sizeof(k);
-  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksize, HIP_LAUNCH_PARAM_END};
-  const hipError_t e = hipModuleLaunchKernel(d->pw[vi], grid, 1, 1, 256, 1, 1, 0, stream, nullptr, extra);
-  if (e != hipSuccess) {
-    set_error("pw: hipModuleLaunchKernel(%s) -> %s", v.name, hipGetErrorString(e));
-    return MI355_E_HIP;
-  }
-  if (stat_rows) *stat_rows = a.stat_partial ? (int)grid : 0;
-  note_kernel("%s", v.name);
-  return 0;
+  return launch_kernel("pw", B_PW + p.vi, p.fn, grid, 1, &k, sizeof(k), stream, stat_rows, a.stat_partial ? (int)grid : 0);
 }
 
-bool pk_legal(const IgemmArgs& a, int nclass) {
+bool pk_pick(const IgemmArgs& a, int nclass, ConvPick* p) {
   if (!knobs().pk || !dconv_enabled()) return false;
   const int v = find_pk(a, nclass, wanted_stats(a));
   if (v < 0) return false;
   const long tiles = (long)a.N * a.Hin * a.Win / g_pk[v].W;   // one partial statistics row per pixel tile
-  return (a.stat_partial == nullptr || tiles <= (a.stat_rows_cap > 0 ? a.stat_rows_cap : 768)) && module_ok();
+  return (a.stat_partial == nullptr || tiles <= stat_rows_cap(a)) && pick(CONV_PK, B_PK, v, p);
 }
 
-int launch_pk(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows) {
-  const int vi = find_pk(a, nclass, wanted_stats(a));
-  MI355_ARG(vi >= 0, "pk: no kernel variant for this launch");
-  const PkVariant& v = g_pk[vi];
-  DevState* d = nullptr;
-  if (!dev_state(&d)) return MI355_E_HIP;
+static int launch_pk(const ConvPick& p, const IgemmArgs& a, hipStream_t stream, int* stat_rows) {
+  const PkVariant& v = g_pk[p.vi];
   struct __attribute__((packed)) KArgs {
-    const void* in;
-    const void* wt;
-    void* out;
-    float* stat;
-    const void* bn_y;
-    const void* bn_bits;
-    const float* bn_mean;
-    const float* bn_invstd;
+    KHead h;
     const void* rsvd;
     unsigned nchunks;
     unsigned pad[13];
@@ -459,66 +440,31 @@ int launch_pk(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows
   static_assert(sizeof(KArgs) == 128, "kernarg layout of asm/pk_gen.py (Gen.KA)");
   MI355_ARG((int)sizeof(KArgs) == v.kernarg, "pk: kernarg size mismatch");
   memset(&k, 0, sizeof(k));
-  k.in = a.in;
-  k.wt = a.wt;
-  k.out = a.out;
-  k.stat = a.stat_partial;
-  k.bn_y = a.bn_y;
-  k.bn_bits = a.bn_bits;
-  k.bn_mean = a.bn_mean;
-  k.bn_invstd = a.bn_invstd;
+  k.h = kernarg_head(a, 0);
   k.nchunks = (unsigned)(a.Ck / 64);
   const unsigned tiles = (unsigned)((long)a.N * a.Hin * a.Win / v.W);
-  size_t ksize = sizeof(k);
-  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksize, HIP_LAUNCH_PARAM_END};
-  const hipError_t e = hipModuleLaunchKernel(d->pk[vi], tiles, (unsigned)(v.N / v.BN), 1, 256, 1, 1, 0, stream, nullptr, extra);
-  if (e != hipSuccess) {
-    set_error("pk: hipModuleLaunchKernel(%s) -> %s", v.name, hipGetErrorString(e));
-    return MI355_E_HIP;
-  }
-  if (stat_rows) *stat_rows = a.stat_partial ? (int)tiles : 0;
-  note_kernel("%s", v.name);
-  return 0;
+  return launch_kernel("pk", B_PK + p.vi, p.fn, tiles, (unsigned)(v.N / v.BN), &k, sizeof(k), stream, stat_rows, a.stat_partial ? (int)tiles : 0);
 }
 
-static bool dconv_legal_of(const IgemmArgs& a, int nclass, int fp8) {
+bool dconv_pick(const IgemmArgs& a, int nclass, int fp8, ConvPick* p) {
   if (!dconv_enabled()) return false;
   const int v = find_variant(a, nclass, wanted_stats(a), fp8);
   if (v < 0) return false;
   if (fp8 && !knobs().dconv_fp8) return false;
   if (g_variants[v].s2d && !knobs().dconv_s2) return false;
   if (g_variants[v].bnin && !knobs().dconv_bn) return false;
-  // one partial statistics row per tile (and class): the caller's buffer must hold them (bn_finalize adds any number of rows, 512 per pass)
-  if (a.stat_partial != nullptr && a.N * g_variants[v].TPI / g_variants[v].IPT * (g_variants[v].s2d ? 4 : 1) > (a.stat_rows_cap > 0 ? a.stat_rows_cap : 768)) return false;
-  return module_ok();
+  // one partial statistics row per tile (and class): the caller's buffer must hold them
+  if (a.stat_partial != nullptr && a.N * g_variants[v].TPI / g_variants[v].IPT * (g_variants[v].s2d ? 4 : 1) > stat_rows_cap(a)) return false;
+  return pick(CONV_DCONV, B_DCONV, v, p);
 }
 
-bool dconv_legal(const IgemmArgs& a, int nclass) { return dconv_legal_of(a, nclass, 0); }
-// the same launch on e4m3 operands (a.in / a.wt one byte per element; launch_igemm_fp8)
-bool dconv_fp8_legal(const IgemmArgs& a, int nclass) { return dconv_legal_of(a, nclass, 1); }
-
-static int launch_dconv_of(const IgemmArgs& a, int nclass, int fp8, float oscale, hipStream_t stream, int* stat_rows);
-int launch_dconv(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows) { return launch_dconv_of(a, nclass, 0, 1.f, stream, stat_rows); }
-int launch_dconv_fp8(const IgemmArgs& a, int nclass, float oscale, hipStream_t stream, int* stat_rows) { return launch_dconv_of(a, nclass, 1, oscale, stream, stat_rows); }
-
-static int launch_dconv_of(const IgemmArgs& a, int nclass, int fp8, float oscale, hipStream_t stream, int* stat_rows) {
-  const int vi = find_variant(a, nclass, wanted_stats(a), fp8);
-  MI355_ARG(vi >= 0, "dconv: no kernel variant for this launch");
-  const DconvVariant& v = g_variants[vi];
-  DevState* d = nullptr;
-  if (!dev_state(&d)) return MI355_E_HIP;
+static int launch_dconv(const ConvPick& p, const IgemmArgs& a, int nclass, float oscale, hipStream_t stream, int* stat_rows) {
+  const DconvVariant& v = g_variants[p.vi];
   int wtap[9];
   if (v.s2d) s2d_tap_table(a, nclass, wtap);
   else tap_table(a.cls[0], wtap);
   struct __attribute__((packed)) KArgs {
-    const void* in;
-    const void* wt;
-    void* out;
-    float* stat;
-    const void* bn_y;
-    const void* bn_bits;
-    const float* bn_mean;
-    const float* bn_invstd;
+    KHead h;
     const void* rsvd;
     unsigned wtap_off[9];
     unsigned nchunks;
@@ -527,24 +473,13 @@ static int launch_dconv_of(const IgemmArgs& a, int nclass, int fp8, float oscale
     unsigned ttable[768];  // bnin kernels only: the transform tables
   } k;
   static_assert(sizeof(KArgs) == 128 + 3072 + 3072, "kernarg layout of asm/dconv_gen.py (Gen.KA; + ttables for Cfg.bnin)");
-  size_t ksize = v.bnin ? sizeof(KArgs) : sizeof(KArgs) - sizeof(k.ttable);
+  const size_t ksize = v.bnin ? sizeof(KArgs) : sizeof(KArgs) - sizeof(k.ttable);
   MI355_ARG((int)ksize == v.kernarg, "dconv: kernarg size mismatch");
-  k.in = a.in;
-  k.wt = a.wt;
-  k.out = a.out;
-  k.stat = a.stat_partial;
-  k.bn_y = a.bn_y;
-  k.bn_bits = a.bn_bits;
-  k.bn_mean = a.bn_mean;
-  k.bn_invstd = a.bn_invstd;
+  k.h = kernarg_head(a, v.bnin);
   k.rsvd = nullptr;
   memset(k.pad, 0, sizeof(k.pad));
   memcpy(k.table, v.table, sizeof(k.table));
-  if (v.bnin) {  // the pointer slots of the BN-backward sums carry the input's BatchNorm: a out, its bits out, [2][Ck] scale / shift
-    k.bn_y = a.bn_in_a;
-    k.bn_bits = a.bn_in_bits;
-    k.bn_mean = a.bn_in;
-    k.bn_invstd = nullptr;
+  if (v.bnin) {
     int ti = -1;
     for (int i = 0; i < NTT; ++i)
       if (strcmp(g_tt[i].name, v.name) == 0) ti = i;
@@ -559,49 +494,31 @@ static int launch_dconv_of(const IgemmArgs& a, int nclass, int fp8, float oscale
     memcpy(&k.pad[1], &oscale, sizeof(float));
     memcpy(&k.pad[2], &a.q_scale_wt, sizeof(void*));
   }
-  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksize, HIP_LAUNCH_PARAM_END};
   const int tiles = a.N * v.TPI / v.IPT;
   const int ncls = v.s2d ? 4 : 1;   // workgroup id y = class * column tiles + column tile: the long classes (4 taps) are dispatched first
-  const hipError_t e = hipModuleLaunchKernel(d->fn[vi], (unsigned)tiles, (unsigned)(a.Ncols / v.BN * ncls), 1, 256, 1, 1, 0, stream, nullptr, extra);
-  if (e != hipSuccess) {
-    set_error("dconv: hipModuleLaunchKernel(%s) -> %s", v.name, hipGetErrorString(e));
-    return MI355_E_HIP;
-  }
-  if (stat_rows) *stat_rows = a.stat_partial ? tiles * ncls : 0;
-  note_kernel("%s", v.name);
-  return 0;
+  return launch_kernel("dconv", B_DCONV + p.vi, p.fn, (unsigned)tiles, (unsigned)(a.Ncols / v.BN * ncls), &k, ksize, stream, stat_rows, a.stat_partial ? tiles * ncls : 0);
 }
 
 // ---- output-heavy pointwise kernels with resident weights (asm/po_gen.py) ---------------------------------------------------------
-namespace {
-
-struct PoPlan {
-  int vi = -1;
-  unsigned T = 0, nct = 0, tpg = 0, G = 0, grid = 0, lognct = 0;
-};
-
-// 1x1 / stride 1, K = the variant's, columns a power-of-two multiple of its BN; statistics 0 / 1 / 2; addend none / plain / under its mask
-bool plan_po(const IgemmArgs& a, int nclass, PoPlan* pl) {
-  if (nclass != 1 || a.IS != 1 || a.OS != 1 || a.pair_delta != 0 || a.wtaps != 1 || a.cls[0].ntaps != 1) return false;
-  if (a.cls[0].taps[0].dh != 0 || a.cls[0].taps[0].dw != 0 || a.cls[0].taps[0].wtap != 0 || a.cls[0].ph != 0 || a.cls[0].pw != 0) return false;
-  if (a.Hsub != a.Hin || a.Wsub != a.Win || a.Hout != a.Hin || a.Wout != a.Win) return false;
-  if (a.pix_stride != a.Ck || a.q_scale_in != nullptr || a.q_scale_wt != nullptr) return false;
+// 1x1 / stride 1, K = the variant's, columns a power-of-two multiple of its BN; statistics 0 / 1 / 2; addend none / plain / under its mask:
+// the variant, or -1
+static int plan_po(const IgemmArgs& a, int nclass, PoPlan* pl) {
+  if (!plain_1x1(a, nclass)) return -1;
   const int stats = wanted_stats(a);
   const int add = a.addend == nullptr ? 0 : (a.addend_sub2 ? 3 : (a.addend_bits != nullptr ? 2 : 1));
-  if (a.addend == nullptr && (a.addend_bits != nullptr || a.addend_sub2)) return false;
-  if (a.addend_sub2 && (a.addend_bits != nullptr || a.Hout % 2 || a.Wout % 2)) return false;
+  if (a.addend == nullptr && (a.addend_bits != nullptr || a.addend_sub2)) return -1;
+  if (a.addend_sub2 && (a.addend_bits != nullptr || a.Hout % 2 || a.Wout % 2)) return -1;
   const long M = (long)a.N * a.Hin * a.Win;
-  if (M * a.Ck * 2 >= (1L << 32) || M * a.Ncols * 2 >= (1L << 32)) return false;  // 32-bit num_records of the tile-by-tile descriptors
+  if (M * a.Ck * 2 >= (1L << 32) || M * a.Ncols * 2 >= (1L << 32)) return -1;  // 32-bit num_records of the tile-by-tile descriptors
   const int bnin = a.bn_in != nullptr ? 1 : 0;
-  if (bnin && (a.bn_in_a == nullptr || a.bn_in_bits == nullptr)) return false;
-  if (a.addend_sub2 && (M + 64) * (a.Wout > a.Hout ? a.Wout : a.Hout) >= (1L << 32)) return false;  // exactness of the kernel's divisions
+  if (bnin && (a.bn_in_a == nullptr || a.bn_in_bits == nullptr)) return -1;
+  if (a.addend_sub2 && (M + 64) * (a.Wout > a.Hout ? a.Wout : a.Hout) >= (1L << 32)) return -1;  // exactness of the kernel's divisions (magic32)
   for (int i = 0; i < NPO; ++i) {
     const PoVariant& v = g_po[i];
     if (v.K != a.Ck || v.stats != stats || v.add != add || a.Ncols % v.BN != 0 || v.bnin != bnin) continue;
     if (v.bnin && M % v.TP != 0) continue;   // (a ragged tile's missing pixels would become relu(shift) instead of zero)
     const unsigned nct = (unsigned)(a.Ncols / v.BN);
     if ((nct & (nct - 1)) != 0 || nct > 32) continue;
-    pl->vi = i;
     pl->nct = nct;
     pl->lognct = 0;
     while ((1u << pl->lognct) < nct) ++pl->lognct;
@@ -611,20 +528,20 @@ bool plan_po(const IgemmArgs& a, int nclass, PoPlan* pl) {
     pl->tpg = (pl->T + gmax - 1) / gmax;
     pl->G = (pl->T + pl->tpg - 1) / pl->tpg;
     pl->grid = (pl->G + 7) / 8 * 8 * nct;                      // workgroup x: XCD x % 8, column tile (x / 8) % nct, run (x / 8 / nct) * 8 + x % 8
-    return true;
+    return i;
   }
-  return false;
+  return -1;
 }
 
-}  // namespace
-
-bool po_legal(const IgemmArgs& a, int nclass) {
+bool po_pick(const IgemmArgs& a, int nclass, ConvPick* p) {
   const int mode = knobs().po;
   if (!mode || !dconv_enabled()) return false;
   PoPlan pl;
-  if (!plan_po(a, nclass, &pl)) return false;
-  if (a.stat_partial != nullptr && (int)pl.G * g_po[pl.vi].WM > (a.stat_rows_cap > 0 ? a.stat_rows_cap : 768)) return false;
-  if (g_po[pl.vi].bnin && !knobs().po_bn) return false;
+  const int vi = plan_po(a, nclass, &pl);
+  if (vi < 0) return false;
+  const PoVariant& v = g_po[vi];
+  if (a.stat_partial != nullptr && (int)pl.G * v.WM > stat_rows_cap(a)) return false;
+  if (v.bnin && !knobs().po_bn) return false;
   if (mode < 2) {
     // MI355_PO=1 (default): the measured rule, per launch shape of the bs-256 step in a serial trace (profiles/r05_ab_po_*.txt):
     //  - 64 -> 256 under the shortcut addend + BN-backward sums (layer 1's conv1 data gradient, 1.39 GB per launch): the implicit-GEMM
@@ -632,7 +549,6 @@ bool po_legal(const IgemmArgs& a, int nclass) {
     //  - (K = 512 with an addend, layer 4's conv1 data gradient: 74 us against 67 with one mask byte load per lane and item; 63 with the
     //    tile-wide mask loads: served here since)
     //  - 512 -> 2048 forward (layer 4's conv3): pk's four-image tiles win by 2 us.
-    const PoVariant& v = g_po[pl.vi];
     if (v.BN == 64 && knobs().po64 < 2) {
       if (!knobs().po64) return false;
     }
@@ -640,34 +556,19 @@ bool po_legal(const IgemmArgs& a, int nclass) {
     // 250-257 on the implicit-GEMM kernel), but the step is 0.06 ms SLOWER with it here (18.03 -> 18.09, four alternations on one box): the 768-workgroup
     // grid shares the chip with the weight-gradient stream better than 256 persistent workgroups do
     if (v.K == 64 && v.add != 0 && v.stats == 2) return false;
-    if (v.K == 512 && a.Ncols >= 2048 && pk_legal(a, nclass)) return false;
+    ConvPick pk;
+    if (v.K == 512 && a.Ncols >= 2048 && pk_pick(a, nclass, &pk)) return false;
   }
-  return module_ok();
+  if (!pick(CONV_PO, B_PO, vi, p)) return false;
+  p->po = pl;
+  return true;
 }
 
-bool igemm_sub2_legal(int dtype, const IgemmArgs& a, int nclass) { return dtype == MI355_BF16 && a.addend_sub2 && po_legal(a, nclass); }
-
-// a launch with the input's BatchNorm + ReLU in the operand path (IgemmArgs::bn_in) has a kernel: the direct 3x3 kernels (conv2 <- bn1) or the
-// resident-weight pointwise kernels (conv3 <- bn2)
-bool igemm_bn_in_legal(int dtype, const IgemmArgs& a, int nclass) {
-  return dtype == MI355_BF16 && a.bn_in != nullptr && (dconv_legal(a, nclass) || po_legal(a, nclass));
-}
-
-int launch_po(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows) {
-  PoPlan pl;
-  MI355_ARG(plan_po(a, nclass, &pl), "po: no kernel variant for this launch");
-  const PoVariant& v = g_po[pl.vi];
-  DevState* d = nullptr;
-  if (!dev_state(&d)) return MI355_E_HIP;
+static int launch_po(const ConvPick& p, const IgemmArgs& a, hipStream_t stream, int* stat_rows) {
+  const PoVariant& v = g_po[p.vi];
+  const PoPlan& pl = p.po;
   struct __attribute__((packed)) KArgs {
-    const void* in;
-    const void* wt;
-    void* out;
-    float* stat;
-    const void* bn_y;
-    const void* bn_bits;
-    const float* bn_mean;
-    const float* bn_invstd;
+    KHead h;
     const void* addend;
     const void* addend_bits;
     unsigned npix, ncols, tpg, ngroups, ntiles, lognct, W, H, magic_w, magic_h;
@@ -676,20 +577,7 @@ int launch_po(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows
   static_assert(sizeof(KArgs) == 128, "kernarg layout of asm/po_gen.py (Gen.KA)");
   MI355_ARG((int)sizeof(KArgs) == v.kernarg, "po: kernarg size mismatch");
   memset(&k, 0, sizeof(k));
-  k.in = a.in;
-  k.wt = a.wt;
-  k.out = a.out;
-  k.stat = a.stat_partial;
-  k.bn_y = a.bn_y;
-  k.bn_bits = a.bn_bits;
-  k.bn_mean = a.bn_mean;
-  k.bn_invstd = a.bn_invstd;
-  if (v.bnin) {  // the pointer slots of the BN-backward sums carry the input's BatchNorm: a out, its bits out, [2][Ck] scale / shift
-    k.bn_y = a.bn_in_a;
-    k.bn_bits = a.bn_in_bits;
-    k.bn_mean = a.bn_in;
-    k.bn_invstd = nullptr;
-  }
+  k.h = kernarg_head(a, v.bnin);
   k.addend = a.addend;
   k.addend_bits = a.addend_bits;
   k.npix = (unsigned)((long)a.N * a.Hin * a.Win);
@@ -700,18 +588,21 @@ int launch_po(const IgemmArgs& a, int nclass, hipStream_t stream, int* stat_rows
   k.lognct = pl.lognct;
   k.W = (unsigned)a.Wout;
   k.H = (unsigned)a.Hout;
-  k.magic_w = (unsigned)((1ull << 32) / (unsigned)a.Wout + 1);  // q / W = mulhi(q, magic) while q * W < 2^32 (plan_po checks)
-  k.magic_h = (unsigned)((1ull << 32) / (unsigned)a.Hout + 1);
-  size_t ksize = sizeof(k);
-  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksize, HIP_LAUNCH_PARAM_END};
-  const hipError_t e = hipModuleLaunchKernel(d->po[pl.vi], pl.grid, 1, 1, 256, 1, 1, 0, stream, nullptr, extra);
-  if (e != hipSuccess) {
-    set_error("po: hipModuleLaunchKernel(%s) -> %s", v.name, hipGetErrorString(e));
-    return MI355_E_HIP;
+  k.magic_w = magic32((unsigned)a.Wout);  // (plan_po checks the range)
+  k.magic_h = magic32((unsigned)a.Hout);
+  return launch_kernel("po", B_PO + p.vi, p.fn, pl.grid, 1, &k, sizeof(k), stream, stat_rows, a.stat_partial ? (int)pl.G * v.WM : 0);
+}
+
+int launch_gen(const ConvPick& p, const IgemmArgs& a, int nclass, float oscale, hipStream_t stream, int* stat_rows) {
+  switch (p.family) {
+    case CONV_DCONV: return launch_dconv(p, a, nclass, oscale, stream, stat_rows);
+    case CONV_PO: return launch_po(p, a, stream, stat_rows);
+    case CONV_PW: return launch_pw(p, a, stream, stat_rows);
+    case CONV_PK: return launch_pk(p, a, stream, stat_rows);
+    default: break;
   }
-  if (stat_rows) *stat_rows = a.stat_partial ? (int)pl.G * v.WM : 0;
-  note_kernel("%s", v.name);
-  return 0;
+  set_error("launch_gen: family %d is not a generated one", (int)p.family);
+  return MI355_E_ARG;
 }
 
 }  // namespace mi355

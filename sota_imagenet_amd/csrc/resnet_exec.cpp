@@ -17,9 +17,6 @@
 
 namespace mi355 {
 
-void build_stem_fwd_args(IgemmArgs& a, int N, int H, int W);
-void build_stem_wgrad_args(WgradArgs& a, int N, int H, int W);
-
 namespace {
 
 constexpr float BN_EPS = 1e-5f;

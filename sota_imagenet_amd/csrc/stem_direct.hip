@@ -8,11 +8,9 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_kernels.h"
 #include "lds_dma.h"
 #include "vec.h"
 
@@ -40,15 +38,6 @@ struct Conv3KArgs {
 #else
 #define C3_PROBE(bit) false
 #endif
-
-void lds_opt_in3(const void* fn) {
-  static std::mutex mu;
-  static std::set<const void*> done;
-  std::lock_guard<std::mutex> g(mu);
-  if (done.count(fn)) return;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  done.insert(fn);
-}
 
 template <int CTRL>
 __device__ __forceinline__ float row_shr_add3(float x) {
@@ -345,8 +334,6 @@ int plan_stem(int Hout, int Wout, int pitch) {
   return best;
 }
 
-unsigned magic32_3(unsigned d) { return (unsigned)((1ull << 32) / d + 1); }
-
 // tile geometry: TH | H rows, row pitch WP >= W + 2 with TH * WP a multiple of 16, at most 32 fragments, the LDS image within
 // the prefetch registers (19 x 256 chunks) — the smallest padded area per output pixel wins
 }  // namespace
@@ -387,15 +374,15 @@ int launch_stem_direct(const IgemmArgs& a, hipStream_t stream, int* stat_rows) {
   if (stat_rows) *stat_rows = stats ? grid : 0;
   if (knobs().stem_dbg) {
     int nb = -1;
-    lds_opt_in3((const void*)stem_direct_kernel<1>);
+    lds_opt_in((const void*)stem_direct_kernel<1>, lds);
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)stem_direct_kernel<1>, 256, lds);
     fprintf(stderr, "stem_direct: TH %d F %d lds %zu grid %d resident/CU %d\n", k.k.TH, k.F, lds, grid, nb);
   }
   if (stats) {
-    lds_opt_in3((const void*)stem_direct_kernel<1>);
+    lds_opt_in((const void*)stem_direct_kernel<1>, lds);
     hipLaunchKernelGGL(stem_direct_kernel<1>, dim3(grid), dim3(256), lds, stream, k);
   } else {
-    lds_opt_in3((const void*)stem_direct_kernel<0>);
+    lds_opt_in((const void*)stem_direct_kernel<0>, lds);
     hipLaunchKernelGGL(stem_direct_kernel<0>, dim3(grid), dim3(256), lds, stream, k);
   }
   MI355_LAUNCH_CHECK();

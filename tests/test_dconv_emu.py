@@ -255,7 +255,7 @@ def test_a_workgroup_beyond_the_last_run_of_a_launch_exits_without_touching_memo
 
 
 def test_the_launch_plan_covers_every_tile_once_at_the_shapes_of_the_step():
-    """dconv.cpp plan_po restated (tools/po_emu_check.plan): runs x tiles per run cover the tile count exactly once, every run has a
+    """gen_kernels.cpp plan_po restated (tools/po_emu_check.plan): runs x tiles per run cover the tile count exactly once, every run has a
     tile, and the grid holds whole XCD rows of (run, column tile) pairs"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import po_emu_check

@@ -1,7 +1,7 @@
 // po_bench.cpp — standalone timing harness for the generated output-heavy pointwise kernels (asm/po_gen.py), tuning only.
 //   hipcc -O2 --offload-arch=gfx950 tools/micro/po_bench.cpp -o /tmp/po_bench
 //   /tmp/po_bench <file.hsaco> <kernel> K BN stats add M N [iters]
-// Launches the kernel with the launch plan of dconv.cpp (plan_po) on random bf16 data; every launch takes its tensors from a pool
+// Launches the kernel with the launch plan of gen_kernels.cpp (plan_po) on random bf16 data; every launch takes its tensors from a pool
 // larger than the Infinity Cache (the condition inside the train step) and the output overwrites the addend in place, as the
 // executor's conv1 data gradient does.  Prints the median / minimum time per launch and the algorithmic TB/s.
 #include <hip/hip_runtime.h>

@@ -16,7 +16,7 @@ from dconv_emu_check import bf16_round, from_bf16_bits, to_bf16_bits  # noqa: E4
 
 
 def plan(M, N, BN, TP, cus=256):
-    """the host-side launch plan of dconv.cpp launch_po(): tiles, column tiles, tiles per group, groups, grid"""
+    """the host-side launch plan of gen_kernels.cpp launch_po(): tiles, column tiles, tiles per group, groups, grid"""
     T = -(-M // TP)
     nct = N // BN
     gmax = max(1, cus // nct)
