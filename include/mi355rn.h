@@ -256,6 +256,46 @@ int mi355_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema
                         float eps, float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled,
                         float grad_scale, float ema_decay, void* stream);
 
+/* fused MADGRAD on a flat fp32 range: src.optimizers.MADGRAD.step of the reference (sota_imagenet/optimizers.py:726-767,
+ * configs/hydra_exp/54.r50_madgrad.yaml:21), in its operation order; p, grad_sum_sq, s in place, g and x0 read-only:
+ *   g = g*grad_scale;  grad_sum_sq += lamb*g*g;  rms = cbrt(grad_sum_sq) + eps;  s += lamb*g;  z = x0 - s/rms
+ *   p = p*momentum + (1 - momentum)*z;  p *= 1 - weight_decay          (decoupled and not scaled by lr, as the reference has it)
+ * lamb = (lr + eps) * sqrt(k + 1) is formed here in double from the optimizer's global counter k (state["k"] BEFORE its increment).
+ * x0 holds the parameters as they were before the first step; grad_sum_sq and s start at 0.
+ * Fails (-1) before any launch on a null or non-16-byte-aligned pointer, momentum outside [0, 1), eps / lr / weight_decay negative or
+ * not finite, k < 0. */
+int mi355_madgrad_step(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, size_t n, double lr, double momentum,
+                       double weight_decay, double eps, int k, float grad_scale, void* stream);
+/* the same step + the moving average of the updated parameters in the same pass (ema_decay in [0, 1]):
+ *   ema += (1 - ema_decay) * (p_new - ema)       replaces the ModelEma callback's lerp (train.py:111-112) under MADGRAD */
+int mi355_madgrad_step_ema(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, float* ema, size_t n, double lr,
+                           double momentum, double weight_decay, double eps, int k, float grad_scale, float ema_decay, void* stream);
+
+/* AdaiS on flat fp32 ranges: src.optimizers.AdaiS.step of the reference (sota_imagenet/optimizers.py:569-639,
+ * configs/hydra_exp/50.r50_adais.yaml:19), whose per-element momentum depends on a statistic of ALL parameters.  Three stages on one
+ * stream, nothing read back by the host; `step` is the range's count after this step's increment (>= 1), bc2 = 1 - beta2^step:
+ *  (a) mi355_adais_moments, once per range (optimizers.py:592-602):  g = g*grad_scale;  v = v*beta2 + (1 - beta2)*g*g  in place, and
+ *      one double per workgroup — the sum of its elements' v / bc2 — into `workspace` (mi355_adais_workspace_bytes(n) bytes, 8-byte
+ *      aligned).  No floating-point atomics; the number of workgroups depends on n alone, so the sums are reproducible bit for bit.
+ *  (b) mi355_adais_mean, once per optimizer step (optimizers.py:605):  mean[0] = (sum of the workspace_bytes / 8 doubles of all ranges,
+ *      laid out back to back, in a fixed order) / param_size.  param_size counts real parameter elements only: padding inside a range
+ *      must hold v = 0 so that it adds nothing.
+ *  (c) mi355_adais_step, once per range (optimizers.py:607-639), reading mean[0] from device memory; p, m, beta1_prod in place:
+ *        p *= 1 - lr*weight_decay  (only when weight_decay != 0);   beta1 = clamp(1 - (v/bc2)/mean*beta0, 0, 1 - eps)
+ *        beta1_prod *= beta1;   m = m*beta1 + (1 - beta1)*g;   p -= lr * m / (1 - beta1_prod)
+ * v starts at ema_norm_init (1e-3), beta1_prod at 1, m at 0.
+ * Each fails (-1) before any launch on a null or misaligned pointer (16 bytes for the element arrays), beta2 outside [0, 1),
+ * step < 1, beta0 / eps / lr / weight_decay negative or not finite, an empty workspace or param_size = 0. */
+size_t mi355_adais_workspace_bytes(size_t n);
+int mi355_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float grad_scale, void* workspace, void* stream);
+int mi355_adais_mean(const void* workspace, size_t workspace_bytes, size_t param_size, float* mean, void* stream);
+int mi355_adais_step(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, size_t n, double lr,
+                     double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale, void* stream);
+/* stage (c) + the moving average of the updated parameters in the same pass:  ema += (1 - ema_decay) * (p_new - ema) */
+int mi355_adais_step_ema(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, float* ema, size_t n,
+                         double lr, double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale,
+                         float ema_decay, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

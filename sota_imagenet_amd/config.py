@@ -28,6 +28,10 @@ TARGET_ALIASES = {
     "torch.optim.AdamW": "sota_imagenet_amd.optim.AdamW",
     "torch.optim._multi_tensor.Adam": "sota_imagenet_amd.optim.Adam",
     "torch.optim.Adam": "sota_imagenet_amd.optim.Adam",
+    "src.optimizers.MADGRAD": "sota_imagenet_amd.optim.MADGRAD",
+    "sota_imagenet.optimizers.MADGRAD": "sota_imagenet_amd.optim.MADGRAD",
+    "src.optimizers.AdaiS": "sota_imagenet_amd.optim.AdaiS",
+    "sota_imagenet.optimizers.AdaiS": "sota_imagenet_amd.optim.AdaiS",
     "pytorch_tools.fit_wrapper.callbacks.Callback": "sota_imagenet_amd.fit_wrapper.Callback",
     "pytorch_tools.fit_wrapper.callbacks.Cutmix": "sota_imagenet_amd.callbacks.Cutmix",
     "pytorch_tools.fit_wrapper.callbacks.Mixup": "sota_imagenet_amd.callbacks.Mixup",

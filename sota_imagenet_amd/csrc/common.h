@@ -336,6 +336,16 @@ int launch_sgd(float* p, const float* g, float* m, size_t n, float lr, float mom
 int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps, float step_size,
                 float bc2_sqrt, double lr, double wd, int decoupled, float gscale, hipStream_t s, float* ema = nullptr,
                 float ema_decay = 0.f);
+// optim.hip: fused MADGRAD step (lamb = (lr + eps) * sqrt(k + 1) is formed here in double), + the parameter average when ema != nullptr
+int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* x0, size_t n, double lr, double momentum, double wd,
+                   double eps, int k, float gscale, hipStream_t st, float* ema = nullptr, float ema_decay = 0.f);
+// optim.hip: the three AdaiS stages; adais_partials(n) = the doubles launch_adais_moments writes for a range of n elements
+size_t adais_partials(size_t n);
+int launch_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float gscale, double* partial, hipStream_t st);
+int launch_adais_mean(const double* partial, size_t count, size_t param_size, float* mean, hipStream_t st);
+int launch_adais_step(float* p, const float* g, float* m, const float* v, float* b1prod, const float* mean, size_t n, double lr, double beta0,
+                      double beta2, double eps, double wd, int step, float gscale, hipStream_t st, float* ema = nullptr,
+                      float ema_decay = 0.f);
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

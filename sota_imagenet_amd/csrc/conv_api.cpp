@@ -553,5 +553,33 @@ int mi355_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema
   return launch_adam(p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lr, weight_decay, decoupled, grad_scale,
                      (hipStream_t)stream, ema, ema_decay);
 }
+int mi355_madgrad_step(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, size_t n, double lr, double momentum,
+                       double weight_decay, double eps, int k, float grad_scale, void* stream) {
+  return launch_madgrad(p, g, grad_sum_sq, s, x0, n, lr, momentum, weight_decay, eps, k, grad_scale, (hipStream_t)stream);
+}
+int mi355_madgrad_step_ema(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, float* ema, size_t n, double lr,
+                           double momentum, double weight_decay, double eps, int k, float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "madgrad_step_ema: null ema");
+  return launch_madgrad(p, g, grad_sum_sq, s, x0, n, lr, momentum, weight_decay, eps, k, grad_scale, (hipStream_t)stream, ema, ema_decay);
+}
+size_t mi355_adais_workspace_bytes(size_t n) { return adais_partials(n) * sizeof(double); }
+int mi355_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float grad_scale, void* workspace, void* stream) {
+  return launch_adais_moments(g, v, n, beta2, step, grad_scale, (double*)workspace, (hipStream_t)stream);
+}
+int mi355_adais_mean(const void* workspace, size_t workspace_bytes, size_t param_size, float* mean, void* stream) {
+  MI355_ARG(workspace_bytes % sizeof(double) == 0, "adais_mean: workspace_bytes=%zu is not a whole number of partial sums", workspace_bytes);
+  return launch_adais_mean((const double*)workspace, workspace_bytes / sizeof(double), param_size, mean, (hipStream_t)stream);
+}
+int mi355_adais_step(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, size_t n, double lr,
+                     double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale, void* stream) {
+  return launch_adais_step(p, g, m, v, beta1_prod, mean, n, lr, beta0, beta2, eps, weight_decay, step, grad_scale, (hipStream_t)stream);
+}
+int mi355_adais_step_ema(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, float* ema, size_t n,
+                         double lr, double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale,
+                         float ema_decay, void* stream) {
+  MI355_ARG(ema, "adais_step_ema: null ema");
+  return launch_adais_step(p, g, m, v, beta1_prod, mean, n, lr, beta0, beta2, eps, weight_decay, step, grad_scale, (hipStream_t)stream, ema,
+                           ema_decay);
+}
 
 }  // extern "C"

@@ -126,4 +126,286 @@ int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double b
   return 0;
 }
 
+// ---- MADGRAD: src.optimizers.MADGRAD.step of the reference (sota_imagenet/optimizers.py:726-767), in its operation order --------------------
+//   g   = g * grad_scale
+//   gss = gss + (lamb * g) * g               (addcmul_, value = lamb), lamb = (lr + eps) * sqrt(k + 1) from the host, in double
+//   rms = cbrt(gss) + eps                    (pow(1/3).add_(eps))
+//   s   = s + lamb * g
+//   z   = x0 + (-s) / rms                    (addcdiv, value = -1)
+//   p   = p * momentum + ck * z              (mul_(1 - ck).add_(z, alpha = ck), ck = 1 - momentum)
+//   p   = p * (1 - weight_decay)             (decoupled and NOT scaled by lr: as the reference has it)
+// 32 B / element (p, gss, s read + write, g, x0 read), 40 B with the average.  Padding (p = g = gss = s = x0 = 0) stays 0 for eps > 0.
+namespace {
+
+struct MadgradArgs {
+  float lamb, eps, mom, ck, wd_mul, gscale, ema_w;
+};
+
+template <bool EMA>
+__device__ __forceinline__ void madgrad_elem(float& p, float g, float& gss, float& s, float x0, float& e, const MadgradArgs& a) {
+  const float ge = g * a.gscale;
+  gss = gss + (a.lamb * ge) * ge;
+  const float rms = cbrtf(gss) + a.eps;
+  s = s + a.lamb * ge;
+  const float z = x0 + (-s) / rms;
+  float pe = p * a.mom + a.ck * z;
+  pe = pe * a.wd_mul;
+  p = pe;
+  if constexpr (EMA) e = e + a.ema_w * (pe - e);
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void madgrad_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ gss,
+                                                      float* __restrict__ s, const float* __restrict__ x0, float* __restrict__ ema, size_t n4,
+                                                      size_t n, MadgradArgs a) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+    const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);  // last use of the gradient
+    f32x4 qv = reinterpret_cast<f32x4*>(gss)[i];
+    f32x4 sv = reinterpret_cast<f32x4*>(s)[i];
+    const f32x4 xv = reinterpret_cast<const f32x4*>(x0)[i];
+    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = pv[k], qk = qv[k], sk = sv[k], ek = ev[k];
+      madgrad_elem<EMA>(pk, gv[k], qk, sk, xv[k], ek, a);
+      pv[k] = pk, qv[k] = qk, sv[k] = sk, ev[k] = ek;
+    }
+    reinterpret_cast<f32x4*>(gss)[i] = qv;
+    reinterpret_cast<f32x4*>(s)[i] = sv;
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const size_t i = n4 * 4 + threadIdx.x;
+    float pk = p[i], qk = gss[i], sk = s[i], ek = EMA ? ema[i] : 0.f;
+    madgrad_elem<EMA>(pk, g[i], qk, sk, x0[i], ek, a);
+    gss[i] = qk, s[i] = sk, p[i] = pk;
+    if constexpr (EMA) ema[i] = ek;
+  }
+}
+
+bool aligned16(const void* q) { return (uintptr_t)q % 16 == 0; }
+
+}  // namespace
+
+int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* x0, size_t n, double lr, double momentum, double wd,
+                   double eps, int k, float gscale, hipStream_t st, float* ema, float ema_decay) {
+  MI355_ARG(p && g && gss && s && x0, "madgrad: null pointer");
+  MI355_ARG(aligned16(p) && aligned16(g) && aligned16(gss) && aligned16(s) && aligned16(x0) && aligned16(ema),
+            "madgrad: pointers must be 16-byte aligned");
+  MI355_ARG(momentum >= 0.0 && momentum < 1.0, "madgrad: momentum=%g outside [0, 1)", momentum);
+  MI355_ARG(std::isfinite(eps) && eps >= 0.0, "madgrad: eps=%g must be finite and >= 0", eps);
+  MI355_ARG(std::isfinite(lr) && lr >= 0.0, "madgrad: lr=%g must be finite and >= 0", lr);
+  MI355_ARG(std::isfinite(wd) && wd >= 0.0, "madgrad: weight_decay=%g must be finite and >= 0", wd);
+  MI355_ARG(k >= 0, "madgrad: step counter k=%d must be >= 0", k);
+  MI355_ARG(std::isfinite(gscale), "madgrad: grad_scale=%g is not finite", (double)gscale);
+  MI355_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "madgrad: ema_decay=%g outside [0, 1]", (double)ema_decay);
+  const double ck = 1.0 - momentum;
+  MadgradArgs a;
+  a.lamb = (float)((lr + eps) * std::pow((double)k + 1.0, 0.5));
+  a.eps = (float)eps;
+  a.mom = (float)(1.0 - ck);  // the reference multiplies by 1 - ck, not by momentum
+  a.ck = (float)ck;
+  a.wd_mul = (float)(1.0 - wd);
+  a.gscale = gscale;
+  a.ema_w = ema ? 1.f - ema_decay : 0.f;
+  const size_t n4 = n / 4;
+  const dim3 grid(adam_grid(n4)), block(256);
+  if (ema) hipLaunchKernelGGL((madgrad_kernel<true>), grid, block, 0, st, p, g, gss, s, x0, ema, n4, n, a);
+  else hipLaunchKernelGGL((madgrad_kernel<false>), grid, block, 0, st, p, g, gss, s, x0, ema, n4, n, a);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- AdaiS: src.optimizers.AdaiS.step of the reference (sota_imagenet/optimizers.py:569-639) as three device stages on one stream ----------------
+// (a) adais_moments_kernel, one launch per flat range:  g = g * grad_scale;  v = v * beta2 + ((1 - beta2) * g) * g;  workgroup b writes the sum of
+//     its elements' v / bc2 (bc2 = 1 - beta2^step of the range) to partial[b].  The sum is taken in double, per thread in element order and then by
+//     a fixed LDS tree: no floating-point atomics, and the grid is a function of n alone, so partial[] does not depend on scheduling.
+// (b) adais_mean_kernel, one workgroup of 1024:  mean = (sum of all partials of all ranges, fixed order, double) / param_size  -> one float on the device.
+// (c) adais_step_kernel, one launch per flat range, reading that float:
+//       p      = p * (1 - lr*wd)                           (only when wd != 0)
+//       beta1  = clamp(1 - ((v / bc2) / mean) * beta0, 0, 1 - eps)
+//       b1prod = b1prod * beta1
+//       m      = m * beta1 + (1 - beta1) * g
+//       p      = p + (-lr) * (m / (1 - b1prod))
+// 12 + 32 = 44 B / element (+ 8 with the average).  Padding holds v = 0 (not ema_norm_init), so it adds nothing to the sum; there beta1 = 1 - eps,
+// b1prod = m = 0 and p stays 0 for every eps.
+namespace {
+
+constexpr int kAdaisMaxBlocks = 16384;  // as adam_grid: fewer workgroups measured slower on this sweep class
+
+int adais_grid(size_t n) {
+  size_t b = (n / 4 + 255) / 256;
+  if (b > (size_t)kAdaisMaxBlocks) b = kAdaisMaxBlocks;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// sum of one double per thread over the T threads of the workgroup, in a fixed order
+template <int T>
+__device__ __forceinline__ double block_sum(double x, double* sh) {
+  sh[threadIdx.x] = x;
+  __syncthreads();
+#pragma unroll
+  for (int w = T / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+__global__ __launch_bounds__(256) void adais_moments_kernel(const float* __restrict__ g, float* __restrict__ v, double* __restrict__ partial,
+                                                            size_t n4, size_t n, float b2, float b2w, float bc2, float gscale) {
+  __shared__ double sh[256];
+  double acc = 0.0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];  // read again by the step kernel: a plain load
+    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float ge = gv[k] * gscale;
+      vv[k] = vv[k] * b2 + (b2w * ge) * ge;
+      acc += (double)(vv[k] / bc2);
+    }
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const size_t i = n4 * 4 + threadIdx.x;
+    const float ge = g[i] * gscale;
+    const float vk = v[i] * b2 + (b2w * ge) * ge;
+    v[i] = vk;
+    acc += (double)(vk / bc2);
+  }
+  const double tot = block_sum<256>(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(1024) void adais_mean_kernel(const double* __restrict__ partial, size_t count, double param_size, float* __restrict__ mean) {
+  __shared__ double sh[1024];
+  double acc = 0.0;
+#pragma unroll 4
+  for (size_t i = threadIdx.x; i < count; i += 1024) acc += partial[i];
+  const double tot = block_sum<1024>(acc, sh);
+  if (threadIdx.x == 0) mean[0] = (float)(tot / param_size);
+}
+
+struct AdaisArgs {
+  float decay;     // 1 - lr*wd (from double)
+  bool apply_wd;   // the reference skips the multiply when wd == 0
+  float bc2, beta0, b1max, neg_lr, gscale, ema_w;
+};
+
+template <bool EMA>
+__device__ __forceinline__ void adais_elem(float& p, float g, float& m, float v, float& bp, float& e, float mean, const AdaisArgs& a) {
+  const float ge = g * a.gscale;
+  float pe = p;
+  if (a.apply_wd) pe = pe * a.decay;
+  float beta1 = 1.0f - ((v / a.bc2) / mean) * a.beta0;
+  beta1 = fminf(fmaxf(beta1, 0.0f), a.b1max);
+  bp = bp * beta1;
+  m = m * beta1 + (1.0f - beta1) * ge;
+  pe = pe + a.neg_lr * (m / (1.0f - bp));
+  p = pe;
+  if constexpr (EMA) e = e + a.ema_w * (pe - e);
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adais_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         const float* __restrict__ v, float* __restrict__ bp, float* __restrict__ ema,
+                                                         const float* __restrict__ mean_ptr, size_t n4, size_t n, AdaisArgs a) {
+  const float mean = mean_ptr[0];
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+    const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);  // last use of the gradient
+    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
+    const f32x4 vv = reinterpret_cast<const f32x4*>(v)[i];
+    f32x4 bv = reinterpret_cast<f32x4*>(bp)[i];
+    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = pv[k], mk = mv[k], bk = bv[k], ek = ev[k];
+      adais_elem<EMA>(pk, gv[k], mk, vv[k], bk, ek, mean, a);
+      pv[k] = pk, mv[k] = mk, bv[k] = bk, ev[k] = ek;
+    }
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(bp)[i] = bv;
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const size_t i = n4 * 4 + threadIdx.x;
+    float pk = p[i], mk = m[i], bk = bp[i], ek = EMA ? ema[i] : 0.f;
+    adais_elem<EMA>(pk, g[i], mk, v[i], bk, ek, mean, a);
+    m[i] = mk, bp[i] = bk, p[i] = pk;
+    if constexpr (EMA) ema[i] = ek;
+  }
+}
+
+// bc2 = 1 - beta2^step in double, as the reference's Python does
+int adais_bc2(const char* who, double beta2, int step, float* bc2) {
+  MI355_ARG(beta2 >= 0.0 && beta2 < 1.0, "%s: beta2=%g outside [0, 1)", who, beta2);
+  MI355_ARG(step >= 1, "%s: step=%d must be >= 1 (the count after this step's increment)", who, step);
+  *bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  return 0;
+}
+
+}  // namespace
+
+size_t adais_partials(size_t n) { return (size_t)adais_grid(n); }
+
+int launch_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float gscale, double* partial, hipStream_t st) {
+  MI355_ARG(g && v && partial, "adais_moments: null pointer");
+  MI355_ARG(aligned16(g) && aligned16(v), "adais_moments: g and v must be 16-byte aligned");
+  MI355_ARG((uintptr_t)partial % 8 == 0, "adais_moments: the workspace must be 8-byte aligned");
+  float bc2;
+  MI355_TRY(adais_bc2("adais_moments", beta2, step, &bc2));
+  MI355_ARG(std::isfinite(gscale), "adais_moments: grad_scale=%g is not finite", (double)gscale);
+  const size_t n4 = n / 4;
+  hipLaunchKernelGGL(adais_moments_kernel, dim3(adais_grid(n)), dim3(256), 0, st, g, v, partial, n4, n, (float)beta2, (float)(1.0 - beta2), bc2,
+                     gscale);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adais_mean(const double* partial, size_t count, size_t param_size, float* mean, hipStream_t st) {
+  MI355_ARG(partial && mean, "adais_mean: null pointer");
+  MI355_ARG((uintptr_t)partial % 8 == 0 && (uintptr_t)mean % 4 == 0, "adais_mean: misaligned pointer");
+  MI355_ARG(count >= 1 && param_size >= 1, "adais_mean: count=%zu and param_size=%zu must be >= 1", count, param_size);
+  hipLaunchKernelGGL(adais_mean_kernel, dim3(1), dim3(1024), 0, st, partial, count, (double)param_size, mean);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adais_step(float* p, const float* g, float* m, const float* v, float* b1prod, const float* mean, size_t n, double lr, double beta0,
+                      double beta2, double eps, double wd, int step, float gscale, hipStream_t st, float* ema, float ema_decay) {
+  MI355_ARG(p && g && m && v && b1prod && mean, "adais_step: null pointer");
+  MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(b1prod) && aligned16(ema),
+            "adais_step: pointers must be 16-byte aligned");
+  MI355_ARG((uintptr_t)mean % 4 == 0, "adais_step: misaligned mean");
+  MI355_ARG(std::isfinite(lr) && lr >= 0.0, "adais_step: lr=%g must be finite and >= 0", lr);
+  MI355_ARG(std::isfinite(beta0) && beta0 >= 0.0, "adais_step: beta0=%g must be finite and >= 0", beta0);
+  MI355_ARG(std::isfinite(eps) && eps >= 0.0, "adais_step: eps=%g must be finite and >= 0", eps);
+  MI355_ARG(std::isfinite(wd) && wd >= 0.0, "adais_step: weight_decay=%g must be finite and >= 0", wd);
+  MI355_ARG(std::isfinite(gscale), "adais_step: grad_scale=%g is not finite", (double)gscale);
+  MI355_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "adais_step: ema_decay=%g outside [0, 1]", (double)ema_decay);
+  AdaisArgs a;
+  MI355_TRY(adais_bc2("adais_step", beta2, step, &a.bc2));
+  a.decay = (float)(1.0 - lr * wd);
+  a.apply_wd = wd != 0.0;
+  a.beta0 = (float)beta0;
+  a.b1max = (float)(1.0 - eps);
+  a.neg_lr = (float)(-lr);
+  a.gscale = gscale;
+  a.ema_w = ema ? 1.f - ema_decay : 0.f;
+  const size_t n4 = n / 4;
+  const dim3 grid(adam_grid(n4)), block(256);
+  if (ema) hipLaunchKernelGGL((adais_step_kernel<true>), grid, block, 0, st, p, g, m, v, b1prod, ema, mean, n4, n, a);
+  else hipLaunchKernelGGL((adais_step_kernel<false>), grid, block, 0, st, p, g, m, v, b1prod, ema, mean, n4, n, a);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mi355

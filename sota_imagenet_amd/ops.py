@@ -354,6 +354,67 @@ def adam_step(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0
     check(_L().mi355_adam_step_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), *args, ema_decay, cur_stream()))
 
 
+def _flat_f32(n, **named):
+    """every named tensor: contiguous CUDA fp32 of n elements"""
+    for name, t in named.items():
+        _need_cuda(t)
+        if t.dtype != torch.float32 or t.numel() != n:
+            raise ValueError(f"{name}: expected a float32 tensor of {n} elements, got {t.dtype} with {t.numel()}")
+
+
+def madgrad_step(p, g, grad_sum_sq, s, x0, k, lr, momentum=0.9, weight_decay=0.0, eps=1e-6, grad_scale=1.0, ema=None, ema_decay=0.0):
+    """one MADGRAD step (the reference's src.optimizers.MADGRAD) of a flat range; k: the optimizer's global counter before this step
+    (lamb = (lr + eps) * sqrt(k + 1) is formed natively in double); ema (optional): the moving average of the updated parameters,
+    advanced in the same kernel (mi355_madgrad_step_ema)"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, grad_sum_sq=grad_sum_sq, s=s, x0=x0)
+    args = (n, float(lr), float(momentum), float(weight_decay), float(eps), int(k), float(grad_scale))
+    if ema is None:
+        check(_L().mi355_madgrad_step(ptr(p), ptr(g), ptr(grad_sum_sq), ptr(s), ptr(x0), *args, cur_stream()))
+        return
+    _flat_f32(n, ema=ema)
+    check(_L().mi355_madgrad_step_ema(ptr(p), ptr(g), ptr(grad_sum_sq), ptr(s), ptr(x0), ptr(ema), *args, float(ema_decay), cur_stream()))
+
+
+def adais_workspace_elems(n):
+    """the number of float64 partial sums adais_moments writes for a range of n elements"""
+    return _L().mi355_adais_workspace_bytes(int(n)) // 8
+
+
+def adais_moments(g, v, step, beta2, workspace, grad_scale=1.0):
+    """AdaiS stage (a): v = v*beta2 + (1 - beta2)*g*g in place and the per-workgroup sums of v / (1 - beta2^step) into `workspace`
+    (float64, adais_workspace_elems(n) elements); step: the range's count after this step's increment"""
+    n = v.numel()
+    _flat_f32(n, g=g, v=v)
+    _need_cuda(workspace)
+    if workspace.dtype != torch.float64 or workspace.numel() != adais_workspace_elems(n):
+        raise ValueError(f"workspace: expected {adais_workspace_elems(n)} float64 elements, got {workspace.dtype} with {workspace.numel()}")
+    check(_L().mi355_adais_moments(ptr(g), ptr(v), n, float(beta2), int(step), float(grad_scale), ptr(workspace), cur_stream()))
+
+
+def adais_mean(workspace, param_size, mean):
+    """AdaiS stage (b): mean[0] = sum(workspace) / param_size, summed in a fixed order on the device (workspace: the float64 partial sums
+    of every range, back to back; mean: a float32 CUDA tensor of one element)"""
+    _need_cuda(workspace, mean)
+    if workspace.dtype != torch.float64 or mean.dtype != torch.float32 or mean.numel() != 1:
+        raise ValueError("adais_mean: workspace must be float64 and mean one float32 element")
+    check(_L().mi355_adais_mean(ptr(workspace), workspace.numel() * 8, int(param_size), ptr(mean), cur_stream()))
+
+
+def adais_step(p, g, m, v, beta1_prod, mean, step, lr, betas=(0.1, 0.99), eps=1e-3, weight_decay=0.0, grad_scale=1.0, ema=None, ema_decay=0.0):
+    """AdaiS stage (c): the parameter update of a flat range from the device-resident mean of stage (b); ema (optional): the moving average
+    of the updated parameters, advanced in the same kernel (mi355_adais_step_ema)"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, m=m, v=v, beta1_prod=beta1_prod)
+    _flat_f32(1, mean=mean)
+    args = (n, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), float(grad_scale))
+    if ema is None:
+        check(_L().mi355_adais_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(beta1_prod), ptr(mean), *args, cur_stream()))
+        return
+    _flat_f32(n, ema=ema)
+    check(_L().mi355_adais_step_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(beta1_prod), ptr(mean), ptr(ema), *args, float(ema_decay), cur_stream()))
+
+
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
 def blurpool_fwd(x):
     _need_cuda(x)

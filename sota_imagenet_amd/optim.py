@@ -1,4 +1,4 @@
-"""`SGD`, `Adam` and `AdamW` plugins: torch.optim-compatible optimizers whose step is ONE fused HIP kernel per flat range.
+"""`SGD`, `Adam`, `AdamW`, `MADGRAD` and `AdaiS` plugins: torch.optim-compatible optimizers whose step is fused HIP kernels over flat ranges.
 
 Drop-in for `_target_: torch.optim._multi_tensor.SGD` (sota_imagenet/arg_parser.py:136-138; r50 recipe adds
 momentum 0.9 / weight_decay 3e-5, configs/hydra_exp/1.r50_baseline.yaml:29-31; built at train.py:92 from
@@ -9,6 +9,8 @@ Parameters that are views of a model's flat fp32 array (models.ResNet50) are upd
 adjacent ranges of one param group collapse into a single launch (the default recipe = 1 launch / step).
 Adam / AdamW (csrc/optim.hip) share that range planner and the rest of the contract (attach_model, attach_ema, grad_scale,
 zero_grad, re-planning after load_state_dict); their per-parameter state is laid out as torch lays it out.
+MADGRAD and AdaiS are the reference's own optimizers (sota_imagenet/optimizers.py) on the same planner: MADGRAD is one launch per range,
+AdaiS three stages (moments + partial sums, the global mean, the update) because its momentum depends on a statistic of all parameters.
 """
 import torch
 from torch.optim import Optimizer
@@ -297,3 +299,160 @@ class AdamW(Adam):
         super().__setstate__(state)
         for group in self.param_groups:
             group["decoupled_weight_decay"] = True
+
+
+class MADGRAD(_FlatOptimizer):
+    """the reference's src.optimizers.MADGRAD (sota_imagenet/optimizers.py:650-770; recipe configs/hydra_exp/54.r50_madgrad.yaml) whose step
+    is one mi355_madgrad_step launch per flat range (csrc/optim.hip).  Signature, defaults and state are the reference's — state[p] =
+    {grad_sum_sq, s, x0} (views of flat arrays; x0 = the parameter before its first step) and the global counter state["k"], a 1-element
+    long CPU tensor — so a state_dict() moves both ways.  The rule, weight decay included (p *= 1 - weight_decay, decoupled and NOT
+    scaled by lr), is reproduced as the reference has it.
+    One deviation: lr == 0 is accepted.  The recipe reaches the constructor with `lr: 0` merged in from the base config and the
+    scheduler writes the real value before the first step, while the reference class raises on lr <= 0 (so the recipe cannot have run
+    with the merged default as written)."""
+
+    def __init__(self, params, lr=1e-2, momentum=0.9, weight_decay=0, eps=1e-6):
+        if momentum < 0 or momentum >= 1:
+            raise ValueError(f"Momentum {momentum} must be in the range [0,1)")
+        if lr < 0:
+            raise ValueError(f"Learning rate {lr} must be non-negative")
+        if weight_decay < 0:
+            raise ValueError(f"Weight decay {weight_decay} must be non-negative")
+        if eps < 0:
+            raise ValueError("Eps must be non-negative")
+        defaults = dict(lr=lr, eps=eps, momentum=momentum, weight_decay=weight_decay)
+        super().__init__(params, defaults)
+
+    # one plan per param group: list of (p, g, grad_sum_sq, s, x0, ema or None)
+    def _build_plans(self):
+        plans = [[] for _ in self.param_groups]
+        # padding inside a range computes 0 / (cbrt(0) + eps): zeros stay zeros only for eps > 0
+        bridge = all(float(g["eps"]) > 0.0 for g in self.param_groups)
+        for pb, gb, b, e, ps, gi in self._merged_ranges(bridge_padding=bridge):
+            fp, fg = self._flat_views(ps, b, e)
+            fq, fs, fx = (torch.zeros(e - b, dtype=torch.float32, device=fp.device) for _ in range(3))
+            for p in ps:
+                fresh = "grad_sum_sq" not in self.state[p]
+                self._state_view(fq, p, b, "grad_sum_sq")
+                self._state_view(fs, p, b, "s")
+                self._state_view(fx, p, b, "x0")
+                if fresh:
+                    self.state[p]["x0"].copy_(p.data)
+            plans[gi].append((fp, fg, fq, fs, fx, self._ema_slice(pb, b, e)))
+        self._check_ema([seg[5] for segs in plans for seg in segs])
+        k = self.state["k"] if "k" in self.state else torch.tensor([0], dtype=torch.long)
+        self.state["k"] = k.detach().to(device="cpu", dtype=torch.long).reshape(1)  # (a checkpoint may have been mapped to the GPU)
+        self._plans = plans
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._plans is None:
+            self._build_plans()
+        k = int(self.state["k"].item())
+        for group, segs in zip(self.param_groups, self._plans):
+            for fp, fg, fq, fs, fx, fe in segs:
+                ops.madgrad_step(fp, fg, fq, fs, fx, k, float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]),
+                                 float(group["eps"]), grad_scale=float(self.grad_scale), ema=fe,
+                                 ema_decay=self._ema[2] if fe is not None else 0.0)
+        self.state["k"] += 1
+        return loss
+
+
+class AdaiS(_FlatOptimizer):
+    """the reference's src.optimizers.AdaiS (sota_imagenet/optimizers.py:522-641; recipe configs/hydra_exp/50.r50_adais.yaml): Adai with
+    stable / decoupled weight decay.  Every element's momentum beta1 depends on the mean of the bias-corrected second moment over ALL
+    parameters of ALL groups, so a step is three device stages on the current stream (csrc/optim.hip) with nothing read back:
+    mi355_adais_moments per flat range, one mi355_adais_mean, mi355_adais_step per flat range.  Signature, defaults, validation and
+    state are the reference's — state[p] = {step: int, exp_avg, exp_avg_sq (from ema_norm_init), beta1_prod (from 1)}, the tensors
+    being views of flat arrays — so a state_dict() moves both ways.  Padding inside a range holds exp_avg_sq = 0 and is not counted in
+    param_size: it never enters the mean.  A launch range holds parameters of one group with equal step counts only."""
+
+    def __init__(self, params, lr=0, betas=(0.1, 0.99), eps=1e-3, weight_decay=0, ema_norm_init=1e-3):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        if not 0.0 <= betas[0]:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__(params, defaults)
+        self.ema_norm_init = ema_norm_init
+        self._planned = []   # the parameters whose state["step"] a step advances
+        self._ws = None      # float64 partial sums of every range, back to back
+        self._mean = None    # exp_avg_sq_hat_mean of the last step: one float32 on the device
+
+    @property
+    def exp_avg_sq_hat_mean(self):
+        """the statistic of the last step (a 1-element CUDA tensor the step kernels read; None before the first step)"""
+        return self._mean
+
+    def _step_count(self, p):
+        return int(self.state[p].get("step", 0))
+
+    # one plan per param group: list of [p, g, exp_avg, exp_avg_sq, beta1_prod, ema or None, step count of the range, workspace slice]
+    def _build_plans(self):
+        plans = [[] for _ in self.param_groups]
+        planned, total, dev = [], 0, None
+        for pb, gb, b, e, ps, gi in self._merged_ranges(split_key=self._step_count):
+            fp, fg = self._flat_views(ps, b, e)
+            if dev is not None and fp.device != dev:
+                raise RuntimeError("AdaiS: all parameters must live on one device (the mean is taken there)")
+            dev = fp.device
+            # zeros first, the initial values through the per-parameter views: padding keeps exp_avg_sq = 0 and stays out of the mean
+            fm, fv, fb = (torch.zeros(e - b, dtype=torch.float32, device=dev) for _ in range(3))
+            for p in ps:
+                fresh = "exp_avg_sq" not in self.state[p]
+                self._state_view(fm, p, b, "exp_avg")
+                self._state_view(fv, p, b, "exp_avg_sq")
+                self._state_view(fb, p, b, "beta1_prod")
+                if fresh:
+                    self.state[p]["step"] = 0
+                    self.state[p]["exp_avg_sq"].fill_(self.ema_norm_init)
+                    self.state[p]["beta1_prod"].fill_(1.0)
+                planned.append(p)
+            cnt = ops.adais_workspace_elems(e - b)
+            plans[gi].append([fp, fg, fm, fv, fb, self._ema_slice(pb, b, e), self._step_count(ps[0]), (total, total + cnt)])
+            total += cnt
+        self._check_ema([seg[5] for segs in plans for seg in segs])
+        self._planned = planned
+        self._param_size = sum(p.numel() for p in planned)
+        if planned:
+            self._ws = torch.zeros(total, dtype=torch.float64, device=dev)
+            self._mean = torch.zeros(1, dtype=torch.float32, device=dev)
+            for segs in plans:
+                for seg in segs:
+                    seg[7] = self._ws[seg[7][0]: seg[7][1]]
+        self._plans = plans
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._plans is None:
+            self._build_plans()
+        if not self._planned:
+            return loss
+        gs = float(self.grad_scale)
+        for group, segs in zip(self.param_groups, self._plans):
+            for seg in segs:
+                ops.adais_moments(seg[1], seg[3], seg[6] + 1, float(group["betas"][1]), seg[7], grad_scale=gs)
+        ops.adais_mean(self._ws, self._param_size, self._mean)
+        for group, segs in zip(self.param_groups, self._plans):
+            for seg in segs:
+                fp, fg, fm, fv, fb, fe, t, _ = seg
+                ops.adais_step(fp, fg, fm, fv, fb, self._mean, t + 1, float(group["lr"]), group["betas"], float(group["eps"]),
+                               float(group["weight_decay"]), grad_scale=gs, ema=fe, ema_decay=self._ema[2] if fe is not None else 0.0)
+                seg[6] = t + 1
+        for p in self._planned:
+            self.state[p]["step"] += 1
+        return loss
