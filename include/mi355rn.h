@@ -296,6 +296,44 @@ int mi355_adais_step_ema(float* p, const float* g, float* m, const float* v, flo
                          double lr, double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale,
                          float ema_decay, void* stream);
 
+/* The layer-wise optimizers of the reference's own tree on flat fp32 arrays: MyNovograd (sota_imagenet/optimizers.py:35-161, recipe
+ * configs/hydra_exp/47.r50_my-nov.yaml), NovogradApex (:189-290, 46.r50_nov.yaml), AdamLayerwise (:293-397, 49.r50_nov-adam.yaml) and
+ * MyAdai (:400-519, 55.r50_adai_2.yaml).  Each uses ONE statistic per parameter tensor (the sum of squares of its gradient; of the
+ * parameter itself for MyNovograd, :138) as a per-tensor scalar of the update.  Three stages on one stream, nothing read back, over two
+ * tables of 16-byte records in device memory that the caller builds once per plan:
+ *   items[]   { int64 off; int32 len; int32 tensor }   len <= mi355_lw_item_elems(), off a multiple of 4, cut from ONE tensor's own range
+ *   tensors[] { int32 first; int32 count; double numel }   the tensor's consecutive items (= its entries of partial[])
+ * A record that does not lie inside the arrays of the launch is skipped by the kernels.
+ *  (a) mi355_lw_sumsq, once per (parameter, gradient) storage pair: partial[i] = sum over items[i] of (src*scale)^2, the product in float,
+ *      the square and the sum in double, in a fixed order (no floating-point atomics).  Replaces grad.pow(2).sum() / .mean() per tensor
+ *      (:138, :270, :369, :488 — the last with an .item() host sync).
+ *  (b) mi355_lw_coef, once per param group: S = the tensor's partials summed in a fixed order -> sums[t]; stat = S, or S/numel with
+ *      flag 1 (MEAN).  In double, rounded once on store into coef[t] = (den, beta1, gw, wdf):
+ *        rule 0 (AdamLayerwise, NovogradApex) and rule 1 (MyNovograd), v = float32[n_tensors], updated in place (:140-146, :273-274, :370-371):
+ *          v = v*beta2 + (1 - beta2)*stat;  den = sqrt(v) + eps;  gw = 1 - beta1
+ *          wdf = 1 - lr*wd;  flag 2 (STABLE_WD): 1 - lr*wd/den (:388);  flag 4 (SOFT_WD, NovogradApex's wd_eps): lr*wd (:288)
+ *        rule 2 (MyAdai, :487-517), v = double[n_tensors] READ ONLY — the class never writes its second moment back into its state —
+ *          and `mean` the mean of those constants (:459), `beta1` the group's beta0:
+ *          vt = v*beta2 + stat*(1 - beta2);  r = vt/mean (flag 16 SQRT_MOM: sqrt(r));  beta1 = clip(1 - r*beta0, 0, 1 - eps)
+ *          gw = 1 - beta1, or 1 with flag 8 (SGD_MOM);  wdf = 1 - lr*wd;  flag 2: 1 - lr*wd/(1 - beta1)
+ *  (c) mi355_lw_update, once per param group over that group's items; p, m in place, g read-only (:144-159, :277-288, :374-391, :504-517):
+ *        g = g*grad_scale
+ *        rule 0:  m = m*beta1 + gw*(g/den);  p += -lr*m        rule 1:  m = m*beta1 + gw*g;  p += -lr*(m/den)
+ *        rule 2:  m = m*beta1 + gw*g;        p += -lr*m
+ *        p *= wdf;   with soft_wd (rule 0 only):  p -= wdf * max(|p| - wd_eps, 0) * sign(p)
+ *      mi355_lw_update_ema: + ema += (1 - ema_decay) * (p_new - ema) in the same pass (train.py:111-112).
+ * p, g, m, ema are the arrays the item offsets count from, n their length.  Each fails (-1) before any launch on a null or misaligned
+ * pointer (16 bytes for the arrays, the tables and coef), an empty table, a rule outside 0..2, betas outside [0, 1), eps / lr negative or not
+ * finite. */
+size_t mi355_lw_item_elems(void);
+int mi355_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, void* partial, void* stream);
+int mi355_lw_coef(int rule, int flags, const void* partial, size_t n_partial, const void* tensors, size_t n_tensors, void* v, float* coef,
+                  void* sums, double beta1, double beta2, double eps, double lr, double weight_decay, double mean, void* stream);
+int mi355_lw_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const float* coef, int n_tensors,
+                    double lr, int soft_wd, double wd_eps, float grad_scale, void* stream);
+int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
+                        int n_tensors, double lr, int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

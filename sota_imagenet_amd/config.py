@@ -38,6 +38,19 @@ TARGET_ALIASES = {
     "sota_imagenet.callbacks.CutmixMixup": "sota_imagenet_amd.callbacks.CutmixMixup",
 }
 
+# the reference's layer-wise optimizers (sota_imagenet/optimizers.py; recipes 46, 47, 49, 55), resolved like TARGET_ALIASES.  A table of its
+# own: tests/test_madgrad_adais_host.py, written while MyAdai was still left out, pins that "src.optimizers.MyAdai" is no key of TARGET_ALIASES
+LAYERWISE_TARGET_ALIASES = {
+    "src.optimizers.NovogradApex": "sota_imagenet_amd.optim.NovogradApex",
+    "sota_imagenet.optimizers.NovogradApex": "sota_imagenet_amd.optim.NovogradApex",
+    "src.optimizers.MyNovograd": "sota_imagenet_amd.optim.MyNovograd",
+    "sota_imagenet.optimizers.MyNovograd": "sota_imagenet_amd.optim.MyNovograd",
+    "src.optimizers.AdamLayerwise": "sota_imagenet_amd.optim.AdamLayerwise",
+    "sota_imagenet.optimizers.AdamLayerwise": "sota_imagenet_amd.optim.AdamLayerwise",
+    "src.optimizers.MyAdai": "sota_imagenet_amd.optim.MyAdai",
+    "sota_imagenet.optimizers.MyAdai": "sota_imagenet_amd.optim.MyAdai",
+}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -274,7 +287,7 @@ def validate(cfg):
 
 
 def resolve_target(path):
-    path = TARGET_ALIASES.get(path, path)
+    path = TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path, path)
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

@@ -346,6 +346,13 @@ int launch_adais_mean(const double* partial, size_t count, size_t param_size, fl
 int launch_adais_step(float* p, const float* g, float* m, const float* v, float* b1prod, const float* mean, size_t n, double lr, double beta0,
                       double beta2, double eps, double wd, int step, float gscale, hipStream_t st, float* ema = nullptr,
                       float ema_decay = 0.f);
+// optim_lw.hip: the layer-wise optimizers' three stages over a work-item table (items / tensors: 16-byte records, see there)
+size_t lw_item_elems();
+int launch_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, double* partial, hipStream_t st);
+int launch_lw_coef(int rule, int flags, const double* partial, size_t n_partial, const void* tensors, size_t n_tensors, void* v, float* coef,
+                   double* sums, double beta1, double beta2, double eps, double lr, double wd, double mean, hipStream_t st);
+int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
+                     int n_tensors, double lr, int soft_wd, double wd_eps, float gscale, float ema_decay, hipStream_t st);
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

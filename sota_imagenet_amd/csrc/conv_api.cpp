@@ -582,4 +582,24 @@ int mi355_adais_step_ema(float* p, const float* g, float* m, const float* v, flo
                            ema_decay);
 }
 
+size_t mi355_lw_item_elems(void) { return lw_item_elems(); }
+int mi355_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, void* partial, void* stream) {
+  return launch_lw_sumsq(src, n, items, n_items, n_tensors, scale, (double*)partial, (hipStream_t)stream);
+}
+int mi355_lw_coef(int rule, int flags, const void* partial, size_t n_partial, const void* tensors, size_t n_tensors, void* v, float* coef,
+                  void* sums, double beta1, double beta2, double eps, double lr, double weight_decay, double mean, void* stream) {
+  return launch_lw_coef(rule, flags, (const double*)partial, n_partial, tensors, n_tensors, v, coef, (double*)sums, beta1, beta2, eps, lr,
+                        weight_decay, mean, (hipStream_t)stream);
+}
+int mi355_lw_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const float* coef, int n_tensors,
+                    double lr, int soft_wd, double wd_eps, float grad_scale, void* stream) {
+  return launch_lw_update(rule, p, g, m, nullptr, n, items, n_items, coef, n_tensors, lr, soft_wd, wd_eps, grad_scale, 0.f, (hipStream_t)stream);
+}
+int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
+                        int n_tensors, double lr, int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "lw_update_ema: null ema");
+  return launch_lw_update(rule, p, g, m, ema, n, items, n_items, coef, n_tensors, lr, soft_wd, wd_eps, grad_scale, ema_decay,
+                          (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "optim_sum.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -186,8 +187,6 @@ __global__ __launch_bounds__(256) void madgrad_kernel(float* __restrict__ p, con
   }
 }
 
-bool aligned16(const void* q) { return (uintptr_t)q % 16 == 0; }
-
 }  // namespace
 
 int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* x0, size_t n, double lr, double momentum, double wd,
@@ -241,19 +240,6 @@ int adais_grid(size_t n) {
   if (b > (size_t)kAdaisMaxBlocks) b = kAdaisMaxBlocks;
   if (b < 1) b = 1;
   return (int)b;
-}
-
-// sum of one double per thread over the T threads of the workgroup, in a fixed order
-template <int T>
-__device__ __forceinline__ double block_sum(double x, double* sh) {
-  sh[threadIdx.x] = x;
-  __syncthreads();
-#pragma unroll
-  for (int w = T / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  return sh[0];
 }
 
 __global__ __launch_bounds__(256) void adais_moments_kernel(const float* __restrict__ g, float* __restrict__ v, double* __restrict__ partial,

@@ -1,0 +1,257 @@
+// optim_lw.hip — the layer-wise optimizers of the reference's own tree (sota_imagenet/optimizers.py: MyNovograd :35-161, NovogradApex :189-290,
+// AdamLayerwise :293-397, MyAdai :400-519) on flat fp32 arrays (gfx950).  Each of them needs one statistic PER PARAMETER TENSOR — the sum of
+// squares of its gradient, or of the parameter itself for MyNovograd — and uses it as a per-tensor scalar in the update.  A step is three
+// stages on one stream, nothing read back by the host, over a work-item table the host builds once per plan:
+//   item   = (element offset, length <= lw_item_elems(), tensor index), cut from one tensor's own dense range: never across two tensors,
+//            never in padding, the cuts a function of the tensor's numel alone; the items of one tensor are consecutive.
+//   (a) lw_sumsq_kernel, one workgroup per item: x = src * scale in float, x * x summed in double — per thread in element order, then the
+//       fixed LDS tree of optim_sum.h — into partial[item].  No floating-point atomics: partial[] does not depend on scheduling.
+//   (b) lw_coef_kernel, one workgroup (one wave) per tensor of a param group: S = sum of the tensor's partials in a fixed order, then in double,
+//       rounded once on store,
+//         rules 0 and 1:  v = v*beta2 + (1 - beta2)*stat  (held in float32 as the reference holds it; stat = S, or S / numel with LW_MEAN)
+//                         den = sqrt(v) + eps;  wdf = 1 - lr*wd,  or 1 - lr*wd/den (LW_STABLE_WD),  or lr*wd (LW_SOFT_WD)
+//         rule 2 (MyAdai): vt = v0*beta2 + (S/numel)*(1 - beta2)   with v0 the constant the class keeps in its state (it never writes vt back)
+//                         beta1 = clip(1 - (vt/mean or sqrt(vt/mean))*beta0, 0, 1 - eps);  gw = 1 (LW_SGD_MOM) or 1 - beta1
+//                         wdf = 1 - lr*wd, or 1 - lr*wd/(1 - beta1) (LW_STABLE_WD)
+//       -> coef[tensor] = (den, beta1, gw, wdf) in float32
+//   (c) lw_update_kernel<RULE, EMA>, one workgroup per item of a param group, the item's coefficients read once per workgroup:
+//         g = g * grad_scale
+//         rule 0 (AdamLayerwise, NovogradApex):  m = m*beta1 + gw*(g/den);  p = p + (-lr)*m
+//         rule 1 (MyNovograd):                   m = m*beta1 + gw*g;        p = p + (-lr)*(m/den)
+//         rule 2 (MyAdai):                       m = m*beta1 + gw*g;        p = p + (-lr)*m
+//         p = p*wdf,  or with LW_SOFT_WD (NovogradApex's wd_eps)  p = p - wdf*(max(|p| - wd_eps, 0)*sign(p))
+//         EMA: ema = ema + (1 - decay)*(p - ema)
+// 4 B / element in (a) + 20 B / element in (c) (p, m read + write, g read once more, non-temporal: its last use), 28 B with the average.
+// The library builds with -ffp-contract=off, and sqrt / '/' stay correctly rounded.
+#include <cmath>
+
+#include "common.h"
+#include "optim_sum.h"
+#include "vec.h"
+
+namespace mi355 {
+namespace {
+
+#ifndef MI355_LW_ITEM_ELEMS
+#define MI355_LW_ITEM_ELEMS 4096  // 16 elements per thread: the ResNet-50 array is 6.3 k work items.  Other values: profiles/layerwise_step.json
+#endif
+constexpr int kLwItemElems = MI355_LW_ITEM_ELEMS;
+static_assert(kLwItemElems >= 256 && kLwItemElems % 4 == 0, "an item is a whole number of float4, at least one per thread of a wave");
+
+struct LwItem {
+  long long off;  // first element, relative to the array pointers of the launch
+  int len;        // 1 .. kLwItemElems
+  int tensor;     // index into coef[]
+};
+struct LwTensor {
+  int first, count;  // its items in the table (and its partial sums in partial[])
+  double numel;
+};
+static_assert(sizeof(LwItem) == 16 && sizeof(LwTensor) == 16, "table records are 16 bytes");
+
+enum { LW_MEAN = 1, LW_STABLE_WD = 2, LW_SOFT_WD = 4, LW_SGD_MOM = 8, LW_SQRT_MOM = 16 };
+
+// a record that does not lie inside the arrays of the launch is skipped: the tables are checked by the host when they are built, this keeps a
+// stale or foreign table from ever becoming an out-of-bounds access
+__device__ __forceinline__ bool item_ok(const LwItem& it, size_t n, int n_tensors) {
+  return it.off >= 0 && it.len > 0 && it.len <= kLwItemElems && (size_t)it.off + (size_t)it.len <= n && it.tensor >= 0 && it.tensor < n_tensors &&
+         (it.off & 3) == 0;
+}
+
+__global__ __launch_bounds__(256) void lw_sumsq_kernel(const float* __restrict__ src, size_t n, const LwItem* __restrict__ items,
+                                                       double* __restrict__ partial, int n_tensors, float scale) {
+  __shared__ double sh[256];
+  const LwItem it = items[blockIdx.x];
+  double acc = 0.0;
+  if (item_ok(it, n, n_tensors)) {
+    const float* s = src + it.off;
+    const int n4 = it.len >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const f32x4 x = reinterpret_cast<const f32x4*>(s)[i];  // read again by the update kernel: a plain load
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const double e = (double)(x[k] * scale);
+        acc += e * e;
+      }
+    }
+    if ((int)threadIdx.x < (it.len & 3)) {
+      const double e = (double)(s[n4 * 4 + threadIdx.x] * scale);
+      acc += e * e;
+    }
+  }
+  const double tot = block_sum<256>(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+struct LwCoefArgs {
+  double beta1, beta2, eps, lr, wd, mean;  // beta1: beta0 for rule 2;  mean: rule 2 only
+  int rule, flags;
+};
+
+__global__ __launch_bounds__(64) void lw_coef_kernel(const double* __restrict__ partial, size_t n_partial, const LwTensor* __restrict__ tens,
+                                                     void* __restrict__ vstate, float* __restrict__ coef, double* __restrict__ sums, LwCoefArgs a) {
+  __shared__ double sh[64];
+  const LwTensor t = tens[blockIdx.x];
+  const bool ok = t.first >= 0 && t.count > 0 && (size_t)t.first + (size_t)t.count <= n_partial;
+  double acc = 0.0;
+  if (ok)
+    for (int i = threadIdx.x; i < t.count; i += 64) acc += partial[t.first + i];
+  const double S = block_sum<64>(acc, sh);
+  if (threadIdx.x != 0 || !ok) return;
+  sums[blockIdx.x] = S;
+  const double stat = (a.flags & LW_MEAN) ? S / t.numel : S;
+  const double lrwd = a.lr * a.wd;
+  double den = 1.0, b1 = a.beta1, gw = 1.0 - a.beta1, wdf = 1.0 - lrwd;
+  if (a.rule != 2) {
+    float* v = reinterpret_cast<float*>(vstate) + blockIdx.x;
+    const float vn = (float)((double)v[0] * a.beta2 + (1.0 - a.beta2) * stat);
+    v[0] = vn;
+    den = sqrt((double)vn) + a.eps;
+    if (a.flags & LW_STABLE_WD) wdf = 1.0 - lrwd / den;
+    if (a.flags & LW_SOFT_WD) wdf = lrwd;
+  } else {
+    const double v0 = reinterpret_cast<const double*>(vstate)[blockIdx.x];
+    const double vt = v0 * a.beta2 + stat * (1.0 - a.beta2);
+    const double r = vt / a.mean;
+    b1 = 1.0 - ((a.flags & LW_SQRT_MOM) ? sqrt(r) : r) * a.beta1;
+    b1 = fmin(fmax(b1, 0.0), 1.0 - a.eps);
+    gw = (a.flags & LW_SGD_MOM) ? 1.0 : 1.0 - b1;
+    if (a.flags & LW_STABLE_WD) wdf = 1.0 - lrwd / (1.0 - b1);
+  }
+  f32x4 c = {(float)den, (float)b1, (float)gw, (float)wdf};
+  reinterpret_cast<f32x4*>(coef)[blockIdx.x] = c;
+}
+
+struct LwUpdArgs {
+  float neg_lr, gscale, ema_w, wd_eps;
+  bool soft_wd;
+};
+
+template <int RULE, bool EMA>
+__device__ __forceinline__ void lw_elem(float& p, float g, float& m, float& e, const f32x4& c, const LwUpdArgs& a) {
+  const float ge = g * a.gscale;
+  float pe;
+  if constexpr (RULE == 0) {
+    m = m * c[1] + c[2] * (ge / c[0]);
+    pe = p + a.neg_lr * m;
+  } else if constexpr (RULE == 1) {
+    m = m * c[1] + c[2] * ge;
+    pe = p + a.neg_lr * (m / c[0]);
+  } else {
+    m = m * c[1] + c[2] * ge;
+    pe = p + a.neg_lr * m;
+  }
+  if (RULE == 0 && a.soft_wd) pe = pe - c[3] * copysignf(fmaxf(fabsf(pe) - a.wd_eps, 0.0f), pe);
+  else pe = pe * c[3];
+  p = pe;
+  if constexpr (EMA) e = e + a.ema_w * (pe - e);
+}
+
+template <int RULE, bool EMA>
+__global__ __launch_bounds__(256) void lw_update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ ema, size_t n, const LwItem* __restrict__ items,
+                                                        const float* __restrict__ coef, int n_tensors, LwUpdArgs a) {
+  const LwItem it = items[blockIdx.x];
+  if (!item_ok(it, n, n_tensors)) return;
+  const f32x4 c = reinterpret_cast<const f32x4*>(coef)[it.tensor];
+  f32x4* p4 = reinterpret_cast<f32x4*>(p + it.off);
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(g + it.off);
+  f32x4* m4 = reinterpret_cast<f32x4*>(m + it.off);
+  f32x4* e4 = EMA ? reinterpret_cast<f32x4*>(ema + it.off) : nullptr;
+  const int n4 = it.len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    f32x4 pv = p4[i];
+    const f32x4 gv = __builtin_nontemporal_load(g4 + i);  // last use of the gradient
+    f32x4 mv = m4[i];
+    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) ev = e4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = pv[k], mk = mv[k], ek = ev[k];
+      lw_elem<RULE, EMA>(pk, gv[k], mk, ek, c, a);
+      pv[k] = pk, mv[k] = mk, ev[k] = ek;
+    }
+    m4[i] = mv;
+    p4[i] = pv;
+    if constexpr (EMA) e4[i] = ev;
+  }
+  if ((int)threadIdx.x < (it.len & 3)) {
+    const size_t i = (size_t)it.off + n4 * 4 + threadIdx.x;
+    float pk = p[i], mk = m[i], ek = EMA ? ema[i] : 0.f;
+    lw_elem<RULE, EMA>(pk, g[i], mk, ek, c, a);
+    m[i] = mk, p[i] = pk;
+    if constexpr (EMA) ema[i] = ek;
+  }
+}
+
+template <int RULE>
+void lw_update_launch(bool ema_on, dim3 grid, hipStream_t st, float* p, const float* g, float* m, float* ema, size_t n, const LwItem* items,
+                      const float* coef, int n_tensors, const LwUpdArgs& a) {
+  if (ema_on) hipLaunchKernelGGL((lw_update_kernel<RULE, true>), grid, dim3(256), 0, st, p, g, m, ema, n, items, coef, n_tensors, a);
+  else hipLaunchKernelGGL((lw_update_kernel<RULE, false>), grid, dim3(256), 0, st, p, g, m, ema, n, items, coef, n_tensors, a);
+}
+
+constexpr size_t kLwMaxGrid = 1u << 30;
+
+}  // namespace
+
+size_t lw_item_elems() { return kLwItemElems; }
+
+int launch_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, double* partial, hipStream_t st) {
+  MI355_ARG(src && items && partial, "lw_sumsq: null pointer");
+  MI355_ARG(aligned16(src) && aligned16(items) && (uintptr_t)partial % 8 == 0, "lw_sumsq: misaligned pointer (16 bytes for the array and the table)");
+  MI355_ARG(n_items >= 1 && n_items <= kLwMaxGrid && n_tensors >= 1, "lw_sumsq: n_items=%zu, n_tensors=%d out of range", n_items, n_tensors);
+  MI355_ARG(std::isfinite(scale), "lw_sumsq: scale=%g is not finite", (double)scale);
+  hipLaunchKernelGGL(lw_sumsq_kernel, dim3((unsigned)n_items), dim3(256), 0, st, src, n, (const LwItem*)items, partial, n_tensors, scale);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_lw_coef(int rule, int flags, const double* partial, size_t n_partial, const void* tensors, size_t n_tensors, void* v, float* coef,
+                   double* sums, double beta1, double beta2, double eps, double lr, double wd, double mean, hipStream_t st) {
+  MI355_ARG(partial && tensors && v && coef && sums, "lw_coef: null pointer");
+  MI355_ARG((uintptr_t)partial % 8 == 0 && aligned16(tensors) && aligned16(coef) && (uintptr_t)sums % 8 == 0 &&
+                (uintptr_t)v % (rule == 2 ? 8 : 4) == 0,
+            "lw_coef: misaligned pointer");
+  MI355_ARG(rule >= 0 && rule <= 2, "lw_coef: rule=%d outside 0..2", rule);
+  MI355_ARG((flags & ~(LW_MEAN | LW_STABLE_WD | LW_SOFT_WD | LW_SGD_MOM | LW_SQRT_MOM)) == 0, "lw_coef: unknown flag in %d", flags);
+  MI355_ARG(n_tensors >= 1 && n_tensors <= kLwMaxGrid && n_partial >= 1, "lw_coef: n_tensors=%zu, n_partial=%zu out of range", n_tensors, n_partial);
+  MI355_ARG(beta1 >= 0.0 && beta1 < 1.0, "lw_coef: beta1=%g outside [0, 1)", beta1);
+  MI355_ARG(beta2 >= 0.0 && beta2 < 1.0, "lw_coef: beta2=%g outside [0, 1)", beta2);
+  MI355_ARG(std::isfinite(eps) && eps >= 0.0, "lw_coef: eps=%g must be finite and >= 0", eps);
+  MI355_ARG(std::isfinite(lr) && lr >= 0.0, "lw_coef: lr=%g must be finite and >= 0", lr);
+  MI355_ARG(std::isfinite(wd), "lw_coef: weight_decay=%g is not finite", wd);
+  MI355_ARG(rule != 2 || (std::isfinite(mean) && mean > 0.0), "lw_coef: mean=%g must be finite and > 0", mean);
+  LwCoefArgs a{beta1, beta2, eps, lr, wd, mean, rule, flags};
+  hipLaunchKernelGGL(lw_coef_kernel, dim3((unsigned)n_tensors), dim3(64), 0, st, partial, n_partial, (const LwTensor*)tensors, v, coef, sums, a);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
+                     int n_tensors, double lr, int soft_wd, double wd_eps, float gscale, float ema_decay, hipStream_t st) {
+  MI355_ARG(p && g && m && items && coef, "lw_update: null pointer");
+  MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(ema) && aligned16(items) && aligned16(coef),
+            "lw_update: pointers must be 16-byte aligned");
+  MI355_ARG(rule >= 0 && rule <= 2, "lw_update: rule=%d outside 0..2", rule);
+  MI355_ARG(n_items >= 1 && n_items <= kLwMaxGrid && n_tensors >= 1, "lw_update: n_items=%zu, n_tensors=%d out of range", n_items, n_tensors);
+  MI355_ARG(std::isfinite(lr) && lr >= 0.0, "lw_update: lr=%g must be finite and >= 0", lr);
+  MI355_ARG(!soft_wd || (rule == 0 && std::isfinite(wd_eps)), "lw_update: wd_eps=%g needs rule 0 and a finite value", wd_eps);
+  MI355_ARG(std::isfinite(gscale), "lw_update: grad_scale=%g is not finite", (double)gscale);
+  MI355_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "lw_update: ema_decay=%g outside [0, 1]", (double)ema_decay);
+  LwUpdArgs a;
+  a.neg_lr = (float)(-lr);
+  a.gscale = gscale;
+  a.ema_w = ema ? 1.f - ema_decay : 0.f;
+  a.wd_eps = soft_wd ? (float)wd_eps : 0.f;
+  a.soft_wd = soft_wd != 0;
+  const dim3 grid((unsigned)n_items);
+  const LwItem* it = (const LwItem*)items;
+  if (rule == 0) lw_update_launch<0>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
+  else if (rule == 1) lw_update_launch<1>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
+  else lw_update_launch<2>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace mi355

@@ -415,6 +415,66 @@ def adais_step(p, g, m, v, beta1_prod, mean, step, lr, betas=(0.1, 0.99), eps=1e
     check(_L().mi355_adais_step_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(beta1_prod), ptr(mean), ptr(ema), *args, float(ema_decay), cur_stream()))
 
 
+# ---- layer-wise optimizers (include/mi355rn.h, csrc/optim_lw.hip): MyNovograd, NovogradApex, AdamLayerwise, MyAdai of the reference ------
+LW_NORMGRAD, LW_NOVOGRAD, LW_ADAI = 0, 1, 2  # the element rule: AdamLayerwise / NovogradApex, MyNovograd, MyAdai
+LW_MEAN, LW_STABLE_WD, LW_SOFT_WD, LW_SGD_MOM, LW_SQRT_MOM = 1, 2, 4, 8, 16
+
+
+def lw_item_elems():
+    """W: the most elements one work item (= one workgroup) covers"""
+    return int(_L().mi355_lw_item_elems())
+
+
+def _lw_table(name, t):
+    _need_cuda(t)
+    if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < 1:
+        raise ValueError(f"{name}: expected a CUDA int64 tensor [n, 2] of 16-byte records, got {t.dtype} {tuple(t.shape)}")
+
+
+def lw_sumsq(src, items, partial, n_tensors, scale=1.0):
+    """stage (a), replaces the per-tensor grad.pow(2).sum() / .mean() of sota_imagenet/optimizers.py:138, :270, :369, :488:
+    partial[i] = sum over work item i of (src * scale)^2 in double; src: the flat fp32 array the item offsets count from"""
+    _flat_f32(src.numel(), src=src)
+    _lw_table("items", items)
+    _need_cuda(partial)
+    if partial.dtype != torch.float64 or partial.numel() != items.shape[0]:
+        raise ValueError(f"partial: expected {items.shape[0]} float64 elements, got {partial.dtype} with {partial.numel()}")
+    check(_L().mi355_lw_sumsq(ptr(src), src.numel(), ptr(items), items.shape[0], int(n_tensors), float(scale), ptr(partial), cur_stream()))
+
+
+def lw_coef(rule, flags, partial, tensors, v, coef, sums, beta1, beta2, eps, lr, weight_decay, mean=1.0):
+    """stage (b), replaces optimizers.py:140-146, :273-274, :370-371, :489-501 for the tensors of one param group: sums[t] = the tensor's
+    partials in a fixed order, v (float32 per tensor, updated in place; LW_ADAI: float64, read only) and coef[t] = (den, beta1, gw, wdf)"""
+    _lw_table("tensors", tensors)
+    nt = tensors.shape[0]
+    _need_cuda(partial, v, coef, sums)
+    if partial.dtype != torch.float64 or sums.dtype != torch.float64 or sums.numel() != nt:
+        raise ValueError("lw_coef: partial and sums must be float64, sums one element per tensor")
+    if v.dtype != (torch.float64 if rule == LW_ADAI else torch.float32) or v.numel() != nt:
+        raise ValueError(f"lw_coef: v must hold one {'float64' if rule == LW_ADAI else 'float32'} per tensor")
+    if coef.dtype != torch.float32 or coef.numel() != 4 * nt:
+        raise ValueError("lw_coef: coef must hold four float32 per tensor")
+    check(_L().mi355_lw_coef(int(rule), int(flags), ptr(partial), partial.numel(), ptr(tensors), nt, ptr(v), ptr(coef), ptr(sums), float(beta1),
+                             float(beta2), float(eps), float(lr), float(weight_decay), float(mean), cur_stream()))
+
+
+def lw_update(rule, p, g, m, items, coef, lr, wd_eps=None, grad_scale=1.0, ema=None, ema_decay=0.0):
+    """stage (c), replaces optimizers.py:144-159, :277-288, :374-391, :504-517 for the work items of one param group; p, g, m (and ema): the
+    flat fp32 arrays the item offsets count from; coef: the whole [n_tensors, 4] table of stage (b)"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, m=m)
+    _lw_table("items", items)
+    _need_cuda(coef)
+    if coef.dtype != torch.float32 or coef.numel() % 4:
+        raise ValueError("lw_update: coef must hold four float32 per tensor")
+    args = (n, ptr(items), items.shape[0], ptr(coef), coef.numel() // 4, float(lr), int(wd_eps is not None), float(wd_eps or 0.0), float(grad_scale))
+    if ema is None:
+        check(_L().mi355_lw_update(int(rule), ptr(p), ptr(g), ptr(m), *args, cur_stream()))
+        return
+    _flat_f32(n, ema=ema)
+    check(_L().mi355_lw_update_ema(int(rule), ptr(p), ptr(g), ptr(m), ptr(ema), *args, float(ema_decay), cur_stream()))
+
+
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
 def blurpool_fwd(x):
     _need_cuda(x)

@@ -1,4 +1,4 @@
-"""`SGD`, `Adam`, `AdamW`, `MADGRAD` and `AdaiS` plugins: torch.optim-compatible optimizers whose step is fused HIP kernels over flat ranges.
+"""`SGD`, `Adam`, `AdamW`, `MADGRAD`, `AdaiS`, `NovogradApex`, `MyNovograd`, `AdamLayerwise` and `MyAdai` plugins: torch.optim-compatible optimizers whose step is fused HIP kernels over flat ranges.
 
 Drop-in for `_target_: torch.optim._multi_tensor.SGD` (sota_imagenet/arg_parser.py:136-138; r50 recipe adds
 momentum 0.9 / weight_decay 3e-5, configs/hydra_exp/1.r50_baseline.yaml:29-31; built at train.py:92 from
@@ -11,7 +11,10 @@ Adam / AdamW (csrc/optim.hip) share that range planner and the rest of the contr
 zero_grad, re-planning after load_state_dict); their per-parameter state is laid out as torch lays it out.
 MADGRAD and AdaiS are the reference's own optimizers (sota_imagenet/optimizers.py) on the same planner: MADGRAD is one launch per range,
 AdaiS three stages (moments + partial sums, the global mean, the update) because its momentum depends on a statistic of all parameters.
+NovogradApex, MyNovograd, AdamLayerwise and MyAdai (the reference's layer-wise optimizers) use one statistic PER TENSOR: they do not merge ranges
+but cut every parameter's own range into work items (lw_plan_items) and run three stages over that table (csrc/optim_lw.hip).
 """
+import numpy as np
 import torch
 from torch.optim import Optimizer
 
@@ -65,12 +68,10 @@ class _FlatOptimizer(Optimizer):
         self._ema = None
         self._plans = None
 
-    def _merged_ranges(self, split_key=None, bridge_padding=True):
-        """[[param base, grad base, first elem, end elem, [params], group index]]: one entry per launch.  Parameters whose
-        split_key differs (Adam: their step counts) never share a range; bridge_padding=False when the update would not keep
-        zeros zero (Adam with eps = 0: 0/0)."""
+    def _entries(self):
+        """[(param base, grad base, first elem, numel, group index, param)] of every parameter with a gradient, group by group"""
         name = type(self).__name__
-        entries = []  # (param base, grad base, first elem, numel, group index, param)
+        entries = []
         for gi, group in enumerate(self.param_groups):
             for p in group["params"]:
                 if p.grad is None:
@@ -81,6 +82,14 @@ class _FlatOptimizer(Optimizer):
                 if rp is None or rg is None or rp[1:] != rg[1:]:
                     raise RuntimeError(f"{name}: parameter and gradient must be dense and share their flat offset")
                 entries.append((rp[0], rg[0], rp[1], rp[2], gi, p))
+        return entries
+
+    def _merged_ranges(self, split_key=None, bridge_padding=True):
+        """[[param base, grad base, first elem, end elem, [params], group index]]: one entry per launch.  Parameters whose
+        split_key differs (Adam: their step counts) never share a range; bridge_padding=False when the update would not keep
+        zeros zero (Adam with eps = 0: 0/0)."""
+        name = type(self).__name__
+        entries = self._entries()
         # Neighbours of one group merge into one launch only when the gap between them is PROVABLY padding (zeros stay
         # zeros under the update): every tensor of the attached models that this optimizer does not update in the same
         # group — frozen parameters, parameters of another group, parameters without a gradient — acts as a barrier.
@@ -456,3 +465,297 @@ class AdaiS(_FlatOptimizer):
         for p in self._planned:
             self.state[p]["step"] += 1
         return loss
+
+
+def lw_plan_items(tensors, W):
+    """the work-item table of the layer-wise optimizers.  tensors: [(first element, numel)] in table order; returns (items, spans):
+    items = [(first element, length, tensor index)], every tensor's own range cut at multiples of W from its start (the cuts depend on numel
+    alone), the items of one tensor consecutive; spans = [(first item, item count)] per tensor.  Nothing outside a tensor's range — alignment
+    gaps, the FC padding — is ever covered."""
+    items, spans = [], []
+    for t, (off, n) in enumerate(tensors):
+        if n < 1:
+            raise ValueError(f"tensor {t}: numel={n} must be >= 1")
+        spans.append((len(items), (n + W - 1) // W))
+        items.extend((off + c, min(W, n - c), t) for c in range(0, n, W))
+    return items, spans
+
+
+class _Layerwise(_FlatOptimizer):
+    """what NovogradApex, MyNovograd, AdamLayerwise and MyAdai share: the work-item plan and the three stages of csrc/optim_lw.hip —
+    (a) one lw_sumsq launch per (parameter storage, gradient storage) pair, (b) one lw_coef launch per param group, (c) one lw_update
+    launch per param group (and storage pair) — 3 launches per step for a flat model in one group, 1 + 2 + 2 with filter_from_wd.
+    The first moment is a view of a flat array as in the other native optimizers.  The second moment, which the reference keeps as a
+    full-size tensor holding ONE value, is one float32 slot per tensor on the device: state[p][key] is a stride-0 view of it with the
+    parameter's shape, state_dict() returns dense copies (the reference loads them), load_state_dict() accepts the reference's dense tensors
+    (checked once for min == max) and keeps element 0."""
+
+    _rule = ops.LW_NORMGRAD
+    _m_key, _v_key = "exp_avg", "exp_avg_sq"
+    _param_stat = False  # MyNovograd: the statistic is taken of the parameter, not of the gradient
+
+    def _v_init(self, group):
+        return self.ema_norm_init
+
+    def _coef_args(self, group):
+        """(flags, beta1, beta2, eps) of stage (b) for one group"""
+        raise NotImplementedError
+
+    def _wd_eps(self):
+        return None
+
+    def _build_plans(self):
+        name = type(self).__name__
+        W = ops.lw_item_elems()
+        entries = self._entries()
+        self._planned = [e[5] for e in entries]
+        self._segs, self._coefs = [], []
+        if not entries:
+            self._plans = []
+            return
+        dev = entries[0][5].device
+        for pb, gb, off, n, gi, p in entries:
+            if p.device != dev:
+                raise RuntimeError(f"{name}: all parameters must live on one device")
+            if (off * 4) % 16 or p.data_ptr() % 16 or p.grad.data_ptr() % 16:
+                raise RuntimeError(f"{name}: flat range not 16-byte aligned")
+        pairs = {}  # (param base, grad base) -> [lo, hi, entry indices]
+        for t, (pb, gb, off, n, gi, p) in enumerate(entries):
+            r = pairs.setdefault((pb, gb), [off, off + n, []])
+            r[0], r[1] = min(r[0], off), max(r[1], off + n)
+            r[2].append(t)
+        # table order: storage pair by storage pair, inside it group by group (entries are in group order); tensor index = entry index
+        order = [t for r in pairs.values() for t in r[2]]
+        lo_of = {t: r[0] for r in pairs.values() for t in r[2]}
+        items, spans = lw_plan_items([(entries[t][2] - lo_of[t], entries[t][3]) for t in order], W)
+        rec = np.zeros(len(items), dtype=[("off", "<i8"), ("len", "<i4"), ("t", "<i4")])
+        ten = np.zeros(len(entries), dtype=[("first", "<i4"), ("count", "<i4"), ("numel", "<f8")])
+        for k, (o, ln, j) in enumerate(items):
+            rec[k] = (o, ln, order[j])
+        for j, (first, count) in enumerate(spans):
+            ten[order[j]] = (first, count, float(entries[order[j]][3]))
+        self._items = torch.from_numpy(rec.view(np.int64).reshape(-1, 2)).to(dev)
+        self._tensors = torch.from_numpy(ten.view(np.int64).reshape(-1, 2)).to(dev)
+        nt = len(entries)
+        self._partial = torch.zeros(len(items), dtype=torch.float64, device=dev)
+        self._sums = torch.zeros(nt, dtype=torch.float64, device=dev)   # S per tensor of the last step (tensor order = group by group)
+        self._coef = torch.zeros(nt, 4, dtype=torch.float32, device=dev)
+        self._v = self._make_v(entries, dev)
+        span_of = {order[j]: spans[j] for j in range(nt)}
+        ema_slices = []
+        for (pb, gb), (lo, hi, ts) in pairs.items():
+            ps = [entries[t][5] for t in ts]
+            fp, fg = self._flat_views(ps, lo, hi)
+            fm = torch.zeros(hi - lo, dtype=torch.float32, device=dev)
+            for p in ps:
+                fresh = self._m_key not in self.state[p]
+                self._state_view(fm, p, lo, self._m_key)
+                if fresh:
+                    self.state[p].setdefault("step", 0)
+            fe = self._ema_slice(pb, lo, hi)
+            ema_slices.append(fe)
+            i0, i1 = span_of[ts[0]][0], span_of[ts[-1]][0] + span_of[ts[-1]][1]
+            by_group = []  # (group index, first item, end item) of the groups present in this pair
+            for t in ts:
+                gi, (first, count) = entries[t][4], span_of[t]
+                if by_group and by_group[-1][0] == gi:
+                    by_group[-1][2] = first + count
+                else:
+                    by_group.append([gi, first, first + count])
+            self._segs.append((fp, fg, fm, fe, i0, i1, by_group))
+        self._check_ema(ema_slices)
+        t0 = 0
+        for gi in range(len(self.param_groups)):  # the tensors of a group are consecutive in tensor order
+            cnt = sum(1 for e in entries if e[4] == gi)
+            if cnt:
+                self._coefs.append((gi, t0, t0 + cnt))
+            t0 += cnt
+        self._plans = self._segs
+
+    def _make_v(self, entries, dev):
+        """one float32 slot per tensor; state[p][v key] becomes a stride-0 view of its slot"""
+        v = torch.empty(len(entries), dtype=torch.float32, device=dev)
+        for t, (_, _, _, _, gi, p) in enumerate(entries):
+            old = self.state[p].get(self._v_key)
+            if old is None:
+                v[t] = self._v_init(self.param_groups[gi])
+            else:
+                v[t] = old[(0,) * old.dim()].to(device=dev, dtype=torch.float32)
+            self.state[p][self._v_key] = torch.as_strided(v, p.shape, (0,) * p.dim(), t)
+        return v
+
+    def _adai_mean(self):
+        return 1.0
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        mean = self._adai_mean()  # (before the plan creates state: the reference's first step sees none)
+        if self._plans is None:
+            self._build_plans()
+        if not self._planned:
+            return loss
+        gs = float(self.grad_scale)
+        nt = self._sums.numel()
+        for fp, fg, fm, fe, i0, i1, _ in self._segs:
+            ops.lw_sumsq(fp if self._param_stat else fg, self._items[i0:i1], self._partial[i0:i1], nt, scale=1.0 if self._param_stat else gs)
+        for gi, t0, t1 in self._coefs:
+            group = self.param_groups[gi]
+            flags, b1, b2, eps = self._coef_args(group)
+            ops.lw_coef(self._rule, flags, self._partial, self._tensors[t0:t1], self._v[t0:t1], self._coef[t0:t1], self._sums[t0:t1], b1, b2, eps,
+                        float(group["lr"]), float(group["weight_decay"]), mean=mean)
+        for fp, fg, fm, fe, _, _, by_group in self._segs:
+            for gi, i0, i1 in by_group:
+                ops.lw_update(self._rule, fp, fg, fm, self._items[i0:i1], self._coef, float(self.param_groups[gi]["lr"]), wd_eps=self._wd_eps(),
+                              grad_scale=gs, ema=fe, ema_decay=self._ema[2] if fe is not None else 0.0)
+        for p in self._planned:
+            self.state[p]["step"] += 1
+        return loss
+
+    def state_dict(self):
+        """the second moment as the reference keeps it: a dense tensor of the parameter's shape"""
+        sd = super().state_dict()
+        sd["state"] = {k: {key: (v.contiguous() if torch.is_tensor(v) and key == self._v_key else v) for key, v in st.items()}
+                       for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        loaded = [(p, st[self._v_key]) for p, st in self.state.items() if torch.is_tensor(st.get(self._v_key))]
+        if loaded:
+            # the reference's tensors hold one value each: checked here, once, then element 0 is kept
+            spread = torch.stack([(t.max() - t.min()).float() for _, t in loaded])
+            if bool((spread != 0).any()):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {self._v_key} must hold one value per tensor (min == max)")
+            for p, t in loaded:
+                self.state[p][self._v_key] = t.reshape(-1)[0].clone().expand(t.shape)
+
+
+def _lw_checks(lr, eps, betas):
+    if not 0.0 <= lr:
+        raise ValueError("Invalid learning rate: {}".format(lr))
+    if not 0.0 <= eps:
+        raise ValueError("Invalid epsilon value: {}".format(eps))
+    if not 0.0 <= betas[0] < 1.0:
+        raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+    if not 0.0 <= betas[1] < 1.0:
+        raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+
+
+class NovogradApex(_Layerwise):
+    """the reference's src.optimizers.NovogradApex (sota_imagenet/optimizers.py:189-290; recipe configs/hydra_exp/46.r50_nov.yaml): the first
+    moment of the gradient divided by sqrt of the running SUM of squares of the tensor's gradient; decoupled weight decay, or with wd_eps a
+    decay of |p| - wd_eps only (p -= lr*wd*max(|p| - wd_eps, 0)*sign(p)).  Signature, defaults, checks and state (step: int, exp_avg,
+    exp_avg_sq) are the reference's.  unitwise_norm (recipe 48) needs a per-output-channel reduction and is not on the hot path."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.95, 0), eps=1e-8, weight_decay=0, ema_norm_init=1e-3, unitwise_norm=False, wd_eps=None):
+        _lw_checks(lr, eps, betas)
+        if unitwise_norm:
+            raise NotImplementedError("unitwise_norm=True is not on the hot path")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.ema_norm_init = ema_norm_init
+        self.unitwise_norm = unitwise_norm
+        self.wd_eps = wd_eps
+
+    def _coef_args(self, group):
+        return (ops.LW_SOFT_WD if self.wd_eps is not None else 0), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"])
+
+    def _wd_eps(self):
+        return None if self.wd_eps is None else float(self.wd_eps)
+
+
+class AdamLayerwise(_Layerwise):
+    """the reference's src.optimizers.AdamLayerwise (sota_imagenet/optimizers.py:293-397; recipe configs/hydra_exp/49.r50_nov-adam.yaml):
+    NovogradApex with the MEAN of squares of the tensor's gradient, and stable_wd (p *= 1 - lr*wd/den).  weight_adapt is not on the hot path."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.95, 0), eps=1e-6, weight_decay=0, ema_norm_init=1e-3, weight_adapt=False, stable_wd=False):
+        _lw_checks(lr, eps, betas)
+        if weight_adapt:
+            raise NotImplementedError("weight_adapt=True is not on the hot path")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.ema_norm_init = ema_norm_init
+        self.weight_adapt = weight_adapt
+        self.stable_wd = stable_wd
+
+    def _coef_args(self, group):
+        return ops.LW_MEAN | (ops.LW_STABLE_WD if self.stable_wd else 0), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"])
+
+
+class MyNovograd(_Layerwise):
+    """the reference's src.optimizers.MyNovograd (sota_imagenet/optimizers.py:35-161; recipe configs/hydra_exp/47.r50_my-nov.yaml): the update
+    is the first moment of the gradient divided by sqrt of a running sum of squares — which the class takes of the PARAMETER, not of the gradient
+    (its grad_norms are built from params_with_grad, :138).  Reproduced as it is.  State keys are ema_grad and ema_norm; eps is an attribute of
+    the optimizer and ema_norm_init a group key, as there.  unitwise_norm is not on the hot path."""
+
+    _rule = ops.LW_NOVOGRAD
+    _m_key, _v_key = "ema_grad", "ema_norm"
+    _param_stat = True
+
+    def __init__(self, params, lr=1e-2, betas=(0.9, 0.99), eps=1e-8, weight_decay=1e-2, ema_norm_init=1e-3, unitwise_norm=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if unitwise_norm:
+            raise NotImplementedError("unitwise_norm=True is not on the hot path")
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay, ema_norm_init=ema_norm_init))
+        self.eps = eps
+        self.unitwise_norm = unitwise_norm
+
+    def _v_init(self, group):
+        return group["ema_norm_init"]
+
+    def _coef_args(self, group):
+        return 0, float(group["betas"][0]), float(group["betas"][1]), float(self.eps)
+
+
+class MyAdai(_Layerwise):
+    """the reference's src.optimizers.MyAdai (sota_imagenet/optimizers.py:400-519; recipe configs/hydra_exp/55.r50_adai_2.yaml) with
+    per_layer=True: every tensor's momentum beta1 = clip(1 - vt/mean * beta0, 0, 1 - eps) from vt = v0*beta2 + (1 - beta2)*mean(g^2).
+    The class never writes vt back into its state (it rebinds a local, :489): state[p]["exp_avg_sq"] stays the Python float it was created
+    with, the "mean over layers" is the mean of those constants (ema_norm_init itself on the very first step, :456-459) and a step has no memory
+    of the one before.  Reproduced as it is; floats that a loaded state carries are kept and used.  per_layer=False is not on the hot path."""
+
+    _rule = ops.LW_ADAI
+
+    def __init__(self, params, lr=1e-3, betas=(0.1, 0.99), eps=1e-3, weight_decay=0, ema_norm_init=1e-3, sgd_mom=False, sqrt_mom=False,
+                 stable_wd=False, per_layer=True):
+        _lw_checks(lr, eps, betas)
+        if not per_layer:
+            raise NotImplementedError("per_layer=False is not on the hot path")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.ema_norm_init = ema_norm_init
+        self.sgd_mom = sgd_mom
+        self.sqrt_mom = sqrt_mom
+        self.stable_wd = stable_wd
+        self.per_layer = per_layer
+
+    def _make_v(self, entries, dev):
+        for _, _, _, _, _, p in entries:
+            self.state[p].setdefault("exp_avg_sq", self.ema_norm_init)
+        return torch.tensor([float(self.state[e[5]]["exp_avg_sq"]) for e in entries], dtype=torch.float64, device=dev)
+
+    def _adai_mean(self):
+        if len(self.state) == 0:
+            return float(self.ema_norm_init)
+        return float(sum(v["exp_avg_sq"] for v in self.state.values()) / len(self.state))
+
+    def _coef_args(self, group):
+        flags = (ops.LW_MEAN | (ops.LW_SGD_MOM if self.sgd_mom else 0) | (ops.LW_SQRT_MOM if self.sqrt_mom else 0)
+                 | (ops.LW_STABLE_WD if self.stable_wd else 0))
+        return flags, float(group["betas"][0]), float(group["betas"][1]), float(group["eps"])
+
+    def state_dict(self):
+        return _FlatOptimizer.state_dict(self)
+
+    def load_state_dict(self, state_dict):
+        _FlatOptimizer.load_state_dict(self, state_dict)
