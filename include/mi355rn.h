@@ -334,6 +334,29 @@ int mi355_lw_update(int rule, float* p, const float* g, float* m, size_t n, cons
 int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
                         int n_tensors, double lr, int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream);
 
+/* The SAMOriginal callback of the reference (adaptive sharpness-aware minimization, sota_imagenet/callbacks.py:279-337; recipe
+ * configs/hydra_exp/49.r50_nov-adam.yaml:46-48) on flat fp32 arrays: between the first backward and the optimizer step every parameter moves
+ * along its gradient, weighted by its own magnitude and normalised by ONE statistic of all tensors; after a second forward / backward there
+ * it moves back.  Four stages on one stream, nothing read back, over the items[] table of the layer-wise optimizers above and
+ *   kind[]  int32 per tensor, indexed by items[].tensor: 1 = weight (a Parameter with ndim > 1), 0 = any other tensor.
+ * With ge = g*grad_scale (float):
+ *  (a) mi355_sam_sumsq, once per (parameter, gradient) storage pair (:327-337, the per-tensor norms):  partial[i] = sum over items[i] of w^2,
+ *      w = ge*max(|p|, eta) for weights, w = ge otherwise, w in float, the square and the sum in double in a fixed order (no atomics).
+ *  (b) mi355_sam_scale, once per step over ALL partials of the step (:337 the norm of the norms and its clamp, :297 the division):
+ *      norm = max(sqrt(sum of partial[]), 2e-5);  out[0] = (float)(rho/norm);  out[1] = (float)norm.
+ *  (c) mi355_sam_perturb, once per storage pair (:298-306):  e = (max(p*p, eta)*ge)*out[0] for weights, e = ge*out[0] otherwise;
+ *      eps = e;  p = p + e.   eps is an array of the caller laid out like p.
+ *  (d) mi355_sam_restore, after the second backward (:319-323):  p = p - eps over the same items.
+ * p, g, eps are the arrays the item offsets count from, n their length; elements outside the items (alignment gaps, padding) are neither read into
+ * the sum nor written.  Each fails (-1) before any launch on a null or misaligned pointer (16 bytes for the arrays and the table, 8 for partial[]
+ * and out[], 4 for kind[]), an empty table, rho not finite or <= 0, eta not finite or negative, grad_scale not finite. */
+int mi355_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
+                    float grad_scale, void* partial, void* stream);
+int mi355_sam_scale(const void* partial, size_t n_partial, double rho, float* out, void* stream);
+int mi355_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
+                      const float* out, float eta, float grad_scale, void* stream);
+int mi355_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

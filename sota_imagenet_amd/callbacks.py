@@ -1,9 +1,10 @@
-"""Input-side callbacks next to the hot path: Mixup / CutMix / CutmixMixup on device, producing the soft targets the
-native cross entropy consumes.
+"""Callbacks next to the hot path: Mixup / CutMix / CutmixMixup on device, producing the soft targets the native cross
+entropy consumes, and SAMOriginal (sharpness-aware minimization), which sits on the step itself.
 
 Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `self.cutmix(*input)` and
 `self.mixup(*input)` with Beta(alpha, alpha) samplers) and the un-vendored pt_clb.Cutmix / pt_clb.Mixup bases as
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
+SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip.
 """
 
 import numpy as np
@@ -159,3 +160,149 @@ class CutmixMixup(Cutmix):
         else:
             self.tb = self.mixup_tb
             self.state.input = self.mixup(*self.state.input)
+
+
+class SAMOriginal(Callback):
+    """sota_imagenet/callbacks.py:279-337 (recipe configs/hydra_exp/49.r50_nov-adam.yaml:46-48): adaptive sharpness-aware minimization as
+    the reference runs it.  After the first backward of a step, with g the gradient the optimizer would see (g * optimizer.grad_scale):
+        norm  = max(sqrt(sum over all tensors of |w|^2), 2e-5),   w = g * max(|p|, eta) for tensors with ndim > 1, w = g for the others
+        eps   = max(p^2, eta) * g * (rho / norm) for ndim > 1,    eps = g * (rho / norm) for the others;   p += eps
+        optimizer.zero_grad(); a second criterion(model(data), target).backward() on the same (already mixed) batch;   p -= eps
+    and the optimizer then steps from the unperturbed parameters on the SECOND gradient.  (p + eps) - eps is in general not p bit for bit:
+    the reference's behaviour, kept.  The very first step, while the optimizer has no state yet (len(optimizer.state) == 0), is a plain step.
+
+    The four stages are HIP kernels over the flat arrays (csrc/optim_sam.hip) on the current stream; nothing is read back in a step.  The
+    plan is built at the first non-skipped step from optimizer.param_groups under the rules of the native optimizers (CUDA fp32, dense,
+    parameter and gradient at the same 16-byte aligned flat offset; one launch set per pair of parameter / gradient storage; the work items
+    of optim.lw_plan_items) and rebuilt when the parameters or their addresses change.  There is no CPU fallback: parameters that do not
+    fit raise.  `norm` and `scale` are 1-element device tensors holding the last step's values, `eps_flat` the last perturbation: one
+    float32 array per storage pair indexed like the storage itself (the array itself when there is one pair, zero outside the parameters).
+
+    As in the reference the second forward runs through state.model in training mode: a data-parallel wrapper reduces the second gradient
+    too, and BatchNorm running statistics and num_batches_tracked advance TWICE per SAM step.
+    Deviations, both deliberate: accumulate_steps != 1 raises at on_begin (the reference's zero_grad would silently discard the accumulated
+    micro-gradients); eps lives in this callback, not in optimizer.state[p]["eps_step"], so no optimizer's state_dict() changes."""
+
+    def __init__(self, rho=0.5, eta=0.01):
+        super().__init__()
+        if not (rho > 0 and np.isfinite(rho)):
+            raise ValueError(f"Invalid rho: {rho}")
+        if not (eta >= 0 and np.isfinite(eta)):
+            raise ValueError(f"Invalid eta: {eta}")
+        self.rho = rho
+        self.eta = eta
+        self._key = None
+        self._segs = []     # per storage pair: (parameter slice, gradient slice, eps slice, first item, end item)
+        self._eps = []      # per storage pair: the eps array, indexed like the storage
+        self._out = None    # (rho / norm, norm) of the last step
+        self.forwards = 0   # second forwards made so far
+
+    @property
+    def scale(self):
+        return None if self._out is None else self._out[0:1]
+
+    @property
+    def norm(self):
+        return None if self._out is None else self._out[1:2]
+
+    @property
+    def eps_flat(self):
+        if not self._eps:
+            return None
+        return self._eps[0] if len(self._eps) == 1 else list(self._eps)
+
+    def on_begin(self):
+        if getattr(self.state, "accumulate_steps", 1) != 1:
+            raise NotImplementedError("SAMOriginal: accumulate_steps != 1 is not supported (the second pass would discard the accumulated "
+                                      "micro-gradients)")
+
+    @staticmethod
+    def _entries(params):
+        """[(param base, grad base, first elem, numel, param)] of the parameters with a gradient: the rules of optim._FlatOptimizer._entries"""
+        from .optim import _dense_range
+
+        entries = []
+        for p in params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.grad.is_cuda and p.grad.dtype == torch.float32):
+                raise RuntimeError("SAMOriginal: parameters and gradients must be CUDA fp32 tensors (no CPU fallback on the hot path)")
+            rp, rg = _dense_range(p.data), _dense_range(p.grad)
+            if rp is None or rg is None or rp[1:] != rg[1:]:
+                raise RuntimeError("SAMOriginal: parameter and gradient must be dense and share their flat offset")
+            if (rp[1] * 4) % 16 or (rp[0] + rp[1] * 4) % 16 or (rg[0] + rg[1] * 4) % 16:
+                raise RuntimeError("SAMOriginal: flat range not 16-byte aligned")
+            entries.append((rp[0], rg[0], rp[1], rp[2], p))
+        return entries
+
+    @staticmethod
+    def plan_tables(tensors, W):
+        """the host side of a plan.  tensors: [(param base, grad base, first elem, numel, ndim)] in param-group order; W: ops.lw_item_elems().
+        Returns (items, kind, pairs): items = [(first element relative to its pair's range, length, tensor index)] from optim.lw_plan_items,
+        storage pair by storage pair; kind[tensor] = 1 for ndim > 1; pairs = [(lo, hi, first item, end item, tensor indices)], one per pair of
+        parameter / gradient storage, [lo, hi) the element range of the storage its tensors span"""
+        from .optim import lw_plan_items
+
+        pairs = {}  # (param base, grad base) -> [lo, hi, tensor indices]
+        for t, (pb, gb, off, n, _) in enumerate(tensors):
+            r = pairs.setdefault((pb, gb), [off, off + n, []])
+            r[0], r[1] = min(r[0], off), max(r[1], off + n)
+            r[2].append(t)
+        order = [t for r in pairs.values() for t in r[2]]  # table order; the tensor index of an item stays the index into `tensors`
+        lo_of = {t: r[0] for r in pairs.values() for t in r[2]}
+        items, spans = lw_plan_items([(tensors[t][2] - lo_of[t], tensors[t][3]) for t in order], W)
+        items = [(o, ln, order[j]) for o, ln, j in items]
+        span_of = {order[j]: spans[j] for j in range(len(order))}
+        out = [(lo, hi, span_of[ts[0]][0], span_of[ts[-1]][0] + span_of[ts[-1]][1], ts) for lo, hi, ts in pairs.values()]
+        return items, [int(t[4] > 1) for t in tensors], out
+
+    def _build_plan(self, entries):
+        from . import ops
+
+        dev = entries[0][4].device
+        if any(e[4].device != dev for e in entries):
+            raise RuntimeError("SAMOriginal: all parameters must live on one device (the norm is taken there)")
+        items, kind, pairs = self.plan_tables([(pb, gb, off, n, p.ndim) for pb, gb, off, n, p in entries], ops.lw_item_elems())
+        rec = np.zeros(len(items), dtype=[("off", "<i8"), ("len", "<i4"), ("t", "<i4")])
+        for k, it in enumerate(items):
+            rec[k] = it
+        self._items = torch.from_numpy(rec.view(np.int64).reshape(-1, 2)).to(dev)
+        self._kind = torch.tensor(kind, dtype=torch.int32, device=dev)
+        self._partial = torch.zeros(len(items), dtype=torch.float64, device=dev)
+        self._out = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._segs, self._eps = [], []
+        for lo, hi, i0, i1, ts in pairs:
+            p0 = entries[ts[0]][4]
+            fp = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.data.untyped_storage(), lo, (hi - lo,))
+            fg = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.grad.untyped_storage(), lo, (hi - lo,))
+            eps = torch.zeros(hi, dtype=torch.float32, device=dev)  # indexed like the storage: eps_flat lines up with a model's flat array
+            self._segs.append((fp, fg, eps[lo:hi], i0, i1))
+            self._eps.append(eps)
+
+    @torch.no_grad()
+    def on_after_backward(self):
+        from . import ops
+
+        opt = self.state.optimizer
+        if len(opt.state) == 0:  # the first step: the optimizer creates its state from a plain step
+            return
+        params = [p for group in opt.param_groups for p in group["params"] if p.grad is not None]
+        if not params:
+            return
+        key = tuple((id(p), p.data_ptr(), p.grad.data_ptr(), p.numel()) for p in params)
+        if key != self._key:  # the first non-skipped step, or the parameters / their addresses changed
+            self._build_plan(self._entries(params))
+            self._key = key
+        gs = float(getattr(opt, "grad_scale", 1.0))
+        nt = self._kind.numel()
+        for fp, fg, fe, i0, i1 in self._segs:
+            ops.sam_sumsq(fp, fg, self._items[i0:i1], self._kind, self._partial[i0:i1], self.eta, grad_scale=gs)
+        ops.sam_scale(self._partial, self.rho, self._out)
+        for fp, fg, fe, i0, i1 in self._segs:
+            ops.sam_perturb(fp, fg, fe, self._items[i0:i1], self._kind, self._out, self.eta, grad_scale=gs)
+        opt.zero_grad()  # (with an attached flat model: marks its gradients clean, the second backward overwrites them)
+        with torch.enable_grad():
+            data, target = self.state.input
+            loss_second = self.state.criterion(self.state.model(data), target)
+            loss_second.backward()
+        self.forwards += 1
+        for fp, fg, fe, i0, i1 in self._segs:
+            ops.sam_restore(fp, fe, self._items[i0:i1], nt)

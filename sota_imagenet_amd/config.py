@@ -51,6 +51,13 @@ LAYERWISE_TARGET_ALIASES = {
     "sota_imagenet.optimizers.MyAdai": "sota_imagenet_amd.optim.MyAdai",
 }
 
+# callbacks of the reference's own tree that sit on the step (sota_imagenet/callbacks.py), consulted after the two tables above, whose contents
+# existing tests pin
+CALLBACK_TARGET_ALIASES = {
+    "src.callbacks.SAMOriginal": "sota_imagenet_amd.callbacks.SAMOriginal",
+    "sota_imagenet.callbacks.SAMOriginal": "sota_imagenet_amd.callbacks.SAMOriginal",
+}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -287,7 +294,7 @@ def validate(cfg):
 
 
 def resolve_target(path):
-    path = TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path, path)
+    path = TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path, path)
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

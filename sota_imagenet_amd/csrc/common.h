@@ -353,6 +353,13 @@ int launch_lw_coef(int rule, int flags, const double* partial, size_t n_partial,
                    double* sums, double beta1, double beta2, double eps, double lr, double wd, double mean, hipStream_t st);
 int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
                      int n_tensors, double lr, int soft_wd, double wd_eps, float gscale, float ema_decay, hipStream_t st);
+// optim_sam.hip: the four stages of the SAMOriginal callback over the same work-item table (kind[tensor]: 1 = weight, 0 = other)
+int launch_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
+                     float gscale, double* partial, hipStream_t st);
+int launch_sam_scale(const double* partial, size_t n_partial, double rho, float* out, hipStream_t st);
+int launch_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
+                       const float* out, float eta, float gscale, hipStream_t st);
+int launch_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, hipStream_t st);
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

@@ -602,4 +602,19 @@ int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema
                           (hipStream_t)stream);
 }
 
+int mi355_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
+                    float grad_scale, void* partial, void* stream) {
+  return launch_sam_sumsq(p, g, n, items, n_items, kind, n_tensors, eta, grad_scale, (double*)partial, (hipStream_t)stream);
+}
+int mi355_sam_scale(const void* partial, size_t n_partial, double rho, float* out, void* stream) {
+  return launch_sam_scale((const double*)partial, n_partial, rho, out, (hipStream_t)stream);
+}
+int mi355_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
+                      const float* out, float eta, float grad_scale, void* stream) {
+  return launch_sam_perturb(p, g, eps, n, items, n_items, kind, n_tensors, out, eta, grad_scale, (hipStream_t)stream);
+}
+int mi355_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, void* stream) {
+  return launch_sam_restore(p, eps, n, items, n_items, n_tensors, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -26,37 +26,20 @@
 #include <cmath>
 
 #include "common.h"
+#include "optim_items.h"
 #include "optim_sum.h"
 #include "vec.h"
 
 namespace mi355 {
 namespace {
 
-#ifndef MI355_LW_ITEM_ELEMS
-#define MI355_LW_ITEM_ELEMS 4096  // 16 elements per thread: the ResNet-50 array is 6.3 k work items.  Other values: profiles/layerwise_step.json
-#endif
-constexpr int kLwItemElems = MI355_LW_ITEM_ELEMS;
-static_assert(kLwItemElems >= 256 && kLwItemElems % 4 == 0, "an item is a whole number of float4, at least one per thread of a wave");
-
-struct LwItem {
-  long long off;  // first element, relative to the array pointers of the launch
-  int len;        // 1 .. kLwItemElems
-  int tensor;     // index into coef[]
-};
 struct LwTensor {
   int first, count;  // its items in the table (and its partial sums in partial[])
   double numel;
 };
-static_assert(sizeof(LwItem) == 16 && sizeof(LwTensor) == 16, "table records are 16 bytes");
+static_assert(sizeof(LwTensor) == 16, "table records are 16 bytes");
 
 enum { LW_MEAN = 1, LW_STABLE_WD = 2, LW_SOFT_WD = 4, LW_SGD_MOM = 8, LW_SQRT_MOM = 16 };
-
-// a record that does not lie inside the arrays of the launch is skipped: the tables are checked by the host when they are built, this keeps a
-// stale or foreign table from ever becoming an out-of-bounds access
-__device__ __forceinline__ bool item_ok(const LwItem& it, size_t n, int n_tensors) {
-  return it.off >= 0 && it.len > 0 && it.len <= kLwItemElems && (size_t)it.off + (size_t)it.len <= n && it.tensor >= 0 && it.tensor < n_tensors &&
-         (it.off & 3) == 0;
-}
 
 __global__ __launch_bounds__(256) void lw_sumsq_kernel(const float* __restrict__ src, size_t n, const LwItem* __restrict__ items,
                                                        double* __restrict__ partial, int n_tensors, float scale) {
@@ -190,8 +173,6 @@ void lw_update_launch(bool ema_on, dim3 grid, hipStream_t st, float* p, const fl
   if (ema_on) hipLaunchKernelGGL((lw_update_kernel<RULE, true>), grid, dim3(256), 0, st, p, g, m, ema, n, items, coef, n_tensors, a);
   else hipLaunchKernelGGL((lw_update_kernel<RULE, false>), grid, dim3(256), 0, st, p, g, m, ema, n, items, coef, n_tensors, a);
 }
-
-constexpr size_t kLwMaxGrid = 1u << 30;
 
 }  // namespace
 

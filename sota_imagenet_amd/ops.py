@@ -475,6 +475,60 @@ def lw_update(rule, p, g, m, items, coef, lr, wd_eps=None, grad_scale=1.0, ema=N
     check(_L().mi355_lw_update_ema(int(rule), ptr(p), ptr(g), ptr(m), ptr(ema), *args, float(ema_decay), cur_stream()))
 
 
+# ---- sharpness-aware minimization (include/mi355rn.h, csrc/optim_sam.hip): the SAMOriginal callback of the reference -----------------------
+def _sam_kind(kind):
+    _need_cuda(kind)
+    if kind.dtype != torch.int32 or kind.dim() != 1 or kind.numel() < 1 or not kind.is_contiguous():
+        raise ValueError(f"kind: expected a contiguous CUDA int32 tensor with one element per tensor, got {kind.dtype} {tuple(kind.shape)}")
+
+
+def sam_sumsq(p, g, items, kind, partial, eta, grad_scale=1.0):
+    """stage (a), replaces the per-tensor norms of sota_imagenet/callbacks.py:327-337: partial[i] = sum over work item i of w^2 in double,
+    w = (g*grad_scale) * max(|p|, eta) for tensors with kind 1 and g*grad_scale for the others; p, g: the flat fp32 arrays the offsets count from"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g)
+    _lw_table("items", items)
+    _sam_kind(kind)
+    _need_cuda(partial)
+    if partial.dtype != torch.float64 or partial.numel() != items.shape[0]:
+        raise ValueError(f"partial: expected {items.shape[0]} float64 elements, got {partial.dtype} with {partial.numel()}")
+    check(_L().mi355_sam_sumsq(ptr(p), ptr(g), n, ptr(items), items.shape[0], ptr(kind), kind.numel(), float(eta), float(grad_scale), ptr(partial),
+                               cur_stream()))
+
+
+def sam_scale(partial, rho, out):
+    """stage (b), replaces callbacks.py:337 and :297: norm = max(sqrt(sum(partial)), 2e-5) in double over ALL partials of the step;
+    out[0] = rho / norm, out[1] = norm (a float32 CUDA tensor of two elements)"""
+    _need_cuda(partial, out)
+    if partial.dtype != torch.float64 or partial.numel() < 1 or not partial.is_contiguous():
+        raise ValueError("sam_scale: partial must be a contiguous float64 tensor")
+    if out.dtype != torch.float32 or out.numel() != 2 or not out.is_contiguous():
+        raise ValueError("sam_scale: out must hold two float32 elements")
+    check(_L().mi355_sam_scale(ptr(partial), partial.numel(), float(rho), ptr(out), cur_stream()))
+
+
+def sam_perturb(p, g, eps, items, kind, out, eta, grad_scale=1.0):
+    """stage (c), replaces callbacks.py:298-306: eps = (max(p*p, eta) * g*grad_scale) * out[0] for kind 1, (g*grad_scale) * out[0] otherwise;
+    p += eps.  eps: a flat fp32 array laid out like p"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, eps=eps)
+    _lw_table("items", items)
+    _sam_kind(kind)
+    _need_cuda(out)
+    if out.dtype != torch.float32 or out.numel() != 2:
+        raise ValueError("sam_perturb: out must be the two float32 elements sam_scale wrote")
+    check(_L().mi355_sam_perturb(ptr(p), ptr(g), ptr(eps), n, ptr(items), items.shape[0], ptr(kind), kind.numel(), ptr(out), float(eta),
+                                 float(grad_scale), cur_stream()))
+
+
+def sam_restore(p, eps, items, n_tensors):
+    """stage (d), replaces callbacks.py:319-323: p -= eps over the same work items"""
+    n = p.numel()
+    _flat_f32(n, p=p, eps=eps)
+    _lw_table("items", items)
+    check(_L().mi355_sam_restore(ptr(p), ptr(eps), n, ptr(items), items.shape[0], int(n_tensors), cur_stream()))
+
+
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
 def blurpool_fwd(x):
     _need_cuda(x)

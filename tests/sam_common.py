@@ -1,0 +1,138 @@
+"""What tests/test_sam_host.py and tests/test_sam_gpu.py share: the fixture recorded from the reference's own SAMOriginal callback
+(tests/golden/sam_ref_trajectories.npz, written by tests/golden/make_sam_golden.py), the rules of the callback as this project documents them
+(include/mi355rn.h) restated in torch on the CPU in a chosen dtype, and the quadratic problem of the fixture."""
+import importlib.util
+import json
+import os
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "sam_ref_trajectories.npz")
+CASES = ["sgd", "adamlw_recipe", "clamp"]
+U = 2.0 ** -24
+FACTOR = 1.5
+NORM_FLOOR = 2e-5
+
+_GEN = None
+
+
+def generator():
+    """tests/golden/make_sam_golden.py as a module: the problem (shapes, groups, seeds, the quadratic module) is stated there once"""
+    global _GEN
+    if _GEN is None:
+        spec = importlib.util.spec_from_file_location("make_sam_golden", os.path.join(HERE, "golden", "make_sam_golden.py"))
+        _GEN = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(_GEN)
+    return _GEN
+
+
+def _js(a):
+    return json.loads(bytes(a).decode())
+
+
+class Fixture:
+    def __init__(self, case):
+        z = np.load(GOLDEN)
+        gen = generator()
+        self.case = case
+        self.shapes, self.groups, self.steps = _js(z["shapes"]), _js(z["groups"]), _js(z["steps"])
+        self.sizes = [int(np.prod(s)) for s in self.shapes]
+        self.offs = np.cumsum([0] + self.sizes)
+        self.p0 = torch.from_numpy(z["p0"])
+        assert torch.equal(self.p0, gen.flat(gen.params0()))  # the seeds rebuild the recorded inputs bit for bit
+        h = _js(z[f"{case}/hyper"])
+        self.cls, self.kw, self.rho, self.eta = h["cls"], h["kw"], h["rho"], h["eta"]
+        self.a = [float(x) for x in z[f"{case}/a"]]
+        self.lrs = [float(x) for x in z[f"{case}/lrs"]]
+        self.norm = z[f"{case}/norm"]
+        self.forwards = [int(x) for x in z[f"{case}/forwards"]]
+        self.eps, self.p_step = torch.from_numpy(z[f"{case}/eps"]), torch.from_numpy(z[f"{case}/p_step"])
+        self.yard = {k: z[f"{case}/yard_{k}"] for k in ("eps", "pert", "step")}
+
+    def targets(self, k):
+        return generator().targets(k)
+
+    def split(self, flat):
+        return [flat[self.offs[i]:self.offs[i + 1]] for i in range(len(self.shapes))]
+
+    def pert(self, k):
+        """the float64 run's parameters at the second forward of step k: the parameters before the step plus eps (exact in float64, asserted by
+        the generator)"""
+        return (self.p0.double() if k == 0 else self.p_step[k - 1]) + self.eps[k]
+
+    def check(self, k, got_flat, what):
+        """got_flat: the native values of step k + 1 (what: "eps", "pert" or "step") in the fixture's tensor order, against the float64 run; the
+        rule and floor of layerwise_common.Fixture.check"""
+        ref_flat = {"eps": self.eps[k], "pert": self.pert(k), "step": self.p_step[k]}[what]
+        ratios = []
+        for i, (got, ref) in enumerate(zip(self.split(got_flat.detach().double().cpu()), self.split(ref_flat))):
+            err = (got - ref).abs().max().item()
+            yard = float(self.yard[what][k, i])
+            floor = 4 * U * ref.abs().max().item()
+            ratios.append(err / max(yard, floor))
+            print(f"{self.case} {what} step {k + 1} tensor {i}: native {err:.3e}  reference fp32 {yard:.3e}  floor {floor:.2e}")
+            assert err <= FACTOR * yard + floor, f"{self.case} {what} step {k + 1} tensor {i}: native {err:.3e} vs reference fp32 {yard:.3e}"
+        return max(ratios)
+
+
+def sam_norm(ps, gs, eta):
+    """max(sqrt(sum over tensors of |w_t|^2), 2e-5): w_t = g * max(|p|, eta) for tensors with more than one dimension, g for the others"""
+    tot = sum((g * p.abs().clamp_min(eta) if p.ndim > 1 else g).pow(2).sum() for p, g in zip(ps, gs))
+    return tot.sqrt().clamp_min(NORM_FLOOR)
+
+
+def sam_eps(ps, gs, rho, eta, norm):
+    """eps_t = (max(p^2, eta) * g) * (rho / norm) for tensors with more than one dimension, g * (rho / norm) for the others"""
+    scale = rho / norm
+    return [(p.pow(2).clamp_min(eta) * g) * scale if p.ndim > 1 else g * scale for p, g in zip(ps, gs)]
+
+
+def _optimizer_step(cls, kw, st, ps, gs, group_of, lr, dtype):
+    """torch.optim.SGD with momentum, or AdamLayerwise as layerwise_common.Restated states it; st: the state carried between steps"""
+    if cls == "SGD":
+        mu, wd = kw["momentum"], kw["weight_decay"]
+        first = "m" not in st
+        m = st.setdefault("m", [None] * len(ps))
+        for i, (p, g) in enumerate(zip(ps, gs)):
+            g = g + (wd if group_of[i] == 0 else 0.0) * p
+            m[i] = g.clone() if first else m[i] * mu + g
+            ps[i] = p - lr * m[i]
+        return
+    assert cls == "AdamLayerwise"
+    from layerwise_common import Restated
+
+    r = st.get("r")
+    if r is None:
+        r = st["r"] = Restated(cls, kw, ps, group_of, [kw["weight_decay"], 0], dtype)
+    r.p = [p.clone() for p in ps]
+    r.step(gs, [lr, lr])
+    ps[:] = r.p
+
+
+def restate_fixture(fx, dtype):
+    """the documented rules on the fixture's problem in `dtype`: per step (norm or NaN, eps flat, parameters at the second forward flat, parameters
+    after the optimizer step flat, forwards made)"""
+    ps = [t.to(dtype).view(s).clone() for t, s in zip(fx.split(fx.p0), fx.shapes)]
+    group_of = [0 if i in fx.groups[0] else 1 for i in range(len(ps))]
+    flat = generator().flat
+    st, out = {}, []
+
+    def grads(ps, k):
+        return [a * (p - c.to(dtype)) for a, p, c in zip(fx.a, ps, fx.targets(k))]
+
+    for k in range(fx.steps):
+        g = grads(ps, k)
+        forwards, norm, eps = 1, float("nan"), [torch.zeros_like(p) for p in ps]
+        pert = list(ps)
+        if st:  # the optimizer has state: every step but the first
+            norm = sam_norm(ps, g, fx.eta)
+            eps = sam_eps(ps, g, fx.rho, fx.eta, norm)
+            pert = [p + e for p, e in zip(ps, eps)]
+            g = grads(pert, k)  # the second gradient, at the perturbed parameters
+            ps = [p - e for p, e in zip(pert, eps)]
+            forwards, norm = 2, float(norm)
+        _optimizer_step(fx.cls, fx.kw, st, ps, g, group_of, fx.lrs[k], dtype)
+        out.append((norm, flat(eps), flat(pert), flat(ps).clone(), forwards))
+    return out
