@@ -4,6 +4,7 @@
 // Reference call sites: sota_imagenet/dali_dataloader.py:113-123 (tensor contract of the batch),
 // sota_imagenet/callbacks.py:316-317 (model / criterion / backward), arg_parser.py:136-142 (SGD, CE).
 #include "common.h"
+#include "optim_sweep.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -544,36 +545,21 @@ __global__ __launch_bounds__(256) void ce_mean_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// EMA: also ema = ema + (1 - decay) * (p_new - ema) — the recipe's ModelEma (train.py:111-112) in the pass that has p in registers anyway
+// EMA: also ema = ema + (1 - decay) * (p_new - ema) — the recipe's ModelEma (train.py:111-112) in the pass that has p in registers anyway.
+// The f32x4 grid-stride loop and its scalar tail are flat_sweep (optim_sweep.h).
 template <bool EMA>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ ema,
                                                   size_t n4, size_t n, float lr, float mom, float wd, float gscale, float ema_w) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
-    f32x4 ev;
-    if constexpr (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float ge = gv[e] * gscale + wd * pv[e];
-      mv[e] = mom * mv[e] + ge;
-      pv[e] = pv[e] - lr * mv[e];
-      if constexpr (EMA) ev[e] = ev[e] + ema_w * (pv[e] - ev[e]);
-    }
-    reinterpret_cast<f32x4*>(m)[i] = mv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
-    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
-  }
-  // tail (n not a multiple of 4)
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const size_t i = n4 * 4 + threadIdx.x;
-    const float ge = g[i] * gscale + wd * p[i];
-    const float me = mom * m[i] + ge;
-    m[i] = me;
-    const float pn = p[i] - lr * me;
-    p[i] = pn;
-    if constexpr (EMA) ema[i] = ema[i] + ema_w * (pn - ema[i]);
+  const auto rule = [&](float& pk, float& gk, float& mk, float& ek) {
+    const float ge = gk * gscale + wd * pk;
+    mk = mom * mk + ge;
+    pk = pk - lr * mk;
+    if constexpr (EMA) ek = ek + ema_w * (pk - ek);
+  };
+  if constexpr (EMA) {
+    flat_sweep(n4, n, rule, upd(p), rd(g), upd(m), upd(ema));
+  } else {
+    flat_sweep(n4, n, [&](float& pk, float& gk, float& mk) { float ek = 0.f; rule(pk, gk, mk, ek); }, upd(p), rd(g), upd(m));
   }
 }
 

@@ -8,10 +8,12 @@
 //   p  = p + (-step_size * m) / (sqrt(v) / bc2_sqrt + eps)     (addcdiv_), step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t)
 //   EMA: ema = ema + (1 - decay) * (p - ema)
 // The library builds with -ffp-contract=off, and sqrtf / '/' stay correctly rounded (no fast-math forms).
+// Every element-wise kernel here states its arrays and its rule; the loop over them is flat_sweep (optim_sweep.h).
 #include <cmath>
 
 #include "common.h"
 #include "optim_sum.h"
+#include "optim_sweep.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -47,36 +49,17 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
   if constexpr (EMA) e = e + a.ema_w * (pe - e);
 }
 
-// f32x4 grid-stride loop + scalar tail (n not a multiple of 4), the shape of sgd_kernel: 28 B / element (36 B with the average).
+// flat_sweep (optim_sweep.h: f32x4 grid-stride loop + scalar tail), as sgd_kernel: 28 B / element (36 B with the average).
 // Measured on the 25.6 M-element array: sgd_kernel's 4096-workgroup cap and plain gradient loads gave 138 us (5.2 TB/s); up to
 // 16384 workgroups and a non-temporal gradient load give 110 us (6.5 TB/s, the rate of sgd_kernel) — profiles/adamw_step.json
 template <bool DECOUPLED, bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, float* __restrict__ ema, size_t n4, size_t n, AdamArgs a) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);  // last use of the gradient
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
-    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float pk = pv[k], mk = mv[k], vk = vv[k], ek = ev[k];
-      adam_elem<DECOUPLED, EMA>(pk, gv[k], mk, vk, ek, a);
-      pv[k] = pk, mv[k] = mk, vv[k] = vk, ev[k] = ek;
-    }
-    reinterpret_cast<f32x4*>(m)[i] = mv;
-    reinterpret_cast<f32x4*>(v)[i] = vv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
-    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const size_t i = n4 * 4 + threadIdx.x;
-    float pk = p[i], mk = m[i], vk = v[i], ek = EMA ? ema[i] : 0.f;
-    adam_elem<DECOUPLED, EMA>(pk, g[i], mk, vk, ek, a);
-    m[i] = mk, v[i] = vk, p[i] = pk;
-    if constexpr (EMA) ema[i] = ek;
+  const auto rule = [&](float& pk, float& gk, float& mk, float& vk, float& ek) { adam_elem<DECOUPLED, EMA>(pk, gk, mk, vk, ek, a); };
+  if constexpr (EMA) {
+    flat_sweep(n4, n, rule, upd(p), last(g), upd(m), upd(v), upd(ema));
+  } else {
+    flat_sweep(n4, n, [&](float& pk, float& gk, float& mk, float& vk) { float ek = 0.f; rule(pk, gk, mk, vk, ek); }, upd(p), last(g), upd(m), upd(v));
   }
 }
 
@@ -92,9 +75,7 @@ int adam_grid(size_t n4) {
 int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps, float step_size,
                 float bc2_sqrt, double lr, double wd, int decoupled, float gscale, hipStream_t s, float* ema, float ema_decay) {
   MI355_ARG(p && g && m && v, "adam: null pointer");
-  MI355_ARG(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
-                ((uintptr_t)ema % 16 == 0),
-            "adam: pointers must be 16-byte aligned");
+  MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema), "adam: pointers must be 16-byte aligned");
   MI355_ARG(beta1 >= 0.0 && beta1 < 1.0, "adam: beta1=%g outside [0, 1)", beta1);
   MI355_ARG(beta2 >= 0.0 && beta2 < 1.0, "adam: beta2=%g outside [0, 1)", beta2);
   MI355_ARG(std::isfinite(eps) && eps >= 0.f, "adam: eps=%g must be finite and >= 0", (double)eps);
@@ -159,31 +140,12 @@ template <bool EMA>
 __global__ __launch_bounds__(256) void madgrad_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ gss,
                                                       float* __restrict__ s, const float* __restrict__ x0, float* __restrict__ ema, size_t n4,
                                                       size_t n, MadgradArgs a) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);  // last use of the gradient
-    f32x4 qv = reinterpret_cast<f32x4*>(gss)[i];
-    f32x4 sv = reinterpret_cast<f32x4*>(s)[i];
-    const f32x4 xv = reinterpret_cast<const f32x4*>(x0)[i];
-    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float pk = pv[k], qk = qv[k], sk = sv[k], ek = ev[k];
-      madgrad_elem<EMA>(pk, gv[k], qk, sk, xv[k], ek, a);
-      pv[k] = pk, qv[k] = qk, sv[k] = sk, ev[k] = ek;
-    }
-    reinterpret_cast<f32x4*>(gss)[i] = qv;
-    reinterpret_cast<f32x4*>(s)[i] = sv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
-    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const size_t i = n4 * 4 + threadIdx.x;
-    float pk = p[i], qk = gss[i], sk = s[i], ek = EMA ? ema[i] : 0.f;
-    madgrad_elem<EMA>(pk, g[i], qk, sk, x0[i], ek, a);
-    gss[i] = qk, s[i] = sk, p[i] = pk;
-    if constexpr (EMA) ema[i] = ek;
+  const auto rule = [&](float& pk, float& gk, float& qk, float& sk, float& xk, float& ek) { madgrad_elem<EMA>(pk, gk, qk, sk, xk, ek, a); };
+  if constexpr (EMA) {
+    flat_sweep(n4, n, rule, upd(p), last(g), upd(gss), upd(s), rd(x0), upd(ema));
+  } else {
+    flat_sweep(n4, n, [&](float& pk, float& gk, float& qk, float& sk, float& xk) { float ek = 0.f; rule(pk, gk, qk, sk, xk, ek); }, upd(p), last(g),
+               upd(gss), upd(s), rd(x0));
   }
 }
 
@@ -233,37 +195,16 @@ int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* 
 // b1prod = m = 0 and p stays 0 for every eps.
 namespace {
 
-constexpr int kAdaisMaxBlocks = 16384;  // as adam_grid: fewer workgroups measured slower on this sweep class
-
-int adais_grid(size_t n) {
-  size_t b = (n / 4 + 255) / 256;
-  if (b > (size_t)kAdaisMaxBlocks) b = kAdaisMaxBlocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 __global__ __launch_bounds__(256) void adais_moments_kernel(const float* __restrict__ g, float* __restrict__ v, double* __restrict__ partial,
                                                             size_t n4, size_t n, float b2, float b2w, float bc2, float gscale) {
   __shared__ double sh[256];
   double acc = 0.0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];  // read again by the step kernel: a plain load
-    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float ge = gv[k] * gscale;
-      vv[k] = vv[k] * b2 + (b2w * ge) * ge;
-      acc += (double)(vv[k] / bc2);
-    }
-    reinterpret_cast<f32x4*>(v)[i] = vv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const size_t i = n4 * 4 + threadIdx.x;
-    const float ge = g[i] * gscale;
-    const float vk = v[i] * b2 + (b2w * ge) * ge;
-    v[i] = vk;
+  const auto rule = [&](float& gk, float& vk) {
+    const float ge = gk * gscale;
+    vk = vk * b2 + (b2w * ge) * ge;
     acc += (double)(vk / bc2);
-  }
+  };
+  flat_sweep(n4, n, rule, rd(g), upd(v));  // g is read again by the step kernel: a plain load
   const double tot = block_sum<256>(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
@@ -302,31 +243,12 @@ __global__ __launch_bounds__(256) void adais_step_kernel(float* __restrict__ p, 
                                                          const float* __restrict__ v, float* __restrict__ bp, float* __restrict__ ema,
                                                          const float* __restrict__ mean_ptr, size_t n4, size_t n, AdaisArgs a) {
   const float mean = mean_ptr[0];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);  // last use of the gradient
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
-    const f32x4 vv = reinterpret_cast<const f32x4*>(v)[i];
-    f32x4 bv = reinterpret_cast<f32x4*>(bp)[i];
-    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float pk = pv[k], mk = mv[k], bk = bv[k], ek = ev[k];
-      adais_elem<EMA>(pk, gv[k], mk, vv[k], bk, ek, mean, a);
-      pv[k] = pk, mv[k] = mk, bv[k] = bk, ev[k] = ek;
-    }
-    reinterpret_cast<f32x4*>(m)[i] = mv;
-    reinterpret_cast<f32x4*>(bp)[i] = bv;
-    reinterpret_cast<f32x4*>(p)[i] = pv;
-    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const size_t i = n4 * 4 + threadIdx.x;
-    float pk = p[i], mk = m[i], bk = bp[i], ek = EMA ? ema[i] : 0.f;
-    adais_elem<EMA>(pk, g[i], mk, v[i], bk, ek, mean, a);
-    m[i] = mk, bp[i] = bk, p[i] = pk;
-    if constexpr (EMA) ema[i] = ek;
+  const auto rule = [&](float& pk, float& gk, float& mk, float& vk, float& bk, float& ek) { adais_elem<EMA>(pk, gk, mk, vk, bk, ek, mean, a); };
+  if constexpr (EMA) {
+    flat_sweep(n4, n, rule, upd(p), last(g), upd(m), rd(v), upd(bp), upd(ema));
+  } else {
+    flat_sweep(n4, n, [&](float& pk, float& gk, float& mk, float& vk, float& bk) { float ek = 0.f; rule(pk, gk, mk, vk, bk, ek); }, upd(p), last(g),
+               upd(m), rd(v), upd(bp));
   }
 }
 
@@ -340,7 +262,7 @@ int adais_bc2(const char* who, double beta2, int step, float* bc2) {
 
 }  // namespace
 
-size_t adais_partials(size_t n) { return (size_t)adais_grid(n); }
+size_t adais_partials(size_t n) { return (size_t)adam_grid(n / 4); }
 
 int launch_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float gscale, double* partial, hipStream_t st) {
   MI355_ARG(g && v && partial, "adais_moments: null pointer");
@@ -350,7 +272,7 @@ int launch_adais_moments(const float* g, float* v, size_t n, double beta2, int s
   MI355_TRY(adais_bc2("adais_moments", beta2, step, &bc2));
   MI355_ARG(std::isfinite(gscale), "adais_moments: grad_scale=%g is not finite", (double)gscale);
   const size_t n4 = n / 4;
-  hipLaunchKernelGGL(adais_moments_kernel, dim3(adais_grid(n)), dim3(256), 0, st, g, v, partial, n4, n, (float)beta2, (float)(1.0 - beta2), bc2,
+  hipLaunchKernelGGL(adais_moments_kernel, dim3(adam_grid(n4)), dim3(256), 0, st, g, v, partial, n4, n, (float)beta2, (float)(1.0 - beta2), bc2,
                      gscale);
   MI355_LAUNCH_CHECK();
   return 0;

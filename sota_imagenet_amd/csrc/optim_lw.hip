@@ -22,12 +22,14 @@
 //         p = p*wdf,  or with LW_SOFT_WD (NovogradApex's wd_eps)  p = p - wdf*(max(|p| - wd_eps, 0)*sign(p))
 //         EMA: ema = ema + (1 - decay)*(p - ema)
 // 4 B / element in (a) + 20 B / element in (c) (p, m read + write, g read once more, non-temporal: its last use), 28 B with the average.
-// The library builds with -ffp-contract=off, and sqrt / '/' stay correctly rounded.
+// The library builds with -ffp-contract=off, and sqrt / '/' stay correctly rounded.  The loop of (a) and (c) over an item's elements is item_sweep
+// (optim_sweep.h: 256 threads, f32x4 body, scalar tail).
 #include <cmath>
 
 #include "common.h"
 #include "optim_items.h"
 #include "optim_sum.h"
+#include "optim_sweep.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -47,20 +49,11 @@ __global__ __launch_bounds__(256) void lw_sumsq_kernel(const float* __restrict__
   const LwItem it = items[blockIdx.x];
   double acc = 0.0;
   if (item_ok(it, n, n_tensors)) {
-    const float* s = src + it.off;
-    const int n4 = it.len >> 2;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      const f32x4 x = reinterpret_cast<const f32x4*>(s)[i];  // read again by the update kernel: a plain load
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const double e = (double)(x[k] * scale);
-        acc += e * e;
-      }
-    }
-    if ((int)threadIdx.x < (it.len & 3)) {
-      const double e = (double)(s[n4 * 4 + threadIdx.x] * scale);
+    const auto rule = [&](float& x) {
+      const double e = (double)(x * scale);
       acc += e * e;
-    }
+    };
+    item_sweep(it.len, rule, rd(src + it.off));  // read again by the update kernel: a plain load
   }
   const double tot = block_sum<256>(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
@@ -137,33 +130,12 @@ __global__ __launch_bounds__(256) void lw_update_kernel(float* __restrict__ p, c
   const LwItem it = items[blockIdx.x];
   if (!item_ok(it, n, n_tensors)) return;
   const f32x4 c = reinterpret_cast<const f32x4*>(coef)[it.tensor];
-  f32x4* p4 = reinterpret_cast<f32x4*>(p + it.off);
-  const f32x4* g4 = reinterpret_cast<const f32x4*>(g + it.off);
-  f32x4* m4 = reinterpret_cast<f32x4*>(m + it.off);
-  f32x4* e4 = EMA ? reinterpret_cast<f32x4*>(ema + it.off) : nullptr;
-  const int n4 = it.len >> 2;
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    f32x4 pv = p4[i];
-    const f32x4 gv = __builtin_nontemporal_load(g4 + i);  // last use of the gradient
-    f32x4 mv = m4[i];
-    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EMA) ev = e4[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float pk = pv[k], mk = mv[k], ek = ev[k];
-      lw_elem<RULE, EMA>(pk, gv[k], mk, ek, c, a);
-      pv[k] = pk, mv[k] = mk, ev[k] = ek;
-    }
-    m4[i] = mv;
-    p4[i] = pv;
-    if constexpr (EMA) e4[i] = ev;
-  }
-  if ((int)threadIdx.x < (it.len & 3)) {
-    const size_t i = (size_t)it.off + n4 * 4 + threadIdx.x;
-    float pk = p[i], mk = m[i], ek = EMA ? ema[i] : 0.f;
-    lw_elem<RULE, EMA>(pk, g[i], mk, ek, c, a);
-    m[i] = mk, p[i] = pk;
-    if constexpr (EMA) ema[i] = ek;
+  const auto rule = [&](float& pk, float& gk, float& mk, float& ek) { lw_elem<RULE, EMA>(pk, gk, mk, ek, c, a); };
+  if constexpr (EMA) {
+    item_sweep(it.len, rule, upd(p + it.off), last(g + it.off), upd(m + it.off), upd(ema + it.off));
+  } else {
+    item_sweep(it.len, [&](float& pk, float& gk, float& mk) { float ek = 0.f; rule(pk, gk, mk, ek); }, upd(p + it.off), last(g + it.off),
+               upd(m + it.off));
   }
 }
 

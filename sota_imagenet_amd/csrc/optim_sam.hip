@@ -14,11 +14,13 @@
 //   (d) sam_restore_kernel:  p = p - eps over the same items  ((p + e) - e is in general not p bit for bit: the reference's behaviour, kept)
 // 8 B / element in (a) (p, g read), 16 B in (c) (p, g read; eps, p written), 12 B in (d) (p, eps read; p written).  Alignment gaps and padding are
 // neither read into the sum nor written.  The library builds with -ffp-contract=off: every product and sum above is rounded on its own.
+// The loop of (a), (c) and (d) over an item's elements is item_sweep (optim_sweep.h: 256 threads, f32x4 body, scalar tail).
 #include <cmath>
 
 #include "common.h"
 #include "optim_items.h"
 #include "optim_sum.h"
+#include "optim_sweep.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -37,22 +39,11 @@ __global__ __launch_bounds__(256) void sam_sumsq_kernel(const float* __restrict_
   double acc = 0.0;
   if (item_ok(it, n, n_tensors)) {
     const bool weight = kind[it.tensor] != 0;
-    const f32x4* p4 = reinterpret_cast<const f32x4*>(p + it.off);
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g + it.off);
-    const int n4 = it.len >> 2;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      const f32x4 pv = p4[i], gv = g4[i];  // both read again by the perturbation: plain loads
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const double w = (double)sam_w(pv[k], gv[k] * gscale, weight, eta);
-        acc += w * w;
-      }
-    }
-    if ((int)threadIdx.x < (it.len & 3)) {
-      const size_t i = (size_t)it.off + n4 * 4 + threadIdx.x;
-      const double w = (double)sam_w(p[i], g[i] * gscale, weight, eta);
+    const auto rule = [&](float& pk, float& gk) {
+      const double w = (double)sam_w(pk, gk * gscale, weight, eta);
       acc += w * w;
-    }
+    };
+    item_sweep(it.len, rule, rd(p + it.off), rd(g + it.off));  // both read again by the perturbation: plain loads
   }
   const double tot = block_sum<256>(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
@@ -76,48 +67,18 @@ __global__ __launch_bounds__(256) void sam_perturb_kernel(float* __restrict__ p,
   if (!item_ok(it, n, n_tensors)) return;
   const bool weight = kind[it.tensor] != 0;
   const float scale = out[0];
-  f32x4* p4 = reinterpret_cast<f32x4*>(p + it.off);
-  const f32x4* g4 = reinterpret_cast<const f32x4*>(g + it.off);
-  f32x4* e4 = reinterpret_cast<f32x4*>(eps + it.off);
-  const int n4 = it.len >> 2;
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    f32x4 pv = p4[i], ev;
-    const f32x4 gv = g4[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      ev[k] = sam_e(pv[k], gv[k] * gscale, weight, eta, scale);
-      pv[k] = pv[k] + ev[k];
-    }
-    e4[i] = ev;
-    p4[i] = pv;
-  }
-  if ((int)threadIdx.x < (it.len & 3)) {
-    const size_t i = (size_t)it.off + n4 * 4 + threadIdx.x;
-    const float pk = p[i];
-    const float e = sam_e(pk, g[i] * gscale, weight, eta, scale);
-    eps[i] = e;
-    p[i] = pk + e;
-  }
+  const auto rule = [&](float& pk, float& gk, float& ek) {
+    ek = sam_e(pk, gk * gscale, weight, eta, scale);  // eps is written, never read
+    pk = pk + ek;
+  };
+  item_sweep(it.len, rule, upd(p + it.off), rd(g + it.off), upd(eps + it.off));
 }
 
 __global__ __launch_bounds__(256) void sam_restore_kernel(float* __restrict__ p, const float* __restrict__ eps, size_t n,
                                                           const LwItem* __restrict__ items, int n_tensors) {
   const LwItem it = items[blockIdx.x];
   if (!item_ok(it, n, n_tensors)) return;
-  f32x4* p4 = reinterpret_cast<f32x4*>(p + it.off);
-  const f32x4* e4 = reinterpret_cast<const f32x4*>(eps + it.off);
-  const int n4 = it.len >> 2;
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    f32x4 pv = p4[i];
-    const f32x4 ev = __builtin_nontemporal_load(e4 + i);  // last use of the perturbation
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pv[k] = pv[k] - ev[k];
-    p4[i] = pv;
-  }
-  if ((int)threadIdx.x < (it.len & 3)) {
-    const size_t i = (size_t)it.off + n4 * 4 + threadIdx.x;
-    p[i] = p[i] - eps[i];
-  }
+  item_sweep(it.len, [](float& pk, float& ek) { pk = pk - ek; }, upd(p + it.off), last(eps + it.off));
 }
 
 }  // namespace

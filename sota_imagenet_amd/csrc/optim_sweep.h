@@ -1,0 +1,80 @@
+// optim_sweep.h — the loop every element-wise optimizer kernel runs over flat fp32 arrays, stated once: an f32x4 body and a scalar tail for the
+// n % 4 elements behind it, both calling the same element rule.  A kernel names its arrays in load order, each with how it is used:
+//   rd(q)    read                                  (const float*)
+//   last(q)  read for the last time in the step: the vector load is non-temporal, the lines are not kept in L2 / Infinity Cache   (const float*)
+//   upd(q)   read, and written back after the rule (float*); an array the rule overwrites without reading it costs no load
+// rule(float&...) gets one reference per array, in the same order; it is called four times per vector and once per tail element, so a reduction
+// that adds into a captured variable sees a thread's elements in array order.  Stores cover the upd() arrays only.  The arrays must not overlap.
+#pragma once
+#include <type_traits>
+#include <utility>
+
+#include "common.h"
+
+namespace mi355 {
+
+template <typename T, bool NONTEMPORAL>
+struct SweepArray {
+  T* q;
+  static constexpr bool kStore = !std::is_const<T>::value;
+  template <typename I>
+  __device__ __forceinline__ f32x4 load4(I i) const {
+    if constexpr (NONTEMPORAL) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q) + i);
+    else return reinterpret_cast<const f32x4*>(q)[i];
+  }
+  template <typename I>
+  __device__ __forceinline__ void store4(I i, const f32x4& x) const {
+    if constexpr (kStore) reinterpret_cast<f32x4*>(q)[i] = x;
+  }
+  template <typename I>
+  __device__ __forceinline__ void store1(I i, float x) const {
+    if constexpr (kStore) q[i] = x;
+  }
+};
+
+__device__ __forceinline__ SweepArray<const float, false> rd(const float* q) { return {q}; }
+__device__ __forceinline__ SweepArray<const float, true> last(const float* q) { return {q}; }
+__device__ __forceinline__ SweepArray<float, false> upd(float* q) { return {q}; }
+
+// vector i of every array
+template <typename I, typename Rule, size_t... J, typename... A>
+__device__ __forceinline__ void sweep_vector(I i, Rule& rule, std::index_sequence<J...>, const A&... a) {
+  f32x4 v[] = {a.load4(i)...};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float x[] = {v[J][k]...};
+    rule(x[J]...);
+    ((v[J][k] = x[J]), ...);
+  }
+  (a.store4(i, v[J]), ...);
+}
+
+// element i of every array
+template <typename I, typename Rule, size_t... J, typename... A>
+__device__ __forceinline__ void sweep_element(I i, Rule& rule, std::index_sequence<J...>, const A&... a) {
+  float x[] = {a.q[i]...};
+  rule(x[J]...);
+  (a.store1(i, x[J]), ...);
+}
+
+// grid-stride form over arrays of n = 4 * n4 + (n & 3) elements: workgroup 0's first n & 3 threads take the tail
+template <typename Rule, typename... A>
+__device__ __forceinline__ void flat_sweep(size_t n4, size_t n, Rule rule, const A&... a) {
+  constexpr std::index_sequence_for<A...> js;
+  // blockDim.x, read as the kernels themselves read it: spelled blockDim.x in a device function it also allows for a partial last workgroup,
+  // which no launch has, and costs every wave a dependent global load before its first vector
+  const size_t threads = __builtin_amdgcn_workgroup_size_x();
+  for (size_t i = blockIdx.x * threads + threadIdx.x; i < n4; i += gridDim.x * threads) sweep_vector(i, rule, js, a...);
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) sweep_element(n4 * 4 + threadIdx.x, rule, js, a...);
+}
+
+// one workgroup of 256 threads per work item of len elements (optim_items.h); the array pointers are already offset to the item
+template <typename Rule, typename... A>
+__device__ __forceinline__ void item_sweep(int len, Rule rule, const A&... a) {
+  constexpr std::index_sequence_for<A...> js;
+  const int n4 = len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) sweep_vector(i, rule, js, a...);
+  if ((int)threadIdx.x < (len & 3)) sweep_element(n4 * 4 + (int)threadIdx.x, rule, js, a...);
+}
+
+}  // namespace mi355
