@@ -357,6 +357,38 @@ int mi355_sam_perturb(float* p, const float* g, float* eps, size_t n, const void
                       const float* out, float eta, float grad_scale, void* stream);
 int mi355_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, void* stream);
 
+/* The SAM callback of the reference (sota_imagenet/callbacks.py:339-420 with unitwise_norm :269-276; the form the recipes write down,
+ * configs/hydra_exp/32.nf_conv-act_sam.yaml:104-106) on flat fp32 arrays: the perturbation is scaled slot by slot, eps = ||w|| / ||g|| * g * rho.
+ * A slot is a whole tensor (:389-391), or with unitwise (:386-387) one output unit of a tensor with more than one dimension: one index of
+ * dim 0, a contiguous run of unit_len = numel / shape[0] elements.  Stages on one stream, nothing read back, no floating-point atomics, over
+ * the items[] table of the layer-wise optimizers above (all tensors) and
+ *   pieces[]   { int64 off; int32 len; int32 slot }        len <= mi355_lw_item_elems(), off ANY element offset, cut from ONE unit
+ *   slots[]    { int32 first; int32 count }                the slot's consecutive entries of partial[]
+ *   tensors[]  { int64 start; int32 unit_len; int32 slot0 }   indexed by items[].tensor: the tensor's first element, elements per slot (numel
+ *                                                          for a whole-tensor slot), the slot of its first element
+ * partial[] holds a PAIR of doubles per entry: (sum of ge^2, sum of p^2), ge = g*grad_scale formed in float, squares and sums in double in a
+ * fixed order.  A record that does not lie inside the arrays of the launch is skipped by the kernels.
+ *  (a)  mi355_sam_lw_sumsq, once per storage pair over the items of the whole-tensor slots:  partial[i] = the pair of sums over items[i].
+ *  (a') mi355_sam_unit_sumsq, once per storage pair over the pieces of the unit slots:  partial[i] = the pair of sums over pieces[i];
+ *       threads_per_piece = 64 (one wave per piece, four pieces per workgroup: what the callback uses) or 256 (one workgroup per piece).
+ *  (b)  mi355_sam_lw_coef, once per step over ALL slots:  (Sg, Sp) = the slot's entries of partial[] summed in a fixed order;
+ *       gn = max((float)sqrt(Sg), 1e-5f);  wn = max((float)sqrt(Sp), 1e-3f)  (:367-368, :386-391);  coef[slot] = wn / gn  (:395);
+ *       norms[slot] = (gn, wn).
+ *  (c)  mi355_sam_lw_perturb, once per storage pair over ALL its items (:396-404):  e = (coef[slot] * ge) * (float)rho;  eps = e;  p = p + e,
+ *       slot = tensors[t].slot0 + (element offset inside tensor t) / tensors[t].unit_len, element by element where an item spans units.
+ *  (d)  mi355_sam_restore above, after the second backward (:418).
+ * p, g, eps are the arrays the offsets count from, n their length; elements outside the tables are neither read into a sum nor written.  Each
+ * fails (-1) before any launch on a null or misaligned pointer (16 bytes for the arrays, items[], pieces[], tensors[] and partial[], 8 for
+ * slots[] and norms[], 4 for coef[]), an empty table, rho not finite or negative (0 is legal: the recipes write rho: 0), grad_scale not finite,
+ * threads_per_piece other than 64 or 256. */
+int mi355_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, int n_tensors, float grad_scale, void* partial,
+                       void* stream);
+int mi355_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* pieces, size_t n_pieces, int n_slots, float grad_scale,
+                         void* partial, int threads_per_piece, void* stream);
+int mi355_sam_lw_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms, void* stream);
+int mi355_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
+                         const float* coef, size_t n_slots, double rho, float grad_scale, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

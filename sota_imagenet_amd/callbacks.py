@@ -1,10 +1,10 @@
 """Callbacks next to the hot path: Mixup / CutMix / CutmixMixup on device, producing the soft targets the native cross
-entropy consumes, and SAMOriginal (sharpness-aware minimization), which sits on the step itself.
+entropy consumes, and SAMOriginal / SAM (sharpness-aware minimization), which sit on the step itself.
 
 Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `self.cutmix(*input)` and
 `self.mixup(*input)` with Beta(alpha, alpha) samplers) and the un-vendored pt_clb.Cutmix / pt_clb.Mixup bases as
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
-SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip.
+SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip.
 """
 
 import numpy as np
@@ -162,7 +162,92 @@ class CutmixMixup(Cutmix):
             self.state.input = self.mixup(*self.state.input)
 
 
-class SAMOriginal(Callback):
+class _SecondPass(Callback):
+    """what SAMOriginal and SAM share: which parameters fit the flat kernels, one launch set per pair of parameter / gradient storage with an
+    eps array of its own, the second forward / backward on the same batch, and the way back (mi355_sam_restore)"""
+
+    def __init__(self):
+        super().__init__()
+        self._key = None
+        self._segs = []     # per storage pair: (parameter slice, gradient slice, eps slice, first item, end item, ...)
+        self._eps = []      # per storage pair: the eps array, indexed like the storage
+        self.forwards = 0   # second forwards made so far
+
+    @property
+    def eps_flat(self):
+        if not self._eps:
+            return None
+        return self._eps[0] if len(self._eps) == 1 else list(self._eps)
+
+    def on_begin(self):
+        if getattr(self.state, "accumulate_steps", 1) != 1:
+            raise NotImplementedError(f"{type(self).__name__}: accumulate_steps != 1 is not supported (the second pass would discard the "
+                                      "accumulated micro-gradients)")
+
+    @classmethod
+    def _entries(cls, params):
+        """[(param base, grad base, first elem, numel, param)] of the parameters with a gradient: the rules of optim._FlatOptimizer._entries"""
+        from .optim import _dense_range
+
+        name = cls.__name__
+        entries = []
+        for p in params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.grad.is_cuda and p.grad.dtype == torch.float32):
+                raise RuntimeError(f"{name}: parameters and gradients must be CUDA fp32 tensors (no CPU fallback on the hot path)")
+            rp, rg = _dense_range(p.data), _dense_range(p.grad)
+            if rp is None or rg is None or rp[1:] != rg[1:]:
+                raise RuntimeError(f"{name}: parameter and gradient must be dense and share their flat offset")
+            if (rp[1] * 4) % 16 or (rp[0] + rp[1] * 4) % 16 or (rg[0] + rg[1] * 4) % 16:
+                raise RuntimeError(f"{name}: flat range not 16-byte aligned")
+            entries.append((rp[0], rg[0], rp[1], rp[2], p))
+        if any(e[4].device != entries[0][4].device for e in entries):
+            raise RuntimeError(f"{name}: all parameters must live on one device (the norm is taken there)")
+        return entries
+
+    def _plan_changed(self, params):
+        """True at the first perturbed step and whenever the parameters or their addresses changed since the plan was built"""
+        key = tuple((id(p), p.data_ptr(), p.grad.data_ptr(), p.numel()) for p in params)
+        changed, self._key = key != self._key, key
+        return changed
+
+    @staticmethod
+    def _table(records, dev):
+        """16-byte records (int64, int32, int32) as the [n, 2] int64 tensor the ops wrappers take"""
+        rec = np.zeros(len(records), dtype=[("a", "<i8"), ("b", "<i4"), ("c", "<i4")])
+        if records:
+            a, b, c = zip(*records)
+            rec["a"], rec["b"], rec["c"] = a, b, c
+        return torch.from_numpy(rec.view(np.int64).reshape(-1, 2)).to(dev)
+
+    def _storage_pairs(self, entries, pairs):
+        """per pair (lo, hi, ..., tensor indices) of a plan: the parameter and gradient storage as flat arrays over [lo, hi) and an eps array
+        indexed like the storage (eps_flat lines up with a model's flat array); fills _eps, returns [(parameters, gradients, eps slice)]"""
+        dev = entries[0][4].device
+        self._eps, out = [], []
+        for lo, hi, *_, ts in pairs:
+            p0 = entries[ts[0]][4]
+            fp = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.data.untyped_storage(), lo, (hi - lo,))
+            fg = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.grad.untyped_storage(), lo, (hi - lo,))
+            eps = torch.zeros(hi, dtype=torch.float32, device=dev)
+            self._eps.append(eps)
+            out.append((fp, fg, eps[lo:hi]))
+        return out
+
+    def _second_pass(self, n_tensors):
+        """zero_grad, a second forward / backward at the perturbed parameters on the same (already mixed) batch, then p -= eps"""
+        from . import ops
+
+        self.state.optimizer.zero_grad()  # (with an attached flat model: marks its gradients clean, the second backward overwrites them)
+        with torch.enable_grad():
+            data, target = self.state.input
+            loss_second = self.state.criterion(self.state.model(data), target)
+            loss_second.backward()
+        self.forwards += 1
+        for fp, fg, fe, i0, i1, *_ in self._segs:
+            ops.sam_restore(fp, fe, self._items[i0:i1], n_tensors)
+
+
+class SAMOriginal(_SecondPass):
     """sota_imagenet/callbacks.py:279-337 (recipe configs/hydra_exp/49.r50_nov-adam.yaml:46-48): adaptive sharpness-aware minimization as
     the reference runs it.  After the first backward of a step, with g the gradient the optimizer would see (g * optimizer.grad_scale):
         norm  = max(sqrt(sum over all tensors of |w|^2), 2e-5),   w = g * max(|p|, eta) for tensors with ndim > 1, w = g for the others
@@ -191,11 +276,7 @@ class SAMOriginal(Callback):
             raise ValueError(f"Invalid eta: {eta}")
         self.rho = rho
         self.eta = eta
-        self._key = None
-        self._segs = []     # per storage pair: (parameter slice, gradient slice, eps slice, first item, end item)
-        self._eps = []      # per storage pair: the eps array, indexed like the storage
         self._out = None    # (rho / norm, norm) of the last step
-        self.forwards = 0   # second forwards made so far
 
     @property
     def scale(self):
@@ -204,34 +285,6 @@ class SAMOriginal(Callback):
     @property
     def norm(self):
         return None if self._out is None else self._out[1:2]
-
-    @property
-    def eps_flat(self):
-        if not self._eps:
-            return None
-        return self._eps[0] if len(self._eps) == 1 else list(self._eps)
-
-    def on_begin(self):
-        if getattr(self.state, "accumulate_steps", 1) != 1:
-            raise NotImplementedError("SAMOriginal: accumulate_steps != 1 is not supported (the second pass would discard the accumulated "
-                                      "micro-gradients)")
-
-    @staticmethod
-    def _entries(params):
-        """[(param base, grad base, first elem, numel, param)] of the parameters with a gradient: the rules of optim._FlatOptimizer._entries"""
-        from .optim import _dense_range
-
-        entries = []
-        for p in params:
-            if not (p.is_cuda and p.dtype == torch.float32 and p.grad.is_cuda and p.grad.dtype == torch.float32):
-                raise RuntimeError("SAMOriginal: parameters and gradients must be CUDA fp32 tensors (no CPU fallback on the hot path)")
-            rp, rg = _dense_range(p.data), _dense_range(p.grad)
-            if rp is None or rg is None or rp[1:] != rg[1:]:
-                raise RuntimeError("SAMOriginal: parameter and gradient must be dense and share their flat offset")
-            if (rp[1] * 4) % 16 or (rp[0] + rp[1] * 4) % 16 or (rg[0] + rg[1] * 4) % 16:
-                raise RuntimeError("SAMOriginal: flat range not 16-byte aligned")
-            entries.append((rp[0], rg[0], rp[1], rp[2], p))
-        return entries
 
     @staticmethod
     def plan_tables(tensors, W):
@@ -258,24 +311,12 @@ class SAMOriginal(Callback):
         from . import ops
 
         dev = entries[0][4].device
-        if any(e[4].device != dev for e in entries):
-            raise RuntimeError("SAMOriginal: all parameters must live on one device (the norm is taken there)")
         items, kind, pairs = self.plan_tables([(pb, gb, off, n, p.ndim) for pb, gb, off, n, p in entries], ops.lw_item_elems())
-        rec = np.zeros(len(items), dtype=[("off", "<i8"), ("len", "<i4"), ("t", "<i4")])
-        for k, it in enumerate(items):
-            rec[k] = it
-        self._items = torch.from_numpy(rec.view(np.int64).reshape(-1, 2)).to(dev)
+        self._items = self._table(items, dev)
         self._kind = torch.tensor(kind, dtype=torch.int32, device=dev)
         self._partial = torch.zeros(len(items), dtype=torch.float64, device=dev)
         self._out = torch.zeros(2, dtype=torch.float32, device=dev)
-        self._segs, self._eps = [], []
-        for lo, hi, i0, i1, ts in pairs:
-            p0 = entries[ts[0]][4]
-            fp = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.data.untyped_storage(), lo, (hi - lo,))
-            fg = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.grad.untyped_storage(), lo, (hi - lo,))
-            eps = torch.zeros(hi, dtype=torch.float32, device=dev)  # indexed like the storage: eps_flat lines up with a model's flat array
-            self._segs.append((fp, fg, eps[lo:hi], i0, i1))
-            self._eps.append(eps)
+        self._segs = [(fp, fg, fe, i0, i1) for (fp, fg, fe), (lo, hi, i0, i1, ts) in zip(self._storage_pairs(entries, pairs), pairs)]
 
     @torch.no_grad()
     def on_after_backward(self):
@@ -287,22 +328,152 @@ class SAMOriginal(Callback):
         params = [p for group in opt.param_groups for p in group["params"] if p.grad is not None]
         if not params:
             return
-        key = tuple((id(p), p.data_ptr(), p.grad.data_ptr(), p.numel()) for p in params)
-        if key != self._key:  # the first non-skipped step, or the parameters / their addresses changed
+        if self._plan_changed(params):  # the first non-skipped step, or the parameters / their addresses changed
             self._build_plan(self._entries(params))
-            self._key = key
         gs = float(getattr(opt, "grad_scale", 1.0))
-        nt = self._kind.numel()
         for fp, fg, fe, i0, i1 in self._segs:
             ops.sam_sumsq(fp, fg, self._items[i0:i1], self._kind, self._partial[i0:i1], self.eta, grad_scale=gs)
         ops.sam_scale(self._partial, self.rho, self._out)
         for fp, fg, fe, i0, i1 in self._segs:
             ops.sam_perturb(fp, fg, fe, self._items[i0:i1], self._kind, self._out, self.eta, grad_scale=gs)
-        opt.zero_grad()  # (with an attached flat model: marks its gradients clean, the second backward overwrites them)
-        with torch.enable_grad():
-            data, target = self.state.input
-            loss_second = self.state.criterion(self.state.model(data), target)
-            loss_second.backward()
-        self.forwards += 1
-        for fp, fg, fe, i0, i1 in self._segs:
-            ops.sam_restore(fp, fe, self._items[i0:i1], nt)
+        self._second_pass(self._kind.numel())
+
+
+class SAM(_SecondPass):
+    """sota_imagenet/callbacks.py:339-420 with unitwise_norm :269-276 (the form the recipes write down, configs/hydra_exp/
+    32.nf_conv-act_sam.yaml:104-106): sharpness-aware minimization with the perturbation scaled slot by slot.  A slot is a whole tensor when
+    unitwise is False or the tensor has at most one dimension; otherwise every index of dim 0 (a filter of a conv, a row of the FC) is a slot of
+    its own.  After the first backward of EVERY step (there is no first-step skip), with g the gradient the optimizer would see
+    (g * optimizer.grad_scale), per slot:
+        gn = max(||g||_2, eps),  wn = max(||p||_2, eps_2),  e = ((wn / gn) * g) * rho;   p += e
+        optimizer.zero_grad(); a second criterion(model(data), target).backward() on the same (already mixed) batch;   p -= e
+    and the optimizer steps from the unperturbed parameters on the SECOND gradient.  (p + e) - e is in general not p bit for bit: the
+    reference's behaviour, kept.  rho = 0 is legal (the recipe file writes rho: 0): the second pass still runs.
+
+    The stages are HIP kernels over the flat arrays (csrc/optim_sam_lw.hip) on the current stream; nothing is read back in a step.  Per pair
+    of parameter / gradient storage: 4 launches layer-wise (whole-tensor sums, coefficients, perturbation, restore), 5 unit-wise (unit sums,
+    whole-tensor sums of the 1-D tensors, coefficients, perturbation, restore); the coefficient launch is one per step for all pairs.  The
+    plan is built at the first step under the placement rules of SAMOriginal and rebuilt when the parameters or their addresses change.  A
+    unit must be one contiguous run of numel / shape[0] elements, i.e. dim 0 the outermost stride (the flat models' OIHW views over KRSC
+    memory are): anything else raises RuntimeError.  There is no CPU fallback.  `coef` ([slots] float32: wn / gn) and `norms` ([slots, 2]:
+    gn, wn) hold the last step's values on the device, slots numbered tensor by tensor in param-group order (slot_ranges: per tensor (first
+    slot, slots)); `eps_flat` is the last perturbation as in SAMOriginal; `forwards` counts the second forwards.
+
+    As in the reference BatchNorm running statistics and num_batches_tracked advance TWICE per step, and a data-parallel wrapper reduces the
+    second gradient too.  Deviations, the two of SAMOriginal: accumulate_steps != 1 raises at on_begin; eps lives in this callback, not in
+    optimizer state."""
+
+    def __init__(self, unitwise=False, rho=0.01):
+        super().__init__()
+        if not (rho >= 0 and np.isfinite(rho)):
+            raise ValueError(f"Invalid rho: {rho}")
+        self.unitwise = bool(unitwise)
+        self.rho = rho
+        self.eps = 1e-5    # floor of the gradient norm (callbacks.py:367); the kernels hold it as a float32 constant
+        self.eps_2 = 1e-3  # floor of the weight norm (:368)
+        self._coef = self._norms = None
+        self.slot_ranges = []
+
+    @property
+    def coef(self):
+        return self._coef
+
+    @property
+    def norms(self):
+        return self._norms
+
+    @staticmethod
+    def unit_len(shape, stride, unitwise):
+        """elements per slot of a dense tensor: numel, or numel / shape[0] for a unit-wise tensor with ndim > 1 — whose dim 0 must be the
+        outermost stride, so that a unit is one contiguous run"""
+        n = int(np.prod(shape)) if len(shape) else 1
+        if not unitwise or len(shape) <= 1:
+            return n
+        u = n // shape[0]
+        if shape[0] > 1 and stride[0] != u:
+            raise RuntimeError(f"SAM: unitwise needs dim 0 as the outermost stride (shape {tuple(shape)}, strides {tuple(stride)}): a unit must be "
+                               "one contiguous run of numel / shape[0] elements")
+        return u
+
+    @staticmethod
+    def plan_tables(tensors, W):
+        """the host side of a plan.  tensors: [(param base, grad base, first elem, numel, unit_len)] in param-group order, unit_len = numel for
+        a whole-tensor slot, less for a tensor taken unit by unit; W: ops.lw_item_elems().  Returns a dict:
+          items    SAMOriginal.plan_tables' work items of ALL tensors (the perturbation and the restore walk them)
+          tensors  [(start relative to its pair's range, unit_len, slot0)] per tensor; slots are numbered tensor by tensor
+          pieces   [(first element relative to the pair's range, length <= W, slot)]: every unit of the unit-wise tensors, cut at multiples of
+                   W from the unit's start
+          whole    the work items of the whole-tensor slots, in the order of `items`
+          slots    [(first, count)] per slot: its consecutive entries of the partial sums, which are laid out pair by pair, a pair's pieces
+                   before its whole-tensor items
+          pairs    [(lo, hi, first item, end item, (first piece, end piece), (first whole item, end), first partial entry, tensor indices)]"""
+        items, _, pairs0 = SAMOriginal.plan_tables([(pb, gb, off, n, 1) for pb, gb, off, n, _ in tensors], W)
+        slot0, n_slots = [], 0
+        for _, _, _, n, u in tensors:
+            if u < 1 or n % u or n >= 1 << 31:
+                raise ValueError(f"numel={n}, unit_len={u}: a tensor is a whole number of units and shorter than 2^31 elements")
+            slot0.append(n_slots)
+            n_slots += n // u
+        trec, pieces, whole, slots, pairs = [None] * len(tensors), [], [], [None] * n_slots, []
+        k = 0  # entries of the partial sums so far
+        for lo, hi, i0, i1, ts in pairs0:
+            pa, wa, k0 = len(pieces), len(whole), k
+            for t in ts:
+                _, _, off, n, u = tensors[t]
+                trec[t] = (off - lo, u, slot0[t])
+                if u == n:
+                    continue
+                per = (u + W - 1) // W
+                for j in range(n // u):
+                    slots[slot0[t] + j] = (k, per)
+                    pieces.extend((off - lo + j * u + c, min(W, u - c), slot0[t] + j) for c in range(0, u, W))
+                    k += per
+            for o, ln, t in items[i0:i1]:
+                if tensors[t][4] != tensors[t][3]:
+                    continue
+                first, count = slots[slot0[t]] or (k, 0)
+                slots[slot0[t]] = (first, count + 1)
+                whole.append((o, ln, t))
+                k += 1
+            pairs.append((lo, hi, i0, i1, (pa, len(pieces)), (wa, len(whole)), k0, ts))
+        return dict(items=items, tensors=trec, pieces=pieces, whole=whole, slots=slots, pairs=pairs)
+
+    def _build_plan(self, entries):
+        from . import ops
+
+        dev = entries[0][4].device
+        tab = self.plan_tables([(pb, gb, off, n, self.unit_len(p.shape, p.stride(), self.unitwise)) for pb, gb, off, n, p in entries],
+                               ops.lw_item_elems())
+        self._items, self._tensors = self._table(tab["items"], dev), self._table(tab["tensors"], dev)
+        self._pieces, self._whole = self._table(tab["pieces"], dev), self._table(tab["whole"], dev)
+        n_slots = len(tab["slots"])
+        self._slots = torch.tensor(tab["slots"], dtype=torch.int32, device=dev)
+        self._partial = torch.zeros(2 * (len(tab["pieces"]) + len(tab["whole"])), dtype=torch.float64, device=dev)
+        self._coef = torch.zeros(n_slots, dtype=torch.float32, device=dev)
+        self._norms = torch.zeros(n_slots, 2, dtype=torch.float32, device=dev)
+        self.slot_ranges = [(s0, e[3] // u) for (_, u, s0), e in zip(tab["tensors"], entries)]
+        self._segs = [(fp, fg, fe, i0, i1, pc, wh, k0) for (fp, fg, fe), (lo, hi, i0, i1, pc, wh, k0, ts)
+                      in zip(self._storage_pairs(entries, tab["pairs"]), tab["pairs"])]
+
+    @torch.no_grad()
+    def on_after_backward(self):
+        from . import ops
+
+        opt = self.state.optimizer
+        params = [p for group in opt.param_groups for p in group["params"] if p.grad is not None]
+        if not params:
+            return
+        if self._plan_changed(params):  # the first step, or the parameters / their addresses changed
+            self._build_plan(self._entries(params))
+        gs = float(getattr(opt, "grad_scale", 1.0))
+        nt, ns = self._tensors.shape[0], self._coef.numel()
+        for fp, fg, fe, i0, i1, (pa, pb), (wa, wb), k0 in self._segs:
+            k1 = k0 + pb - pa
+            if pb > pa:
+                ops.sam_unit_sumsq(fp, fg, self._pieces[pa:pb], self._partial[2 * k0:2 * k1], ns, grad_scale=gs)
+            if wb > wa:
+                ops.sam_lw_sumsq(fp, fg, self._whole[wa:wb], self._partial[2 * k1:2 * (k1 + wb - wa)], nt, grad_scale=gs)
+        ops.sam_lw_coef(self._partial, self._slots, self._coef, self._norms)
+        for fp, fg, fe, i0, i1, *_ in self._segs:
+            ops.sam_lw_perturb(fp, fg, fe, self._items[i0:i1], self._tensors, self._coef, self.rho, grad_scale=gs)
+        self._second_pass(nt)

@@ -56,6 +56,8 @@ LAYERWISE_TARGET_ALIASES = {
 CALLBACK_TARGET_ALIASES = {
     "src.callbacks.SAMOriginal": "sota_imagenet_amd.callbacks.SAMOriginal",
     "sota_imagenet.callbacks.SAMOriginal": "sota_imagenet_amd.callbacks.SAMOriginal",
+    "src.callbacks.SAM": "sota_imagenet_amd.callbacks.SAM",
+    "sota_imagenet.callbacks.SAM": "sota_imagenet_amd.callbacks.SAM",
 }
 
 

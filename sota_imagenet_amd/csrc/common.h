@@ -360,6 +360,14 @@ int launch_sam_scale(const double* partial, size_t n_partial, double rho, float*
 int launch_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
                        const float* out, float eta, float gscale, hipStream_t st);
 int launch_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, hipStream_t st);
+// optim_sam_lw.hip: the stages of the SAM callback, one norm pair per slot (a whole tensor, or one output unit of it); tables: see there
+int launch_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, int n_tensors, float gscale, double* partial,
+                        hipStream_t st);
+int launch_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* pieces, size_t n_pieces, int n_slots, float gscale,
+                          double* partial, int threads_per_piece, hipStream_t st);
+int launch_sam_lw_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms, hipStream_t st);
+int launch_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
+                          const float* coef, size_t n_slots, double rho, float gscale, hipStream_t st);
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

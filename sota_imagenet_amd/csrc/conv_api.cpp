@@ -617,4 +617,20 @@ int mi355_sam_restore(float* p, const float* eps, size_t n, const void* items, s
   return launch_sam_restore(p, eps, n, items, n_items, n_tensors, (hipStream_t)stream);
 }
 
+int mi355_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, int n_tensors, float grad_scale, void* partial,
+                       void* stream) {
+  return launch_sam_lw_sumsq(p, g, n, items, n_items, n_tensors, grad_scale, (double*)partial, (hipStream_t)stream);
+}
+int mi355_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* pieces, size_t n_pieces, int n_slots, float grad_scale,
+                         void* partial, int threads_per_piece, void* stream) {
+  return launch_sam_unit_sumsq(p, g, n, pieces, n_pieces, n_slots, grad_scale, (double*)partial, threads_per_piece, (hipStream_t)stream);
+}
+int mi355_sam_lw_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms, void* stream) {
+  return launch_sam_lw_coef((const double*)partial, n_partial, slots, n_slots, coef, norms, (hipStream_t)stream);
+}
+int mi355_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
+                         const float* coef, size_t n_slots, double rho, float grad_scale, void* stream) {
+  return launch_sam_lw_perturb(p, g, eps, n, items, n_items, tensors, n_tensors, coef, n_slots, rho, grad_scale, (hipStream_t)stream);
+}
+
 }  // extern "C"

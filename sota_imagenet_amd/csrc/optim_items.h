@@ -1,4 +1,4 @@
-// optim_items.h — the work-item table that the kernels of optim_lw.hip and optim_sam.hip walk: its record and the test every kernel makes before
+// optim_items.h — the work-item table that the kernels of optim_lw.hip, optim_sam.hip and optim_sam_lw.hip walk: its record and the test every kernel makes before
 // it touches memory through one.
 #pragma once
 #include <cstddef>

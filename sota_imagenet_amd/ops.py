@@ -529,6 +529,69 @@ def sam_restore(p, eps, items, n_tensors):
     check(_L().mi355_sam_restore(ptr(p), ptr(eps), n, ptr(items), items.shape[0], int(n_tensors), cur_stream()))
 
 
+# ---- the SAM callback of the reference (include/mi355rn.h, csrc/optim_sam_lw.hip): one pair of norms per slot -----------------------------------
+SAM_THREADS_PER_PIECE = 64  # one wave per piece: profiles/sam_lw_step.json
+
+
+def _sam_partial(name, partial, entries):
+    _need_cuda(partial)
+    if partial.dtype != torch.float64 or partial.numel() != 2 * entries or not partial.is_contiguous():
+        raise ValueError(f"{name}: partial must hold {entries} contiguous pairs of float64, got {partial.dtype} with {partial.numel()} elements")
+
+
+def _sam_slots(name, coef, n_slots=None):
+    _need_cuda(coef)
+    if coef.dtype != torch.float32 or coef.dim() != 1 or coef.numel() < 1 or not coef.is_contiguous() or n_slots not in (None, coef.numel()):
+        raise ValueError(f"{name}: coef must be a contiguous CUDA float32 tensor with one element per slot, got {coef.dtype} {tuple(coef.shape)}")
+
+
+def sam_lw_sumsq(p, g, items, partial, n_tensors, grad_scale=1.0):
+    """stage (a), the whole-tensor norms of sota_imagenet/callbacks.py:389-391: partial[i] = (sum of (g*grad_scale)^2, sum of p^2) over work item
+    i, in double; p, g: the flat fp32 arrays the offsets count from"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g)
+    _lw_table("items", items)
+    _sam_partial("sam_lw_sumsq", partial, items.shape[0])
+    check(_L().mi355_sam_lw_sumsq(ptr(p), ptr(g), n, ptr(items), items.shape[0], int(n_tensors), float(grad_scale), ptr(partial), cur_stream()))
+
+
+def sam_unit_sumsq(p, g, pieces, partial, n_slots, grad_scale=1.0, threads_per_piece=SAM_THREADS_PER_PIECE):
+    """stage (a'), the per-output-unit norms of callbacks.py:269-276, :386-387: the same pair of sums over every piece { off, len, slot } of
+    `pieces`, a piece cut from one unit at any element offset; one wave (threads_per_piece 64) or one workgroup (256) per piece"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g)
+    _lw_table("pieces", pieces)
+    _sam_partial("sam_unit_sumsq", partial, pieces.shape[0])
+    check(_L().mi355_sam_unit_sumsq(ptr(p), ptr(g), n, ptr(pieces), pieces.shape[0], int(n_slots), float(grad_scale), ptr(partial),
+                                    int(threads_per_piece), cur_stream()))
+
+
+def sam_lw_coef(partial, slots, coef, norms):
+    """stage (b), callbacks.py:386-395 for every slot: (Sg, Sp) = the slot's entries of partial[] in a fixed order; gn = max(sqrt(Sg), 1e-5),
+    wn = max(sqrt(Sp), 1e-3) in float32; coef[slot] = wn / gn, norms[slot] = (gn, wn).  slots: CUDA int32 [n_slots, 2] of (first, count)"""
+    _need_cuda(partial, slots, norms)
+    if partial.dtype != torch.float64 or partial.numel() < 2 or partial.numel() % 2 or not partial.is_contiguous():
+        raise ValueError("sam_lw_coef: partial must be a contiguous float64 tensor of pairs")
+    if slots.dtype != torch.int32 or slots.dim() != 2 or slots.shape[1] != 2 or slots.shape[0] < 1 or not slots.is_contiguous():
+        raise ValueError(f"sam_lw_coef: slots must be a contiguous CUDA int32 tensor [n, 2], got {slots.dtype} {tuple(slots.shape)}")
+    _sam_slots("sam_lw_coef", coef, slots.shape[0])
+    if norms.dtype != torch.float32 or norms.numel() != 2 * slots.shape[0] or not norms.is_contiguous():
+        raise ValueError("sam_lw_coef: norms must hold two contiguous float32 per slot")
+    check(_L().mi355_sam_lw_coef(ptr(partial), partial.numel() // 2, ptr(slots), slots.shape[0], ptr(coef), ptr(norms), cur_stream()))
+
+
+def sam_lw_perturb(p, g, eps, items, tensors, coef, rho, grad_scale=1.0):
+    """stage (c), callbacks.py:395-404: eps = (coef[slot] * (g*grad_scale)) * rho, p += eps over the work items of all tensors; the slot of an
+    element from its tensor's record { start, unit_len, slot0 } in `tensors`.  eps: a flat fp32 array laid out like p"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, eps=eps)
+    _lw_table("items", items)
+    _lw_table("tensors", tensors)
+    _sam_slots("sam_lw_perturb", coef)
+    check(_L().mi355_sam_lw_perturb(ptr(p), ptr(g), ptr(eps), n, ptr(items), items.shape[0], ptr(tensors), tensors.shape[0], ptr(coef),
+                                    coef.numel(), float(rho), float(grad_scale), cur_stream()))
+
+
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
 def blurpool_fwd(x):
     _need_cuda(x)
