@@ -7,10 +7,14 @@ SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip.
 """
 
+from collections import namedtuple
+
 import numpy as np
 import torch
 
+from . import ops
 from .fit_wrapper import Callback
+from .item_plan import flat_views, pack_records, place, storage_pairs
 
 
 class _DeviceMixer:
@@ -162,14 +166,22 @@ class CutmixMixup(Cutmix):
             self.state.input = self.mixup(*self.state.input)
 
 
+# one pair of parameter / gradient storage in a plan: the two storages as flat arrays over the pair's element range [lo, hi), the pair's eps array
+# over the same range and (first item, end item); SAM adds the pair's part of the reduction tables: (first piece, end piece), (first whole-tensor
+# item, end) and its first entry of the partial sums (its pieces, then its whole-tensor items)
+_Seg = namedtuple("_Seg", "p g eps items")
+_SamSeg = namedtuple("_SamSeg", _Seg._fields + ("pieces", "whole", "partial0"))
+
+
 class _SecondPass(Callback):
-    """what SAMOriginal and SAM share: which parameters fit the flat kernels, one launch set per pair of parameter / gradient storage with an
-    eps array of its own, the second forward / backward on the same batch, and the way back (mi355_sam_restore)"""
+    """what SAMOriginal and SAM share: the plan built from a parameter list under item_plan's placement rule (build_plan), one launch set per
+    pair of parameter / gradient storage with an eps array of its own, the re-plan test, the second forward / backward on the same batch, and the
+    way back (mi355_sam_restore)"""
 
     def __init__(self):
         super().__init__()
         self._key = None
-        self._segs = []     # per storage pair: (parameter slice, gradient slice, eps slice, first item, end item, ...)
+        self._segs = []     # per storage pair: a _Seg / _SamSeg
         self._eps = []      # per storage pair: the eps array, indexed like the storage
         self.forwards = 0   # second forwards made so far
 
@@ -184,67 +196,39 @@ class _SecondPass(Callback):
             raise NotImplementedError(f"{type(self).__name__}: accumulate_steps != 1 is not supported (the second pass would discard the "
                                       "accumulated micro-gradients)")
 
-    @classmethod
-    def _entries(cls, params):
-        """[(param base, grad base, first elem, numel, param)] of the parameters with a gradient: the rules of optim._FlatOptimizer._entries"""
-        from .optim import _dense_range
-
-        name = cls.__name__
-        entries = []
-        for p in params:
-            if not (p.is_cuda and p.dtype == torch.float32 and p.grad.is_cuda and p.grad.dtype == torch.float32):
-                raise RuntimeError(f"{name}: parameters and gradients must be CUDA fp32 tensors (no CPU fallback on the hot path)")
-            rp, rg = _dense_range(p.data), _dense_range(p.grad)
-            if rp is None or rg is None or rp[1:] != rg[1:]:
-                raise RuntimeError(f"{name}: parameter and gradient must be dense and share their flat offset")
-            if (rp[1] * 4) % 16 or (rp[0] + rp[1] * 4) % 16 or (rg[0] + rg[1] * 4) % 16:
-                raise RuntimeError(f"{name}: flat range not 16-byte aligned")
-            entries.append((rp[0], rg[0], rp[1], rp[2], p))
-        if any(e[4].device != entries[0][4].device for e in entries):
-            raise RuntimeError(f"{name}: all parameters must live on one device (the norm is taken there)")
-        return entries
-
     def _plan_changed(self, params):
         """True at the first perturbed step and whenever the parameters or their addresses changed since the plan was built"""
         key = tuple((id(p), p.data_ptr(), p.grad.data_ptr(), p.numel()) for p in params)
         changed, self._key = key != self._key, key
         return changed
 
-    @staticmethod
-    def _table(records, dev):
-        """16-byte records (int64, int32, int32) as the [n, 2] int64 tensor the ops wrappers take"""
-        rec = np.zeros(len(records), dtype=[("a", "<i8"), ("b", "<i4"), ("c", "<i4")])
-        if records:
-            a, b, c = zip(*records)
-            rec["a"], rec["b"], rec["c"] = a, b, c
-        return torch.from_numpy(rec.view(np.int64).reshape(-1, 2)).to(dev)
+    _table = staticmethod(pack_records)  # (records, device): the packer under the name earlier callers of the callbacks know
 
-    def _storage_pairs(self, entries, pairs):
-        """per pair (lo, hi, ..., tensor indices) of a plan: the parameter and gradient storage as flat arrays over [lo, hi) and an eps array
-        indexed like the storage (eps_flat lines up with a model's flat array); fills _eps, returns [(parameters, gradients, eps slice)]"""
-        dev = entries[0][4].device
-        self._eps, out = [], []
-        for lo, hi, *_, ts in pairs:
-            p0 = entries[ts[0]][4]
-            fp = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.data.untyped_storage(), lo, (hi - lo,))
-            fg = torch.empty(0, dtype=torch.float32, device=dev).set_(p0.grad.untyped_storage(), lo, (hi - lo,))
-            eps = torch.zeros(hi, dtype=torch.float32, device=dev)
-            self._eps.append(eps)
-            out.append((fp, fg, eps[lo:hi]))
-        return out
+    def build_plan(self, params):
+        """the plan for `params` (parameters that all have a gradient, in param-group order): the tables on the device and one segment per
+        storage pair.  Anything item_plan.place refuses raises RuntimeError."""
+        entries = place(params, type(self).__name__, aligned=True, one_device=True)
+        self._eps = []
+        self._segs = self._build(entries, entries[0][4].device, ops.lw_item_elems())
+
+    def _pair_views(self, p, lo, hi):
+        """the storages of p and of its gradient as flat arrays over [lo, hi) and a new eps array for the pair, indexed like the storage (eps_flat
+        lines up with a model's flat array): (parameters, gradients, eps slice)"""
+        eps = torch.zeros(hi, dtype=torch.float32, device=p.device)
+        self._eps.append(eps)
+        return (*flat_views(p, lo, hi), eps[lo:hi])
 
     def _second_pass(self, n_tensors):
         """zero_grad, a second forward / backward at the perturbed parameters on the same (already mixed) batch, then p -= eps"""
-        from . import ops
-
         self.state.optimizer.zero_grad()  # (with an attached flat model: marks its gradients clean, the second backward overwrites them)
         with torch.enable_grad():
             data, target = self.state.input
             loss_second = self.state.criterion(self.state.model(data), target)
             loss_second.backward()
         self.forwards += 1
-        for fp, fg, fe, i0, i1, *_ in self._segs:
-            ops.sam_restore(fp, fe, self._items[i0:i1], n_tensors)
+        for seg in self._segs:
+            i0, i1 = seg.items
+            ops.sam_restore(seg.p, seg.eps, self._items[i0:i1], n_tensors)
 
 
 class SAMOriginal(_SecondPass):
@@ -259,8 +243,8 @@ class SAMOriginal(_SecondPass):
     The four stages are HIP kernels over the flat arrays (csrc/optim_sam.hip) on the current stream; nothing is read back in a step.  The
     plan is built at the first non-skipped step from optimizer.param_groups under the rules of the native optimizers (CUDA fp32, dense,
     parameter and gradient at the same 16-byte aligned flat offset; one launch set per pair of parameter / gradient storage; the work items
-    of optim.lw_plan_items) and rebuilt when the parameters or their addresses change.  There is no CPU fallback: parameters that do not
-    fit raise.  `norm` and `scale` are 1-element device tensors holding the last step's values, `eps_flat` the last perturbation: one
+    of item_plan.py, where the plan's host side lives) and rebuilt when the parameters or their addresses change.  There is no CPU fallback:
+    parameters that do not fit raise.  `norm` and `scale` are 1-element device tensors holding the last step's values, `eps_flat` the last perturbation: one
     float32 array per storage pair indexed like the storage itself (the array itself when there is one pair, zero outside the parameters).
 
     As in the reference the second forward runs through state.model in training mode: a data-parallel wrapper reduces the second gradient
@@ -289,39 +273,22 @@ class SAMOriginal(_SecondPass):
     @staticmethod
     def plan_tables(tensors, W):
         """the host side of a plan.  tensors: [(param base, grad base, first elem, numel, ndim)] in param-group order; W: ops.lw_item_elems().
-        Returns (items, kind, pairs): items = [(first element relative to its pair's range, length, tensor index)] from optim.lw_plan_items,
-        storage pair by storage pair; kind[tensor] = 1 for ndim > 1; pairs = [(lo, hi, first item, end item, tensor indices)], one per pair of
-        parameter / gradient storage, [lo, hi) the element range of the storage its tensors span"""
-        from .optim import lw_plan_items
+        Returns (items, kind, pairs): items and pairs = [(lo, hi, first item, end item, tensor indices)] from item_plan.storage_pairs — items =
+        [(first element relative to its pair's range, length, tensor index)], storage pair by storage pair, [lo, hi) the element range of the
+        storage a pair's tensors span; kind[tensor] = 1 for ndim > 1"""
+        items, _, pairs = storage_pairs(tensors, W)
+        return items, [int(t[4] > 1) for t in tensors], pairs
 
-        pairs = {}  # (param base, grad base) -> [lo, hi, tensor indices]
-        for t, (pb, gb, off, n, _) in enumerate(tensors):
-            r = pairs.setdefault((pb, gb), [off, off + n, []])
-            r[0], r[1] = min(r[0], off), max(r[1], off + n)
-            r[2].append(t)
-        order = [t for r in pairs.values() for t in r[2]]  # table order; the tensor index of an item stays the index into `tensors`
-        lo_of = {t: r[0] for r in pairs.values() for t in r[2]}
-        items, spans = lw_plan_items([(tensors[t][2] - lo_of[t], tensors[t][3]) for t in order], W)
-        items = [(o, ln, order[j]) for o, ln, j in items]
-        span_of = {order[j]: spans[j] for j in range(len(order))}
-        out = [(lo, hi, span_of[ts[0]][0], span_of[ts[-1]][0] + span_of[ts[-1]][1], ts) for lo, hi, ts in pairs.values()]
-        return items, [int(t[4] > 1) for t in tensors], out
-
-    def _build_plan(self, entries):
-        from . import ops
-
-        dev = entries[0][4].device
-        items, kind, pairs = self.plan_tables([(pb, gb, off, n, p.ndim) for pb, gb, off, n, p in entries], ops.lw_item_elems())
-        self._items = self._table(items, dev)
+    def _build(self, entries, dev, W):
+        items, kind, pairs = self.plan_tables([(pb, gb, off, n, p.ndim) for pb, gb, off, n, p in entries], W)
+        self._items = pack_records(items, dev)
         self._kind = torch.tensor(kind, dtype=torch.int32, device=dev)
         self._partial = torch.zeros(len(items), dtype=torch.float64, device=dev)
         self._out = torch.zeros(2, dtype=torch.float32, device=dev)
-        self._segs = [(fp, fg, fe, i0, i1) for (fp, fg, fe), (lo, hi, i0, i1, ts) in zip(self._storage_pairs(entries, pairs), pairs)]
+        return [_Seg(*self._pair_views(entries[ts[0]][4], lo, hi), (i0, i1)) for lo, hi, i0, i1, ts in pairs]
 
     @torch.no_grad()
     def on_after_backward(self):
-        from . import ops
-
         opt = self.state.optimizer
         if len(opt.state) == 0:  # the first step: the optimizer creates its state from a plain step
             return
@@ -329,13 +296,15 @@ class SAMOriginal(_SecondPass):
         if not params:
             return
         if self._plan_changed(params):  # the first non-skipped step, or the parameters / their addresses changed
-            self._build_plan(self._entries(params))
+            self.build_plan(params)
         gs = float(getattr(opt, "grad_scale", 1.0))
-        for fp, fg, fe, i0, i1 in self._segs:
-            ops.sam_sumsq(fp, fg, self._items[i0:i1], self._kind, self._partial[i0:i1], self.eta, grad_scale=gs)
+        for seg in self._segs:
+            i0, i1 = seg.items
+            ops.sam_sumsq(seg.p, seg.g, self._items[i0:i1], self._kind, self._partial[i0:i1], self.eta, grad_scale=gs)
         ops.sam_scale(self._partial, self.rho, self._out)
-        for fp, fg, fe, i0, i1 in self._segs:
-            ops.sam_perturb(fp, fg, fe, self._items[i0:i1], self._kind, self._out, self.eta, grad_scale=gs)
+        for seg in self._segs:
+            i0, i1 = seg.items
+            ops.sam_perturb(seg.p, seg.g, seg.eps, self._items[i0:i1], self._kind, self._out, self.eta, grad_scale=gs)
         self._second_pass(self._kind.numel())
 
 
@@ -399,7 +368,7 @@ class SAM(_SecondPass):
     def plan_tables(tensors, W):
         """the host side of a plan.  tensors: [(param base, grad base, first elem, numel, unit_len)] in param-group order, unit_len = numel for
         a whole-tensor slot, less for a tensor taken unit by unit; W: ops.lw_item_elems().  Returns a dict:
-          items    SAMOriginal.plan_tables' work items of ALL tensors (the perturbation and the restore walk them)
+          items    item_plan.storage_pairs' work items of ALL tensors (the perturbation and the restore walk them)
           tensors  [(start relative to its pair's range, unit_len, slot0)] per tensor; slots are numbered tensor by tensor
           pieces   [(first element relative to the pair's range, length <= W, slot)]: every unit of the unit-wise tensors, cut at multiples of
                    W from the unit's start
@@ -407,7 +376,7 @@ class SAM(_SecondPass):
           slots    [(first, count)] per slot: its consecutive entries of the partial sums, which are laid out pair by pair, a pair's pieces
                    before its whole-tensor items
           pairs    [(lo, hi, first item, end item, (first piece, end piece), (first whole item, end), first partial entry, tensor indices)]"""
-        items, _, pairs0 = SAMOriginal.plan_tables([(pb, gb, off, n, 1) for pb, gb, off, n, _ in tensors], W)
+        items, _, pairs0 = storage_pairs(tensors, W)
         slot0, n_slots = [], 0
         for _, _, _, n, u in tensors:
             if u < 1 or n % u or n >= 1 << 31:
@@ -438,42 +407,37 @@ class SAM(_SecondPass):
             pairs.append((lo, hi, i0, i1, (pa, len(pieces)), (wa, len(whole)), k0, ts))
         return dict(items=items, tensors=trec, pieces=pieces, whole=whole, slots=slots, pairs=pairs)
 
-    def _build_plan(self, entries):
-        from . import ops
-
-        dev = entries[0][4].device
-        tab = self.plan_tables([(pb, gb, off, n, self.unit_len(p.shape, p.stride(), self.unitwise)) for pb, gb, off, n, p in entries],
-                               ops.lw_item_elems())
-        self._items, self._tensors = self._table(tab["items"], dev), self._table(tab["tensors"], dev)
-        self._pieces, self._whole = self._table(tab["pieces"], dev), self._table(tab["whole"], dev)
+    def _build(self, entries, dev, W):
+        tab = self.plan_tables([(pb, gb, off, n, self.unit_len(p.shape, p.stride(), self.unitwise)) for pb, gb, off, n, p in entries], W)
+        self._items, self._tensors = pack_records(tab["items"], dev), pack_records(tab["tensors"], dev)
+        self._pieces, self._whole = pack_records(tab["pieces"], dev), pack_records(tab["whole"], dev)
         n_slots = len(tab["slots"])
         self._slots = torch.tensor(tab["slots"], dtype=torch.int32, device=dev)
         self._partial = torch.zeros(2 * (len(tab["pieces"]) + len(tab["whole"])), dtype=torch.float64, device=dev)
         self._coef = torch.zeros(n_slots, dtype=torch.float32, device=dev)
         self._norms = torch.zeros(n_slots, 2, dtype=torch.float32, device=dev)
         self.slot_ranges = [(s0, e[3] // u) for (_, u, s0), e in zip(tab["tensors"], entries)]
-        self._segs = [(fp, fg, fe, i0, i1, pc, wh, k0) for (fp, fg, fe), (lo, hi, i0, i1, pc, wh, k0, ts)
-                      in zip(self._storage_pairs(entries, tab["pairs"]), tab["pairs"])]
+        return [_SamSeg(*self._pair_views(entries[ts[0]][4], lo, hi), (i0, i1), pc, wh, k0) for lo, hi, i0, i1, pc, wh, k0, ts in tab["pairs"]]
 
     @torch.no_grad()
     def on_after_backward(self):
-        from . import ops
-
         opt = self.state.optimizer
         params = [p for group in opt.param_groups for p in group["params"] if p.grad is not None]
         if not params:
             return
         if self._plan_changed(params):  # the first step, or the parameters / their addresses changed
-            self._build_plan(self._entries(params))
+            self.build_plan(params)
         gs = float(getattr(opt, "grad_scale", 1.0))
         nt, ns = self._tensors.shape[0], self._coef.numel()
-        for fp, fg, fe, i0, i1, (pa, pb), (wa, wb), k0 in self._segs:
+        for seg in self._segs:
+            (pa, pb), (wa, wb), k0 = seg.pieces, seg.whole, seg.partial0
             k1 = k0 + pb - pa
             if pb > pa:
-                ops.sam_unit_sumsq(fp, fg, self._pieces[pa:pb], self._partial[2 * k0:2 * k1], ns, grad_scale=gs)
+                ops.sam_unit_sumsq(seg.p, seg.g, self._pieces[pa:pb], self._partial[2 * k0:2 * k1], ns, grad_scale=gs)
             if wb > wa:
-                ops.sam_lw_sumsq(fp, fg, self._whole[wa:wb], self._partial[2 * k1:2 * (k1 + wb - wa)], nt, grad_scale=gs)
+                ops.sam_lw_sumsq(seg.p, seg.g, self._whole[wa:wb], self._partial[2 * k1:2 * (k1 + wb - wa)], nt, grad_scale=gs)
         ops.sam_lw_coef(self._partial, self._slots, self._coef, self._norms)
-        for fp, fg, fe, i0, i1, *_ in self._segs:
-            ops.sam_lw_perturb(fp, fg, fe, self._items[i0:i1], self._tensors, self._coef, self.rho, grad_scale=gs)
+        for seg in self._segs:
+            i0, i1 = seg.items
+            ops.sam_lw_perturb(seg.p, seg.g, seg.eps, self._items[i0:i1], self._tensors, self._coef, self.rho, grad_scale=gs)
         self._second_pass(nt)

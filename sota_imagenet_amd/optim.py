@@ -12,28 +12,18 @@ zero_grad, re-planning after load_state_dict); their per-parameter state is laid
 MADGRAD and AdaiS are the reference's own optimizers (sota_imagenet/optimizers.py) on the same planner: MADGRAD is one launch per range,
 AdaiS three stages (moments + partial sums, the global mean, the update) because its momentum depends on a statistic of all parameters.
 NovogradApex, MyNovograd, AdamLayerwise and MyAdai (the reference's layer-wise optimizers) use one statistic PER TENSOR: they do not merge ranges
-but cut every parameter's own range into work items (lw_plan_items) and run three stages over that table (csrc/optim_lw.hip).
+but cut every parameter's own range into work items and run three stages over that table (csrc/optim_lw.hip).  That plan — the placement rule,
+the storage pairs, the work items, the packed records — lives in item_plan.py, which the SAM callbacks build on as well.
 """
-import numpy as np
+from collections import namedtuple
+from itertools import groupby
+
 import torch
 from torch.optim import Optimizer
 
 from . import ops
-
-
-def _dense_range(t):
-    """(storage base ptr, first elem, numel) if `t` covers a dense memory range (any permutation of strides)."""
-    n = t.numel()
-    sizes_strides = sorted(zip(t.stride(), t.size()))
-    expect = 1
-    for st, sz in sizes_strides:
-        if sz == 1:
-            continue
-        if st != expect:
-            return None
-        expect *= sz
-    base = t.untyped_storage().data_ptr()
-    return base, (t.data_ptr() - base) // t.element_size(), n
+from .item_plan import TENSOR_FIELDS, dense_range, flat_views, pack_records, place, storage_pairs
+from .item_plan import plan_items as lw_plan_items  # noqa: F401  (the name its callers know)
 
 
 class _FlatOptimizer(Optimizer):
@@ -68,21 +58,12 @@ class _FlatOptimizer(Optimizer):
         self._ema = None
         self._plans = None
 
-    def _entries(self):
-        """[(param base, grad base, first elem, numel, group index, param)] of every parameter with a gradient, group by group"""
-        name = type(self).__name__
-        entries = []
-        for gi, group in enumerate(self.param_groups):
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not (p.is_cuda and p.dtype == torch.float32):
-                    raise RuntimeError(f"{name}: parameters must be CUDA fp32 tensors (no CPU fallback on the hot path)")
-                rp, rg = _dense_range(p.data), _dense_range(p.grad)
-                if rp is None or rg is None or rp[1:] != rg[1:]:
-                    raise RuntimeError(f"{name}: parameter and gradient must be dense and share their flat offset")
-                entries.append((rp[0], rg[0], rp[1], rp[2], gi, p))
-        return entries
+    def _entries(self, **rules):
+        """[(param base, grad base, first elem, numel, group index, param)] of every parameter with a gradient, group by group, under
+        item_plan.place's rule (rules: its options)"""
+        mine = [(gi, p) for gi, group in enumerate(self.param_groups) for p in group["params"] if p.grad is not None]
+        placed = place([p for _, p in mine], type(self).__name__, **rules)
+        return [(pb, gb, off, n, gi, p) for (pb, gb, off, n, p), (gi, _) in zip(placed, mine)]
 
     def _merged_ranges(self, split_key=None, bridge_padding=True):
         """[[param base, grad base, first elem, end elem, [params], group index]]: one entry per launch.  Parameters whose
@@ -101,7 +82,7 @@ class _FlatOptimizer(Optimizer):
             for q in mdl.parameters():
                 if id(q) in mine:
                     continue
-                r = _dense_range(q.data)
+                r = dense_range(q.data)
                 if r is not None:
                     barriers.setdefault(r[0], []).append((r[1], r[1] + r[2]))
         max_gap = (64 * 2048 if self._models else 64) if bridge_padding else 1
@@ -123,18 +104,10 @@ class _FlatOptimizer(Optimizer):
                 raise RuntimeError(f"{name}: flat range not 16-byte aligned")
         return merged
 
-    @staticmethod
-    def _flat_views(ps, b, e):
-        """the (parameter, gradient) slices [b, e) of the flat arrays the parameters ps live in"""
-        dev = ps[0].device
-        fp = torch.empty(0, dtype=torch.float32, device=dev).set_(ps[0].data.untyped_storage(), b, (e - b,))
-        fg = torch.empty(0, dtype=torch.float32, device=dev).set_(ps[0].grad.untyped_storage(), b, (e - b,))
-        return fp, fg
-
     def _state_view(self, flat, p, b, key):
         """state[p][key] := the view of the flat state array `flat` (starting at element b) that covers p; a tensor already there
         (loaded from a checkpoint, train.py:144, or kept across a re-plan) is carried over into it"""
-        r = _dense_range(p.data)
+        r = dense_range(p.data)
         view = torch.as_strided(flat, p.shape, p.stride(), r[1] - b)
         old = self.state[p].get(key)
         if old is not None:
@@ -143,7 +116,7 @@ class _FlatOptimizer(Optimizer):
 
     def _ema_slice(self, pb, b, e):
         if self._ema is not None:
-            r = _dense_range(self._ema[0])
+            r = dense_range(self._ema[0])
             if r is not None and r[0] == pb and r[1] <= b and e <= r[1] + r[2]:
                 return self._ema[1][b - r[1]: e - r[1]]
         return None
@@ -182,7 +155,7 @@ class SGD(_FlatOptimizer):
     def _build_plans(self):
         plans = [[] for _ in self.param_groups]
         for pb, gb, b, e, ps, gi in self._merged_ranges():
-            fp, fg = self._flat_views(ps, b, e)
+            fp, fg = flat_views(ps[0], b, e)
             fm = torch.zeros(e - b, dtype=torch.float32, device=fp.device)
             for p in ps:  # expose momentum buffers per parameter (state_dict compatibility)
                 self._state_view(fm, p, b, "momentum_buffer")
@@ -258,7 +231,7 @@ class Adam(_FlatOptimizer):
         planned = []
         bridge = all(float(g["eps"]) > 0.0 for g in self.param_groups)
         for pb, gb, b, e, ps, gi in self._merged_ranges(split_key=self._step_count, bridge_padding=bridge):
-            fp, fg = self._flat_views(ps, b, e)
+            fp, fg = flat_views(ps[0], b, e)
             fm = torch.zeros(e - b, dtype=torch.float32, device=fp.device)
             fv = torch.zeros(e - b, dtype=torch.float32, device=fp.device)
             t = self._step_count(ps[0])
@@ -338,7 +311,7 @@ class MADGRAD(_FlatOptimizer):
         # padding inside a range computes 0 / (cbrt(0) + eps): zeros stay zeros only for eps > 0
         bridge = all(float(g["eps"]) > 0.0 for g in self.param_groups)
         for pb, gb, b, e, ps, gi in self._merged_ranges(bridge_padding=bridge):
-            fp, fg = self._flat_views(ps, b, e)
+            fp, fg = flat_views(ps[0], b, e)
             fq, fs, fx = (torch.zeros(e - b, dtype=torch.float32, device=fp.device) for _ in range(3))
             for p in ps:
                 fresh = "grad_sum_sq" not in self.state[p]
@@ -411,7 +384,7 @@ class AdaiS(_FlatOptimizer):
         plans = [[] for _ in self.param_groups]
         planned, total, dev = [], 0, None
         for pb, gb, b, e, ps, gi in self._merged_ranges(split_key=self._step_count):
-            fp, fg = self._flat_views(ps, b, e)
+            fp, fg = flat_views(ps[0], b, e)
             if dev is not None and fp.device != dev:
                 raise RuntimeError("AdaiS: all parameters must live on one device (the mean is taken there)")
             dev = fp.device
@@ -467,22 +440,19 @@ class AdaiS(_FlatOptimizer):
         return loss
 
 
-def lw_plan_items(tensors, W):
-    """the work-item table of the layer-wise optimizers.  tensors: [(first element, numel)] in table order; returns (items, spans):
-    items = [(first element, length, tensor index)], every tensor's own range cut at multiples of W from its start (the cuts depend on numel
-    alone), the items of one tensor consecutive; spans = [(first item, item count)] per tensor.  Nothing outside a tensor's range — alignment
-    gaps, the FC padding — is ever covered."""
-    items, spans = [], []
-    for t, (off, n) in enumerate(tensors):
-        if n < 1:
-            raise ValueError(f"tensor {t}: numel={n} must be >= 1")
-        spans.append((len(items), (n + W - 1) // W))
-        items.extend((off + c, min(W, n - c), t) for c in range(0, n, W))
-    return items, spans
+def _runs(indices, keys):
+    """[(key, first index, last index)] of the runs of equal keys[index] among consecutive indices"""
+    return [(k, run[0], run[-1]) for k, run in ((k, list(run)) for k, run in groupby(indices, keys.__getitem__))]
+
+
+# one pair of parameter / gradient storage in a layer-wise plan: the two storages as flat arrays over the pair's element range [lo, hi), the first
+# moment of that range, the moving average's slice of it or None, (first item, end item), [(group index, first item, end item)] of the groups present
+_LwSeg = namedtuple("_LwSeg", "p g m ema items by_group")
 
 
 class _Layerwise(_FlatOptimizer):
-    """what NovogradApex, MyNovograd, AdamLayerwise and MyAdai share: the work-item plan and the three stages of csrc/optim_lw.hip —
+    """what NovogradApex, MyNovograd, AdamLayerwise and MyAdai share: the work-item plan (plan_tables, the pure host part on item_plan.py;
+    _build_plans adds what needs the device: one _LwSeg per storage pair) and the three stages of csrc/optim_lw.hip —
     (a) one lw_sumsq launch per (parameter storage, gradient storage) pair, (b) one lw_coef launch per param group, (c) one lw_update
     launch per param group (and storage pair) — 3 launches per step for a flat model in one group, 1 + 2 + 2 with filter_from_wd.
     The first moment is a view of a flat array as in the other native optimizers.  The second moment, which the reference keeps as a
@@ -504,72 +474,47 @@ class _Layerwise(_FlatOptimizer):
     def _wd_eps(self):
         return None
 
+    @staticmethod
+    def plan_tables(tensors, W):
+        """the host side of a plan.  tensors: [(param base, grad base, first elem, numel, group index)] in param-group order; W:
+        ops.lw_item_elems().  Returns a dict:
+          items    item_plan.storage_pairs' work items: storage pair by storage pair, inside it group by group; tensor index = index into `tensors`
+          tensors  [(first item, item count, numel)] per tensor: the records of lw_coef
+          pairs    [(lo, hi, first item, end item, [(group index, first item, end item)] of the groups present in the pair, tensor indices)]
+          groups   [(group index, first tensor, end tensor)] of the groups present: the tensors of a group are consecutive"""
+        items, spans, pairs = storage_pairs(tensors, W)
+        group_of = [t[4] for t in tensors]
+        return dict(items=items, tensors=[(first, count, float(t[3])) for (first, count), t in zip(spans, tensors)],
+                    pairs=[(lo, hi, i0, i1, [(gi, spans[a][0], sum(spans[b])) for gi, a, b in _runs(ts, group_of)], ts) for lo, hi, i0, i1, ts in pairs],
+                    groups=[(gi, a, b + 1) for gi, a, b in _runs(range(len(tensors)), group_of)])
+
     def _build_plans(self):
-        name = type(self).__name__
-        W = ops.lw_item_elems()
-        entries = self._entries()
+        entries = self._entries(aligned=True, one_device=True)
         self._planned = [e[5] for e in entries]
         self._segs, self._coefs = [], []
         if not entries:
             self._plans = []
             return
-        dev = entries[0][5].device
-        for pb, gb, off, n, gi, p in entries:
-            if p.device != dev:
-                raise RuntimeError(f"{name}: all parameters must live on one device")
-            if (off * 4) % 16 or p.data_ptr() % 16 or p.grad.data_ptr() % 16:
-                raise RuntimeError(f"{name}: flat range not 16-byte aligned")
-        pairs = {}  # (param base, grad base) -> [lo, hi, entry indices]
-        for t, (pb, gb, off, n, gi, p) in enumerate(entries):
-            r = pairs.setdefault((pb, gb), [off, off + n, []])
-            r[0], r[1] = min(r[0], off), max(r[1], off + n)
-            r[2].append(t)
-        # table order: storage pair by storage pair, inside it group by group (entries are in group order); tensor index = entry index
-        order = [t for r in pairs.values() for t in r[2]]
-        lo_of = {t: r[0] for r in pairs.values() for t in r[2]}
-        items, spans = lw_plan_items([(entries[t][2] - lo_of[t], entries[t][3]) for t in order], W)
-        rec = np.zeros(len(items), dtype=[("off", "<i8"), ("len", "<i4"), ("t", "<i4")])
-        ten = np.zeros(len(entries), dtype=[("first", "<i4"), ("count", "<i4"), ("numel", "<f8")])
-        for k, (o, ln, j) in enumerate(items):
-            rec[k] = (o, ln, order[j])
-        for j, (first, count) in enumerate(spans):
-            ten[order[j]] = (first, count, float(entries[order[j]][3]))
-        self._items = torch.from_numpy(rec.view(np.int64).reshape(-1, 2)).to(dev)
-        self._tensors = torch.from_numpy(ten.view(np.int64).reshape(-1, 2)).to(dev)
-        nt = len(entries)
-        self._partial = torch.zeros(len(items), dtype=torch.float64, device=dev)
+        dev, nt = entries[0][5].device, len(entries)
+        tab = self.plan_tables([e[:5] for e in entries], ops.lw_item_elems())
+        self._items = pack_records(tab["items"], dev)
+        self._tensors = pack_records(tab["tensors"], dev, TENSOR_FIELDS)
+        self._partial = torch.zeros(len(tab["items"]), dtype=torch.float64, device=dev)
         self._sums = torch.zeros(nt, dtype=torch.float64, device=dev)   # S per tensor of the last step (tensor order = group by group)
         self._coef = torch.zeros(nt, 4, dtype=torch.float32, device=dev)
         self._v = self._make_v(entries, dev)
-        span_of = {order[j]: spans[j] for j in range(nt)}
-        ema_slices = []
-        for (pb, gb), (lo, hi, ts) in pairs.items():
+        self._coefs = tab["groups"]
+        for lo, hi, i0, i1, by_group, ts in tab["pairs"]:
             ps = [entries[t][5] for t in ts]
-            fp, fg = self._flat_views(ps, lo, hi)
+            fp, fg = flat_views(ps[0], lo, hi)
             fm = torch.zeros(hi - lo, dtype=torch.float32, device=dev)
             for p in ps:
                 fresh = self._m_key not in self.state[p]
                 self._state_view(fm, p, lo, self._m_key)
                 if fresh:
                     self.state[p].setdefault("step", 0)
-            fe = self._ema_slice(pb, lo, hi)
-            ema_slices.append(fe)
-            i0, i1 = span_of[ts[0]][0], span_of[ts[-1]][0] + span_of[ts[-1]][1]
-            by_group = []  # (group index, first item, end item) of the groups present in this pair
-            for t in ts:
-                gi, (first, count) = entries[t][4], span_of[t]
-                if by_group and by_group[-1][0] == gi:
-                    by_group[-1][2] = first + count
-                else:
-                    by_group.append([gi, first, first + count])
-            self._segs.append((fp, fg, fm, fe, i0, i1, by_group))
-        self._check_ema(ema_slices)
-        t0 = 0
-        for gi in range(len(self.param_groups)):  # the tensors of a group are consecutive in tensor order
-            cnt = sum(1 for e in entries if e[4] == gi)
-            if cnt:
-                self._coefs.append((gi, t0, t0 + cnt))
-            t0 += cnt
+            self._segs.append(_LwSeg(fp, fg, fm, self._ema_slice(entries[ts[0]][0], lo, hi), (i0, i1), by_group))
+        self._check_ema([seg.ema for seg in self._segs])
         self._plans = self._segs
 
     def _make_v(self, entries, dev):
@@ -600,17 +545,18 @@ class _Layerwise(_FlatOptimizer):
             return loss
         gs = float(self.grad_scale)
         nt = self._sums.numel()
-        for fp, fg, fm, fe, i0, i1, _ in self._segs:
-            ops.lw_sumsq(fp if self._param_stat else fg, self._items[i0:i1], self._partial[i0:i1], nt, scale=1.0 if self._param_stat else gs)
+        for seg in self._segs:
+            i0, i1 = seg.items
+            ops.lw_sumsq(seg.p if self._param_stat else seg.g, self._items[i0:i1], self._partial[i0:i1], nt, scale=1.0 if self._param_stat else gs)
         for gi, t0, t1 in self._coefs:
             group = self.param_groups[gi]
             flags, b1, b2, eps = self._coef_args(group)
             ops.lw_coef(self._rule, flags, self._partial, self._tensors[t0:t1], self._v[t0:t1], self._coef[t0:t1], self._sums[t0:t1], b1, b2, eps,
                         float(group["lr"]), float(group["weight_decay"]), mean=mean)
-        for fp, fg, fm, fe, _, _, by_group in self._segs:
-            for gi, i0, i1 in by_group:
-                ops.lw_update(self._rule, fp, fg, fm, self._items[i0:i1], self._coef, float(self.param_groups[gi]["lr"]), wd_eps=self._wd_eps(),
-                              grad_scale=gs, ema=fe, ema_decay=self._ema[2] if fe is not None else 0.0)
+        for seg in self._segs:
+            for gi, i0, i1 in seg.by_group:
+                ops.lw_update(self._rule, seg.p, seg.g, seg.m, self._items[i0:i1], self._coef, float(self.param_groups[gi]["lr"]),
+                              wd_eps=self._wd_eps(), grad_scale=gs, ema=seg.ema, ema_decay=self._ema[2] if seg.ema is not None else 0.0)
         for p in self._planned:
             self.state[p]["step"] += 1
         return loss

@@ -1,6 +1,6 @@
 """What tests/test_sam_lw_host.py and tests/test_sam_lw_gpu.py share: the fixture recorded from the reference's own SAM callback
 (tests/golden/sam_lw_ref_trajectories.npz, written by tests/golden/make_sam_lw_golden.py), the rules of the callback as this project documents
-them (include/mi355rn.h) restated in torch on the CPU in a chosen dtype, and the layout helpers of the GPU tests."""
+them (include/mi355rn.h) restated in torch on the CPU in a chosen dtype.  (The layout helpers: tests/plan_common.py.)"""
 import importlib.util
 import json
 import os
@@ -119,20 +119,3 @@ def restate_fixture(fx, dtype):
         _optimizer_step(fx.cls, fx.kw, st, ps, g, group_of, fx.lrs[k], dtype)
         out.append((torch.cat([r[1] for r in res]), torch.cat([r[2] for r in res]), flat(eps), flat(pert), flat(ps).clone(), 2))
     return out
-
-
-def layout(sizes, order=None):
-    """64-element aligned offsets of the tensors, laid out in `order`; returns (offsets by tensor, total with a trailing gap)"""
-    offs, n = [0] * len(sizes), 0
-    for i in (order if order is not None else range(len(sizes))):
-        offs[i] = n
-        n += (sizes[i] + 63) // 64 * 64
-    return offs, n + 64
-
-
-def resnet50_table():
-    """[(name, flat offset, shape)] of the ResNet-50 parameters and the flat array's length, from the recorded layout"""
-    with open(os.path.join(HERE, "golden", "flat_layouts.json")) as fh:
-        lay = json.load(fh)
-    table = lay["tables"][lay["configs"]["resnet50/fp32"]["table"]]
-    return [(name, off, tuple(shape)) for name, kind, off, nd, shape in table if kind == 0], lay["configs"]["resnet50/fp32"]["flat_param_elems"]

@@ -17,19 +17,11 @@ import pytest
 import torch
 
 from layerwise_common import CASES, FACTOR, U, Fixture, Restated
+from plan_common import layout as _layout
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float("nan")
-
-
-def _layout(sizes, order=None):
-    """64-element aligned offsets of the tensors, laid out in `order`; returns (offsets by tensor, total)"""
-    offs, n = [0] * len(sizes), 0
-    for i in (order if order is not None else range(len(sizes))):
-        offs[i] = n
-        n += (sizes[i] + 63) // 64 * 64
-    return offs, n + 64  # a trailing gap as well
 
 
 def _flat_params(sizes, shapes, values, dev, order=None, separate=False):

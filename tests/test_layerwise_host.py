@@ -4,18 +4,16 @@ tests/golden/layerwise_ref_trajectories.npz; the work-item planner covers every 
 reference's targets resolve, the constructors keep the reference's domains, the flags that are not on the hot path raise, the recipe
 configs compose, and the C-ABI entries refuse bad arguments before any launch."""
 import ctypes
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from layerwise_common import CASES, Fixture, restate_fixture
+from plan_common import resnet50_params as _resnet50_params
 from sota_imagenet_amd import config as C
 from sota_imagenet_amd import native
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 CLASSES = ("NovogradApex", "MyNovograd", "AdamLayerwise", "MyAdai")
 
 
@@ -35,14 +33,6 @@ def test_float64_restatement_reproduces_the_reference_trajectory(case):
         assert (fx.beta1 == 0).any() and ((fx.beta1 > 0) & (fx.beta1 < hi)).any()  # the regimes the generator asserted
         assert (fx.beta1 == hi).any() == (case == "myadai_alt")
         assert list(fx.v0) == [fx.hyper.get("ema_norm_init", 1e-3)] * 5  # the state's second moment is still the constant it was created with
-
-
-def _resnet50_params():
-    with open(os.path.join(HERE, "golden", "flat_layouts.json")) as fh:
-        lay = json.load(fh)
-    table = lay["tables"][lay["configs"]["resnet50/fp32"]["table"]]
-    params = [(off, int(np.prod(shape))) for name, kind, off, nd, shape in table if kind == 0]
-    return params, lay["configs"]["resnet50/fp32"]["flat_param_elems"]
 
 
 def test_item_planner_covers_every_parameter_element_once_and_no_padding():

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from plan_common import layout as _layout
+from plan_common import table
 from sam_common import CASES, NORM_FLOOR, U, Fixture, generator
 
 pytestmark = pytest.mark.gpu
@@ -20,15 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float("nan")
 SENTINEL = 123.0
 RHO, ETA = 0.5, 0.01
-
-
-def _layout(sizes, order=None):
-    """64-element aligned offsets of the tensors, laid out in `order`; returns (offsets by tensor, total)"""
-    offs, n = [0] * len(sizes), 0
-    for i in (order if order is not None else range(len(sizes))):
-        offs[i] = n
-        n += (sizes[i] + 63) // 64 * 64
-    return offs, n + 64  # a trailing gap as well
 
 
 # ---- the kernels, driven directly --------------------------------------------------------------------------------------------------------
@@ -58,11 +51,8 @@ class _Arrays:
         tensors = [(self.fp[self.where[i][0]].data_ptr(), self.fg[self.where[i][0]].data_ptr(), self.where[i][1], sizes[i], 1 + kinds[i]) for i in order]
         items, kind, self.pairs = SAMOriginal.plan_tables(tensors, ops.lw_item_elems())
         assert kind == [kinds[i] for i in order] and len(self.pairs) == nbuf
-        rec = np.zeros(len(items), dtype=[("off", "<i8"), ("len", "<i4"), ("t", "<i4")])
-        for k, it in enumerate(items):
-            rec[k] = it
         self.order = order
-        self.items = torch.from_numpy(rec.view(np.int64).reshape(-1, 2)).to(dev)
+        self.items = table(items, dev)
         self.kind = torch.tensor(kind, dtype=torch.int32, device=dev)
         self.partial = torch.full((len(items),), NAN, dtype=torch.float64, device=dev)
         self.out = torch.full((2,), NAN, device=dev)

@@ -3,19 +3,17 @@ compose, accumulate_steps != 1 is refused, the documented rules — restated in 
 the reference's own callback recorded in tests/golden/sam_ref_trajectories.npz, the plan marks the ndim > 1 tensors as weights and covers every
 parameter element exactly once, and the four C-ABI entries refuse bad arguments before any launch."""
 import ctypes
-import json
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from plan_common import resnet50_table as _resnet50_table
 from sam_common import CASES, NORM_FLOOR, Fixture, restate_fixture
 from sota_imagenet_amd import config as C
 from sota_imagenet_amd import native
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def test_reference_targets_resolve_to_the_native_callback():
@@ -105,13 +103,6 @@ def test_float64_restatement_reproduces_the_reference_trajectory(case):
     if case == "clamp":
         assert list(fx.norm[1:]) == [NORM_FLOOR] * 3
     assert (got[-1][3] - fx.p0.double()).abs().max().item() > (1e-9 if case == "clamp" else 1e-3)  # the steps moved the parameters
-
-
-def _resnet50_table():
-    with open(os.path.join(HERE, "golden", "flat_layouts.json")) as fh:
-        lay = json.load(fh)
-    table = lay["tables"][lay["configs"]["resnet50/fp32"]["table"]]
-    return [(name, off, tuple(shape)) for name, kind, off, nd, shape in table if kind == 0], lay["configs"]["resnet50/fp32"]["flat_param_elems"]
 
 
 def test_plan_marks_the_weights_and_covers_every_element_once():

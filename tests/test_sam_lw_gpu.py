@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from sam_lw_common import CASES, U, Fixture, generator, layout
+from plan_common import layout, table
+from sam_lw_common import CASES, U, Fixture, generator
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,8 +54,8 @@ class _Arrays:
         self.tab = tab = SAM.plan_tables(tensors, ops.lw_item_elems())
         assert len(tab["pairs"]) == nbuf
         self.slot0 = {i: tab["tensors"][j][2] for j, i in enumerate(order)}
-        self.items, self.tensors = SAM._table(tab["items"], dev), SAM._table(tab["tensors"], dev)
-        self.pieces, self.whole = SAM._table(tab["pieces"], dev), SAM._table(tab["whole"], dev)
+        self.items, self.tensors = table(tab["items"], dev), table(tab["tensors"], dev)
+        self.pieces, self.whole = table(tab["pieces"], dev), table(tab["whole"], dev)
         self.slots = torch.tensor(tab["slots"], dtype=torch.int32, device=dev)
         ns = len(tab["slots"])
         self.partial = torch.full((2 * (len(tab["pieces"]) + len(tab["whole"])),), NAN, dtype=torch.float64, device=dev)

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from sam_lw_common import CASES, GN_FLOOR, WN_FLOOR, Fixture, resnet50_table, restate_fixture
+from plan_common import resnet50_table
+from sam_lw_common import CASES, GN_FLOOR, WN_FLOOR, Fixture, restate_fixture
 from sota_imagenet_amd import config as C
 from sota_imagenet_amd import native
 

@@ -67,8 +67,9 @@ def main(argv=None):
 
     def stage_a(o):
         def f():
-            for fp, fg, fm, fe, i0, i1, _ in o._segs:
-                ops.lw_sumsq(fp if o._param_stat else fg, o._items[i0:i1], o._partial[i0:i1], o._sums.numel())
+            for seg in o._segs:
+                i0, i1 = seg.items
+                ops.lw_sumsq(seg.p if o._param_stat else seg.g, o._items[i0:i1], o._partial[i0:i1], o._sums.numel())
         return f
 
     def stage_b(o):
@@ -82,9 +83,9 @@ def main(argv=None):
 
     def stage_c(o):
         def f():
-            for fp, fg, fm, fe, _, _, by_group in o._segs:
-                for gi, i0, i1 in by_group:
-                    ops.lw_update(o._rule, fp, fg, fm, o._items[i0:i1], o._coef, 1e-3, wd_eps=o._wd_eps(), ema=fe, ema_decay=0.9993)
+            for seg in o._segs:
+                for gi, i0, i1 in seg.by_group:
+                    ops.lw_update(o._rule, seg.p, seg.g, seg.m, o._items[i0:i1], o._coef, 1e-3, wd_eps=o._wd_eps(), ema=seg.ema, ema_decay=0.9993)
         return f
 
     def stages(o):

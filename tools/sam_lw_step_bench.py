@@ -36,31 +36,35 @@ def kernel_part(a, torch):
     p0 = m.flat_params.clone()
     orig, lw, un = SAMOriginal(), SAM(unitwise=False), SAM(unitwise=True)
     for c in (orig, lw, un):
-        c._build_plan(c._entries(params))
-    (ofp, ofg, ofe, oi0, oi1), = orig._segs
+        c.build_plan(params)
+    (oseg,) = orig._segs
+    ofp, ofg, ofe, (oi0, oi1) = oseg.p, oseg.g, oseg.eps, oseg.items
 
     def sums(c, tpp=ops.SAM_THREADS_PER_PIECE, unit=True, whole=True):
         nt, ns = c._tensors.shape[0], c._coef.numel()
-        for fp, fg, fe, i0, i1, (pa, pb), (wa, wb), k0 in c._segs:
+        for seg in c._segs:
+            (pa, pb), (wa, wb), k0 = seg.pieces, seg.whole, seg.partial0
             k1 = k0 + pb - pa
             if pb > pa and unit:
-                ops.sam_unit_sumsq(fp, fg, c._pieces[pa:pb], c._partial[2 * k0:2 * k1], ns, threads_per_piece=tpp)
+                ops.sam_unit_sumsq(seg.p, seg.g, c._pieces[pa:pb], c._partial[2 * k0:2 * k1], ns, threads_per_piece=tpp)
             if wb > wa and whole:
-                ops.sam_lw_sumsq(fp, fg, c._whole[wa:wb], c._partial[2 * k1:2 * (k1 + wb - wa)], nt)
+                ops.sam_lw_sumsq(seg.p, seg.g, c._whole[wa:wb], c._partial[2 * k1:2 * (k1 + wb - wa)], nt)
 
     def coef(c):
         ops.sam_lw_coef(c._partial, c._slots, c._coef, c._norms)
 
     def perturb(c):
-        for fp, fg, fe, i0, i1, *_ in c._segs:
-            ops.sam_lw_perturb(fp, fg, fe, c._items[i0:i1], c._tensors, c._coef, c.rho)
+        for seg in c._segs:
+            i0, i1 = seg.items
+            ops.sam_lw_perturb(seg.p, seg.g, seg.eps, c._items[i0:i1], c._tensors, c._coef, c.rho)
 
     def stages(c):
         sums(c)
         coef(c)
         perturb(c)
-        for fp, fg, fe, i0, i1, *_ in c._segs:
-            ops.sam_restore(fp, fe, c._items[i0:i1], c._tensors.shape[0])
+        for seg in c._segs:
+            i0, i1 = seg.items
+            ops.sam_restore(seg.p, seg.eps, c._items[i0:i1], c._tensors.shape[0])
 
     B = n_real
     n1d = n_real - n_unit

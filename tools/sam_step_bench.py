@@ -34,7 +34,7 @@ def kernel_part(a, torch):
     m.flat_grads.copy_(torch.randn(n_flat, device="cuda", generator=gen) * 1e-3)
     p0 = m.flat_params.clone()
     sam = SAMOriginal()
-    sam._build_plan(sam._entries(params))
+    sam.build_plan(params)
     s1, s2 = torch.zeros_like(p0), torch.zeros_like(p0)
     step = [0]
 
@@ -43,19 +43,22 @@ def kernel_part(a, torch):
         step[0] += 1
 
     def sumsq():
-        for fp, fg, fe, i0, i1 in sam._segs:
-            ops.sam_sumsq(fp, fg, sam._items[i0:i1], sam._kind, sam._partial[i0:i1], sam.eta)
+        for seg in sam._segs:
+            i0, i1 = seg.items
+            ops.sam_sumsq(seg.p, seg.g, sam._items[i0:i1], sam._kind, sam._partial[i0:i1], sam.eta)
 
     def scale():
         ops.sam_scale(sam._partial, sam.rho, sam._out)
 
     def perturb():
-        for fp, fg, fe, i0, i1 in sam._segs:
-            ops.sam_perturb(fp, fg, fe, sam._items[i0:i1], sam._kind, sam._out, sam.eta)
+        for seg in sam._segs:
+            i0, i1 = seg.items
+            ops.sam_perturb(seg.p, seg.g, seg.eps, sam._items[i0:i1], sam._kind, sam._out, sam.eta)
 
     def restore():
-        for fp, fg, fe, i0, i1 in sam._segs:
-            ops.sam_restore(fp, fe, sam._items[i0:i1], sam._kind.numel())
+        for seg in sam._segs:
+            i0, i1 = seg.items
+            ops.sam_restore(seg.p, seg.eps, sam._items[i0:i1], sam._kind.numel())
 
     def four():
         sumsq()
