@@ -334,6 +334,41 @@ int mi355_lw_update(int rule, float* p, const float* g, float* m, size_t n, cons
 int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
                         int n_tensors, double lr, int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream);
 
+/* unitwise_norm=True of MyNovograd and NovogradApex (sota_imagenet/optimizers.py:16-22, :134-135, :267-268; recipe
+ * configs/hydra_exp/48.r50_my-nov-unit.yaml) on flat fp32 arrays.  The statistic is taken per SLOT: a whole tensor for tensors with ndim <= 1,
+ * one index of dim 0 otherwise (a filter of a conv, a row of the FC: a contiguous run of unit_len = numel / shape[0] elements).  It is the NORM,
+ * sqrt of the sum of squares — also for the 1-D tensors — where the layer-wise rule above takes the sum of squares itself.  With x = g*grad_scale
+ * (NovogradApex, rule 0) or x = the PARAMETER (MyNovograd, rule 1, :135), per slot:
+ *   S = sum of (double)x^2;  v = v*beta2 + (1 - beta2)*sqrt(S)  in double, rounded once to the float32 v[slot];  den = (float)(sqrt((double)v) + eps)
+ * Stages on one stream, nothing read back, no floating-point atomics, over items[] of the layer-wise optimizers above (all tensors) and the tables
+ * of the SAM callback below:
+ *   pieces[]   { int64 off; int32 len; int32 slot }        len <= mi355_lw_item_elems(), off ANY element offset, cut from ONE unit
+ *   slots[]    { int32 first; int32 count }                the slot's consecutive entries of partial[]
+ *   tensors[]  { int64 start; int32 unit_len; int32 slot0 }   indexed by items[].tensor
+ *  (a) mi355_lw_unit_sumsq, once per storage pair over the pieces of the unit slots: partial[i] = sum over pieces[i] of (src*scale)^2, the product
+ *      in float, square and sum in double in a fixed order; one wave per piece.  The whole-tensor slots go through mi355_lw_sumsq over their items.
+ *  (b) mi355_lw_unit_coef, once per param group over its (consecutive) slots: sums[slot] = S, the slot's entries of partial[] in a fixed order;
+ *      v[slot] updated in place; den[slot] as above.  v, den, sums are indexed like slots[] (the pointers of the group's first slot).
+ *  (c) mi355_lw_unit_update, once per param group over that group's items; p, m in place, g read-only, den[] the WHOLE array, n_slots its length:
+ *        g = g*grad_scale;  den = den[tensors[t].slot0 + (element offset inside tensor t) / tensors[t].unit_len]
+ *        rule 0:  m = m*beta1 + (1 - beta1)*(g/den);  p += -lr*m;      p *= 1 - lr*wd,  or with soft_wd  p -= lr*wd * max(|p| - wd_eps, 0) * sign(p)
+ *        rule 1:  m = m*beta1 + (1 - beta1)*g;        p += -lr*(m/den);  p *= 1 - lr*wd
+ *      beta1, 1 - beta1, -lr and 1 - lr*wd (lr*wd with soft_wd) are formed in double and rounded once to float32; the element update is float32.
+ *      mi355_lw_unit_update_ema: + ema += (1 - ema_decay) * (p_new - ema) in the same pass.
+ * A record that does not lie inside the arrays of the launch is skipped by the kernels.  Each fails (-1) before any launch on a null or
+ * misaligned pointer (16 bytes for the arrays, items[], pieces[] and tensors[], 8 for partial[], slots[] and sums[], 4 for v[] and den[]), an
+ * empty table, a rule outside 0..1, beta1 / beta2 outside [0, 1), eps or lr negative or not finite, scale / grad_scale not finite, soft_wd with
+ * rule 1. */
+int mi355_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, void* partial, void* stream);
+int mi355_lw_unit_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, void* sums, double beta2,
+                       double eps, void* stream);
+int mi355_lw_unit_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const void* tensors,
+                         int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay, int soft_wd, double wd_eps,
+                         float grad_scale, void* stream);
+int mi355_lw_unit_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                             const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay,
+                             int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream);
+
 /* The SAMOriginal callback of the reference (adaptive sharpness-aware minimization, sota_imagenet/callbacks.py:279-337; recipe
  * configs/hydra_exp/49.r50_nov-adam.yaml:46-48) on flat fp32 arrays: between the first backward and the optimizer step every parameter moves
  * along its gradient, weighted by its own magnitude and normalised by ONE statistic of all tensors; after a second forward / backward there

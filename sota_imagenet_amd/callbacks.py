@@ -14,6 +14,7 @@ import torch
 
 from . import ops
 from .fit_wrapper import Callback
+from . import item_plan
 from .item_plan import flat_views, pack_records, place, storage_pairs
 
 
@@ -355,14 +356,7 @@ class SAM(_SecondPass):
     def unit_len(shape, stride, unitwise):
         """elements per slot of a dense tensor: numel, or numel / shape[0] for a unit-wise tensor with ndim > 1 — whose dim 0 must be the
         outermost stride, so that a unit is one contiguous run"""
-        n = int(np.prod(shape)) if len(shape) else 1
-        if not unitwise or len(shape) <= 1:
-            return n
-        u = n // shape[0]
-        if shape[0] > 1 and stride[0] != u:
-            raise RuntimeError(f"SAM: unitwise needs dim 0 as the outermost stride (shape {tuple(shape)}, strides {tuple(stride)}): a unit must be "
-                               "one contiguous run of numel / shape[0] elements")
-        return u
+        return item_plan.unit_len(shape, stride, unitwise, "SAM")
 
     @staticmethod
     def plan_tables(tensors, W):
@@ -375,37 +369,9 @@ class SAM(_SecondPass):
           whole    the work items of the whole-tensor slots, in the order of `items`
           slots    [(first, count)] per slot: its consecutive entries of the partial sums, which are laid out pair by pair, a pair's pieces
                    before its whole-tensor items
-          pairs    [(lo, hi, first item, end item, (first piece, end piece), (first whole item, end), first partial entry, tensor indices)]"""
-        items, _, pairs0 = storage_pairs(tensors, W)
-        slot0, n_slots = [], 0
-        for _, _, _, n, u in tensors:
-            if u < 1 or n % u or n >= 1 << 31:
-                raise ValueError(f"numel={n}, unit_len={u}: a tensor is a whole number of units and shorter than 2^31 elements")
-            slot0.append(n_slots)
-            n_slots += n // u
-        trec, pieces, whole, slots, pairs = [None] * len(tensors), [], [], [None] * n_slots, []
-        k = 0  # entries of the partial sums so far
-        for lo, hi, i0, i1, ts in pairs0:
-            pa, wa, k0 = len(pieces), len(whole), k
-            for t in ts:
-                _, _, off, n, u = tensors[t]
-                trec[t] = (off - lo, u, slot0[t])
-                if u == n:
-                    continue
-                per = (u + W - 1) // W
-                for j in range(n // u):
-                    slots[slot0[t] + j] = (k, per)
-                    pieces.extend((off - lo + j * u + c, min(W, u - c), slot0[t] + j) for c in range(0, u, W))
-                    k += per
-            for o, ln, t in items[i0:i1]:
-                if tensors[t][4] != tensors[t][3]:
-                    continue
-                first, count = slots[slot0[t]] or (k, 0)
-                slots[slot0[t]] = (first, count + 1)
-                whole.append((o, ln, t))
-                k += 1
-            pairs.append((lo, hi, i0, i1, (pa, len(pieces)), (wa, len(whole)), k0, ts))
-        return dict(items=items, tensors=trec, pieces=pieces, whole=whole, slots=slots, pairs=pairs)
+          pairs    [(lo, hi, first item, end item, (first piece, end piece), (first whole item, end), first partial entry, tensor indices)]
+        (item_plan.plan_units, which the unit-wise optimizers build on as well)"""
+        return item_plan.plan_units(tensors, W)
 
     def _build(self, entries, dev, W):
         tab = self.plan_tables([(pb, gb, off, n, self.unit_len(p.shape, p.stride(), self.unitwise)) for pb, gb, off, n, p in entries], W)

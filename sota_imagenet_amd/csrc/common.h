@@ -353,6 +353,14 @@ int launch_lw_coef(int rule, int flags, const double* partial, size_t n_partial,
                    double* sums, double beta1, double beta2, double eps, double lr, double wd, double mean, hipStream_t st);
 int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
                      int n_tensors, double lr, int soft_wd, double wd_eps, float gscale, float ema_decay, hipStream_t st);
+// the unit-wise form (unitwise_norm=True): one statistic, the norm, per slot (optim_items.h: pieces, slots, tensor records)
+int launch_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, double* partial,
+                         hipStream_t st);
+int launch_lw_unit_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, double* sums,
+                        double beta2, double eps, hipStream_t st);
+int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                          const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double wd, int soft_wd,
+                          double wd_eps, float gscale, float ema_decay, hipStream_t st);
 // optim_sam.hip: the four stages of the SAMOriginal callback over the same work-item table (kind[tensor]: 1 = weight, 0 = other)
 int launch_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
                      float gscale, double* partial, hipStream_t st);

@@ -602,6 +602,27 @@ int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema
                           (hipStream_t)stream);
 }
 
+int mi355_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, void* partial, void* stream) {
+  return launch_lw_unit_sumsq(src, n, pieces, n_pieces, n_slots, scale, (double*)partial, (hipStream_t)stream);
+}
+int mi355_lw_unit_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, void* sums, double beta2,
+                       double eps, void* stream) {
+  return launch_lw_unit_coef((const double*)partial, n_partial, slots, n_slots, v, den, (double*)sums, beta2, eps, (hipStream_t)stream);
+}
+int mi355_lw_unit_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const void* tensors,
+                         int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay, int soft_wd, double wd_eps,
+                         float grad_scale, void* stream) {
+  return launch_lw_unit_update(rule, p, g, m, nullptr, n, items, n_items, tensors, n_tensors, den, n_slots, beta1, lr, weight_decay, soft_wd,
+                               wd_eps, grad_scale, 0.f, (hipStream_t)stream);
+}
+int mi355_lw_unit_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                             const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay,
+                             int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "lw_unit_update_ema: null ema");
+  return launch_lw_unit_update(rule, p, g, m, ema, n, items, n_items, tensors, n_tensors, den, n_slots, beta1, lr, weight_decay, soft_wd, wd_eps,
+                               grad_scale, ema_decay, (hipStream_t)stream);
+}
+
 int mi355_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
                     float grad_scale, void* partial, void* stream) {
   return launch_sam_sumsq(p, g, n, items, n_items, kind, n_tensors, eta, grad_scale, (double*)partial, (hipStream_t)stream);

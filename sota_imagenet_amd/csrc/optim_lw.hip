@@ -1,4 +1,4 @@
-// optim_lw.hip — the layer-wise optimizers of the reference's own tree (sota_imagenet/optimizers.py: MyNovograd :35-161, NovogradApex :189-290,
+// optim_lw.hip — the layer-wise and unit-wise optimizers of the reference's own tree (sota_imagenet/optimizers.py: MyNovograd :35-161, NovogradApex :189-290,
 // AdamLayerwise :293-397, MyAdai :400-519) on flat fp32 arrays (gfx950).  Each of them needs one statistic PER PARAMETER TENSOR — the sum of
 // squares of its gradient, or of the parameter itself for MyNovograd — and uses it as a per-tensor scalar in the update.  A step is three
 // stages on one stream, nothing read back by the host, over a work-item table the host builds once per plan:
@@ -22,6 +22,15 @@
 //         p = p*wdf,  or with LW_SOFT_WD (NovogradApex's wd_eps)  p = p - wdf*(max(|p| - wd_eps, 0)*sign(p))
 //         EMA: ema = ema + (1 - decay)*(p - ema)
 // 4 B / element in (a) + 20 B / element in (c) (p, m read + write, g read once more, non-temporal: its last use), 28 B with the average.
+// unitwise_norm=True (MyNovograd, NovogradApex; recipe 48, optimizers.py:16-22, :134-135, :267-268) takes the statistic per SLOT — a whole tensor
+// with ndim <= 1, one index of dim 0 otherwise — and it is the NORM, sqrt of the sum of squares, also for the 1-D tensors:
+//   (a') lw_unit_sumsq_kernel, one wave per piece of a unit (optim_items.h: any element offset), four pieces per workgroup; the 1-D tensors go
+//        through lw_sumsq_kernel over their items.  One double per piece or item.
+//   (b') lw_unit_coef_kernel, one wave per slot, four slots per workgroup, one launch per param group: S = the slot's consecutive partials in a
+//        fixed order; v[slot] = v*beta2 + (1 - beta2)*sqrt(S) in double, rounded once to float32; den[slot] = (float)(sqrt((double)v) + eps).
+//   (c') lw_unit_update_kernel<RULE, EMA>, rules 0 and 1, one workgroup per item: beta1, 1 - beta1, -lr and wdf are the same for the whole launch
+//        (formed in double, rounded once, as lw_coef_kernel stores them); den comes from the slot of each element, slot0 + (offset inside the
+//        tensor) / unit_len.  An item inside one slot reads den once and runs item_sweep; any other walks (unit, place) element by element.
 // The library builds with -ffp-contract=off, and sqrt / '/' stay correctly rounded.  The loop of (a) and (c) over an item's elements is item_sweep
 // (optim_sweep.h: 256 threads, f32x4 body, scalar tail).
 #include <cmath>
@@ -146,6 +155,127 @@ void lw_update_launch(bool ema_on, dim3 grid, hipStream_t st, float* p, const fl
   else hipLaunchKernelGGL((lw_update_kernel<RULE, false>), grid, dim3(256), 0, st, p, g, m, ema, n, items, coef, n_tensors, a);
 }
 
+__global__ __launch_bounds__(256) void lw_unit_sumsq_kernel(const float* __restrict__ src, size_t n, const UnitPiece* __restrict__ pieces,
+                                                            size_t n_pieces, int n_slots, double* __restrict__ partial, float scale) {
+  __shared__ double sh[256];
+  const int l = threadIdx.x & 63;
+  const size_t k = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
+  double acc = 0.0;
+  if (k < n_pieces) {
+    const UnitPiece pc = pieces[k];
+    if (piece_ok(pc, n, n_slots)) {
+      const float* sp = src + pc.off;
+      const auto add = [&](float x) {
+        const double e = (double)(x * scale);
+        acc += e * e;
+      };
+      piece_walk<64>(
+          pc, l, [&](int i) { add(sp[i]); },
+          [&](int head, int i) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(sp + head)[i];  // read again by the update kernel: a plain load
+#pragma unroll
+            for (int j = 0; j < 4; ++j) add(v[j]);
+          });
+    }
+  }
+  const double tot = group_sum<64>(acc, sh);
+  if (l == 0 && k < n_pieces) partial[k] = tot;
+}
+
+__global__ __launch_bounds__(256) void lw_unit_coef_kernel(const double* __restrict__ partial, size_t n_partial, const UnitSlot* __restrict__ slots,
+                                                           size_t n_slots, float* __restrict__ v, float* __restrict__ den,
+                                                           double* __restrict__ sums, double beta2, double eps) {
+  __shared__ double sh[256];
+  const int l = threadIdx.x & 63;
+  const size_t s = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
+  double acc = 0.0;
+  bool ok = false;
+  if (s < n_slots) {
+    const UnitSlot sl = slots[s];
+    ok = sl.first >= 0 && sl.count > 0 && (size_t)sl.first + (size_t)sl.count <= n_partial;
+    if (ok)
+      for (int i = l; i < sl.count; i += 64) acc += partial[(size_t)sl.first + i];
+  }
+  const double S = group_sum<64>(acc, sh);
+  if (l != 0 || !ok) return;
+  sums[s] = S;
+  const float vn = (float)((double)v[s] * beta2 + (1.0 - beta2) * sqrt(S));  // the NORM, where the layer-wise rule takes S itself
+  v[s] = vn;
+  den[s] = (float)(sqrt((double)vn) + eps);
+}
+
+template <int RULE, bool EMA>
+__global__ __launch_bounds__(256) void lw_unit_update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ ema, size_t n, const LwItem* __restrict__ items,
+                                                             const UnitTensor* __restrict__ tens, int n_tensors, const float* __restrict__ den,
+                                                             int n_slots, f32x4 c0, LwUpdArgs a) {
+  const LwItem it = items[blockIdx.x];
+  if (!item_ok(it, n, n_tensors)) return;
+  const UnitTensor t = tens[it.tensor];
+  const long long e0 = it.off - t.start;  // the item's first element inside its tensor
+  if (t.unit_len <= 0 || t.slot0 < 0 || e0 < 0 || e0 + it.len > 0x7fffffffLL) return;
+  const int u = t.unit_len, first = (int)e0 / u, lastu = ((int)e0 + it.len - 1) / u;
+  if ((long long)t.slot0 + lastu >= n_slots) return;
+  const float* d = den + t.slot0;
+  const auto ap = upd(p + it.off);
+  const auto ag = last(g + it.off);
+  const auto am = upd(m + it.off);
+  if (first == lastu) {
+    f32x4 c = c0;
+    c[0] = d[first];
+    if constexpr (EMA) {
+      item_sweep(it.len, [&](float& pk, float& gk, float& mk, float& ek) { lw_elem<RULE, true>(pk, gk, mk, ek, c, a); }, ap, ag, am,
+                 upd(ema + it.off));
+    } else {
+      item_sweep(it.len, [&](float& pk, float& gk, float& mk) { float ek = 0.f; lw_elem<RULE, false>(pk, gk, mk, ek, c, a); }, ap, ag, am);
+    }
+    return;
+  }
+  // the item spans several units: the rule walks (unit, place inside it) along the elements it is given
+  int s = 0, r = 0;
+  const auto elem = [&](float& pk, float& gk, float& mk, float& ek) {
+    f32x4 c = c0;
+    c[0] = d[s];
+    lw_elem<RULE, EMA>(pk, gk, mk, ek, c, a);
+    if (++r == u) r = 0, ++s;
+  };
+  const int n4 = it.len >> 2;
+  const auto at = [&](int e) { s = ((int)e0 + e) / u, r = (int)e0 + e - s * u; };
+  if constexpr (EMA) {
+    auto rule = elem;
+    const auto ae = upd(ema + it.off);
+    constexpr std::index_sequence<0, 1, 2, 3> js;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      at(4 * i);
+      sweep_vector(i, rule, js, ap, ag, am, ae);
+    }
+    if ((int)threadIdx.x < (it.len & 3)) {
+      at(4 * n4 + (int)threadIdx.x);
+      sweep_element(4 * n4 + (int)threadIdx.x, rule, js, ap, ag, am, ae);
+    }
+  } else {
+    auto rule = [&](float& pk, float& gk, float& mk) { float ek = 0.f; elem(pk, gk, mk, ek); };
+    constexpr std::index_sequence<0, 1, 2> js;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      at(4 * i);
+      sweep_vector(i, rule, js, ap, ag, am);
+    }
+    if ((int)threadIdx.x < (it.len & 3)) {
+      at(4 * n4 + (int)threadIdx.x);
+      sweep_element(4 * n4 + (int)threadIdx.x, rule, js, ap, ag, am);
+    }
+  }
+}
+
+template <int RULE>
+void lw_unit_update_launch(bool ema_on, dim3 grid, hipStream_t st, float* p, const float* g, float* m, float* ema, size_t n, const LwItem* items,
+                           const UnitTensor* tens, int n_tensors, const float* den, int n_slots, const f32x4& c0, const LwUpdArgs& a) {
+  if (ema_on)
+    hipLaunchKernelGGL((lw_unit_update_kernel<RULE, true>), grid, dim3(256), 0, st, p, g, m, ema, n, items, tens, n_tensors, den, n_slots, c0, a);
+  else
+    hipLaunchKernelGGL((lw_unit_update_kernel<RULE, false>), grid, dim3(256), 0, st, p, g, m, ema, n, items, tens, n_tensors, den, n_slots, c0, a);
+}
+
 }  // namespace
 
 size_t lw_item_elems() { return kLwItemElems; }
@@ -203,6 +333,66 @@ int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, s
   if (rule == 0) lw_update_launch<0>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
   else if (rule == 1) lw_update_launch<1>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
   else lw_update_launch<2>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, double* partial,
+                         hipStream_t st) {
+  MI355_ARG(src && pieces && partial, "lw_unit_sumsq: null pointer");
+  MI355_ARG(aligned16(src) && aligned16(pieces) && (uintptr_t)partial % 8 == 0,
+            "lw_unit_sumsq: misaligned pointer (16 bytes for the array and the table, 8 for partial[])");
+  MI355_ARG(n_pieces >= 1 && n_pieces <= kLwMaxGrid && n_slots >= 1, "lw_unit_sumsq: n_pieces=%zu, n_slots=%d out of range", n_pieces, n_slots);
+  MI355_ARG(std::isfinite(scale), "lw_unit_sumsq: scale=%g is not finite", (double)scale);
+  hipLaunchKernelGGL(lw_unit_sumsq_kernel, dim3((unsigned)((n_pieces + 3) / 4)), dim3(256), 0, st, src, n, (const UnitPiece*)pieces, n_pieces,
+                     n_slots, partial, scale);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_lw_unit_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, double* sums,
+                        double beta2, double eps, hipStream_t st) {
+  MI355_ARG(partial && slots && v && den && sums, "lw_unit_coef: null pointer");
+  MI355_ARG((uintptr_t)partial % 8 == 0 && (uintptr_t)slots % 8 == 0 && (uintptr_t)v % 4 == 0 && (uintptr_t)den % 4 == 0 && (uintptr_t)sums % 8 == 0,
+            "lw_unit_coef: misaligned pointer (8 bytes for partial[], slots[] and sums[], 4 for v[] and den[])");
+  MI355_ARG(n_partial >= 1 && n_partial <= kLwMaxGrid && n_slots >= 1 && n_slots <= kLwMaxGrid, "lw_unit_coef: n_partial=%zu, n_slots=%zu out of range",
+            n_partial, n_slots);
+  MI355_ARG(beta2 >= 0.0 && beta2 < 1.0, "lw_unit_coef: beta2=%g outside [0, 1)", beta2);
+  MI355_ARG(std::isfinite(eps) && eps >= 0.0, "lw_unit_coef: eps=%g must be finite and >= 0", eps);
+  hipLaunchKernelGGL(lw_unit_coef_kernel, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, st, partial, n_partial, (const UnitSlot*)slots, n_slots,
+                     v, den, sums, beta2, eps);
+  MI355_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                          const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double wd, int soft_wd,
+                          double wd_eps, float gscale, float ema_decay, hipStream_t st) {
+  MI355_ARG(p && g && m && items && tensors && den, "lw_unit_update: null pointer");
+  MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(ema) && aligned16(items) && aligned16(tensors) && (uintptr_t)den % 4 == 0,
+            "lw_unit_update: misaligned pointer (16 bytes for the arrays and the tables, 4 for den[])");
+  MI355_ARG(rule >= 0 && rule <= 1, "lw_unit_update: rule=%d outside 0..1", rule);
+  MI355_ARG(n_items >= 1 && n_items <= kLwMaxGrid && n_tensors >= 1 && n_slots >= 1 && n_slots <= 0x7fffffffu,
+            "lw_unit_update: n_items=%zu, n_tensors=%d, n_slots=%zu out of range", n_items, n_tensors, n_slots);
+  MI355_ARG(beta1 >= 0.0 && beta1 < 1.0, "lw_unit_update: beta1=%g outside [0, 1)", beta1);
+  MI355_ARG(std::isfinite(lr) && lr >= 0.0, "lw_unit_update: lr=%g must be finite and >= 0", lr);
+  MI355_ARG(std::isfinite(wd), "lw_unit_update: weight_decay=%g is not finite", wd);
+  MI355_ARG(!soft_wd || (rule == 0 && std::isfinite(wd_eps)), "lw_unit_update: wd_eps=%g needs rule 0 and a finite value", wd_eps);
+  MI355_ARG(std::isfinite(gscale), "lw_unit_update: grad_scale=%g is not finite", (double)gscale);
+  MI355_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "lw_unit_update: ema_decay=%g outside [0, 1]", (double)ema_decay);
+  LwUpdArgs a;
+  a.neg_lr = (float)(-lr);
+  a.gscale = gscale;
+  a.ema_w = ema ? 1.f - ema_decay : 0.f;
+  a.wd_eps = soft_wd ? (float)wd_eps : 0.f;
+  a.soft_wd = soft_wd != 0;
+  const double lrwd = lr * wd;
+  const f32x4 c0 = {1.f, (float)beta1, (float)(1.0 - beta1), (float)(soft_wd ? lrwd : 1.0 - lrwd)};  // what lw_coef_kernel stores, den aside
+  const dim3 grid((unsigned)n_items);
+  const LwItem* it = (const LwItem*)items;
+  const UnitTensor* tn = (const UnitTensor*)tensors;
+  if (rule == 0) lw_unit_update_launch<0>(ema != nullptr, grid, st, p, g, m, ema, n, it, tn, n_tensors, den, (int)n_slots, c0, a);
+  else lw_unit_update_launch<1>(ema != nullptr, grid, st, p, g, m, ema, n, it, tn, n_tensors, den, (int)n_slots, c0, a);
   MI355_LAUNCH_CHECK();
   return 0;
 }

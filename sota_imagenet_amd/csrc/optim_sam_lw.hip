@@ -30,39 +30,6 @@
 namespace mi355 {
 namespace {
 
-struct SamPiece {
-  long long off;  // first element, relative to the array pointers of the launch; any alignment
-  int len;        // 1 .. kLwItemElems, inside one unit
-  int slot;       // the unit's slot
-};
-struct SamSlot {
-  int first, count;  // the slot's consecutive entries of partial[] (pairs of doubles)
-};
-struct SamTensor {
-  long long start;  // the tensor's first element, relative to the array pointers of the launch
-  int unit_len;     // elements per slot: numel for a whole-tensor slot
-  int slot0;        // slot of the tensor's first element
-};
-static_assert(sizeof(SamPiece) == 16 && sizeof(SamTensor) == 16 && sizeof(SamSlot) == 8, "table records are 16 / 16 / 8 bytes");
-
-__device__ __forceinline__ bool piece_ok(const SamPiece& pc, size_t n, int n_slots) {
-  return pc.off >= 0 && pc.len > 0 && pc.len <= kLwItemElems && (size_t)pc.off + (size_t)pc.len <= n && pc.slot >= 0 && pc.slot < n_slots;
-}
-
-// sum of one double per thread over each group of G consecutive threads of the 256-thread workgroup, in a fixed order
-template <int G>
-__device__ __forceinline__ double group_sum(double x, double* sh) {
-  const int t = threadIdx.x, l = t & (G - 1);
-  sh[t] = x;
-  __syncthreads();
-#pragma unroll
-  for (int w = G / 2; w > 0; w >>= 1) {
-    if (l < w) sh[t] += sh[t + w];
-    __syncthreads();
-  }
-  return sh[t - l];
-}
-
 __global__ __launch_bounds__(256) void sam_lw_sumsq_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n,
                                                            const LwItem* __restrict__ items, int n_tensors, double* __restrict__ partial,
                                                            float gscale) {
@@ -86,14 +53,14 @@ __global__ __launch_bounds__(256) void sam_lw_sumsq_kernel(const float* __restri
 
 template <int G>
 __global__ __launch_bounds__(256) void sam_unit_sumsq_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n,
-                                                             const SamPiece* __restrict__ pieces, size_t n_pieces, int n_slots,
+                                                             const UnitPiece* __restrict__ pieces, size_t n_pieces, int n_slots,
                                                              double* __restrict__ partial, float gscale) {
   __shared__ double shg[256], shp[256];
   const int l = threadIdx.x & (G - 1);
   const size_t k = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
   double ag = 0.0, ap = 0.0;
   if (k < n_pieces) {
-    const SamPiece pc = pieces[k];
+    const UnitPiece pc = pieces[k];
     if (piece_ok(pc, n, n_slots)) {
       const float* pp = p + pc.off;
       const float* gp = g + pc.off;
@@ -102,17 +69,13 @@ __global__ __launch_bounds__(256) void sam_unit_sumsq_kernel(const float* __rest
         ag += ge * ge;
         ap += pd * pd;
       };
-      const int head = min((int)((4 - (pc.off & 3)) & 3), pc.len);  // the arrays are 16-byte aligned: off & 3 is the element's place in its vector
-      const int n4 = (pc.len - head) >> 2, tail = (pc.len - head) & 3;
-      if (l < head) add(pp[l], gp[l]);
-      const f32x4* p4 = reinterpret_cast<const f32x4*>(pp + head);
-      const f32x4* g4 = reinterpret_cast<const f32x4*>(gp + head);
-      for (int i = l; i < n4; i += G) {
-        const f32x4 pv = p4[i], gv = g4[i];
+      piece_walk<G>(
+          pc, l, [&](int i) { add(pp[i], gp[i]); },
+          [&](int head, int i) {
+            const f32x4 pv = reinterpret_cast<const f32x4*>(pp + head)[i], gv = reinterpret_cast<const f32x4*>(gp + head)[i];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) add(pv[j], gv[j]);
-      }
-      if (l < tail) add(pp[head + 4 * n4 + l], gp[head + 4 * n4 + l]);
+            for (int j = 0; j < 4; ++j) add(pv[j], gv[j]);
+          });
     }
   }
   const double sg = group_sum<G>(ag, shg), sp = group_sum<G>(ap, shp);
@@ -122,7 +85,7 @@ __global__ __launch_bounds__(256) void sam_unit_sumsq_kernel(const float* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void sam_lw_coef_kernel(const double* __restrict__ partial, size_t n_partial, const SamSlot* __restrict__ slots,
+__global__ __launch_bounds__(256) void sam_lw_coef_kernel(const double* __restrict__ partial, size_t n_partial, const UnitSlot* __restrict__ slots,
                                                           size_t n_slots, float* __restrict__ coef, float* __restrict__ norms) {
   __shared__ double shg[256], shp[256];
   const int l = threadIdx.x & 63;
@@ -130,7 +93,7 @@ __global__ __launch_bounds__(256) void sam_lw_coef_kernel(const double* __restri
   double ag = 0.0, ap = 0.0;
   bool ok = false;
   if (s < n_slots) {
-    const SamSlot sl = slots[s];
+    const UnitSlot sl = slots[s];
     ok = sl.first >= 0 && sl.count > 0 && (size_t)sl.first + (size_t)sl.count <= n_partial;
     if (ok)
       for (int i = l; i < sl.count; i += 64) {
@@ -147,11 +110,11 @@ __global__ __launch_bounds__(256) void sam_lw_coef_kernel(const double* __restri
 }
 
 __global__ __launch_bounds__(256) void sam_lw_perturb_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ eps, size_t n,
-                                                             const LwItem* __restrict__ items, const SamTensor* __restrict__ tens, int n_tensors,
+                                                             const LwItem* __restrict__ items, const UnitTensor* __restrict__ tens, int n_tensors,
                                                              const float* __restrict__ coef, int n_slots, float rho, float gscale) {
   const LwItem it = items[blockIdx.x];
   if (!item_ok(it, n, n_tensors)) return;
-  const SamTensor t = tens[it.tensor];
+  const UnitTensor t = tens[it.tensor];
   const long long e0 = it.off - t.start;  // the item's first element inside its tensor
   if (t.unit_len <= 0 || t.slot0 < 0 || e0 < 0 || e0 + it.len > 0x7fffffffLL) return;
   const int u = t.unit_len, first = (int)e0 / u, lastu = ((int)e0 + it.len - 1) / u;
@@ -212,7 +175,7 @@ int launch_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* 
   MI355_ARG(n_pieces >= 1 && n_pieces <= kLwMaxGrid && n_slots >= 1, "sam_unit_sumsq: n_pieces=%zu, n_slots=%d out of range", n_pieces, n_slots);
   MI355_ARG(std::isfinite(gscale), "sam_unit_sumsq: grad_scale=%g is not finite", (double)gscale);
   MI355_ARG(threads_per_piece == 64 || threads_per_piece == 256, "sam_unit_sumsq: threads_per_piece=%d must be 64 or 256", threads_per_piece);
-  const SamPiece* pc = (const SamPiece*)pieces;
+  const UnitPiece* pc = (const UnitPiece*)pieces;
   if (threads_per_piece == 64)
     hipLaunchKernelGGL(sam_unit_sumsq_kernel<64>, dim3((unsigned)((n_pieces + 3) / 4)), dim3(256), 0, st, p, g, n, pc, n_pieces, n_slots, partial,
                        gscale);
@@ -228,7 +191,7 @@ int launch_sam_lw_coef(const double* partial, size_t n_partial, const void* slot
             "sam_lw_coef: misaligned pointer (16 bytes for the pairs of partial sums, 8 for the slot table and norms[], 4 for coef[])");
   MI355_ARG(n_partial >= 1 && n_partial <= kLwMaxGrid && n_slots >= 1 && n_slots <= kLwMaxGrid, "sam_lw_coef: n_partial=%zu, n_slots=%zu out of range",
             n_partial, n_slots);
-  hipLaunchKernelGGL(sam_lw_coef_kernel, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, st, partial, n_partial, (const SamSlot*)slots, n_slots,
+  hipLaunchKernelGGL(sam_lw_coef_kernel, dim3((unsigned)((n_slots + 3) / 4)), dim3(256), 0, st, partial, n_partial, (const UnitSlot*)slots, n_slots,
                      coef, norms);
   MI355_LAUNCH_CHECK();
   return 0;
@@ -244,7 +207,7 @@ int launch_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const 
   MI355_ARG(std::isfinite(rho) && rho >= 0.0, "sam_lw_perturb: rho=%g must be finite and >= 0", rho);
   MI355_ARG(std::isfinite(gscale), "sam_lw_perturb: grad_scale=%g is not finite", (double)gscale);
   hipLaunchKernelGGL(sam_lw_perturb_kernel, dim3((unsigned)n_items), dim3(256), 0, st, p, g, eps, n, (const LwItem*)items,
-                     (const SamTensor*)tensors, n_tensors, coef, (int)n_slots, (float)rho, gscale);
+                     (const UnitTensor*)tensors, n_tensors, coef, (int)n_slots, (float)rho, gscale);
   MI355_LAUNCH_CHECK();
   return 0;
 }

@@ -1,4 +1,4 @@
-// optim_sum.h — what the optimizer kernels of optim.hip and optim_lw.hip share: the fixed-order workgroup sum and the alignment test.
+// optim_sum.h — what the optimizer kernels of optim.hip, optim_lw.hip and optim_sam_lw.hip share: the fixed-order workgroup and group sums and the alignment test.
 #pragma once
 #include <cstdint>
 
@@ -17,6 +17,20 @@ __device__ __forceinline__ double block_sum(double x, double* sh) {
     __syncthreads();
   }
   return sh[0];
+}
+
+// sum of one double per thread over each group of G consecutive threads of the 256-thread workgroup, in a fixed order
+template <int G>
+__device__ __forceinline__ double group_sum(double x, double* sh) {
+  const int t = threadIdx.x, l = t & (G - 1);
+  sh[t] = x;
+  __syncthreads();
+#pragma unroll
+  for (int w = G / 2; w > 0; w >>= 1) {
+    if (l < w) sh[t] += sh[t + w];
+    __syncthreads();
+  }
+  return sh[t - l];
 }
 
 inline bool aligned16(const void* q) { return (uintptr_t)q % 16 == 0; }

@@ -1,7 +1,8 @@
 """The host side of the work-item plan, written once: what the layer-wise optimizers (optim._Layerwise) and the sharpness-aware callbacks
 (callbacks.SAMOriginal, callbacks.SAM) run on.  Which parameters fit the flat kernels (place), the parameters grouped by pair of parameter /
 gradient storage with every tensor cut into work items of at most W elements (plan_items, storage_pairs), the 16-byte records the kernels read
-(pack_records) and a storage as flat arrays (flat_views).  Everything up to pack_records is pure Python on plain tuples, so a planner is pinned
+(pack_records) and a storage as flat arrays (flat_views); for the statistics taken per output unit (callbacks.SAM, the unit-wise optimizers of
+optim.py) the unit rule (unit_len) and the tables of pieces, slots and tensor records (plan_units).  Everything up to pack_records is pure Python on plain tuples, so a planner is pinned
 without a GPU (tests/test_item_plan_host.py); the device side of the records is csrc/optim_items.h.  The merged-range planner of SGD / Adam /
 MADGRAD / AdaiS (optim._merged_ranges) takes place and flat_views only."""
 import numpy as np
@@ -75,6 +76,62 @@ def storage_pairs(tensors, W):
     items, in_order = plan_items([(tensors[t][2] - lo_of[t], tensors[t][3]) for t in order], W, order)
     spans = [span for _, span in sorted(zip(order, in_order))]  # by tensor index
     return items, spans, [(lo, hi, spans[ts[0]][0], sum(spans[ts[-1]]), ts) for lo, hi, ts in pairs.values()]
+
+
+def unit_len(shape, stride, unitwise, name):
+    """elements per slot of a dense tensor: numel, or numel / shape[0] for a unit-wise tensor with ndim > 1 — whose dim 0 must be the
+    outermost stride, so that a unit is one contiguous run; anything else raises RuntimeError in the name of class `name`"""
+    n = int(np.prod(shape)) if len(shape) else 1
+    if not unitwise or len(shape) <= 1:
+        return n
+    u = n // shape[0]
+    if shape[0] > 1 and stride[0] != u:
+        raise RuntimeError(f"{name}: unitwise needs dim 0 as the outermost stride (shape {tuple(shape)}, strides {tuple(stride)}): a unit must be "
+                           "one contiguous run of numel / shape[0] elements")
+    return u
+
+
+def plan_units(tensors, W):
+    """the tables of a plan with one statistic per slot.  tensors: [(param base, grad base, first elem, numel, unit_len)] in param-group order,
+    unit_len = numel for a whole-tensor slot, less for a tensor taken unit by unit; W: ops.lw_item_elems().  Returns a dict:
+      items    storage_pairs' work items of ALL tensors
+      tensors  [(start relative to its pair's range, unit_len, slot0)] per tensor; slots are numbered tensor by tensor
+      pieces   [(first element relative to the pair's range, length <= W, slot)]: every unit of the unit-wise tensors, cut at multiples of
+               W from the unit's start
+      whole    the work items of the whole-tensor slots, in the order of `items`
+      slots    [(first, count)] per slot: its consecutive entries of the partial sums, which are laid out pair by pair, a pair's pieces
+               before its whole-tensor items
+      pairs    [(lo, hi, first item, end item, (first piece, end piece), (first whole item, end), first partial entry, tensor indices)]"""
+    items, _, pairs0 = storage_pairs(tensors, W)
+    slot0, n_slots = [], 0
+    for _, _, _, n, u in tensors:
+        if u < 1 or n % u or n >= 1 << 31:
+            raise ValueError(f"numel={n}, unit_len={u}: a tensor is a whole number of units and shorter than 2^31 elements")
+        slot0.append(n_slots)
+        n_slots += n // u
+    trec, pieces, whole, slots, pairs = [None] * len(tensors), [], [], [None] * n_slots, []
+    k = 0  # entries of the partial sums so far
+    for lo, hi, i0, i1, ts in pairs0:
+        pa, wa, k0 = len(pieces), len(whole), k
+        for t in ts:
+            _, _, off, n, u = tensors[t]
+            trec[t] = (off - lo, u, slot0[t])
+            if u == n:
+                continue
+            per = (u + W - 1) // W
+            for j in range(n // u):
+                slots[slot0[t] + j] = (k, per)
+                pieces.extend((off - lo + j * u + c, min(W, u - c), slot0[t] + j) for c in range(0, u, W))
+                k += per
+        for o, ln, t in items[i0:i1]:
+            if tensors[t][4] != tensors[t][3]:
+                continue
+            first, count = slots[slot0[t]] or (k, 0)
+            slots[slot0[t]] = (first, count + 1)
+            whole.append((o, ln, t))
+            k += 1
+        pairs.append((lo, hi, i0, i1, (pa, len(pieces)), (wa, len(whole)), k0, ts))
+    return dict(items=items, tensors=trec, pieces=pieces, whole=whole, slots=slots, pairs=pairs)
 
 
 def pack_records(records, device=None, fields=ITEM_FIELDS):

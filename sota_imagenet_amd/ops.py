@@ -475,6 +475,57 @@ def lw_update(rule, p, g, m, items, coef, lr, wd_eps=None, grad_scale=1.0, ema=N
     check(_L().mi355_lw_update_ema(int(rule), ptr(p), ptr(g), ptr(m), ptr(ema), *args, float(ema_decay), cur_stream()))
 
 
+# ---- unitwise_norm=True of MyNovograd / NovogradApex (include/mi355rn.h, csrc/optim_lw.hip): one norm per slot ----------------------------------
+def _unit_slots(name, slots):
+    _need_cuda(slots)
+    if slots.dtype != torch.int32 or slots.dim() != 2 or slots.shape[1] != 2 or slots.shape[0] < 1:
+        raise ValueError(f"{name}: slots must be a contiguous CUDA int32 tensor [n, 2], got {slots.dtype} {tuple(slots.shape)}")
+
+
+def lw_unit_sumsq(src, pieces, partial, n_slots, scale=1.0):
+    """stage (a), the per-output-unit sums behind unitwise_norm of sota_imagenet/optimizers.py:22: partial[i] = sum over piece i { off, len, slot }
+    of (src * scale)^2 in double, a piece cut from one unit at any element offset; one wave per piece"""
+    _flat_f32(src.numel(), src=src)
+    _lw_table("pieces", pieces)
+    _need_cuda(partial)
+    if partial.dtype != torch.float64 or partial.numel() != pieces.shape[0]:
+        raise ValueError(f"partial: expected {pieces.shape[0]} float64 elements, got {partial.dtype} with {partial.numel()}")
+    check(_L().mi355_lw_unit_sumsq(ptr(src), src.numel(), ptr(pieces), pieces.shape[0], int(n_slots), float(scale), ptr(partial), cur_stream()))
+
+
+def lw_unit_coef(partial, slots, v, den, sums, beta2, eps):
+    """stage (b), replaces optimizers.py:134-146 and :267-274 for the slots of one param group: sums[s] = the slot's entries of partial[] (the
+    WHOLE array) in a fixed order; v[s] = v[s]*beta2 + (1 - beta2)*sqrt(sums[s]), float32 in place; den[s] = sqrt(v[s]) + eps.  slots: CUDA int32
+    [n, 2] of (first, count); v, den, sums: the group's slices, one element per slot"""
+    _unit_slots("lw_unit_coef", slots)
+    ns = slots.shape[0]
+    _need_cuda(partial, v, den, sums)
+    if partial.dtype != torch.float64 or sums.dtype != torch.float64 or sums.numel() != ns:
+        raise ValueError("lw_unit_coef: partial and sums must be float64, sums one element per slot")
+    if v.dtype != torch.float32 or den.dtype != torch.float32 or v.numel() != ns or den.numel() != ns:
+        raise ValueError("lw_unit_coef: v and den must hold one float32 per slot")
+    check(_L().mi355_lw_unit_coef(ptr(partial), partial.numel(), ptr(slots), ns, ptr(v), ptr(den), ptr(sums), float(beta2), float(eps), cur_stream()))
+
+
+def lw_unit_update(rule, p, g, m, items, tensors, den, beta1, lr, weight_decay, wd_eps=None, grad_scale=1.0, ema=None, ema_decay=0.0):
+    """stage (c), replaces optimizers.py:144-159 and :277-288 for the work items of one param group; p, g, m (and ema): the flat fp32 arrays the
+    item offsets count from; tensors: the records { start, unit_len, slot0 } of ALL tensors; den: the whole per-slot array of stage (b)"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, m=m)
+    _lw_table("items", items)
+    _lw_table("tensors", tensors)
+    _need_cuda(den)
+    if den.dtype != torch.float32 or den.dim() != 1 or den.numel() < 1:
+        raise ValueError("lw_unit_update: den must hold one float32 per slot")
+    args = (n, ptr(items), items.shape[0], ptr(tensors), tensors.shape[0], ptr(den), den.numel(), float(beta1), float(lr), float(weight_decay),
+            int(wd_eps is not None), float(wd_eps or 0.0), float(grad_scale))
+    if ema is None:
+        check(_L().mi355_lw_unit_update(int(rule), ptr(p), ptr(g), ptr(m), *args, cur_stream()))
+        return
+    _flat_f32(n, ema=ema)
+    check(_L().mi355_lw_unit_update_ema(int(rule), ptr(p), ptr(g), ptr(m), ptr(ema), *args, float(ema_decay), cur_stream()))
+
+
 # ---- sharpness-aware minimization (include/mi355rn.h, csrc/optim_sam.hip): the SAMOriginal callback of the reference -----------------------
 def _sam_kind(kind):
     _need_cuda(kind)

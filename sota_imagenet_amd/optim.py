@@ -12,7 +12,9 @@ zero_grad, re-planning after load_state_dict); their per-parameter state is laid
 MADGRAD and AdaiS are the reference's own optimizers (sota_imagenet/optimizers.py) on the same planner: MADGRAD is one launch per range,
 AdaiS three stages (moments + partial sums, the global mean, the update) because its momentum depends on a statistic of all parameters.
 NovogradApex, MyNovograd, AdamLayerwise and MyAdai (the reference's layer-wise optimizers) use one statistic PER TENSOR: they do not merge ranges
-but cut every parameter's own range into work items and run three stages over that table (csrc/optim_lw.hip).  That plan — the placement rule,
+but cut every parameter's own range into work items and run three stages over that table (csrc/optim_lw.hip).  With unitwise_norm=True
+NovogradApex and MyNovograd take the statistic per output unit instead (one slot per filter of a conv or row of the FC; the pieces and slots of
+item_plan.plan_units).  That plan — the placement rule,
 the storage pairs, the work items, the packed records — lives in item_plan.py, which the SAM callbacks build on as well.
 """
 from collections import namedtuple
@@ -22,7 +24,7 @@ import torch
 from torch.optim import Optimizer
 
 from . import ops
-from .item_plan import TENSOR_FIELDS, dense_range, flat_views, pack_records, place, storage_pairs
+from .item_plan import TENSOR_FIELDS, dense_range, flat_views, pack_records, place, plan_units, storage_pairs, unit_len
 from .item_plan import plan_items as lw_plan_items  # noqa: F401  (the name its callers know)
 
 
@@ -450,6 +452,15 @@ def _runs(indices, keys):
 _LwSeg = namedtuple("_LwSeg", "p g m ema items by_group")
 
 
+def _unit_strides(ndim):
+    """strides of the view that shows one value per slot in a tensor's own shape: 1 on dim 0 of a unit-wise tensor, 0 everywhere else"""
+    return ((1,) + (0,) * (ndim - 1)) if ndim > 1 else (0,) * ndim
+
+
+# the same for a unit-wise plan: + (first piece, end piece), (first whole item, end) and the pair's first entry of the partial sums
+_LwUnitSeg = namedtuple("_LwUnitSeg", "p g m ema items by_group pieces whole partial0")
+
+
 class _Layerwise(_FlatOptimizer):
     """what NovogradApex, MyNovograd, AdamLayerwise and MyAdai share: the work-item plan (plan_tables, the pure host part on item_plan.py;
     _build_plans adds what needs the device: one _LwSeg per storage pair) and the three stages of csrc/optim_lw.hip —
@@ -458,7 +469,16 @@ class _Layerwise(_FlatOptimizer):
     The first moment is a view of a flat array as in the other native optimizers.  The second moment, which the reference keeps as a
     full-size tensor holding ONE value, is one float32 slot per tensor on the device: state[p][key] is a stride-0 view of it with the
     parameter's shape, state_dict() returns dense copies (the reference loads them), load_state_dict() accepts the reference's dense tensors
-    (checked once for min == max) and keeps element 0."""
+    (checked once for min == max) and keeps element 0.
+
+    unitwise_norm=True (NovogradApex and MyNovograd; the reference's optimizers.py:16-22) takes the statistic per SLOT — a whole tensor with
+    ndim <= 1, one index of dim 0 otherwise — and it is the NORM of the slot, not the sum of squares, for the 1-D tensors too.  The plan is
+    plan_unit_tables; a step is unit sums and 1-D sums per storage pair, one lw_unit_coef and one lw_unit_update per param group: 4 launches on
+    a flat model in one group, 1 + 1 + 2 + 2 with filter_from_wd.  The second moment is one float32 per slot on the device; state[p][key] is a
+    strided view of it with the parameter's shape (stride 1 on dim 0 and 0 elsewhere, all zeros for the 1-D tensors); load_state_dict()
+    accepts the reference's dense tensors, keeps the first element of every unit and allows inside a unit the relative spread the
+    reference's own float32 run shows: 2^-23 / (1 - beta2), one rounding per step damped by beta2.  There is no CPU path: with
+    unitwise_norm=True the constructor and add_param_group raise NotImplementedError for any parameter that is not a CUDA tensor."""
 
     _rule = ops.LW_NORMGRAD
     _m_key, _v_key = "exp_avg", "exp_avg_sq"
@@ -488,12 +508,108 @@ class _Layerwise(_FlatOptimizer):
                     pairs=[(lo, hi, i0, i1, [(gi, spans[a][0], sum(spans[b])) for gi, a, b in _runs(ts, group_of)], ts) for lo, hi, i0, i1, ts in pairs],
                     groups=[(gi, a, b + 1) for gi, a, b in _runs(range(len(tensors)), group_of)])
 
+    @staticmethod
+    def plan_unit_tables(tensors, W):
+        """the host side of a unit-wise plan.  tensors: [(param base, grad base, first elem, numel, group index, unit_len)] in param-group
+        order.  Returns item_plan.plan_units' dict (items, tensors, pieces, whole, slots, pairs) with two additions: every entry of `pairs`
+        ends with [(group index, first item, end item)] of the groups present in the pair, and
+          groups   [(group index, first slot, end slot)] of the groups present: slots are numbered tensor by tensor in param-group order, so the
+                   slots of a group are consecutive"""
+        tab = plan_units([t[:4] + (t[5],) for t in tensors], W)
+        lw = _Layerwise.plan_tables([t[:5] for t in tensors], W)
+        assert lw["items"] == tab["items"]
+        ends = [s0 + t[3] // t[5] for (_, _, s0), t in zip(tab["tensors"], tensors)]
+        tab["pairs"] = [pr + (lp[4],) for pr, lp in zip(tab["pairs"], lw["pairs"])]
+        tab["groups"] = [(gi, tab["tensors"][a][2], ends[b - 1]) for gi, a, b in lw["groups"]]
+        return tab
+
+    def _check_unit_placement(self, group):
+        """unitwise_norm=True: placement is checked when the parameters arrive (there is no CPU path to fall back to)"""
+        for p in group["params"]:
+            if not p.is_cuda:
+                raise NotImplementedError(f"unitwise_norm=True has no CPU path: {type(self).__name__} needs CUDA parameters, got a "
+                                          f"{p.device.type} tensor of shape {tuple(p.shape)}")
+
+    def add_param_group(self, group):
+        super().add_param_group(group)
+        if getattr(self, "unitwise_norm", False):
+            self._check_unit_placement(self.param_groups[-1])
+
+    def _build_unit_plans(self, entries):
+        dev, name = entries[0][5].device, type(self).__name__
+        tab = self.plan_unit_tables([e[:5] + (unit_len(e[5].shape, e[5].stride(), True, name),) for e in entries], ops.lw_item_elems())
+        self._items, self._tensors = pack_records(tab["items"], dev), pack_records(tab["tensors"], dev)
+        self._pieces = pack_records(tab["pieces"], dev) if tab["pieces"] else None
+        self._whole = pack_records(tab["whole"], dev) if tab["whole"] else None
+        ns = len(tab["slots"])
+        self._slots = torch.tensor(tab["slots"], dtype=torch.int32, device=dev)
+        self._partial = torch.zeros(len(tab["pieces"]) + len(tab["whole"]), dtype=torch.float64, device=dev)
+        self._sums = torch.zeros(ns, dtype=torch.float64, device=dev)  # S per slot of the last step
+        self._den = torch.zeros(ns, dtype=torch.float32, device=dev)
+        self.slot_ranges = [(s0, e[3] // u) for (_, u, s0), e in zip(tab["tensors"], entries)]  # per planned tensor: (first slot, slots)
+        self._v = self._make_unit_v(entries, dev, ns)
+        self._coefs = tab["groups"]
+        for lo, hi, i0, i1, pc, wh, k0, ts, by_group in tab["pairs"]:
+            fp, fg, fm = self._pair_state(entries, ts, lo, hi, dev)
+            self._segs.append(_LwUnitSeg(fp, fg, fm, self._ema_slice(entries[ts[0]][0], lo, hi), (i0, i1), by_group, pc, wh, k0))
+
+    def _pair_state(self, entries, ts, lo, hi, dev):
+        """the flat arrays of one storage pair over [lo, hi): parameters, gradients and a new first moment that state[p] views"""
+        ps = [entries[t][5] for t in ts]
+        fp, fg = flat_views(ps[0], lo, hi)
+        fm = torch.zeros(hi - lo, dtype=torch.float32, device=dev)
+        for p in ps:
+            fresh = self._m_key not in self.state[p]
+            self._state_view(fm, p, lo, self._m_key)
+            if fresh:
+                self.state[p].setdefault("step", 0)
+        return fp, fg, fm
+
+    def _make_unit_v(self, entries, dev, n_slots):
+        """one float32 per slot; state[p][v key] becomes a view of the tensor's slots with the parameter's shape: stride 1 on dim 0 (a unit-wise
+        tensor) and 0 elsewhere.  A tensor already there gives the first element of every unit."""
+        v = torch.empty(n_slots, dtype=torch.float32, device=dev)
+        for (s0, cnt), (_, _, _, _, gi, p) in zip(self.slot_ranges, entries):
+            old = self.state[p].get(self._v_key)
+            if old is None:
+                v[s0:s0 + cnt] = self._v_init(self.param_groups[gi])
+            else:
+                v[s0:s0 + cnt] = old.reshape(cnt, -1)[:, 0].to(device=dev, dtype=torch.float32)
+            self.state[p][self._v_key] = torch.as_strided(v, p.shape, _unit_strides(p.dim()), s0)
+        return v
+
+    def _unit_step(self, gs):
+        src_scale = 1.0 if self._param_stat else gs
+        nt, ns = self._tensors.shape[0], self._den.numel()
+        for seg in self._segs:
+            (pa, pb), (wa, wb), k0 = seg.pieces, seg.whole, seg.partial0
+            k1 = k0 + pb - pa
+            src = seg.p if self._param_stat else seg.g
+            if pb > pa:
+                ops.lw_unit_sumsq(src, self._pieces[pa:pb], self._partial[k0:k1], ns, scale=src_scale)
+            if wb > wa:
+                ops.lw_sumsq(src, self._whole[wa:wb], self._partial[k1:k1 + wb - wa], nt, scale=src_scale)
+        for gi, s0, s1 in self._coefs:
+            _, _, b2, eps = self._coef_args(self.param_groups[gi])
+            ops.lw_unit_coef(self._partial, self._slots[s0:s1], self._v[s0:s1], self._den[s0:s1], self._sums[s0:s1], b2, eps)
+        for seg in self._segs:
+            for gi, i0, i1 in seg.by_group:
+                group = self.param_groups[gi]
+                ops.lw_unit_update(self._rule, seg.p, seg.g, seg.m, self._items[i0:i1], self._tensors, self._den, self._coef_args(group)[1],
+                                   float(group["lr"]), float(group["weight_decay"]), wd_eps=self._wd_eps(), grad_scale=gs, ema=seg.ema,
+                                   ema_decay=self._ema[2] if seg.ema is not None else 0.0)
+
     def _build_plans(self):
         entries = self._entries(aligned=True, one_device=True)
         self._planned = [e[5] for e in entries]
         self._segs, self._coefs = [], []
         if not entries:
             self._plans = []
+            return
+        if getattr(self, "unitwise_norm", False):
+            self._build_unit_plans(entries)
+            self._check_ema([seg.ema for seg in self._segs])
+            self._plans = self._segs
             return
         dev, nt = entries[0][5].device, len(entries)
         tab = self.plan_tables([e[:5] for e in entries], ops.lw_item_elems())
@@ -505,14 +621,7 @@ class _Layerwise(_FlatOptimizer):
         self._v = self._make_v(entries, dev)
         self._coefs = tab["groups"]
         for lo, hi, i0, i1, by_group, ts in tab["pairs"]:
-            ps = [entries[t][5] for t in ts]
-            fp, fg = flat_views(ps[0], lo, hi)
-            fm = torch.zeros(hi - lo, dtype=torch.float32, device=dev)
-            for p in ps:
-                fresh = self._m_key not in self.state[p]
-                self._state_view(fm, p, lo, self._m_key)
-                if fresh:
-                    self.state[p].setdefault("step", 0)
+            fp, fg, fm = self._pair_state(entries, ts, lo, hi, dev)
             self._segs.append(_LwSeg(fp, fg, fm, self._ema_slice(entries[ts[0]][0], lo, hi), (i0, i1), by_group))
         self._check_ema([seg.ema for seg in self._segs])
         self._plans = self._segs
@@ -544,6 +653,11 @@ class _Layerwise(_FlatOptimizer):
         if not self._planned:
             return loss
         gs = float(self.grad_scale)
+        if getattr(self, "unitwise_norm", False):
+            self._unit_step(gs)
+            for p in self._planned:
+                self.state[p]["step"] += 1
+            return loss
         nt = self._sums.numel()
         for seg in self._segs:
             i0, i1 = seg.items
@@ -571,13 +685,29 @@ class _Layerwise(_FlatOptimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         loaded = [(p, st[self._v_key]) for p, st in self.state.items() if torch.is_tensor(st.get(self._v_key))]
-        if loaded:
+        if loaded and getattr(self, "unitwise_norm", False):
+            self._load_unit_v(loaded)
+        elif loaded:
             # the reference's tensors hold one value each: checked here, once, then element 0 is kept
             spread = torch.stack([(t.max() - t.min()).float() for _, t in loaded])
             if bool((spread != 0).any()):
                 raise ValueError(f"{type(self).__name__}.load_state_dict: {self._v_key} must hold one value per tensor (min == max)")
             for p, t in loaded:
                 self.state[p][self._v_key] = t.reshape(-1)[0].clone().expand(t.shape)
+
+    def _load_unit_v(self, loaded):
+        """the reference's dense second moments: one value per unit up to the jitter its own float32 run shows (_foreach_add_ rounds its vector
+        body and its scalar tail differently) — a relative spread of 2^-23 / (1 - beta2) inside a unit, beyond which ValueError.  The first
+        element of every unit is kept; a layer-wise state (one value per tensor) loads as it is."""
+        beta2 = {id(p): float(self._coef_args(g)[2]) for g in self.param_groups for p in g["params"]}
+        rows = [(t.reshape(t.shape[0] if t.dim() > 1 else 1, -1), 2.0 ** -23 / (1.0 - beta2[id(p)])) for p, t in loaded]
+        bad = torch.stack([((r.max(1).values - r.min(1).values).double() > tol * r.abs().max(1).values.double()).any() for r, tol in rows])
+        if bool(bad.any()):
+            raise ValueError(f"{type(self).__name__}.load_state_dict: {self._v_key} must hold one value per unit (a relative spread inside a unit "
+                             "of at most 2^-23 / (1 - beta2))")
+        for (p, t), (r, _) in zip(loaded, rows):
+            first = r[:, 0].clone()
+            self.state[p][self._v_key] = torch.as_strided(first, t.shape, _unit_strides(t.dim()))
 
 
 def _lw_checks(lr, eps, betas):
@@ -595,15 +725,14 @@ class NovogradApex(_Layerwise):
     """the reference's src.optimizers.NovogradApex (sota_imagenet/optimizers.py:189-290; recipe configs/hydra_exp/46.r50_nov.yaml): the first
     moment of the gradient divided by sqrt of the running SUM of squares of the tensor's gradient; decoupled weight decay, or with wd_eps a
     decay of |p| - wd_eps only (p -= lr*wd*max(|p| - wd_eps, 0)*sign(p)).  Signature, defaults, checks and state (step: int, exp_avg,
-    exp_avg_sq) are the reference's.  unitwise_norm (recipe 48) needs a per-output-channel reduction and is not on the hot path."""
+    exp_avg_sq) are the reference's.  unitwise_norm=True takes the NORM of the gradient per output unit instead (see _Layerwise): native on CUDA
+    parameters only — there is no CPU path, the constructor raises NotImplementedError for anything else."""
 
     def __init__(self, params, lr=1e-3, betas=(0.95, 0), eps=1e-8, weight_decay=0, ema_norm_init=1e-3, unitwise_norm=False, wd_eps=None):
         _lw_checks(lr, eps, betas)
-        if unitwise_norm:
-            raise NotImplementedError("unitwise_norm=True is not on the hot path")
+        self.unitwise_norm = unitwise_norm  # (before the groups arrive: add_param_group checks their placement)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.ema_norm_init = ema_norm_init
-        self.unitwise_norm = unitwise_norm
         self.wd_eps = wd_eps
 
     def _coef_args(self, group):
@@ -634,7 +763,9 @@ class MyNovograd(_Layerwise):
     """the reference's src.optimizers.MyNovograd (sota_imagenet/optimizers.py:35-161; recipe configs/hydra_exp/47.r50_my-nov.yaml): the update
     is the first moment of the gradient divided by sqrt of a running sum of squares — which the class takes of the PARAMETER, not of the gradient
     (its grad_norms are built from params_with_grad, :138).  Reproduced as it is.  State keys are ema_grad and ema_norm; eps is an attribute of
-    the optimizer and ema_norm_init a group key, as there.  unitwise_norm is not on the hot path."""
+    the optimizer and ema_norm_init a group key, as there.  unitwise_norm=True (recipe configs/hydra_exp/48.r50_my-nov-unit.yaml) takes the NORM of
+    the parameter per output unit instead (see _Layerwise): native on CUDA parameters only — there is no CPU path, the constructor raises
+    NotImplementedError for anything else."""
 
     _rule = ops.LW_NOVOGRAD
     _m_key, _v_key = "ema_grad", "ema_norm"
@@ -651,11 +782,9 @@ class MyNovograd(_Layerwise):
             raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        if unitwise_norm:
-            raise NotImplementedError("unitwise_norm=True is not on the hot path")
+        self.unitwise_norm = unitwise_norm  # (before the groups arrive: add_param_group checks their placement)
         super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay, ema_norm_init=ema_norm_init))
         self.eps = eps
-        self.unitwise_norm = unitwise_norm
 
     def _v_init(self, group):
         return group["ema_norm_init"]
