@@ -369,6 +369,52 @@ int mi355_lw_unit_update_ema(int rule, float* p, const float* g, float* m, float
                              const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay,
                              int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream);
 
+/* AdamP (`_target_: adamp.AdamP`, the reference's recipes configs/hydra_exp/51.r50_adamp.yaml:19-22 and 52.r50_adamp_low-eps.yaml:20-23) on
+ * flat fp32 arrays: Adam whose update loses its component along the weight, and whose weight decay is scaled by wd_ratio, where gradient and weight
+ * are nearly orthogonal.  PROVENANCE: the `adamp` package is neither part of the reference tree nor available where this was written; the rule
+ * is the published adamp.AdamP.step (package 0.3.0) written down from memory of the public package, and parity is against a torch restatement of
+ * it (tests/adamp_common.py), UNPINNED against the package itself.  pytorch_tools.optim.adamp.AdamP (recipes 12, 13) is a modified variant whose
+ * code is not available and stays unresolved.  Per tensor, with bc1 = 1 - beta1^step, bc2 = 1 - beta2^step and ge = g*grad_scale:
+ *   m = beta1*m + (1 - beta1)*ge;  v = beta2*v + ((1 - beta2)*ge)*ge;  den = sqrt(v)/sqrt(bc2) + eps;  u = m/den
+ *                                                                      (nesterov: u = (beta1*m + (1 - beta1)*ge)/den)
+ *   ndim > 1: for rows = the output units (one index of dim 0), then for the whole tensor as one row:
+ *               cos = |sum(ge*p)| / (max(||ge||, eps) * max(||p||, eps)) per row;  if max over the rows < delta / sqrt(row length):
+ *                 d = ||p||_row + eps;  u = u - (p/d) * (sum over the row of (p/d)*u);  ratio = wd_ratio;  stop
+ *   p = p*(1 - lr*wd*ratio)  (wd > 0);   p = p + (-lr/bc1)*u        (ratio = 1 without a projection; the projection uses p before the decay)
+ * Three stages on one stream, nothing read back, no floating-point atomics, over items[], pieces[], slots[] and tensors[] of the unit-wise
+ * optimizers above (every tensor with ndim > 1 taken unit by unit, every other tensor one whole slot) and
+ *   decide[]  { int32 slot0; int32 n_slots; int32 unit_len; int32 kind }   per tensor; kind 1: ndim > 1, 0: any other tensor
+ * The element arithmetic is float32, one rounding per operation, written once for (a) and (c); beta1, 1 - beta1, beta2, 1 - beta2, sqrt(bc2) and
+ * -lr/bc1 are formed in double and rounded once.
+ *  (a) mi355_adamp_unit_sums, once per storage pair and param group over the pieces of its ndim > 1 tensors; reads p, g, m, v and writes none of
+ *      them: u from the OLD m, v in registers, partial[4k .. 4k+3] = sums over pieces[k] of (ge^2, p^2, ge*p, p*u), operands converted to double
+ *      before the product, in a fixed order; one wave per piece.
+ *  (b) mi355_adamp_coef, once per param group, one workgroup per record of decide[] (the group's slice; coef[] and slots[] are the WHOLE arrays,
+ *      wdf[] and mode[] the group's slices), in double: the slot sums = the slot's entries of partial[] in a fixed order, the layer sums = the slot
+ *      sums in a fixed order;  mode 1 (the units) if max cos_slot < delta/sqrt(unit_len): coef[slot] = (d, s) = (sqrt(Spp) + eps, Spu/(sqrt(Spp) + eps))
+ *      per slot;  else mode 2 (the layer) if cos_layer < delta/sqrt(n_slots*unit_len): every slot gets the layer's (d, s);  else mode 0 and (1, 0),
+ *      as for kind 0.  wdf[t] = (float)(1 - lr*wd*(mode ? wd_ratio : 1)), exactly 1 for wd <= 0;  mode[t] = mode.
+ *      s = sum(p*u)/d where the rule above has sum((p/d)*u): a deliberate rounding-level deviation that saves a second reduction pass.
+ *  (c) mi355_adamp_update, once per storage pair and param group over that group's items; p, m, v in place, g read-only:
+ *        (m, v, u) as in (a);  pn = p/d;  u = u - pn*s;  p = p*wdf[t];  p = p + (float)(-lr/bc1)*u     with (d, s) = coef[slot],
+ *        slot = tensors[t].slot0 + (element offset inside tensor t) / tensors[t].unit_len, element by element where an item spans units.
+ *      mi355_adamp_update_ema: + ema += (1 - ema_decay) * (p_new - ema) in the same pass.
+ * 16 B / element in (a) + 28 B / element in (c), 36 B with the average.  A record that does not lie inside the arrays of the launch is skipped by
+ * the kernels.  Each fails (-1) before any launch on a null or misaligned pointer (16 bytes for the arrays and the 16-byte tables, 8 for
+ * partial[], slots[] and coef[], 4 for wdf[] and mode[]), an empty table, betas outside [0, 1), eps / lr / delta / wd_ratio negative or not
+ * finite, weight_decay not finite, step < 1, grad_scale not finite. */
+int mi355_adamp_unit_sums(const float* p, const float* g, const float* m, const float* v, size_t n, const void* pieces, size_t n_pieces,
+                          int n_slots, double beta1, double beta2, double eps, int step, int nesterov, float grad_scale, void* partial,
+                          void* stream);
+int mi355_adamp_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, const void* decide, size_t n_tensors, float* coef,
+                     float* wdf, int* mode, double lr, double weight_decay, double eps, double delta, double wd_ratio, void* stream);
+int mi355_adamp_update(float* p, const float* g, float* m, float* v, size_t n, const void* items, size_t n_items, const void* tensors,
+                       int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1, double beta2, double eps,
+                       int step, int nesterov, float grad_scale, void* stream);
+int mi355_adamp_update_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
+                           const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1,
+                           double beta2, double eps, int step, int nesterov, float grad_scale, float ema_decay, void* stream);
+
 /* The SAMOriginal callback of the reference (adaptive sharpness-aware minimization, sota_imagenet/callbacks.py:279-337; recipe
  * configs/hydra_exp/49.r50_nov-adam.yaml:46-48) on flat fp32 arrays: between the first backward and the optimizer step every parameter moves
  * along its gradient, weighted by its own magnitude and normalised by ONE statistic of all tensors; after a second forward / backward there

@@ -60,6 +60,10 @@ CALLBACK_TARGET_ALIASES = {
     "sota_imagenet.callbacks.SAM": "sota_imagenet_amd.callbacks.SAM",
 }
 
+# AdamP of the public `adamp` package (recipes 51, 52), consulted after the three tables above, whose contents existing tests pin.
+# pytorch_tools.optim.adamp.AdamP (recipes 12, 13) is a modified variant whose code is not available: it stays unresolved, on purpose.
+ADAMP_TARGET_ALIASES = {"adamp.AdamP": "sota_imagenet_amd.optim.AdamP"}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -296,7 +300,8 @@ def validate(cfg):
 
 
 def resolve_target(path):
-    path = TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path, path)
+    path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
+            or ADAMP_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

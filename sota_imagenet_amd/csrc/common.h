@@ -361,6 +361,15 @@ int launch_lw_unit_coef(const double* partial, size_t n_partial, const void* slo
 int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
                           const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double wd, int soft_wd,
                           double wd_eps, float gscale, float ema_decay, hipStream_t st);
+// optim_adamp.hip: AdamP's three stages over the same tables plus one record { slot0, n_slots, unit_len, kind } per tensor for the decision
+int launch_adamp_unit_sums(const float* p, const float* g, const float* m, const float* v, size_t n, const void* pieces, size_t n_pieces,
+                           int n_slots, double beta1, double beta2, double eps, int step, int nesterov, float gscale, double* partial,
+                           hipStream_t st);
+int launch_adamp_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, const void* tensors, size_t n_tensors,
+                      float* coef, float* wdf, int* mode, double lr, double wd, double eps, double delta, double wd_ratio, hipStream_t st);
+int launch_adamp_update(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
+                        const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1,
+                        double beta2, double eps, int step, int nesterov, float gscale, float ema_decay, hipStream_t st);
 // optim_sam.hip: the four stages of the SAMOriginal callback over the same work-item table (kind[tensor]: 1 = weight, 0 = other)
 int launch_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
                      float gscale, double* partial, hipStream_t st);

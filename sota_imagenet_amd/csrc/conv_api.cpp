@@ -623,6 +623,31 @@ int mi355_lw_unit_update_ema(int rule, float* p, const float* g, float* m, float
                                grad_scale, ema_decay, (hipStream_t)stream);
 }
 
+int mi355_adamp_unit_sums(const float* p, const float* g, const float* m, const float* v, size_t n, const void* pieces, size_t n_pieces,
+                          int n_slots, double beta1, double beta2, double eps, int step, int nesterov, float grad_scale, void* partial,
+                          void* stream) {
+  return launch_adamp_unit_sums(p, g, m, v, n, pieces, n_pieces, n_slots, beta1, beta2, eps, step, nesterov, grad_scale, (double*)partial,
+                                (hipStream_t)stream);
+}
+int mi355_adamp_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, const void* decide, size_t n_tensors, float* coef,
+                     float* wdf, int* mode, double lr, double weight_decay, double eps, double delta, double wd_ratio, void* stream) {
+  return launch_adamp_coef((const double*)partial, n_partial, slots, n_slots, decide, n_tensors, coef, wdf, mode, lr, weight_decay, eps, delta,
+                           wd_ratio, (hipStream_t)stream);
+}
+int mi355_adamp_update(float* p, const float* g, float* m, float* v, size_t n, const void* items, size_t n_items, const void* tensors,
+                       int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1, double beta2, double eps,
+                       int step, int nesterov, float grad_scale, void* stream) {
+  return launch_adamp_update(p, g, m, v, nullptr, n, items, n_items, tensors, n_tensors, coef, n_slots, wdf, lr, beta1, beta2, eps, step,
+                             nesterov, grad_scale, 0.f, (hipStream_t)stream);
+}
+int mi355_adamp_update_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
+                           const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1,
+                           double beta2, double eps, int step, int nesterov, float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "adamp_update_ema: null ema");
+  return launch_adamp_update(p, g, m, v, ema, n, items, n_items, tensors, n_tensors, coef, n_slots, wdf, lr, beta1, beta2, eps, step, nesterov,
+                             grad_scale, ema_decay, (hipStream_t)stream);
+}
+
 int mi355_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
                     float grad_scale, void* partial, void* stream) {
   return launch_sam_sumsq(p, g, n, items, n_items, kind, n_tensors, eta, grad_scale, (double*)partial, (hipStream_t)stream);

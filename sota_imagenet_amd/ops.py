@@ -526,6 +526,67 @@ def lw_unit_update(rule, p, g, m, items, tensors, den, beta1, lr, weight_decay, 
     check(_L().mi355_lw_unit_update_ema(int(rule), ptr(p), ptr(g), ptr(m), ptr(ema), *args, float(ema_decay), cur_stream()))
 
 
+# ---- AdamP (include/mi355rn.h, csrc/optim_adamp.hip): Adam with the projection of adamp.AdamP, restated from the published package --------------
+def _adamp_coef_arrays(name, coef, wdf):
+    _need_cuda(coef, wdf)
+    if coef.dtype != torch.float32 or coef.dim() != 2 or coef.shape[1] != 2 or coef.shape[0] < 1 or not coef.is_contiguous():
+        raise ValueError(f"{name}: coef must be a contiguous CUDA float32 tensor [n_slots, 2], got {coef.dtype} {tuple(coef.shape)}")
+    if wdf.dtype != torch.float32 or wdf.dim() != 1 or wdf.numel() < 1:
+        raise ValueError(f"{name}: wdf must hold one float32 per tensor")
+
+
+def adamp_unit_sums(p, g, m, v, pieces, partial, n_slots, step, betas=(0.9, 0.999), eps=1e-8, nesterov=False, grad_scale=1.0):
+    """stage (a): partial[k] = (sum ge^2, sum p^2, sum ge*p, sum p*u) over piece k { off, len, slot }, in double, ge = g*grad_scale and u the Adam
+    direction of this step formed in registers from the OLD m and v (neither is written); step: the count after this step's increment;
+    partial: float64 [n_pieces, 4]"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, m=m, v=v)
+    _lw_table("pieces", pieces)
+    _need_cuda(partial)
+    if partial.dtype != torch.float64 or partial.numel() != 4 * pieces.shape[0] or not partial.is_contiguous():
+        raise ValueError(f"partial: expected {pieces.shape[0]} contiguous quadruples of float64, got {partial.dtype} with {partial.numel()} elements")
+    check(_L().mi355_adamp_unit_sums(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(pieces), pieces.shape[0], int(n_slots), float(betas[0]),
+                                     float(betas[1]), float(eps), int(step), int(bool(nesterov)), float(grad_scale), ptr(partial), cur_stream()))
+
+
+def adamp_coef(partial, slots, decide, coef, wdf, mode, lr, weight_decay, eps=1e-8, delta=0.1, wd_ratio=0.1):
+    """stage (b) for the tensors of one param group: decide = their records { slot0, n_slots, unit_len, kind } (CUDA int32 [n, 4]); partial
+    (float64 [entries, 4]), slots (int32 [n_slots, 2]) and coef (float32 [n_slots, 2]) are the WHOLE arrays, wdf (float32) and mode (int32) the
+    group's slices.  Writes coef[slot] = (d, s), wdf[t] and mode[t] (0: none, 1: the units, 2: the layer)"""
+    _unit_slots("adamp_coef", slots)
+    _adamp_coef_arrays("adamp_coef", coef, wdf)
+    _need_cuda(partial, decide, mode)
+    nt = decide.shape[0]
+    if decide.dtype != torch.int32 or decide.dim() != 2 or decide.shape[1] != 4 or nt < 1:
+        raise ValueError(f"adamp_coef: decide must be a contiguous CUDA int32 tensor [n, 4], got {decide.dtype} {tuple(decide.shape)}")
+    if partial.dtype != torch.float64 or partial.numel() < 4 or partial.numel() % 4:
+        raise ValueError("adamp_coef: partial must be a contiguous float64 tensor of quadruples")
+    if coef.shape[0] != slots.shape[0] or wdf.numel() != nt or mode.dtype != torch.int32 or mode.numel() != nt:
+        raise ValueError("adamp_coef: coef must hold one pair per slot, wdf one float32 and mode one int32 per tensor record")
+    check(_L().mi355_adamp_coef(ptr(partial), partial.numel() // 4, ptr(slots), slots.shape[0], ptr(decide), nt, ptr(coef), ptr(wdf), ptr(mode),
+                                float(lr), float(weight_decay), float(eps), float(delta), float(wd_ratio), cur_stream()))
+
+
+def adamp_update(p, g, m, v, items, tensors, coef, wdf, step, lr, betas=(0.9, 0.999), eps=1e-8, nesterov=False, grad_scale=1.0, ema=None,
+                 ema_decay=0.0):
+    """stage (c) for the work items of one param group; p, g, m, v (and ema): the flat fp32 arrays the item offsets count from; tensors: the
+    records { start, unit_len, slot0 } of ALL tensors; coef [n_slots, 2] and wdf [n_tensors]: the whole arrays of stage (b)"""
+    n = p.numel()
+    _flat_f32(n, p=p, g=g, m=m, v=v)
+    _lw_table("items", items)
+    _lw_table("tensors", tensors)
+    _adamp_coef_arrays("adamp_update", coef, wdf)
+    if wdf.numel() != tensors.shape[0]:
+        raise ValueError("adamp_update: wdf must hold one float32 per tensor record")
+    args = (n, ptr(items), items.shape[0], ptr(tensors), tensors.shape[0], ptr(coef), coef.shape[0], ptr(wdf), float(lr), float(betas[0]),
+            float(betas[1]), float(eps), int(step), int(bool(nesterov)), float(grad_scale))
+    if ema is None:
+        check(_L().mi355_adamp_update(ptr(p), ptr(g), ptr(m), ptr(v), *args, cur_stream()))
+        return
+    _flat_f32(n, ema=ema)
+    check(_L().mi355_adamp_update_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), *args, float(ema_decay), cur_stream()))
+
+
 # ---- sharpness-aware minimization (include/mi355rn.h, csrc/optim_sam.hip): the SAMOriginal callback of the reference -----------------------
 def _sam_kind(kind):
     _need_cuda(kind)

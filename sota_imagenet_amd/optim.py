@@ -1,4 +1,4 @@
-"""`SGD`, `Adam`, `AdamW`, `MADGRAD`, `AdaiS`, `NovogradApex`, `MyNovograd`, `AdamLayerwise` and `MyAdai` plugins: torch.optim-compatible optimizers whose step is fused HIP kernels over flat ranges.
+"""`SGD`, `Adam`, `AdamW`, `MADGRAD`, `AdaiS`, `NovogradApex`, `MyNovograd`, `AdamLayerwise`, `MyAdai` and `AdamP` plugins: torch.optim-compatible optimizers whose step is fused HIP kernels over flat ranges.
 
 Drop-in for `_target_: torch.optim._multi_tensor.SGD` (sota_imagenet/arg_parser.py:136-138; r50 recipe adds
 momentum 0.9 / weight_decay 3e-5, configs/hydra_exp/1.r50_baseline.yaml:29-31; built at train.py:92 from
@@ -16,6 +16,9 @@ but cut every parameter's own range into work items and run three stages over th
 NovogradApex and MyNovograd take the statistic per output unit instead (one slot per filter of a conv or row of the FC; the pieces and slots of
 item_plan.plan_units).  That plan — the placement rule,
 the storage pairs, the work items, the packed records — lives in item_plan.py, which the SAM callbacks build on as well.
+AdamP (`adamp.AdamP`, recipes 51 and 52; restated from the published package, which is not available here: see the class) runs on the same
+unit-wise tables: per-piece sums of four products, one decision per tensor on the device, and an update that takes each element's projection
+coefficients from its slot (csrc/optim_adamp.hip).
 """
 from collections import namedtuple
 from itertools import groupby
@@ -834,3 +837,180 @@ class MyAdai(_Layerwise):
 
     def load_state_dict(self, state_dict):
         _FlatOptimizer.load_state_dict(self, state_dict)
+
+
+# one pair of parameter / gradient storage in an AdamP plan: the two storages as flat arrays over the pair's element range, both moments of that
+# range, the moving average's slice or None, [(group index, first item, end item)] of the groups present and the launches of stage (a):
+# [(group index, first piece, end piece, first entry of the partial sums)]
+_AdamPSeg = namedtuple("_AdamPSeg", "p g m v ema by_group sums")
+
+
+class AdamP(_FlatOptimizer):
+    """`adamp.AdamP` (the reference's recipes configs/hydra_exp/51.r50_adamp.yaml and 52.r50_adamp_low-eps.yaml): Adam whose update loses its
+    component along the weight, and whose weight decay is scaled by wd_ratio, for every tensor with more than one dimension whose gradient is
+    nearly orthogonal to it — per output unit first, then per whole tensor; cosine under delta / sqrt(row length).
+
+    Provenance: the `adamp` package is neither in the reference tree nor available where this was written.  The rule is the published
+    adamp.AdamP.step (package 0.3.0) written down from memory of the public package (include/mi355rn.h states it); parity is against the torch
+    restatement of tests/adamp_common.py and is unpinned against the package itself.  pytorch_tools.optim.adamp.AdamP (recipes 12, 13) is a
+    modified variant whose code is not available: it does not resolve.
+
+    Signature, group keys and state are the package's — state[p] = {step: int, exp_avg, exp_avg_sq}, the tensors being views of flat arrays, one
+    per storage pair — so a state_dict() is meant to move both ways.  A step is three stages of csrc/optim_adamp.hip on the current stream with
+    nothing read back (the package asks the host `cosine_sim.max() < ...` per tensor): adamp_unit_sums per storage pair and param group over the
+    pieces of the group's ndim > 1 tensors, adamp_coef per param group, adamp_update per storage pair and param group: 3 launches on a flat model
+    in one group, at most 5 with filter_from_wd (its no-decay group holds 1-D tensors only: no pieces).  All planned tensors of one group share
+    `step`; a loaded state that differs inside a group raises ValueError.  There is no CPU path: parameters that are not CUDA tensors raise
+    NotImplementedError at construction and in add_param_group."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, delta=0.1, wd_ratio=0.1, nesterov=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        for i, b in enumerate(betas):
+            if not 0.0 <= float(b) < 1.0:
+                raise ValueError(f"Invalid beta parameter at index {i}: {b}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not 0.0 <= delta:
+            raise ValueError(f"Invalid delta value: {delta}")
+        if not 0.0 <= wd_ratio:
+            raise ValueError(f"Invalid wd_ratio value: {wd_ratio}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, delta=delta, wd_ratio=wd_ratio, nesterov=nesterov))
+        self._planned, self._segs, self._modes = [], [], None
+        self.slot_ranges = []
+
+    def add_param_group(self, group):
+        super().add_param_group(group)
+        for p in self.param_groups[-1]["params"]:
+            if not p.is_cuda:
+                raise NotImplementedError(f"AdamP has no CPU path: it needs CUDA parameters, got a {p.device.type} tensor of shape "
+                                          f"{tuple(p.shape)}")
+
+    @property
+    def projection_modes(self):
+        """what the last step decided, one int32 per planned tensor in param-group order, on the device: 0 no projection, 1 per output unit,
+        2 per whole tensor (None before the first step)"""
+        return self._modes
+
+    @staticmethod
+    def plan_tables(tensors, W):
+        """the host side of a plan.  tensors: [(param base, grad base, first elem, numel, group index, unit_len, kind)] in param-group order,
+        kind 1 for ndim > 1; W: ops.lw_item_elems().  Returns item_plan.plan_units' dict (items, tensors, pieces, whole, slots, pairs) and
+          decide      [(slot0, slot count, unit_len, kind)] per tensor: the records of stage (b)
+          sum_pieces  the table of stage (a): a pair's `pieces`, then — plan_units takes a tensor whose unit is the whole tensor, dim 0 of 1,
+                      through whole-tensor items — the whole items of its kind-1 tensors as pieces { off, len, slot }
+          groups      [(group index, first tensor, end tensor)] of the groups present
+        and every entry of `pairs` ends with [(group index, first item, end item)] of the groups present in the pair and the launches of stage
+        (a), [(group index, first, end in sum_pieces, first entry of the partial sums)]: consecutive records whose entries are consecutive"""
+        tab = plan_units([t[:4] + (t[5],) for t in tensors], W)
+        lw = _Layerwise.plan_tables([t[:5] for t in tensors], W)
+        assert lw["items"] == tab["items"]
+        slot0 = [r[2] for r in tab["tensors"]]
+        tab["decide"] = [(s0, t[3] // t[5], t[5], int(t[6])) for s0, t in zip(slot0, tensors)]
+        tab["groups"] = lw["groups"]
+        tensor_of_slot = [i for i, t in enumerate(tensors) for _ in range(t[3] // t[5])]
+        sum_pieces, pairs = [], []
+        for (lo, hi, i0, i1, (pa, pb), (wa, wb), k0, ts), lp in zip(tab["pairs"], lw["pairs"]):
+            # (record, its entry of the partial sums, group): the unit pieces, then the whole items of the kind-1 tensors
+            recs = [(pc, k0 + j, tensors[tensor_of_slot[pc[2]]][4]) for j, pc in enumerate(tab["pieces"][pa:pb])]
+            recs += [((o, ln, slot0[t]), k0 + pb - pa + j, tensors[t][4]) for j, (o, ln, t) in enumerate(tab["whole"][wa:wb]) if tensors[t][6]]
+            sums = []
+            for pc, k, gi in recs:
+                if sums and sums[-1][0] == gi and sums[-1][3] + sums[-1][2] - sums[-1][1] == k:
+                    sums[-1][2] += 1
+                else:
+                    sums.append([gi, len(sum_pieces), len(sum_pieces) + 1, k])
+                sum_pieces.append(pc)
+            pairs.append((lo, hi, i0, i1, (pa, pb), (wa, wb), k0, ts, lp[4], [tuple(x) for x in sums]))
+        tab["sum_pieces"], tab["pairs"] = sum_pieces, pairs
+        return tab
+
+    def _step_count(self, p):
+        return int(self.state[p].get("step", 0))
+
+    def _group_steps(self, params_of):
+        """{group index: the step count its tensors share}; ValueError where they differ inside a group"""
+        out = {}
+        for gi, ps in params_of.items():
+            counts = {self._step_count(p) for p in ps}
+            if len(counts) > 1:
+                raise ValueError(f"AdamP: the tensors of param group {gi} carry different step counts {sorted(counts)}: one launch takes one "
+                                 "bias correction")
+            out[gi] = counts.pop() if counts else 0
+        return out
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._group_steps({gi: [p for p in g["params"] if "step" in self.state.get(p, {})] for gi, g in enumerate(self.param_groups)})
+
+    def _build_plans(self):
+        entries = self._entries(aligned=True, one_device=True)
+        self._planned = [e[5] for e in entries]
+        self._segs, self._groups = [], []
+        if not entries:
+            self._plans = []
+            return
+        dev, name = entries[0][5].device, type(self).__name__
+        by_group = {}
+        for e in entries:
+            by_group.setdefault(e[4], []).append(e[5])
+        self._gstep = self._group_steps(by_group)
+        tab = self.plan_tables([e[:5] + (unit_len(e[5].shape, e[5].stride(), True, name), e[5].dim() > 1) for e in entries], ops.lw_item_elems())
+        self._items, self._tensors = pack_records(tab["items"], dev), pack_records(tab["tensors"], dev)
+        self._sum_pieces = pack_records(tab["sum_pieces"], dev) if tab["sum_pieces"] else None
+        ns, nt = len(tab["slots"]), len(entries)
+        self._slots = torch.tensor(tab["slots"], dtype=torch.int32, device=dev)
+        self._decide = torch.tensor(tab["decide"], dtype=torch.int32, device=dev)
+        self._partial = torch.zeros(len(tab["pieces"]) + len(tab["whole"]), 4, dtype=torch.float64, device=dev)
+        self._coef = torch.zeros(ns, 2, dtype=torch.float32, device=dev)
+        self._wdf = torch.ones(nt, dtype=torch.float32, device=dev)
+        self._modes = torch.zeros(nt, dtype=torch.int32, device=dev)
+        self.slot_ranges = [(s0, cnt) for s0, cnt, _, _ in tab["decide"]]  # per planned tensor: (first slot, slots)
+        self._groups = tab["groups"]
+        for lo, hi, i0, i1, _, _, _, ts, items_by_group, sums in tab["pairs"]:
+            ps = [entries[t][5] for t in ts]
+            fp, fg = flat_views(ps[0], lo, hi)
+            fm, fv = (torch.zeros(hi - lo, dtype=torch.float32, device=dev) for _ in range(2))
+            for p in ps:
+                self._state_view(fm, p, lo, "exp_avg")
+                self._state_view(fv, p, lo, "exp_avg_sq")
+                self.state[p]["step"] = self._step_count(p)
+            self._segs.append(_AdamPSeg(fp, fg, fm, fv, self._ema_slice(entries[ts[0]][0], lo, hi), items_by_group, sums))
+        self._check_ema([seg.ema for seg in self._segs])
+        self._plans = self._segs
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._plans is None:
+            self._build_plans()
+        if not self._planned:
+            return loss
+        gs, ns = float(self.grad_scale), self._coef.shape[0]
+
+        def adam(gi):
+            group = self.param_groups[gi]
+            return dict(step=self._gstep[gi] + 1, betas=group["betas"], eps=float(group["eps"]), nesterov=bool(group["nesterov"]), grad_scale=gs)
+
+        for seg in self._segs:
+            for gi, a, b, k in seg.sums:
+                ops.adamp_unit_sums(seg.p, seg.g, seg.m, seg.v, self._sum_pieces[a:b], self._partial[k:k + b - a], ns, **adam(gi))
+        for gi, t0, t1 in self._groups:
+            group = self.param_groups[gi]
+            ops.adamp_coef(self._partial, self._slots, self._decide[t0:t1], self._coef, self._wdf[t0:t1], self._modes[t0:t1], float(group["lr"]),
+                           float(group["weight_decay"]), float(group["eps"]), float(group["delta"]), float(group["wd_ratio"]))
+        for seg in self._segs:
+            for gi, i0, i1 in seg.by_group:
+                ops.adamp_update(seg.p, seg.g, seg.m, seg.v, self._items[i0:i1], self._tensors, self._coef, self._wdf,
+                                 lr=float(self.param_groups[gi]["lr"]), ema=seg.ema, ema_decay=self._ema[2] if seg.ema is not None else 0.0,
+                                 **adam(gi))
+        for gi in self._gstep:
+            self._gstep[gi] += 1
+        for p in self._planned:
+            self.state[p]["step"] += 1
+        return loss
