@@ -556,11 +556,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     pk = pk - lr * mk;
     if constexpr (EMA) ek = ek + ema_w * (pk - ek);
   };
-  if constexpr (EMA) {
-    flat_sweep(n4, n, rule, upd(p), rd(g), upd(m), upd(ema));
-  } else {
-    flat_sweep(n4, n, [&](float& pk, float& gk, float& mk) { float ek = 0.f; rule(pk, gk, mk, ek); }, upd(p), rd(g), upd(m));
-  }
+  flat_sweep(n4, n, rule, upd(p), rd(g), upd(m), upd_if<EMA>(ema));
 }
 
 __global__ void bias_slice_kernel(const float* __restrict__ tmp, int ld, const float* __restrict__ bias,

@@ -56,11 +56,7 @@ template <bool DECOUPLED, bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, float* __restrict__ ema, size_t n4, size_t n, AdamArgs a) {
   const auto rule = [&](float& pk, float& gk, float& mk, float& vk, float& ek) { adam_elem<DECOUPLED, EMA>(pk, gk, mk, vk, ek, a); };
-  if constexpr (EMA) {
-    flat_sweep(n4, n, rule, upd(p), last(g), upd(m), upd(v), upd(ema));
-  } else {
-    flat_sweep(n4, n, [&](float& pk, float& gk, float& mk, float& vk) { float ek = 0.f; rule(pk, gk, mk, vk, ek); }, upd(p), last(g), upd(m), upd(v));
-  }
+  flat_sweep(n4, n, rule, upd(p), last(g), upd(m), upd(v), upd_if<EMA>(ema));
 }
 
 int adam_grid(size_t n4) {
@@ -141,12 +137,7 @@ __global__ __launch_bounds__(256) void madgrad_kernel(float* __restrict__ p, con
                                                       float* __restrict__ s, const float* __restrict__ x0, float* __restrict__ ema, size_t n4,
                                                       size_t n, MadgradArgs a) {
   const auto rule = [&](float& pk, float& gk, float& qk, float& sk, float& xk, float& ek) { madgrad_elem<EMA>(pk, gk, qk, sk, xk, ek, a); };
-  if constexpr (EMA) {
-    flat_sweep(n4, n, rule, upd(p), last(g), upd(gss), upd(s), rd(x0), upd(ema));
-  } else {
-    flat_sweep(n4, n, [&](float& pk, float& gk, float& qk, float& sk, float& xk) { float ek = 0.f; rule(pk, gk, qk, sk, xk, ek); }, upd(p), last(g),
-               upd(gss), upd(s), rd(x0));
-  }
+  flat_sweep(n4, n, rule, upd(p), last(g), upd(gss), upd(s), rd(x0), upd_if<EMA>(ema));
 }
 
 }  // namespace
@@ -244,12 +235,7 @@ __global__ __launch_bounds__(256) void adais_step_kernel(float* __restrict__ p, 
                                                          const float* __restrict__ mean_ptr, size_t n4, size_t n, AdaisArgs a) {
   const float mean = mean_ptr[0];
   const auto rule = [&](float& pk, float& gk, float& mk, float& vk, float& bk, float& ek) { adais_elem<EMA>(pk, gk, mk, vk, bk, ek, mean, a); };
-  if constexpr (EMA) {
-    flat_sweep(n4, n, rule, upd(p), last(g), upd(m), rd(v), upd(bp), upd(ema));
-  } else {
-    flat_sweep(n4, n, [&](float& pk, float& gk, float& mk, float& vk, float& bk) { float ek = 0.f; rule(pk, gk, mk, vk, bk, ek); }, upd(p), last(g),
-               upd(m), rd(v), upd(bp));
-  }
+  flat_sweep(n4, n, rule, upd(p), last(g), upd(m), rd(v), upd(bp), upd_if<EMA>(ema));
 }
 
 // bc2 = 1 - beta2^step in double, as the reference's Python does

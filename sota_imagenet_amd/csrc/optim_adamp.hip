@@ -25,8 +25,7 @@
 //       the package's form would need a second reduction pass after d is known.
 //   (c) adamp_update_kernel<EMA>, one workgroup per item: (m', v', u) from adamp_elem;  pn = p/d;  u = u - pn*s;  p = p*wdf;  p = p + nss*u;
 //       m', v', p stored.  With mode 0, (d, s) = (1, 0), this is the plain Adam step.  The slot of an element is slot0 + (offset inside the
-//       tensor)/unit_len: an item inside one slot reads its coefficient once and runs item_sweep, an item that spans units walks (unit, place)
-//       element by element as sam_lw_perturb_kernel does — an f32x4 may straddle units or cover several.  EMA: ema += (1 - decay)*(p_new - ema).
+//       tensor)/unit_len: unit_item_sweep (optim_items.h).  EMA: ema += (1 - decay)*(p_new - ema).
 // Traffic: 16 B / element in (a), 28 B in (c) (36 B with the average): 44 B a step against AdamW's 28 B.  There is no separate moments pass.
 // Every table record is checked against the arrays of the launch before any access through it.
 #include <cmath>
@@ -67,38 +66,17 @@ __global__ __launch_bounds__(256) void adamp_unit_sums_kernel(const float* __res
                                                               const float* __restrict__ m, const float* __restrict__ v, size_t n,
                                                               const UnitPiece* __restrict__ pieces, size_t n_pieces, int n_slots,
                                                               double* __restrict__ partial, AdampArgs a) {
+  const auto add = [&](double(&acc)[4], float pk, float gk, float mk, float vk) {
+    float mn, vn, u;
+    adamp_elem(gk, mk, vk, a, mn, vn, u);
+    const double ge = (double)(gk * a.gscale), pd = (double)pk;
+    acc[0] += ge * ge;
+    acc[1] += pd * pd;
+    acc[2] += ge * pd;
+    acc[3] += pd * (double)u;
+  };
   __shared__ double sh[4][256];
-  const int l = threadIdx.x & 63;
-  const size_t k = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
-  double agg = 0.0, app = 0.0, agp = 0.0, apu = 0.0;
-  if (k < n_pieces) {
-    const UnitPiece pc = pieces[k];
-    if (piece_ok(pc, n, n_slots)) {
-      const float *pp = p + pc.off, *gp = g + pc.off, *mp = m + pc.off, *vp = v + pc.off;
-      const auto add = [&](float pk, float gk, float mk, float vk) {
-        float mn, vn, u;
-        adamp_elem(gk, mk, vk, a, mn, vn, u);
-        const double ge = (double)(gk * a.gscale), pd = (double)pk;
-        agg += ge * ge;
-        app += pd * pd;
-        agp += ge * pd;
-        apu += pd * (double)u;
-      };
-      piece_walk<64>(
-          pc, l, [&](int i) { add(pp[i], gp[i], mp[i], vp[i]); },
-          [&](int head, int i) {  // all four are read again by the update kernel: plain loads
-            const f32x4 pv = reinterpret_cast<const f32x4*>(pp + head)[i], gv = reinterpret_cast<const f32x4*>(gp + head)[i];
-            const f32x4 mv = reinterpret_cast<const f32x4*>(mp + head)[i], vv = reinterpret_cast<const f32x4*>(vp + head)[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) add(pv[j], gv[j], mv[j], vv[j]);
-          });
-    }
-  }
-  const double sgg = group_sum<64>(agg, sh[0]), spp = group_sum<64>(app, sh[1]), sgp = group_sum<64>(agp, sh[2]), spu = group_sum<64>(apu, sh[3]);
-  if (l == 0 && k < n_pieces) {
-    double* o = partial + 4 * k;
-    o[0] = sgg, o[1] = spp, o[2] = sgp, o[3] = spu;
-  }
+  piece_sums<64>(pieces, n_pieces, n, n_slots, partial, {sh[0], sh[1], sh[2], sh[3]}, add, p, g, m, v);
 }
 
 struct AdampCoefArgs {
@@ -127,7 +105,7 @@ __global__ __launch_bounds__(256) void adamp_coef_kernel(const double* __restric
     const auto slot_sums = [&](int j, double& Sgg, double& Spp, double& Sgp, double& Spu) {
       const UnitSlot s = slots[t.slot0 + j];
       Sgg = Spp = Sgp = Spu = 0.0;
-      if (s.first < 0 || s.count <= 0 || (size_t)s.first + (size_t)s.count > n_partial) return false;
+      if (!slot_ok(s, n_partial)) return false;
       for (int i = 0; i < s.count; ++i) {
         const double* q = partial + 4 * ((size_t)s.first + i);
         Sgg += q[0], Spp += q[1], Sgp += q[2], Spu += q[3];
@@ -207,61 +185,15 @@ __global__ __launch_bounds__(256) void adamp_update_kernel(float* __restrict__ p
                                                            AdampArgs a) {
   const LwItem it = items[blockIdx.x];
   if (!item_ok(it, n, n_tensors)) return;
-  const UnitTensor t = tens[it.tensor];
-  const long long e0 = it.off - t.start;  // the item's first element inside its tensor
-  if (t.unit_len <= 0 || t.slot0 < 0 || e0 < 0 || e0 + it.len > 0x7fffffffLL) return;
-  const int u = t.unit_len, first = (int)e0 / u, lastu = ((int)e0 + it.len - 1) / u;
-  if ((long long)t.slot0 + lastu >= n_slots) return;
-  const float2* c = reinterpret_cast<const float2*>(coef) + t.slot0;
+  UnitSpan sp;
+  if (!unit_span(it, tens[it.tensor], n_slots, sp)) return;
+  const float2* c = reinterpret_cast<const float2*>(coef) + sp.slot0;
   const float wdf = wdfs[it.tensor];
-  const auto ap = upd(p + it.off);
-  const auto ag = last(g + it.off);
-  const auto am = upd(m + it.off);
-  const auto av = upd(v + it.off);
-  if (first == lastu) {
-    const float2 ds = c[first];
-    if constexpr (EMA) {
-      item_sweep(it.len, [&](float& pk, float& gk, float& mk, float& vk, float& ek) { adamp_step_elem<true>(pk, gk, mk, vk, ek, ds.x, ds.y, wdf, a); },
-                 ap, ag, am, av, upd(ema + it.off));
-    } else {
-      item_sweep(it.len, [&](float& pk, float& gk, float& mk, float& vk) { float ek = 0.f; adamp_step_elem<false>(pk, gk, mk, vk, ek, ds.x, ds.y, wdf, a); },
-                 ap, ag, am, av);
-    }
-    return;
-  }
-  // the item spans several units: the rule walks (unit, place inside it) along the elements it is given
-  int s = 0, r = 0;
-  const auto elem = [&](float& pk, float& gk, float& mk, float& vk, float& ek) {
-    const float2 ds = c[s];
+  const auto elem = [&](const float2& ds, float& pk, float& gk, float& mk, float& vk, float& ek) {
     adamp_step_elem<EMA>(pk, gk, mk, vk, ek, ds.x, ds.y, wdf, a);
-    if (++r == u) r = 0, ++s;
   };
-  const int n4 = it.len >> 2;
-  const auto at = [&](int e) { s = ((int)e0 + e) / u, r = (int)e0 + e - s * u; };
-  if constexpr (EMA) {
-    auto rule = elem;
-    const auto ae = upd(ema + it.off);
-    constexpr std::index_sequence<0, 1, 2, 3, 4> js;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      at(4 * i);
-      sweep_vector(i, rule, js, ap, ag, am, av, ae);
-    }
-    if ((int)threadIdx.x < (it.len & 3)) {
-      at(4 * n4 + (int)threadIdx.x);
-      sweep_element(4 * n4 + (int)threadIdx.x, rule, js, ap, ag, am, av, ae);
-    }
-  } else {
-    auto rule = [&](float& pk, float& gk, float& mk, float& vk) { float ek = 0.f; elem(pk, gk, mk, vk, ek); };
-    constexpr std::index_sequence<0, 1, 2, 3> js;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      at(4 * i);
-      sweep_vector(i, rule, js, ap, ag, am, av);
-    }
-    if ((int)threadIdx.x < (it.len & 3)) {
-      at(4 * n4 + (int)threadIdx.x);
-      sweep_element(4 * n4 + (int)threadIdx.x, rule, js, ap, ag, am, av);
-    }
-  }
+  unit_item_sweep(it.len, sp, [&](int unit) { return c[unit]; }, elem, upd(p + it.off), last(g + it.off), upd(m + it.off), upd(v + it.off),
+                  upd_if<EMA>(ema + it.off));
 }
 
 // the scalars both (a) and (c) need, formed in double and rounded once; false with a message for values outside the rule's domain

@@ -1,10 +1,14 @@
-// optim_items.h — the tables that the kernels of optim_lw.hip, optim_sam.hip and optim_sam_lw.hip walk: the work items, and for the statistics
-// taken per output unit the pieces, slots and tensor records; the test every kernel makes before it touches memory through a record, and the walk
-// over the elements of a piece.
+// optim_items.h — the tables that the kernels of optim_lw.hip, optim_adamp.hip, optim_sam.hip and optim_sam_lw.hip walk: the work items, and
+// for the statistics taken per output unit the pieces, slots and tensor records; the test every kernel makes before it touches memory through a
+// record; and the three loops over them that the unit-wise families share: the sums of a piece (piece_sums), the gather of a slot's partial
+// sums (slot_gather) and the update of an item whose elements take a coefficient per slot (unit_item_sweep).
 #pragma once
 #include <cstddef>
 
 #include <hip/hip_runtime.h>
+
+#include "optim_sum.h"
+#include "optim_sweep.h"
 
 namespace mi355 {
 
@@ -60,6 +64,102 @@ __device__ __forceinline__ void piece_walk(const UnitPiece& pc, int l, One one, 
   if (l < head) one(l);
   for (int i = l; i < n4; i += G) four(head, i);
   if (l < tail) one(head + 4 * n4 + l);
+}
+
+// K sums per piece, one group of G threads per piece, 256 / G pieces per workgroup: add(acc, x...) takes one element of every array of src, in
+// the order piece_walk gives a thread its elements; each acc[j] then goes through group_sum, and the group's first thread writes
+// partial[K*k .. K*k + K-1] of piece k.  Plain loads: what is summed here is read again by the update.  sh: one LDS array of 256 doubles per
+// sum, which the kernel declares — as separate arrays where it can: a tree over a row of one two-dimensional array costs an address add a step.
+template <int G, int K, typename Add, typename... P>
+__device__ __forceinline__ void piece_sums(const UnitPiece* __restrict__ pieces, size_t n_pieces, size_t n, int n_slots,
+                                           double* __restrict__ partial, double* const (&sh)[K], Add add, const P*... src) {
+  const int l = threadIdx.x & (G - 1);
+  const size_t k = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  double acc[K] = {};
+  if (k < n_pieces) {
+    const UnitPiece pc = pieces[k];
+    if (piece_ok(pc, n, n_slots)) {
+      const auto walk = [&](const auto*... sp) {  // the arrays at the piece's first element
+        piece_walk<G>(
+            pc, l, [&](int i) { add(acc, sp[i]...); },
+            [&](int head, int i) {
+              [&](const auto&... v) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) add(acc, v[j]...);
+              }(reinterpret_cast<const f32x4*>(sp + head)[i]...);
+            });
+      };
+      walk((src + pc.off)...);
+    }
+  }
+  double tot[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) tot[j] = group_sum<G>(acc[j], sh[j]);
+  if (l == 0 && k < n_pieces) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) partial[K * k + j] = tot[j];
+  }
+}
+
+// a slot's entries lie inside partial[] (n_partial entries of K doubles each)
+__device__ __forceinline__ bool slot_ok(const UnitSlot& sl, size_t n_partial) {
+  return sl.first >= 0 && sl.count > 0 && (size_t)sl.first + (size_t)sl.count <= n_partial;
+}
+
+// thread l of G adds entries l, l + G, ... of the slot's K-wide partial sums into acc[]
+template <int G, int K>
+__device__ __forceinline__ void slot_gather(const UnitSlot& sl, const double* __restrict__ partial, int l, double (&acc)[K]) {
+  for (int i = l; i < sl.count; i += G) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] += partial[K * ((size_t)sl.first + i) + j];
+  }
+}
+
+// Where an item lies among the units of its tensor: the slot of an element is slot0 + (its offset inside the tensor) / unit_len.
+struct UnitSpan {
+  int e0;           // the item's first element inside its tensor
+  int unit_len;
+  int first, last;  // the units of its first and last element
+  int slot0;        // slot of the tensor's unit 0; slot0 + last is inside the launch's slots
+};
+
+// false for a record through which the item would reach outside the launch's n_slots slots
+__device__ __forceinline__ bool unit_span(const LwItem& it, const UnitTensor& t, int n_slots, UnitSpan& sp) {
+  const long long e0 = it.off - t.start;
+  if (t.unit_len <= 0 || t.slot0 < 0 || e0 < 0 || e0 + it.len > 0x7fffffffLL) return false;
+  sp.e0 = (int)e0, sp.unit_len = t.unit_len, sp.slot0 = t.slot0;
+  sp.first = sp.e0 / t.unit_len, sp.last = (sp.e0 + it.len - 1) / t.unit_len;
+  return (long long)t.slot0 + sp.last < n_slots;
+}
+
+// item_sweep for an item whose elements take a coefficient per unit: coef_of(unit of the tensor) -> C, elem(const C&, float&...) with one
+// reference per array; the array pointers are already offset to the item.  An item inside one unit — every item of a whole-tensor slot —
+// takes its coefficient once and runs item_sweep.  Any other item sets (unit, place inside it) at the start of every vector and of a tail
+// element and advances it element by element: an f32x4 can straddle two units or, with unit_len < 4, cover several.
+template <typename CoefOf, typename Elem, typename... A>
+__device__ __forceinline__ void unit_item_sweep(int len, const UnitSpan& sp, CoefOf coef_of, Elem elem, const A&... a) {
+  if (sp.first == sp.last) {
+    const auto c = coef_of(sp.first);
+    item_sweep(len, [&](auto&... x) { elem(c, x...); }, a...);
+    return;
+  }
+  const int u = sp.unit_len;
+  int s = 0, r = 0;
+  auto rule = [&](auto&... x) {
+    elem(coef_of(s), x...);
+    if (++r == u) r = 0, ++s;
+  };
+  const auto at = [&](int e) { s = (sp.e0 + e) / u, r = sp.e0 + e - s * u; };
+  constexpr std::index_sequence_for<A...> js;
+  const int n4 = len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    at(4 * i);
+    sweep_vector(i, rule, js, a...);
+  }
+  if ((int)threadIdx.x < (len & 3)) {
+    at(4 * n4 + (int)threadIdx.x);
+    sweep_element(4 * n4 + (int)threadIdx.x, rule, js, a...);
+  }
 }
 
 }  // namespace mi355

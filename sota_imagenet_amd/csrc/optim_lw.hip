@@ -30,7 +30,7 @@
 //        fixed order; v[slot] = v*beta2 + (1 - beta2)*sqrt(S) in double, rounded once to float32; den[slot] = (float)(sqrt((double)v) + eps).
 //   (c') lw_unit_update_kernel<RULE, EMA>, rules 0 and 1, one workgroup per item: beta1, 1 - beta1, -lr and wdf are the same for the whole launch
 //        (formed in double, rounded once, as lw_coef_kernel stores them); den comes from the slot of each element, slot0 + (offset inside the
-//        tensor) / unit_len.  An item inside one slot reads den once and runs item_sweep; any other walks (unit, place) element by element.
+//        tensor) / unit_len: unit_item_sweep (optim_items.h).
 // The library builds with -ffp-contract=off, and sqrt / '/' stay correctly rounded.  The loop of (a) and (c) over an item's elements is item_sweep
 // (optim_sweep.h: 256 threads, f32x4 body, scalar tail).
 #include <cmath>
@@ -77,11 +77,11 @@ __global__ __launch_bounds__(64) void lw_coef_kernel(const double* __restrict__ 
                                                      void* __restrict__ vstate, float* __restrict__ coef, double* __restrict__ sums, LwCoefArgs a) {
   __shared__ double sh[64];
   const LwTensor t = tens[blockIdx.x];
-  const bool ok = t.first >= 0 && t.count > 0 && (size_t)t.first + (size_t)t.count <= n_partial;
-  double acc = 0.0;
-  if (ok)
-    for (int i = threadIdx.x; i < t.count; i += 64) acc += partial[t.first + i];
-  const double S = block_sum<64>(acc, sh);
+  const UnitSlot span{t.first, t.count};
+  const bool ok = slot_ok(span, n_partial);
+  double acc[1] = {};
+  if (ok) slot_gather<64>(span, partial, threadIdx.x, acc);
+  const double S = block_sum<64>(acc[0], sh);
   if (threadIdx.x != 0 || !ok) return;
   sums[blockIdx.x] = S;
   const double stat = (a.flags & LW_MEAN) ? S / t.numel : S;
@@ -112,6 +112,16 @@ struct LwUpdArgs {
   bool soft_wd;
 };
 
+LwUpdArgs lw_upd_args(double lr, int soft_wd, double wd_eps, float gscale, const float* ema, float ema_decay) {
+  LwUpdArgs a;
+  a.neg_lr = (float)(-lr);
+  a.gscale = gscale;
+  a.ema_w = ema ? 1.f - ema_decay : 0.f;
+  a.wd_eps = soft_wd ? (float)wd_eps : 0.f;
+  a.soft_wd = soft_wd != 0;
+  return a;
+}
+
 template <int RULE, bool EMA>
 __device__ __forceinline__ void lw_elem(float& p, float g, float& m, float& e, const f32x4& c, const LwUpdArgs& a) {
   const float ge = g * a.gscale;
@@ -140,12 +150,7 @@ __global__ __launch_bounds__(256) void lw_update_kernel(float* __restrict__ p, c
   if (!item_ok(it, n, n_tensors)) return;
   const f32x4 c = reinterpret_cast<const f32x4*>(coef)[it.tensor];
   const auto rule = [&](float& pk, float& gk, float& mk, float& ek) { lw_elem<RULE, EMA>(pk, gk, mk, ek, c, a); };
-  if constexpr (EMA) {
-    item_sweep(it.len, rule, upd(p + it.off), last(g + it.off), upd(m + it.off), upd(ema + it.off));
-  } else {
-    item_sweep(it.len, [&](float& pk, float& gk, float& mk) { float ek = 0.f; rule(pk, gk, mk, ek); }, upd(p + it.off), last(g + it.off),
-               upd(m + it.off));
-  }
+  item_sweep(it.len, rule, upd(p + it.off), last(g + it.off), upd(m + it.off), upd_if<EMA>(ema + it.off));
 }
 
 template <int RULE>
@@ -157,29 +162,12 @@ void lw_update_launch(bool ema_on, dim3 grid, hipStream_t st, float* p, const fl
 
 __global__ __launch_bounds__(256) void lw_unit_sumsq_kernel(const float* __restrict__ src, size_t n, const UnitPiece* __restrict__ pieces,
                                                             size_t n_pieces, int n_slots, double* __restrict__ partial, float scale) {
+  const auto add = [&](double(&acc)[1], float x) {
+    const double e = (double)(x * scale);
+    acc[0] += e * e;
+  };
   __shared__ double sh[256];
-  const int l = threadIdx.x & 63;
-  const size_t k = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
-  double acc = 0.0;
-  if (k < n_pieces) {
-    const UnitPiece pc = pieces[k];
-    if (piece_ok(pc, n, n_slots)) {
-      const float* sp = src + pc.off;
-      const auto add = [&](float x) {
-        const double e = (double)(x * scale);
-        acc += e * e;
-      };
-      piece_walk<64>(
-          pc, l, [&](int i) { add(sp[i]); },
-          [&](int head, int i) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(sp + head)[i];  // read again by the update kernel: a plain load
-#pragma unroll
-            for (int j = 0; j < 4; ++j) add(v[j]);
-          });
-    }
-  }
-  const double tot = group_sum<64>(acc, sh);
-  if (l == 0 && k < n_pieces) partial[k] = tot;
+  piece_sums<64>(pieces, n_pieces, n, n_slots, partial, {sh}, add, src);
 }
 
 __global__ __launch_bounds__(256) void lw_unit_coef_kernel(const double* __restrict__ partial, size_t n_partial, const UnitSlot* __restrict__ slots,
@@ -188,15 +176,14 @@ __global__ __launch_bounds__(256) void lw_unit_coef_kernel(const double* __restr
   __shared__ double sh[256];
   const int l = threadIdx.x & 63;
   const size_t s = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
-  double acc = 0.0;
+  double acc[1] = {};
   bool ok = false;
   if (s < n_slots) {
     const UnitSlot sl = slots[s];
-    ok = sl.first >= 0 && sl.count > 0 && (size_t)sl.first + (size_t)sl.count <= n_partial;
-    if (ok)
-      for (int i = l; i < sl.count; i += 64) acc += partial[(size_t)sl.first + i];
+    ok = slot_ok(sl, n_partial);
+    if (ok) slot_gather<64>(sl, partial, l, acc);
   }
-  const double S = group_sum<64>(acc, sh);
+  const double S = group_sum<64>(acc[0], sh);
   if (l != 0 || !ok) return;
   sums[s] = S;
   const float vn = (float)((double)v[s] * beta2 + (1.0 - beta2) * sqrt(S));  // the NORM, where the layer-wise rule takes S itself
@@ -211,60 +198,16 @@ __global__ __launch_bounds__(256) void lw_unit_update_kernel(float* __restrict__
                                                              int n_slots, f32x4 c0, LwUpdArgs a) {
   const LwItem it = items[blockIdx.x];
   if (!item_ok(it, n, n_tensors)) return;
-  const UnitTensor t = tens[it.tensor];
-  const long long e0 = it.off - t.start;  // the item's first element inside its tensor
-  if (t.unit_len <= 0 || t.slot0 < 0 || e0 < 0 || e0 + it.len > 0x7fffffffLL) return;
-  const int u = t.unit_len, first = (int)e0 / u, lastu = ((int)e0 + it.len - 1) / u;
-  if ((long long)t.slot0 + lastu >= n_slots) return;
-  const float* d = den + t.slot0;
-  const auto ap = upd(p + it.off);
-  const auto ag = last(g + it.off);
-  const auto am = upd(m + it.off);
-  if (first == lastu) {
+  UnitSpan sp;
+  if (!unit_span(it, tens[it.tensor], n_slots, sp)) return;
+  const float* d = den + sp.slot0;
+  const auto coef_of = [&](int unit) {
     f32x4 c = c0;
-    c[0] = d[first];
-    if constexpr (EMA) {
-      item_sweep(it.len, [&](float& pk, float& gk, float& mk, float& ek) { lw_elem<RULE, true>(pk, gk, mk, ek, c, a); }, ap, ag, am,
-                 upd(ema + it.off));
-    } else {
-      item_sweep(it.len, [&](float& pk, float& gk, float& mk) { float ek = 0.f; lw_elem<RULE, false>(pk, gk, mk, ek, c, a); }, ap, ag, am);
-    }
-    return;
-  }
-  // the item spans several units: the rule walks (unit, place inside it) along the elements it is given
-  int s = 0, r = 0;
-  const auto elem = [&](float& pk, float& gk, float& mk, float& ek) {
-    f32x4 c = c0;
-    c[0] = d[s];
-    lw_elem<RULE, EMA>(pk, gk, mk, ek, c, a);
-    if (++r == u) r = 0, ++s;
+    c[0] = d[unit];
+    return c;
   };
-  const int n4 = it.len >> 2;
-  const auto at = [&](int e) { s = ((int)e0 + e) / u, r = (int)e0 + e - s * u; };
-  if constexpr (EMA) {
-    auto rule = elem;
-    const auto ae = upd(ema + it.off);
-    constexpr std::index_sequence<0, 1, 2, 3> js;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      at(4 * i);
-      sweep_vector(i, rule, js, ap, ag, am, ae);
-    }
-    if ((int)threadIdx.x < (it.len & 3)) {
-      at(4 * n4 + (int)threadIdx.x);
-      sweep_element(4 * n4 + (int)threadIdx.x, rule, js, ap, ag, am, ae);
-    }
-  } else {
-    auto rule = [&](float& pk, float& gk, float& mk) { float ek = 0.f; elem(pk, gk, mk, ek); };
-    constexpr std::index_sequence<0, 1, 2> js;
-    for (int i = threadIdx.x; i < n4; i += 256) {
-      at(4 * i);
-      sweep_vector(i, rule, js, ap, ag, am);
-    }
-    if ((int)threadIdx.x < (it.len & 3)) {
-      at(4 * n4 + (int)threadIdx.x);
-      sweep_element(4 * n4 + (int)threadIdx.x, rule, js, ap, ag, am);
-    }
-  }
+  const auto elem = [&](const f32x4& c, float& pk, float& gk, float& mk, float& ek) { lw_elem<RULE, EMA>(pk, gk, mk, ek, c, a); };
+  unit_item_sweep(it.len, sp, coef_of, elem, upd(p + it.off), last(g + it.off), upd(m + it.off), upd_if<EMA>(ema + it.off));
 }
 
 template <int RULE>
@@ -322,12 +265,7 @@ int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, s
   MI355_ARG(!soft_wd || (rule == 0 && std::isfinite(wd_eps)), "lw_update: wd_eps=%g needs rule 0 and a finite value", wd_eps);
   MI355_ARG(std::isfinite(gscale), "lw_update: grad_scale=%g is not finite", (double)gscale);
   MI355_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "lw_update: ema_decay=%g outside [0, 1]", (double)ema_decay);
-  LwUpdArgs a;
-  a.neg_lr = (float)(-lr);
-  a.gscale = gscale;
-  a.ema_w = ema ? 1.f - ema_decay : 0.f;
-  a.wd_eps = soft_wd ? (float)wd_eps : 0.f;
-  a.soft_wd = soft_wd != 0;
+  const LwUpdArgs a = lw_upd_args(lr, soft_wd, wd_eps, gscale, ema, ema_decay);
   const dim3 grid((unsigned)n_items);
   const LwItem* it = (const LwItem*)items;
   if (rule == 0) lw_update_launch<0>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
@@ -380,12 +318,7 @@ int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* e
   MI355_ARG(!soft_wd || (rule == 0 && std::isfinite(wd_eps)), "lw_unit_update: wd_eps=%g needs rule 0 and a finite value", wd_eps);
   MI355_ARG(std::isfinite(gscale), "lw_unit_update: grad_scale=%g is not finite", (double)gscale);
   MI355_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "lw_unit_update: ema_decay=%g outside [0, 1]", (double)ema_decay);
-  LwUpdArgs a;
-  a.neg_lr = (float)(-lr);
-  a.gscale = gscale;
-  a.ema_w = ema ? 1.f - ema_decay : 0.f;
-  a.wd_eps = soft_wd ? (float)wd_eps : 0.f;
-  a.soft_wd = soft_wd != 0;
+  const LwUpdArgs a = lw_upd_args(lr, soft_wd, wd_eps, gscale, ema, ema_decay);
   const double lrwd = lr * wd;
   const f32x4 c0 = {1.f, (float)beta1, (float)(1.0 - beta1), (float)(soft_wd ? lrwd : 1.0 - lrwd)};  // what lw_coef_kernel stores, den aside
   const dim3 grid((unsigned)n_items);

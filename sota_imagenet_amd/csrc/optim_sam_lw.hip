@@ -12,9 +12,7 @@
 //   (b) sam_lw_coef_kernel, one wave per slot, 4 slots per workgroup: Sg, Sp = the slot's consecutive partials in a fixed order (double);
 //       gn = fmaxf((float)sqrt(Sg), 1e-5f);  wn = fmaxf((float)sqrt(Sp), 1e-3f);  coef[slot] = wn / gn;  norms[slot] = (gn, wn).
 //   (c) sam_lw_perturb_kernel, one workgroup per work item of ALL tensors.  The slot of an element is slot0 + (its offset inside its tensor) /
-//       unit_len, from the tensor's 16-byte record { int64 start; int32 unit_len; int32 slot0 }.  An item that lies in one slot reads its
-//       coefficient once and runs item_sweep; any other item takes the coefficient element by element — an f32x4 can straddle two units (or, with
-//       unit_len < 4, cover several).
+//       unit_len, from the tensor's 16-byte record { int64 start; int32 unit_len; int32 slot0 }: unit_item_sweep (optim_items.h).
 //   (d) restore: sam_restore_kernel of optim_sam.hip, unchanged.
 // 8 B / element in (a) and (a'), 16 B in (c): the bytes of sam_sumsq_kernel and sam_perturb_kernel.  Alignment gaps and padding are neither read
 // into a sum nor written.  Every record is checked against the arrays of the launch before any access through it.  -ffp-contract=off: every
@@ -55,34 +53,13 @@ template <int G>
 __global__ __launch_bounds__(256) void sam_unit_sumsq_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n,
                                                              const UnitPiece* __restrict__ pieces, size_t n_pieces, int n_slots,
                                                              double* __restrict__ partial, float gscale) {
+  const auto add = [&](double(&acc)[2], float pk, float gk) {
+    const double ge = (double)(gk * gscale), pd = (double)pk;
+    acc[0] += ge * ge;
+    acc[1] += pd * pd;
+  };
   __shared__ double shg[256], shp[256];
-  const int l = threadIdx.x & (G - 1);
-  const size_t k = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
-  double ag = 0.0, ap = 0.0;
-  if (k < n_pieces) {
-    const UnitPiece pc = pieces[k];
-    if (piece_ok(pc, n, n_slots)) {
-      const float* pp = p + pc.off;
-      const float* gp = g + pc.off;
-      const auto add = [&](float pk, float gk) {
-        const double ge = (double)(gk * gscale), pd = (double)pk;
-        ag += ge * ge;
-        ap += pd * pd;
-      };
-      piece_walk<G>(
-          pc, l, [&](int i) { add(pp[i], gp[i]); },
-          [&](int head, int i) {
-            const f32x4 pv = reinterpret_cast<const f32x4*>(pp + head)[i], gv = reinterpret_cast<const f32x4*>(gp + head)[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) add(pv[j], gv[j]);
-          });
-    }
-  }
-  const double sg = group_sum<G>(ag, shg), sp = group_sum<G>(ap, shp);
-  if (l == 0 && k < n_pieces) {
-    partial[2 * k] = sg;
-    partial[2 * k + 1] = sp;
-  }
+  piece_sums<G>(pieces, n_pieces, n, n_slots, partial, {shg, shp}, add, p, g);
 }
 
 __global__ __launch_bounds__(256) void sam_lw_coef_kernel(const double* __restrict__ partial, size_t n_partial, const UnitSlot* __restrict__ slots,
@@ -90,6 +67,7 @@ __global__ __launch_bounds__(256) void sam_lw_coef_kernel(const double* __restri
   __shared__ double shg[256], shp[256];
   const int l = threadIdx.x & 63;
   const size_t s = (size_t)blockIdx.x * 4 + threadIdx.x / 64;
+  // slot_ok and slot_gather<64, 2> written out: with them this kernel measured 0.5 % slower (profiles/optim_units_ab.json)
   double ag = 0.0, ap = 0.0;
   bool ok = false;
   if (s < n_slots) {
@@ -114,43 +92,14 @@ __global__ __launch_bounds__(256) void sam_lw_perturb_kernel(float* __restrict__
                                                              const float* __restrict__ coef, int n_slots, float rho, float gscale) {
   const LwItem it = items[blockIdx.x];
   if (!item_ok(it, n, n_tensors)) return;
-  const UnitTensor t = tens[it.tensor];
-  const long long e0 = it.off - t.start;  // the item's first element inside its tensor
-  if (t.unit_len <= 0 || t.slot0 < 0 || e0 < 0 || e0 + it.len > 0x7fffffffLL) return;
-  const int u = t.unit_len, first = (int)e0 / u, lastu = ((int)e0 + it.len - 1) / u;
-  if ((long long)t.slot0 + lastu >= n_slots) return;
-  const float* c = coef + t.slot0;
-  if (first == lastu) {
-    const float ck = c[first];
-    const auto rule = [&](float& pk, float& gk, float& ek) {
-      ek = (ck * (gk * gscale)) * rho;  // eps is written, never read
-      pk = pk + ek;
-    };
-    item_sweep(it.len, rule, upd(p + it.off), rd(g + it.off), upd(eps + it.off));
-    return;
-  }
-  // the item spans several units: the rule walks (unit, place inside it) along the elements it is given
-  int s = 0, r = 0;
-  auto rule = [&](float& pk, float& gk, float& ek) {
-    ek = (c[s] * (gk * gscale)) * rho;
+  UnitSpan sp;
+  if (!unit_span(it, tens[it.tensor], n_slots, sp)) return;
+  const float* c = coef + sp.slot0;
+  const auto elem = [&](const float& ck, float& pk, float& gk, float& ek) {
+    ek = (ck * (gk * gscale)) * rho;  // eps is written, never read
     pk = pk + ek;
-    if (++r == u) r = 0, ++s;
   };
-  const auto a0 = upd(p + it.off);
-  const auto a1 = rd(g + it.off);
-  const auto a2 = upd(eps + it.off);
-  constexpr std::index_sequence<0, 1, 2> js;
-  const int n4 = it.len >> 2;
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    const int e = (int)e0 + 4 * i;
-    s = e / u, r = e - s * u;
-    sweep_vector(i, rule, js, a0, a1, a2);
-  }
-  if ((int)threadIdx.x < (it.len & 3)) {
-    const int e = (int)e0 + 4 * n4 + (int)threadIdx.x;
-    s = e / u, r = e - s * u;
-    sweep_element(4 * n4 + (int)threadIdx.x, rule, js, a0, a1, a2);
-  }
+  unit_item_sweep(it.len, sp, [&](int unit) { return c[unit]; }, elem, upd(p + it.off), rd(g + it.off), upd(eps + it.off));
 }
 
 }  // namespace

@@ -1,4 +1,6 @@
-// optim_sum.h — what the optimizer kernels of optim.hip, optim_lw.hip and optim_sam_lw.hip share: the fixed-order workgroup and group sums and the alignment test.
+// optim_sum.h — what the optimizer kernels of optim.hip, optim_lw.hip, optim_adamp.hip, optim_sam.hip and optim_sam_lw.hip share: the
+// fixed-order workgroup and group sums (block_sum; group_sum, which piece_sums of optim_items.h and the per-slot coefficient kernels call) and
+// the alignment test.
 #pragma once
 #include <cstdint>
 

@@ -3,6 +3,8 @@
 //   rd(q)    read                                  (const float*)
 //   last(q)  read for the last time in the step: the vector load is non-temporal, the lines are not kept in L2 / Infinity Cache   (const float*)
 //   upd(q)   read, and written back after the rule (float*); an array the rule overwrites without reading it costs no load
+//   upd_if<ON>(q)  upd(q) where ON; an array that is not there otherwise (the moving average of a step without one): nothing is loaded or
+//            stored through q and the rule gets a zero, so a kernel names the array once and only its element rule asks whether it exists
 // rule(float&...) gets one reference per array, in the same order; it is called four times per vector and once per tail element, so a reduction
 // that adds into a captured variable sees a thread's elements in array order.  Stores cover the upd() arrays only.  The arrays must not overlap.
 #pragma once
@@ -13,14 +15,20 @@
 
 namespace mi355 {
 
-template <typename T, bool NONTEMPORAL>
+template <typename T, bool NONTEMPORAL, bool ON = true>
 struct SweepArray {
   T* q;
-  static constexpr bool kStore = !std::is_const<T>::value;
+  static constexpr bool kStore = ON && !std::is_const<T>::value;
   template <typename I>
   __device__ __forceinline__ f32x4 load4(I i) const {
-    if constexpr (NONTEMPORAL) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q) + i);
+    if constexpr (!ON) return f32x4{0.f, 0.f, 0.f, 0.f};
+    else if constexpr (NONTEMPORAL) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q) + i);
     else return reinterpret_cast<const f32x4*>(q)[i];
+  }
+  template <typename I>
+  __device__ __forceinline__ float load1(I i) const {
+    if constexpr (ON) return q[i];
+    else return 0.f;
   }
   template <typename I>
   __device__ __forceinline__ void store4(I i, const f32x4& x) const {
@@ -35,6 +43,8 @@ struct SweepArray {
 __device__ __forceinline__ SweepArray<const float, false> rd(const float* q) { return {q}; }
 __device__ __forceinline__ SweepArray<const float, true> last(const float* q) { return {q}; }
 __device__ __forceinline__ SweepArray<float, false> upd(float* q) { return {q}; }
+template <bool ON>
+__device__ __forceinline__ SweepArray<float, false, ON> upd_if(float* q) { return {q}; }
 
 // vector i of every array
 template <typename I, typename Rule, size_t... J, typename... A>
@@ -52,7 +62,7 @@ __device__ __forceinline__ void sweep_vector(I i, Rule& rule, std::index_sequenc
 // element i of every array
 template <typename I, typename Rule, size_t... J, typename... A>
 __device__ __forceinline__ void sweep_element(I i, Rule& rule, std::index_sequence<J...>, const A&... a) {
-  float x[] = {a.q[i]...};
+  float x[] = {a.load1(i)...};
   rule(x[J]...);
   (a.store1(i, x[J]), ...);
 }
