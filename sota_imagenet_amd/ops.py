@@ -765,14 +765,17 @@ def eca_fwd(x, w):
     return y, pooled, gate
 
 
-def eca_bwd(dy, x, w, pooled, gate):
-    """returns (dx, dw [k] fp32)"""
-    _need_cuda(dy, x, w, pooled, gate)
+def eca_bwd(dy, x, w, pooled, gate, dw=None, beta=0.0):
+    """returns (dx, dw [k] fp32); with dw given: dw = beta * dw + the gradient (beta 0: dw is only written)"""
+    _need_cuda(dy, x, w, pooled, gate, dw)
     N, H, W, C = x.shape
     dx = torch.empty_like(x)
-    dw = torch.empty_like(w)
+    if dw is None:
+        dw = torch.empty_like(w)
+    elif dw.dtype != torch.float32 or dw.numel() != w.numel():
+        raise ValueError("eca_bwd: dw must be fp32 with one element per tap")
     ws = torch.empty(2 * N * C + 128 * 9, dtype=torch.float32, device=x.device)  # mi355_eca_bwd: sprod, dpool, dw partials
-    check(_L().mi355_eca_bwd(dtype_code(x.dtype), ptr(dy), ptr(x), ptr(w), w.numel(), ptr(pooled), ptr(gate), ptr(dx), ptr(dw), 0.0, ptr(ws),
+    check(_L().mi355_eca_bwd(dtype_code(x.dtype), ptr(dy), ptr(x), ptr(w), w.numel(), ptr(pooled), ptr(gate), ptr(dx), ptr(dw), beta, ptr(ws),
                              N, H * W, C, cur_stream()))
     return dx, dw
 
@@ -789,11 +792,15 @@ def weight_std_fwd(w, eps=1e-5):
     return w_hat, invstd
 
 
-def weight_std_bwd(dw_hat, w_hat, invstd):
-    _need_cuda(dw_hat, w_hat, invstd)
+def weight_std_bwd(dw_hat, w_hat, invstd, dw=None, beta=0.0):
+    """with dw given: dw = beta * dw + the gradient (beta 0: dw is only written)"""
+    _need_cuda(dw_hat, w_hat, invstd, dw)
     Cout = w_hat.shape[0]
-    dw = torch.empty_like(w_hat)
-    check(_L().mi355_weight_std_bwd(ptr(dw_hat), ptr(w_hat), ptr(invstd), ptr(dw), 0.0, Cout, w_hat.numel() // Cout, cur_stream()))
+    if dw is None:
+        dw = torch.empty_like(w_hat)
+    elif dw.dtype != torch.float32 or dw.numel() != w_hat.numel():
+        raise ValueError("weight_std_bwd: dw must be fp32 with the shape of w_hat")
+    check(_L().mi355_weight_std_bwd(ptr(dw_hat), ptr(w_hat), ptr(invstd), ptr(dw), beta, Cout, w_hat.numel() // Cout, cur_stream()))
     return dw
 
 

@@ -1,6 +1,11 @@
 """BResNet-50 variant blocks (BASELINE configs[3]; csrc/variant.hip, bresnet.py) on the GPU against the torch-CPU oracle
 (oracle/ops_ref.py per op, oracle/bresnet50_ref.py whole model).  Tolerances as in test_ops_gpu.py: normalised max error
-fp32 2e-5 (1e-4 where a backward sums many terms), bf16 2e-2."""
+fp32 2e-5 (1e-4 where a backward sums many terms), bf16 2e-2.
+
+The per-op tests here are the first look at each kernel.  tests/test_variant_ops_gpu.py pins the same kernels against fp64 references
+(tests/variant_common.py) where they can go wrong unnoticed here: the segmented row walk and the tie rule of the max pool with its argmax codes, ECA
+at every kernel width on data with pooled means of order 1, the accumulate mode of the weight gradients, the null-pointer forms of residual_act,
+single values of the keep_scale stream, a launch past the grid cap."""
 import pytest
 import torch
 
