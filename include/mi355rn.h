@@ -470,6 +470,27 @@ int mi355_sam_lw_coef(const void* partial, size_t n_partial, const void* slots, 
 int mi355_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
                          const float* coef, size_t n_slots, double rho, float grad_scale, void* stream);
 
+/* Orthogonal initialisation: the reference's `src.callbacks.OrthoInitClb` (sota_imagenet/callbacks.py:250-266, torch.nn.init.orthogonal_ on every
+ * nn.Conv2d / nn.Linear weight; recipes 46-48, 50-53, 55) over a flat fp32 array — csrc/init_ortho.hip.  The caller fills the matrices with N(0,1)
+ * draws; one launch turns every matrix of the table, in place, into the Q of its QR factorisation with a positive diagonal of R, times gain.
+ *   mats[]  { int64 off; int32 rows; int32 chans; int32 taps; int32 pad }   24 bytes;  cols = chans * taps
+ *           logical element M[r][ci*taps + t] lives at w[off + r*cols + t*chans + ci]   (taps == 1: plain row-major [rows][cols], an FC weight;
+ *           taps > 1: a conv weight [rows = Cout][taps = KH*KW][chans = Cin], KRSC memory under the logical [Cout][Cin*KH*KW] matrix)
+ * Per record, as orthogonal_ does (transpose when rows < cols, qr, Q *= sign(diag R), transpose back):
+ *   rows < cols   the vectors are the rows, in order r = 0, 1, ...
+ *   otherwise     the vectors are the columns, in LOGICAL order c = ci*taps + t (not memory order when taps > 1)
+ *   each vector loses its components along all earlier vectors and is normalised (Gram-Schmidt, every vector projected twice, sums in double in a
+ *   fixed order, no floating-point atomics: two runs on the same input agree bit for bit); every stored element is then fl(q * gain), one float
+ *   multiply, so gain == 1 stores q itself.  Elements outside the records (alignment gaps, the FC padding rows) are neither read nor written.
+ * One workgroup per matrix, the matrices side by side, no workgroup waits on another.  Records must not overlap.  status[i] (device, n_mats ints):
+ *   0  done
+ *   1  a vector's residual norm was zero, non-finite or below 2^-12 of its norm before projection (rank-deficient input): that vector is zeroed,
+ *      the vectors before it are orthonormal (gain not applied), the ones behind it keep their input — finite contents for finite input
+ *   2  the record does not fit: off >= 0, rows, chans, taps >= 1 and off + rows*cols <= n are tested before anything is accessed through it;
+ *      such a record is skipped and its memory untouched
+ * Fails (-1) before the launch on a null or misaligned pointer (8 bytes for mats[], 4 for w and status[]), n == 0, an empty table, gain not finite. */
+int mi355_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

@@ -4,16 +4,18 @@ entropy consumes, and SAMOriginal / SAM (sharpness-aware minimization), which si
 Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `self.cutmix(*input)` and
 `self.mixup(*input)` with Beta(alpha, alpha) samplers) and the un-vendored pt_clb.Cutmix / pt_clb.Mixup bases as
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
-SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip.
+SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
+over csrc/init_ortho.hip.
 """
 
+import logging
 from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import ops
-from .fit_wrapper import Callback
+from .fit_wrapper import Callback, _unwrap
 from . import item_plan
 from .item_plan import flat_views, pack_records, place, storage_pairs
 
@@ -165,6 +167,80 @@ class CutmixMixup(Cutmix):
         else:
             self.tb = self.mixup_tb
             self.state.input = self.mixup(*self.state.input)
+
+
+class OrthoInitClb(Callback):
+    """sota_imagenet/callbacks.py:250-266 (recipes 46-48, 50-53, 55): orthogonal initialisation of every conv and FC weight, once per process at the
+    first on_begin (`has_been_init`: fit runs once per stage).  For a weight [O, I, kh, kw] or [O, I], rows = O and cols = I*kh*kw: a rows x cols
+    matrix of N(0,1) draws becomes gain * Q, Q the factor of its QR factorisation (of the transpose when rows < cols) with the signs of diag R
+    folded in — torch.nn.init.orthogonal_.  BatchNorm tensors, biases, Conv1d (ECA) weights and buffers are not touched.
+
+    The reference walks model.modules() and calls a vendor QR per weight; here the model is a flat-array model (models._FlatModel) on a CUDA
+    device, anything else raises NotImplementedError (there is no CPU path), and on_begin is
+        fill()            N(0,1) draws from a torch.Generator on the model's device seeded with state.random_seed — the same numbers on every rank
+                          —, tensor by tensor in table order, each drawn in its logical OIHW order and copied through the parameter view
+        orthogonalise()   ONE launch over all matrices (csrc/init_ortho.hip: Gram-Schmidt, every vector projected twice) and one
+                          readback of its status; a matrix the kernel refuses raises RuntimeError naming the tensor
+    which are callable on their own.  `records` is the planned table [(off, rows, chans, taps)], `names` the tensors' names, `status` the last
+    launch's status tensor.  Deviations, both deliberate: a fit that starts at an epoch > 0 (state.start_epoch, which Runner.fit records: a resumed
+    run) skips the initialisation with a log line, where the reference would overwrite the loaded weights; the reference's silent
+    `except RuntimeError` for tensors of fewer than two dimensions has no counterpart, the planner never selects them.  The parameter average
+    (ModelEma) was cloned before fit, as in the reference, and is left as it is."""
+
+    def __init__(self, gain=1):
+        super().__init__()
+        self.gain = gain
+        self.has_been_init = False
+        self.records, self.names, self.status = [], [], None
+
+    def _flat_model(self):
+        from .models import _FlatModel
+
+        m = _unwrap(self.state.model)
+        if not isinstance(m, _FlatModel) or not m.flat_params.is_cuda:
+            raise NotImplementedError("OrthoInitClb runs on a flat-array model (models.resnet50) on a CUDA device: there is no CPU path and no "
+                                      f"module walk (got {type(m).__name__} on {getattr(getattr(m, 'flat_params', None), 'device', 'no flat array')})")
+        return m
+
+    def _plan(self, m):
+        self.records = item_plan.ortho_records(m._table)
+        by_off = {off: (f"{m._name_of(leaf)}.{attr}", leaf._parameters[attr]) for leaf, attr, kind, off, _ in m._entries if kind == 0}
+        self.names = [by_off[r[0]][0] for r in self.records]
+        return [by_off[r[0]][1] for r in self.records]
+
+    @torch.no_grad()
+    def fill(self):
+        """the planned tensors filled with N(0,1) draws, in table order"""
+        m = self._flat_model()
+        dev = m.flat_params.device
+        g = torch.Generator(device=dev).manual_seed(int(getattr(self.state, "random_seed", 0) or 0))
+        for p in self._plan(m):
+            p.copy_(torch.randn(tuple(p.shape), generator=g, device=dev, dtype=torch.float32))
+
+    @torch.no_grad()
+    def orthogonalise(self):
+        """one launch over the planned matrices, one readback; RuntimeError for a matrix the kernel could not orthogonalise"""
+        m = self._flat_model()
+        self._plan(m)
+        dev = m.flat_params.device
+        self.status = ops.ortho_init_(m.flat_params, self.records, pack_records(self.records, dev, item_plan.ORTHO_FIELDS), self.gain)
+        bad = [(n, s) for n, s in zip(self.names, self.status.tolist()) if s != 0]
+        if bad:
+            what = {1: "a vector with no component outside the span of the earlier ones", 2: "a record outside the flat array"}
+            raise RuntimeError("OrthoInitClb: " + "; ".join(f"{n}: {what.get(s, f'status {s}')}" for n, s in bad))
+
+    def on_begin(self):
+        if self.has_been_init:
+            return
+        self._flat_model()
+        start = int(getattr(self.state, "start_epoch", 0) or 0)
+        if start > 0:
+            logging.getLogger(__name__).info(f"OrthoInitClb: the fit starts at epoch {start}: the loaded weights are kept, no orthogonal initialisation")
+        else:
+            logging.getLogger(__name__).info("Applying orthogonal initialization")
+            self.fill()
+            self.orthogonalise()
+        self.has_been_init = True
 
 
 # one pair of parameter / gradient storage in a plan: the two storages as flat arrays over the pair's element range [lo, hi), the pair's eps array

@@ -64,6 +64,13 @@ CALLBACK_TARGET_ALIASES = {
 # pytorch_tools.optim.adamp.AdamP (recipes 12, 13) is a modified variant whose code is not available: it stays unresolved, on purpose.
 ADAMP_TARGET_ALIASES = {"adamp.AdamP": "sota_imagenet_amd.optim.AdamP"}
 
+# callbacks that run once before training (sota_imagenet/callbacks.py:250-266; recipes 46-48, 50-53, 55), consulted after the four tables above,
+# whose contents existing tests pin
+INIT_CALLBACK_TARGET_ALIASES = {
+    "src.callbacks.OrthoInitClb": "sota_imagenet_amd.callbacks.OrthoInitClb",
+    "sota_imagenet.callbacks.OrthoInitClb": "sota_imagenet_amd.callbacks.OrthoInitClb",
+}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -301,7 +308,7 @@ def validate(cfg):
 
 def resolve_target(path):
     path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
-            or ADAMP_TARGET_ALIASES.get(path, path))
+            or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

@@ -385,6 +385,8 @@ int launch_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* 
 int launch_sam_lw_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms, hipStream_t st);
 int launch_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
                           const float* coef, size_t n_slots, double rho, float gscale, hipStream_t st);
+// init_ortho.hip: Gram-Schmidt, in place, over a table of matrices { off, rows, chans, taps } of one flat array (the OrthoInitClb callback)
+int launch_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, hipStream_t st);
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

@@ -679,4 +679,8 @@ int mi355_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const v
   return launch_sam_lw_perturb(p, g, eps, n, items, n_items, tensors, n_tensors, coef, n_slots, rho, grad_scale, (hipStream_t)stream);
 }
 
+int mi355_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, void* stream) {
+  return launch_ortho_init(w, n, mats, n_mats, gain, status, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -449,6 +449,7 @@ class Runner:
         m = _unwrap(self.state.model)
         if hasattr(m, "reseed"):  # device-side drop-connect / dropout: one stream per (run seed, rank), like CutmixMixup
             m.reseed(self.state.random_seed, self.state.rank)
+        self.state.start_epoch = start_epoch  # callbacks that initialise (OrthoInitClb) leave a resumed model alone
         self.callbacks.on_begin()
         for epoch in range(start_epoch, epochs):
             self.state.is_train = True

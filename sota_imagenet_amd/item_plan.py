@@ -10,6 +10,7 @@ import torch
 
 ITEM_FIELDS = ("<i8", "<i4", "<i4")    # work items, SAM's pieces { first element, length, tensor or slot } and tensor records { start, unit_len, slot0 }
 TENSOR_FIELDS = ("<i4", "<i4", "<f8")  # the tensor records of lw_coef { first item, item count, numel }
+ORTHO_FIELDS = ("<i8", "<i4", "<i4", "<i4", "<i4")  # the matrices of ortho_init_ { first element, rows, chans, taps, pad }: 24 bytes
 
 
 def dense_range(t):
@@ -134,10 +135,26 @@ def plan_units(tensors, W):
     return dict(items=items, tensors=trec, pieces=pieces, whole=whole, slots=slots, pairs=pairs)
 
 
+def ortho_records(table):
+    """the matrices the OrthoInitClb callback orthogonalises.  table: a flat model's [(name, kind, offset, shape)]; returns [(off, rows, chans,
+    taps)] for every parameter (kind 0) with 4 or 2 dimensions, in table order: a conv weight [O, I, kh, kw] (KRSC memory) gives (off, O, I, kh*kw),
+    an FC weight [O, I] gives (off, O, I, 1) — without the padding rows behind it.  BatchNorm tensors, biases, 3-D (Conv1d) weights and buffers
+    are not selected (sota_imagenet/callbacks.py:260-261 walks nn.Conv2d / nn.Linear)"""
+    out = []
+    for _, kind, off, shape in table:
+        if kind == 0 and len(shape) == 4:
+            out.append((off, shape[0], shape[1], shape[2] * shape[3]))
+        elif kind == 0 and len(shape) == 2:
+            out.append((off, shape[0], shape[1], 1))
+    return out
+
+
 def pack_records(records, device=None, fields=ITEM_FIELDS):
-    """16-byte records (tuples of three `fields`) as the [n, 2] int64 tensor the ops wrappers take, on `device` (the CPU if None)"""
+    """records (tuples of `fields`, 16 bytes for the default three) as the [n, bytes / 8] int64 tensor the ops wrappers take, on `device` (the
+    CPU if None); a record shorter than `fields` is padded with zeros"""
+    records = [tuple(r) + (0,) * (len(fields) - len(r)) for r in records]
     rec = np.array(records, dtype=[(f"f{i}", f) for i, f in enumerate(fields)])
-    t = torch.from_numpy(rec.view(np.int64).reshape(-1, 2))
+    t = torch.from_numpy(rec.view(np.int64).reshape(-1, rec.dtype.itemsize // 8))
     return t if device is None else t.to(device)
 
 

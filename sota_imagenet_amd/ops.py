@@ -704,6 +704,30 @@ def sam_lw_perturb(p, g, eps, items, tensors, coef, rho, grad_scale=1.0):
                                     coef.numel(), float(rho), float(grad_scale), cur_stream()))
 
 
+# ---- orthogonal initialisation (include/mi355rn.h, csrc/init_ortho.hip): the OrthoInitClb callback of the reference ---------------------------------
+def ortho_init_(flat, records_host, records_dev, gain=1.0):
+    """replaces the nn.init.orthogonal_ calls of sota_imagenet/callbacks.py:260-265: every matrix of the table, filled with N(0,1) draws by the
+    caller, becomes in place the sign-fixed Q of its QR factorisation times gain.  flat: the fp32 array the offsets count from; records_host:
+    [(off, rows, chans, taps)] (item_plan.ortho_records), records_dev: the same table packed for the device (item_plan.pack_records with
+    ORTHO_FIELDS, CUDA int64 [n, 3]).  Records that overlap would race and raise here; one that does not fit the array is the kernel's to refuse.
+    Returns status (CUDA int32 per record: 0 done, 1 rank-deficient input, 2 the record does not fit), not read back."""
+    _flat_f32(flat.numel(), flat=flat)
+    _need_cuda(records_dev)
+    n_mats = len(records_host)
+    if records_dev.dtype != torch.int64 or records_dev.dim() != 2 or records_dev.shape[1] != 3 or records_dev.shape[0] != n_mats or n_mats < 1:
+        raise ValueError(f"records_dev: expected a CUDA int64 tensor [{n_mats}, 3] of 24-byte records, got {records_dev.dtype} {tuple(records_dev.shape)}")
+    if records_dev.device != flat.device:
+        raise ValueError("ortho_init_: the records and the array must live on one device")
+    end = None
+    for off, rows, chans, taps in sorted(records_host):
+        if end is not None and off < end:
+            raise ValueError(f"ortho_init_: the record at offset {off} overlaps the one before it (which ends at {end})")
+        end = off + max(rows, 0) * max(chans, 0) * max(taps, 0)
+    status = torch.empty(n_mats, dtype=torch.int32, device=flat.device)
+    check(_L().mi355_ortho_init(ptr(flat), flat.numel(), ptr(records_dev), n_mats, float(gain), ptr(status), cur_stream()))
+    return status
+
+
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
 def blurpool_fwd(x):
     _need_cuda(x)

@@ -187,6 +187,7 @@ def main(argv=None):
 
     if cfg.run.evaluate:
         data_manager.set_stage(0)
+        runner.state.start_epoch = cfg.run.start_epoch  # (what Runner.fit records: OrthoInitClb keeps a loaded model)
         runner.callbacks.on_begin()
         runner.evaluate(data_manager.val_loader, steps=(None, 20)[cfg.debug])
         logger.info(fw._fmt_metrics("Val  ", runner.state.loss_meter.avg, runner.state.metric_meters))
