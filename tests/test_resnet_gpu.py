@@ -7,8 +7,9 @@ Gradients and multi-step curves of a randomly initialised ResNet-50 on noise ima
 torch's OWN fp32 CPU path deviates ~1.5e-2 (relative L2) from an fp64 run of the same oracle, and its bf16
 autocast path ~1e-1..3e-1 on the logits.  Those quantities are therefore judged with the reference as the
 yardstick: the native path's distance to the fp64 oracle must not exceed ~the torch-CPU path's own distance
-to it in the same precision (factor + floor written at each assert).  Layer-wise, teacher-forced checks
-(test_teacher_forced_layers) pin every stage without the chaotic amplification.
+to it in the same precision (factor + floor written at each assert).  Layer-wise, teacher-forced checks pin every
+stage without the chaotic amplification: the forward here (test_teacher_forced_layers), the backward segment by segment
+in test_resnet_bwd_gpu.py.
 """
 import os
 
