@@ -491,6 +491,30 @@ int mi355_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const v
  * Fails (-1) before the launch on a null or misaligned pointer (8 bytes for mats[], 4 for w and status[]), n == 0, an empty table, gain not finite. */
 int mi355_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, void* stream);
 
+/* The log-histogram callback of the reference: `src.callbacks.GradDistributionTB` (sota_imagenet/callbacks.py:30-60; recipes 46, 49-55) over flat
+ * fp32 arrays — csrc/optim_hist.hip.  The reference sorts |x| of every tensor, keeps every subsample-th value, sorts the concatenation, keeps every
+ * subsample-th value again and draws a histogram of log10 of the rest.  The kept ranks 0, s, 2s, ... of a sorted tensor include exactly
+ * ceil(c / s) values below a threshold, c the number of its elements below it, so the bin counts of the twice-subsampled set follow exactly from
+ * per-tensor bin counts; no sort is made.  Integer arithmetic only: exact, and the same bit for bit in every run.
+ *   bins     512 (csrc/absbin.h):  bin(x) = clamp((bits(x) with the sign cleared >> 20) - 618, 0, 511) — eight bins per octave, linear in the
+ *            mantissa; bin 0 is everything below 2^-50 * 1.375 = 1.2212e-15 (zeros, denormals, all the reference clamps to -15), bin b >= 1
+ *            starts at the float with bits (618 + b) << 20, bin 511 at 2^14 * 1.125 and also takes infinities and NaN.
+ *   items[]  { int64 first; int32 len; int32 tensor }   the work-item table of the layer-wise optimizers above, len <= mi355_lw_item_elems(),
+ *            but first may be ANY element offset (a state stored once per tensor or per output unit starts anywhere)
+ *  mi355_absbin_hist ADDS the bin counts of the elements of items[i] into hist[items[i].tensor][512] (the caller zeroes the table; several
+ *      launches — one per storage — fill one table): a workgroup histogram in LDS, then integer atomicAdd of its non-zero bins.  src is the array
+ *      the offsets count from, n its length; elements outside the items (alignment gaps, the FC padding rows) are never read into a count, and a
+ *      record that does not lie inside [0, n), or whose tensor is not in [0, n_tensors), is skipped.  Fails (-1) before any launch on a null or
+ *      misaligned pointer (16 bytes for src, items[] and hist[]) or an empty table.
+ *  mi355_subsample_counts, one workgroup:  c_t(k) = rep[t] * (sum of hist[t][0..k-1]);  C(k) = sum over t of ceil(c_t(k) / subsample);
+ *      counts[k] = ceil(C(k+1) / subsample) - ceil(C(k) / subsample) for k = 0..511, in 64 bits.  rep[t] >= 1 (device memory) counts a state that
+ *      is stored once and shown broadcast: rep[t] = shown elements per stored element.  Fails (-1) before the launch on a null or misaligned
+ *      pointer (16 bytes for hist[], 8 for counts[], 4 for rep[]), n_tensors < 1 or subsample < 1.  rep[] lives on the device and is not read
+ *      back before the launch: if any rep[t] < 1 the kernel writes ~0 (no possible count) into all of counts[], for the caller to test where it
+ *      reads counts[] anyway. */
+int mi355_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, void* stream);
+int mi355_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

@@ -5,7 +5,7 @@ Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `
 `self.mixup(*input)` with Beta(alpha, alpha) samplers) and the un-vendored pt_clb.Cutmix / pt_clb.Mixup bases as
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
-over csrc/init_ortho.hip.
+over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip.
 """
 
 import logging
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .fit_wrapper import Callback, _unwrap
+from .fit_wrapper import Callback, _unwrap, env_rank
 from . import item_plan
 from .item_plan import flat_views, pack_records, place, storage_pairs
 
@@ -241,6 +241,134 @@ class OrthoInitClb(Callback):
             self.fill()
             self.orthogonalise()
         self.has_been_init = True
+
+
+class GradDistributionTB(Callback):
+    """sota_imagenet/callbacks.py:30-60 (recipes 46, 49-55): every log_every-th training step, a histogram of log10 |x| of a twice-subsampled
+    selection of the optimizer's states (`optim/{key}_log` for every key of state_keys, taken as the reference takes them: optimizer.state.values(),
+    v[key]) and of the model's parameters (`optim/model_params_log`), on rank 0 only.  The reference sorts every tensor, keeps every subsample-th
+    value, sorts the concatenation and keeps every subsample-th value again; here no sort is made: the kept ranks 0, s, 2s, ... of a sorted tensor
+    include exactly ceil(c / s) values below a threshold, c the tensor's elements below it, so the bin counts of the reference's selection follow
+    exactly from per-tensor bin counts (csrc/optim_hist.hip).  The bins are ops.ABSBIN_*: eight per octave from 1.22e-15 to
+    1.8e4, bin 0 everything the reference clamps to -15, the last bin everything above including infinities and NaN.
+
+    The plan — what to read of every tensor (item_plan.hist_records: dense views as they are, a state stored once and shown broadcast counted
+    once with its multiplicity), the tensors grouped by storage, the work items on the device — is built at the first logged step and rebuilt when
+    the set of tensors or their addresses change.  A logged step is one zero_ of the histograms, one ops.absbin_hist per storage and tag, one
+    ops.subsample_counts per tag and ONE copy of the [tags, 512] counts to the host, the callback's only host synchronisation.  `last` =
+    {tag: (bucket_limits float64 [512]: log10 of the bins' upper edges, counts int64 [512])} holds the last logged step; with a state.tb_logger it
+    goes out through add_histogram_raw at state.global_sample_step: num is exact, min and max are the outer limits of the first and last non-empty
+    bins, sum and sum_squares are formed from the bins' midpoints (TensorBoard uses them for display only).
+
+    A missing key raises KeyError naming the optimizer class and the key, a state that is no tensor TypeError (MyAdai keeps exp_avg_sq as a Python
+    float; the reference would fail on .flatten() there, which is why recipe 55 lists exp_avg only), an optimizer without any state yet
+    RuntimeError (the reference's torch.cat of nothing), parameters or states that are not CUDA fp32 NotImplementedError: there is no CPU path.
+    One deviation, deliberate: validation batches do not log.  The reference's on_batch_end has no is_train test and would write the same unchanged
+    arrays again at the same global_sample_step."""
+
+    def __init__(self, log_every=500, subsample=10, state_keys=['exp_avg', 'exp_avg_sq']):
+        super().__init__()
+        if int(log_every) < 1 or int(subsample) < 1:
+            raise ValueError(f"GradDistributionTB: log_every={log_every} and subsample={subsample} must be >= 1")
+        self.log_every = int(log_every)
+        self.subsample = int(subsample)
+        self.state_keys = list(state_keys)
+        self.last = {}
+        self.logged = 0     # logged steps so far
+        self._key = None
+        self._tags = []     # per tag: (name, [(flat source array, items on the device)] per storage, rep on the device, its rows of the histograms)
+        self._limits = ops.absbin_log10_limits()
+
+    def _tensors(self):
+        """[(tag, [tensor])] as the reference gathers them"""
+        opt = self.state.optimizer
+        states = list(opt.state.values())
+        if self.state_keys and not states:
+            raise RuntimeError(f"GradDistributionTB: {type(opt).__name__} has no state yet (no step was made): nothing to gather")
+        out = []
+        for key in self.state_keys:
+            ts = []
+            for v in states:
+                if key not in v:
+                    raise KeyError(f"GradDistributionTB: {type(opt).__name__} keeps no state '{key}' (it has {sorted(map(str, v))})")
+                if not torch.is_tensor(v[key]):
+                    raise TypeError(f"GradDistributionTB: state '{key}' of {type(opt).__name__} is a {type(v[key]).__name__}, not a tensor")
+                ts.append(v[key])
+            out.append((f"optim/{key}_log", ts))
+        out.append(("optim/model_params_log", [p.data for p in _unwrap(self.state.model).parameters()]))
+        return out
+
+    def build_plan(self, tagged):
+        """tagged: [(tag, [tensor])]; the tables on the device, one launch per storage and tag"""
+        recs = [(tag, ts, [item_plan.hist_records(t) for t in ts]) for tag, ts in tagged]
+        W = ops.lw_item_elems()
+        devs = {t.device for _, ts, _ in recs for t in ts}
+        if len(devs) != 1:
+            raise RuntimeError(f"GradDistributionTB: all parameters and states must live on one device (got {sorted(map(str, devs))})")
+        dev = devs.pop()
+        rows = sum(len(ts) for _, ts, _ in recs)
+        self._hist = torch.zeros(rows, ops.ABSBIN_BINS, dtype=torch.int32, device=dev)
+        self._counts = torch.zeros(len(recs), ops.ABSBIN_BINS, dtype=torch.int64, device=dev)
+        self._tags, row0 = [], 0
+        for tag, ts, rs in recs:
+            by_storage = {}  # storage base -> tensor indices, in order of first appearance
+            for i, r in enumerate(rs):
+                by_storage.setdefault(r[0], []).append(i)
+            launches = []
+            for base, idx in by_storage.items():
+                if base % 16:
+                    raise RuntimeError(f"GradDistributionTB: a storage of {tag} does not start on a 16-byte boundary")
+                lo = min(rs[i][1] for i in idx) & ~3  # the flat array starts on a 16-byte boundary of the storage
+                hi = max(rs[i][1] + rs[i][2] for i in idx)
+                src = torch.empty(0, dtype=torch.float32, device=dev).set_(ts[idx[0]].untyped_storage(), lo, (hi - lo,))
+                items, _ = item_plan.plan_items([(rs[i][1] - lo, rs[i][2]) for i in idx], W, idx)
+                launches.append((src, pack_records(items, dev)))
+            rep = [r[3] for r in rs]
+            if max(rep) >= 1 << 31:
+                raise RuntimeError(f"GradDistributionTB: a tensor of {tag} has 2^31 elements or more")
+            self._tags.append((tag, launches, torch.tensor(rep, dtype=torch.int32, device=dev), (row0, row0 + len(ts))))
+            row0 += len(ts)
+
+    @torch.no_grad()
+    def log(self):
+        """one logged step: `last`, and the histograms to state.tb_logger if there is one"""
+        tagged = self._tensors()
+        key = tuple((tag, tuple((t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, t.device) for t in ts)) for tag, ts in tagged)
+        if key != self._key:
+            self.build_plan(tagged)
+            self._key = key
+        self._hist.zero_()
+        for k, (tag, launches, rep, (r0, r1)) in enumerate(self._tags):
+            for src, items in launches:
+                ops.absbin_hist(src, items, self._hist[r0:r1])
+            ops.subsample_counts(self._hist[r0:r1], rep, self.subsample, self._counts[k])
+        counts = self._counts.cpu().numpy()  # the one host synchronisation of a logged step
+        if (counts < 0).any():
+            raise RuntimeError("GradDistributionTB: the counting kernel refused its table (a multiplicity below 1)")
+        self.last = {tag: (self._limits, counts[k].copy()) for k, (tag, *_) in enumerate(self._tags)}
+        self.logged += 1
+        tb = self.state.tb_logger
+        if tb is not None:
+            for tag, (limits, c) in self.last.items():
+                tb.add_histogram_raw(tag, *self.raw_stats(limits, c), bucket_limits=limits.tolist(), bucket_counts=c.tolist(),
+                                     global_step=self.state.global_sample_step)
+
+    @staticmethod
+    def raw_stats(limits, counts):
+        """(min, max, num, sum, sum_squares) of add_histogram_raw: num exact; min / max the outer limits of the first / last non-empty bin (-15 below
+        bin 0); sum and sum_squares from the bins' midpoints in log10, for display only"""
+        lower = np.concatenate(([-15.0], limits[:-1]))
+        num = int(counts.sum())
+        nz = np.nonzero(counts)[0]
+        if not len(nz):
+            return 0.0, 0.0, 0, 0.0, 0.0
+        mid = 0.5 * (lower + limits)
+        return float(lower[nz[0]]), float(limits[nz[-1]]), num, float((mid * counts).sum()), float((mid * mid * counts).sum())
+
+    def on_batch_end(self):
+        if self.state.rank != 0 or env_rank() != 0 or not self.state.is_train or self.state.step % self.log_every != 0:
+            return
+        self.log()
 
 
 # one pair of parameter / gradient storage in a plan: the two storages as flat arrays over the pair's element range [lo, hi), the pair's eps array

@@ -71,6 +71,11 @@ INIT_CALLBACK_TARGET_ALIASES = {
     "sota_imagenet.callbacks.OrthoInitClb": "sota_imagenet_amd.callbacks.OrthoInitClb",
 }
 
+# callbacks that only log (sota_imagenet/callbacks.py:30-60; recipes 46, 49-55), consulted after the five tables above, whose contents existing
+# tests pin
+LOGGING_CALLBACK_TARGET_ALIASES = {"src.callbacks.GradDistributionTB": "sota_imagenet_amd.callbacks.GradDistributionTB"}
+
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -308,7 +313,7 @@ def validate(cfg):
 
 def resolve_target(path):
     path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
-            or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path, path))
+            or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path) or LOGGING_CALLBACK_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

@@ -683,4 +683,11 @@ int mi355_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float 
   return launch_ortho_init(w, n, mats, n_mats, gain, status, (hipStream_t)stream);
 }
 
+int mi355_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, void* stream) {
+  return launch_absbin_hist(src, n, items, n_items, n_tensors, hist, (hipStream_t)stream);
+}
+int mi355_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, void* stream) {
+  return launch_subsample_counts(hist, rep, n_tensors, subsample, counts, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -149,6 +149,32 @@ def ortho_records(table):
     return out
 
 
+def hist_records(t):
+    """what the histogram of callbacks.GradDistributionTB counts of the CUDA fp32 tensor view `t`: (storage base ptr, first element, source
+    elements, rep) — the elements to read and how many shown elements each stands for.  A dense view (dense_range) is read as it is, rep 1; a view
+    with stride 0 on every dimension (exp_avg_sq of the layer-wise optimizers) is ONE element shown numel times; the unit form of
+    optim._unit_strides (stride 1 on dim 0, 0 on the others) is shape[0] elements shown numel / shape[0] times each.  Dimensions of size 1 carry
+    no stride.  Anything else raises RuntimeError naming the shape and strides."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+        raise NotImplementedError(f"hist_records: a CUDA fp32 tensor is needed (there is no CPU path), got {getattr(t, 'dtype', type(t).__name__)} "
+                                  f"on {getattr(t, 'device', 'the host')}")
+    n = t.numel()
+    if n < 1:
+        raise RuntimeError(f"hist_records: an empty tensor (shape {tuple(t.shape)}) has nothing to count")
+    base = t.untyped_storage().data_ptr()
+    first = (t.data_ptr() - base) // t.element_size()
+    r = dense_range(t)
+    if r is not None:
+        return base, first, n, 1
+    strides = [st if sz > 1 else 0 for st, sz in zip(t.stride(), t.size())]
+    if not any(strides):
+        return base, first, 1, n
+    if strides[0] == 1 and not any(strides[1:]):
+        return base, first, t.shape[0], n // t.shape[0]
+    raise RuntimeError(f"hist_records: shape {tuple(t.shape)} with strides {tuple(t.stride())} is neither dense, nor one value shown broadcast, "
+                       "nor one value per index of dim 0")
+
+
 def pack_records(records, device=None, fields=ITEM_FIELDS):
     """records (tuples of `fields`, 16 bytes for the default three) as the [n, bytes / 8] int64 tensor the ops wrappers take, on `device` (the
     CPU if None); a record shorter than `fields` is padded with zeros"""

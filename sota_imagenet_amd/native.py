@@ -23,6 +23,9 @@ _BASE = {
     "double": ctypes.c_double,
     "size_t": ctypes.c_size_t,
     "uint8_t": ctypes.c_uint8,
+    "uint32_t": ctypes.c_uint32,
+    "int32_t": ctypes.c_int32,
+    "uint64_t": ctypes.c_uint64,
     "unsigned": ctypes.c_uint,
     "unsigned long long": ctypes.c_ulonglong,
     "unsigned char": ctypes.c_ubyte,

@@ -6,6 +6,7 @@ Every function enqueues on torch's current stream and raises RuntimeError on any
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import native
@@ -726,6 +727,56 @@ def ortho_init_(flat, records_host, records_dev, gain=1.0):
     status = torch.empty(n_mats, dtype=torch.int32, device=flat.device)
     check(_L().mi355_ortho_init(ptr(flat), flat.numel(), ptr(records_dev), n_mats, float(gain), ptr(status), cur_stream()))
     return status
+
+
+# ---- the log histogram of |x| (include/mi355rn.h, csrc/optim_hist.hip): the GradDistributionTB callback of the reference ----------------------------
+# the bins, stated once for the host; csrc/absbin.h states them for the kernels and tests/test_grad_dist_host.py holds the two together
+ABSBIN_BINS, ABSBIN_SHIFT, ABSBIN_K0 = 512, 20, (77 << 3) + 2
+ABSBIN_BAD_REP = 2 ** 64 - 1  # what mi355_subsample_counts writes into every count when a rep[t] < 1
+
+
+def absbin_edges():
+    """float32 [511]: the lower edges of bins 1..511 (= the upper edges of bins 0..510), the floats with bits (K0 + b) << SHIFT"""
+    return ((np.arange(1, ABSBIN_BINS, dtype=np.int64) + ABSBIN_K0) << ABSBIN_SHIFT).astype(np.uint32).view(np.float32)
+
+
+def absbin_log10_limits():
+    """float64 [512]: log10 of the bins' upper edges, formed in double — the bucket limits of the histogram; the last bin takes everything up to
+    infinity and NaN and is closed at the largest float32.  The lower side of bin 0 is -15, the reference's clamp."""
+    return np.log10(np.append(absbin_edges().astype(np.float64), float(np.finfo(np.float32).max)))
+
+
+def absbin_hist(src, items, hist):
+    """replaces the per-tensor .abs().sort() of sota_imagenet/callbacks.py:47 and :56: ADDS into hist[t] (CUDA int32 [n_tensors, 512], read as
+    unsigned; zeroed by the caller) the bin counts of |src| over the work items { first element, length <= lw_item_elems(), t } of `items`; src:
+    the flat fp32 array the item offsets count from.  Elements outside the items are not counted, an item outside src is skipped."""
+    _flat_f32(src.numel(), src=src)
+    _lw_table("items", items)
+    _need_cuda(hist)
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != ABSBIN_BINS or hist.shape[0] < 1:
+        raise ValueError(f"hist: expected a contiguous CUDA int32 tensor [n_tensors, {ABSBIN_BINS}], got {hist.dtype} {tuple(hist.shape)}")
+    if not (src.device == items.device == hist.device):
+        raise ValueError("absbin_hist: the array, the table and the histograms must live on one device")
+    check(_L().mi355_absbin_hist(ptr(src), src.numel(), ptr(items), items.shape[0], hist.shape[0], ptr(hist), cur_stream()))
+
+
+def subsample_counts(hist, rep, subsample, counts, rep_host=None):
+    """replaces the [::subsample], torch.cat, second sort and second [::subsample] of callbacks.py:47-50 and :56-59: counts[k] (CUDA int64 [512]) =
+    the number of values of the twice-subsampled set in bin k, from the per-tensor histograms hist [n, 512] and rep (CUDA int32 [n]: shown elements
+    per counted element, >= 1).  rep lives on the device: a rep < 1 makes the kernel write -1 (ABSBIN_BAD_REP unsigned) into every count; rep_host,
+    the same numbers on the host where the caller has them, is tested here and raises ValueError."""
+    _need_cuda(hist, rep, counts)
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != ABSBIN_BINS or hist.shape[0] < 1:
+        raise ValueError(f"hist: expected a contiguous CUDA int32 tensor [n_tensors, {ABSBIN_BINS}], got {hist.dtype} {tuple(hist.shape)}")
+    if rep.dtype != torch.int32 or rep.dim() != 1 or rep.numel() != hist.shape[0]:
+        raise ValueError(f"rep: expected {hist.shape[0]} int32 elements, got {rep.dtype} {tuple(rep.shape)}")
+    if counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != ABSBIN_BINS:
+        raise ValueError(f"counts: expected {ABSBIN_BINS} int64 elements, got {counts.dtype} {tuple(counts.shape)}")
+    if not (hist.device == rep.device == counts.device):
+        raise ValueError("subsample_counts: the histograms, rep and counts must live on one device")
+    if rep_host is not None and (len(rep_host) != hist.shape[0] or any(int(r) < 1 for r in rep_host)):
+        raise ValueError(f"subsample_counts: rep must hold one number >= 1 per tensor, got {list(rep_host)[:8]}...")
+    check(_L().mi355_subsample_counts(ptr(hist), ptr(rep), hist.shape[0], int(subsample), ptr(counts), cur_stream()))
 
 
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
