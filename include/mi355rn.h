@@ -515,6 +515,27 @@ int mi355_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float 
 int mi355_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, void* stream);
 int mi355_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, void* stream);
 
+/* The per-epoch weight histograms of the reference: `WeightDistributionTB` (sota_imagenet/callbacks.py:11-17, added by train.py:140 when
+ * `log.histogram` is set: recipes 4, 11-14, 45-55), which hands every entry of model.state_dict() to
+ * tb_logger.add_histogram("model/<name>", p.flatten(), global_sample_step) — csrc/optim_wdist.hip.  add_histogram with its defaults copies the
+ * tensor to the host and runs np.histogram(values.astype(float64), bins) over TensorBoard's default bins, then takes min, max, sum and the sum
+ * of squares in double.  mi355_tbbin_hist is that over the work items of one flat fp32 array, in one pass:
+ *   edges[]    the 774 positive edges, ascending, as doubles in device memory: v = 1e-12, v *= 1.1 while v < 1e20, formed by the caller with this
+ *              recurrence in double (the table is the rule; ops.tbbin_edges()[775:]).  The full table is their negatives reversed, 0, and they:
+ *              1549 edges E_0..E_1548, 1548 bins; bin i is [E_i, E_i+1), the last one also takes x == E_1548.  Every comparison is made in double.
+ *   items[]    { int64 first; int32 len; int32 tensor }, len <= mi355_lw_item_elems(), first ANY element offset (as for mi355_absbin_hist)
+ *   hist[][]   uint32 [n_tensors][1552]: the counts of items[i] are ADDED into hist[items[i].tensor][0..1547] (the caller zeroes the table; several
+ *              launches — one per storage — fill one table); entry 1548 counts the elements that np.histogram puts in no bin: NaN, both
+ *              infinities, everything below E_0 or above E_1548; entries 1549..1551 pad the row to 16 bytes and stay untouched.
+ *   partial[]  double [n_items][5]: { min, max, sum, sum of squares, 1.0 if a NaN was seen else 0.0 } of the item's elements; min and max skip
+ *              NaN (+inf / -inf if the item holds nothing else), the sums take every element.  Fixed order inside the workgroup, no floating-point
+ *              atomics: the caller adds a tensor's items in table order and gets the same bits in every run.
+ * Elements outside the items are never read; a record that does not lie inside [0, n), or whose tensor is not in [0, n_tensors), is skipped and its
+ * partial[] entry stays as it was.  Fails (MI355_E_ARG) before the launch on a null or misaligned pointer (16 bytes for src, items[] and hist[],
+ * 8 for edges[] and partial[]), an empty table, n_tensors < 1 or n_edges != 774. */
+int mi355_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges, uint32_t* hist,
+                     double* partial, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

@@ -5,7 +5,7 @@ Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `
 `self.mixup(*input)` with Beta(alpha, alpha) samplers) and the un-vendored pt_clb.Cutmix / pt_clb.Mixup bases as
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
-over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip.
+over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip.
 """
 
 import logging
@@ -367,6 +367,180 @@ class GradDistributionTB(Callback):
 
     def on_batch_end(self):
         if self.state.rank != 0 or env_rank() != 0 or not self.state.is_train or self.state.step % self.log_every != 0:
+            return
+        self.log()
+
+
+def tb_trim(counts, edges):
+    """the trimming of add_histogram (torch/utils/tensorboard/summary.py, make_histogram): counts [bins] over edges [bins + 1] -> (bucket_limits,
+    bucket_counts) from the first to the last non-empty bin, with one empty bin in front so that the leftmost limit is kept — the bin to the left
+    of the first non-empty one, or a zero where that is bin 0.  No counted value raises ValueError, as upstream does."""
+    nz = np.flatnonzero(counts)
+    if not len(nz):
+        raise ValueError("The histogram is empty: no value lies inside the bins")
+    start, end = int(nz[0]), int(nz[-1])
+    kept = counts[start - 1: end + 1] if start > 0 else np.concatenate(([0], counts[: end + 1]))
+    return edges[start: end + 2].tolist(), [int(c) for c in kept]
+
+
+def tb_host_counts(values, edges):
+    """np.histogram(values, bins=edges) of float64 values, stated by position: bin i is [edges[i], edges[i+1]), the last bin also takes
+    values == edges[-1]; NaN, infinities and everything outside the edges are counted nowhere"""
+    idx = np.searchsorted(edges, values, side="right") - 1  # the last edge <= x; NaN sorts behind every edge
+    idx[values == edges[-1]] = len(edges) - 2
+    ok = (idx >= 0) & (idx <= len(edges) - 2) & ~np.isnan(values)
+    return np.bincount(idx[ok], minlength=len(edges) - 1)
+
+
+class _WeightDistPlan:
+    """what WeightDistributionTB keeps between epochs: rows / spans (item_plan.dist_plan), launches = [(flat source array, items on the device,
+    (first item, end item))], gathers = [(source tensor, first, end)] into `other`, where = {entry: (first, numel)} in `other`, and the one device
+    buffer `buf` with its three views hist [rows, TBBIN_ROW] int32, partial [items, TBBIN_STATS] float64 and other float64"""
+
+
+class WeightDistributionTB(Callback):
+    """sota_imagenet/callbacks.py:11-17, added by train.py:140 when `log.histogram` is set (recipes 4, 11-14, 45-55): at every epoch's begin, on rank 0
+    only, every entry of state.model.state_dict(), in its order and under the tag "model/" + its name, as the histogram that
+    SummaryWriter.add_histogram(tag, p.flatten(), global_sample_step) draws with its defaults.  The reference copies the entries to the host one
+    by one and runs np.histogram over the 1549 default edges on each; here the CUDA fp32 entries (whatever item_plan.hist_records takes as a dense
+    view) are counted where they lie, by one ops.tbbin_hist per storage — two launches for models.resnet50: the flat parameters and the flat
+    buffers — which also gives min, max, sum and sum of squares per work item (csrc/optim_wdist.hip).  Every other entry —
+    the int64 num_batches_tracked, which are views of one array — is gathered on the device, one cast to float64 per storage, and binned on the
+    host by the same rule (tb_host_counts).  Counts, statistics and gathered values share one device buffer: a logged epoch is one zero_ of the
+    table, the launches, and ONE copy to the host, the callback's only host synchronisation.  The plan is built at the first logged epoch and
+    rebuilt when the names, addresses, shapes, strides or dtypes change.
+
+    `last` = {tag: dict(min, max, num, sum, sum_squares, bucket_limits, bucket_counts)} holds the last logged epoch: limits and counts trimmed as
+    add_histogram trims them (tb_trim), min / max / sum / sum_squares in float64 over all values, counted or not (min and max NaN where the
+    tensor holds a NaN), num = numel.  With a state.tb_logger every tag goes out through add_histogram_raw at state.global_sample_step.  The sums
+    are added in a fixed order (inside a workgroup, then a tensor's work items in table order on the host): two runs agree bit for bit; against
+    numpy's order they differ by rounding.  An entry without a counted value — empty, or all NaN / out of range — raises ValueError as
+    add_histogram does; CPU tensors raise NotImplementedError: there is no CPU path."""
+
+    def __init__(self):
+        super().__init__()
+        self.last = {}
+        self.logged = 0  # logged epochs so far
+        self._key = None
+        self._plan = None
+        self._edges = ops.tbbin_edges()
+
+    def build_plan(self, named):
+        """named: [(name, tensor)] of the state_dict"""
+        for name, t in named:
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise NotImplementedError(f"WeightDistributionTB: {name} is not a CUDA tensor (there is no CPU path)")
+            if t.numel() < 1:
+                raise ValueError(f"WeightDistributionTB: {name} has no element")
+        devs = {t.device for _, t in named}
+        if len(devs) != 1:
+            raise RuntimeError(f"WeightDistributionTB: the state_dict must live on one device (got {sorted(map(str, devs))})")
+        dev = devs.pop()
+        records = []
+        for _, t in named:
+            rec = None
+            if t.dtype == torch.float32:
+                try:
+                    base, first, n, rep = item_plan.hist_records(t)
+                    if rep == 1 and base % 16 == 0 and n < 1 << 31:
+                        rec = (base, first, n)
+                except RuntimeError:  # neither dense nor one of the broadcast forms: the host rule takes it
+                    pass
+            records.append(rec)
+        P = _WeightDistPlan()
+        P.rows, launches, P.spans, n_items = item_plan.dist_plan(records, ops.lw_item_elems())
+        # every other entry: grouped by storage and dtype where it is a dense view, else on its own
+        groups, loose = {}, []
+        for k, (_, t) in enumerate(named):
+            if records[k] is not None:
+                continue
+            r = item_plan.dense_range(t)
+            if r is None:
+                loose.append(k)
+                continue
+            g = groups.setdefault((r[0], t.dtype), [r[1], r[1] + r[2], []])
+            g[0], g[1] = min(g[0], r[1]), max(g[1], r[1] + r[2])
+            g[2].append((k, r[1], r[2]))
+        P.gathers, P.where, n_other = [], {}, 0
+        for (_, dtype), (lo, hi, members) in groups.items():
+            t0 = named[members[0][0]][1]
+            flat = torch.empty(0, dtype=dtype, device=dev).set_(t0.untyped_storage(), lo, (hi - lo,))
+            P.gathers.append((flat, n_other, n_other + hi - lo))
+            for k, first, n in members:
+                P.where[k] = (n_other + first - lo, n)
+            n_other += hi - lo
+        for k in loose:
+            t = named[k][1]
+            P.gathers.append((t, n_other, n_other + t.numel()))
+            P.where[k] = (n_other, t.numel())
+            n_other += t.numel()
+        h, p = len(P.rows) * ops.TBBIN_ROW // 2, n_items * ops.TBBIN_STATS  # in 8-byte words
+        P.buf = torch.zeros(h + p + n_other, dtype=torch.int64, device=dev)
+        P.cuts = (h, h + p)
+        P.hist = P.buf[:h].view(torch.int32).view(len(P.rows), ops.TBBIN_ROW)
+        P.partial = P.buf[h: h + p].view(torch.float64).view(n_items, ops.TBBIN_STATS)
+        P.other = P.buf[h + p:].view(torch.float64)
+        P.launches = []
+        for base, lo, hi, items, i0 in launches:
+            t0 = named[P.rows[items[0][2]]][1]
+            src = torch.empty(0, dtype=torch.float32, device=dev).set_(t0.untyped_storage(), lo, (hi - lo,))
+            P.launches.append((src, pack_records(items, dev), (i0, i0 + len(items))))
+        return P
+
+    @torch.no_grad()
+    def log(self):
+        """one logged epoch: `last`, and the histograms to state.tb_logger if there is one"""
+        named = list(self.state.model.state_dict().items())
+        key = tuple((name, t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, t.device) if torch.is_tensor(t) else (name, None)
+                    for name, t in named)
+        if key != self._key:
+            self._plan = self.build_plan(named)
+            self._key = key
+        P = self._plan
+        P.hist.zero_()
+        for src, items, (i0, i1) in P.launches:
+            ops.tbbin_hist(src, items, P.hist, P.partial[i0:i1])
+        for t, a, b in P.gathers:
+            P.other[a:b].copy_(t.reshape(-1))
+        host = P.buf.cpu().numpy()  # the one host synchronisation of a logged epoch
+        h, p = P.cuts
+        hist = host[:h].view(np.uint32).reshape(len(P.rows), ops.TBBIN_ROW)
+        partial = host[h:p].view(np.float64).reshape(-1, ops.TBBIN_STATS)
+        other = host[p:].view(np.float64)
+        row_of = {k: r for r, k in enumerate(P.rows)}
+        edges, last = self._edges, {}
+        for k, (name, t) in enumerate(named):
+            if k in row_of:
+                r = row_of[k]
+                i0, c = P.spans[r]
+                st = partial[i0: i0 + c]
+                counts = hist[r, : ops.TBBIN_BINS].astype(np.int64)
+                if int(counts.sum()) + int(hist[r, ops.TBBIN_NOBIN]) != t.numel():
+                    raise RuntimeError(f"WeightDistributionTB: {name}: the counting kernel skipped a work item of its table")
+                nan = bool(st[:, 4].any())
+                # cumsum adds strictly in table order
+                stats = dict(min=float("nan") if nan else float(st[:, 0].min()), max=float("nan") if nan else float(st[:, 1].max()),
+                             num=t.numel(), sum=float(np.cumsum(st[:, 2])[-1]), sum_squares=float(np.cumsum(st[:, 3])[-1]))
+            else:
+                a, n = P.where[k]
+                v = other[a: a + n]
+                counts = tb_host_counts(v, edges)
+                stats = dict(min=float(v.min()), max=float(v.max()), num=n, sum=float(v.sum()), sum_squares=float(v.dot(v)))
+            try:
+                limits, kept = tb_trim(counts, edges)
+            except ValueError as e:
+                raise ValueError(f"WeightDistributionTB: {name}: {e}") from None
+            last["model/" + name] = dict(stats, bucket_limits=limits, bucket_counts=kept)
+        self.last = last
+        self.logged += 1
+        tb = self.state.tb_logger
+        if tb is not None:
+            for tag, d in last.items():
+                tb.add_histogram_raw(tag, d["min"], d["max"], d["num"], d["sum"], d["sum_squares"], bucket_limits=d["bucket_limits"],
+                                     bucket_counts=d["bucket_counts"], global_step=self.state.global_sample_step)
+
+    def on_epoch_begin(self):
+        if self.state.rank != 0 or env_rank() != 0:
             return
         self.log()
 

@@ -75,6 +75,10 @@ INIT_CALLBACK_TARGET_ALIASES = {
 # tests pin
 LOGGING_CALLBACK_TARGET_ALIASES = {"src.callbacks.GradDistributionTB": "sota_imagenet_amd.callbacks.GradDistributionTB"}
 
+# the per-epoch weight histograms (sota_imagenet/callbacks.py:11-17).  The reference's train.py:140 adds the callback itself when log.histogram
+# is set, and so does train.py here (histogram_callback); the alias lets a config list it too.  Consulted last, in a table of its own: an
+# existing test pins the table above to its one key
+WEIGHT_HISTOGRAM_TARGET_ALIASES = {"src.callbacks.WeightDistributionTB": "sota_imagenet_amd.callbacks.WeightDistributionTB"}
 
 
 def default_config():
@@ -313,7 +317,8 @@ def validate(cfg):
 
 def resolve_target(path):
     path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
-            or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path) or LOGGING_CALLBACK_TARGET_ALIASES.get(path, path))
+            or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path) or LOGGING_CALLBACK_TARGET_ALIASES.get(path)
+            or WEIGHT_HISTOGRAM_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

@@ -390,6 +390,9 @@ int launch_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float
 // optim_hist.hip: per-tensor histograms of |x| over the bins of absbin.h and the bin counts of the twice-subsampled set (the GradDistributionTB callback)
 int launch_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, hipStream_t st);
 int launch_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, hipStream_t st);
+// optim_wdist.hip: per-tensor histograms over TensorBoard's default bins and the items' min / max / sums (the WeightDistributionTB callback)
+int launch_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges,
+                      uint32_t* hist, double* partial, hipStream_t st);
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

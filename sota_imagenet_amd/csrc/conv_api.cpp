@@ -689,5 +689,9 @@ int mi355_absbin_hist(const float* src, size_t n, const void* items, size_t n_it
 int mi355_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, void* stream) {
   return launch_subsample_counts(hist, rep, n_tensors, subsample, counts, (hipStream_t)stream);
 }
+int mi355_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges,
+                     uint32_t* hist, double* partial, void* stream) {
+  return launch_tbbin_hist(src, n, items, n_items, n_tensors, edges, n_edges, hist, partial, (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -175,6 +175,30 @@ def hist_records(t):
                        "nor one value per index of dim 0")
 
 
+def dist_plan(records, W):
+    """the launches of callbacks.WeightDistributionTB.  records: per entry of a state_dict, in its order, (storage base ptr, first element, numel)
+    for a tensor the counting kernel reads, None for one it does not.  The tensors are numbered in that order (their rows of the histogram table)
+    and grouped by storage, one launch per storage in order of first appearance.  Returns (rows, launches, spans, n_items): rows[r] = the entry of
+    row r; launches = [(base, lo, hi, items, first item)], [lo, hi) the element range of the storage that the launch's flat array covers (lo a
+    multiple of 4 elements), items = plan_items' table with offsets relative to lo and the row as tensor index, first item = the launch's place
+    in an array of per-item results shared by all launches (n_items entries); spans[r] = (first item, item count) of row r there."""
+    rows = [k for k, r in enumerate(records) if r is not None]
+    by_storage = {}
+    for r, k in enumerate(rows):
+        by_storage.setdefault(records[k][0], []).append(r)
+    launches, spans, n_items = [], [None] * len(rows), 0
+    for base, rs in by_storage.items():
+        recs = [records[rows[r]] for r in rs]
+        lo = min(first for _, first, _ in recs) & ~3
+        hi = max(first + n for _, first, n in recs)
+        items, sp = plan_items([(first - lo, n) for _, first, n in recs], W, rs)
+        for r, (i0, c) in zip(rs, sp):
+            spans[r] = (n_items + i0, c)
+        launches.append((base, lo, hi, items, n_items))
+        n_items += len(items)
+    return rows, launches, spans, n_items
+
+
 def pack_records(records, device=None, fields=ITEM_FIELDS):
     """records (tuples of `fields`, 16 bytes for the default three) as the [n, bytes / 8] int64 tensor the ops wrappers take, on `device` (the
     CPU if None); a record shorter than `fields` is padded with zeros"""

@@ -779,6 +779,49 @@ def subsample_counts(hist, rep, subsample, counts, rep_host=None):
     check(_L().mi355_subsample_counts(ptr(hist), ptr(rep), hist.shape[0], int(subsample), ptr(counts), cur_stream()))
 
 
+# ---- the histogram over TensorBoard's default bins (include/mi355rn.h, csrc/optim_wdist.hip): the WeightDistributionTB callback ---------------------
+TBBIN_POS = 774                 # positive edges
+TBBIN_BINS = 2 * TBBIN_POS      # 1548 bins between 1549 edges
+TBBIN_NOBIN = TBBIN_BINS        # the row's entry that counts what lies in no bin: NaN, infinities, values outside the table
+TBBIN_ROW = 1552                # entries per row of hist[]: a whole number of 16-byte vectors
+TBBIN_STATS = 5                 # doubles per work item in partial[]: min, max, sum, sum of squares, NaN seen
+_tbbin_dev = {}                 # device -> the positive edges there
+
+
+def tbbin_edges():
+    """float64 [1549]: the default bins of SummaryWriter.add_histogram (bins="tensorflow") — v = 1e-12, v *= 1.1 in double while v < 1e20 gives the
+    774 positive edges; the table is their negatives reversed, 0, and they.  Formed by the recurrence, not by a power: the rounding of every
+    product is part of the rule."""
+    pos, v = [], 1e-12
+    while v < 1e20:
+        pos.append(v)
+        v *= 1.1
+    assert len(pos) == TBBIN_POS
+    return np.array([-e for e in reversed(pos)] + [0.0] + pos, dtype=np.float64)
+
+
+def tbbin_hist(src, items, hist, partial):
+    """replaces the per-tensor p.flatten() -> host -> np.histogram / min / max / sum / dot of add_histogram (sota_imagenet/callbacks.py:16): ADDS into
+    hist[t] (CUDA int32 [n_tensors, 1552], read as unsigned; zeroed by the caller) the counts of src over the 1548 default bins, entry TBBIN_NOBIN
+    counting what lies in no bin, for the work items { first element, length <= lw_item_elems(), t } of `items`, and writes partial[i] (CUDA float64
+    [n_items, 5]) = min, max, sum, sum of squares, NaN seen of item i.  src: the flat fp32 array the item offsets count from.  Elements outside the
+    items are not read, an item outside src is skipped."""
+    _flat_f32(src.numel(), src=src)
+    _lw_table("items", items)
+    _need_cuda(hist, partial)
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != TBBIN_ROW or hist.shape[0] < 1:
+        raise ValueError(f"hist: expected a contiguous CUDA int32 tensor [n_tensors, {TBBIN_ROW}], got {hist.dtype} {tuple(hist.shape)}")
+    if partial.dtype != torch.float64 or tuple(partial.shape) != (items.shape[0], TBBIN_STATS):
+        raise ValueError(f"partial: expected a float64 tensor [{items.shape[0]}, {TBBIN_STATS}], got {partial.dtype} {tuple(partial.shape)}")
+    if not (src.device == items.device == hist.device == partial.device):
+        raise ValueError("tbbin_hist: the array, the table, the histograms and the partial statistics must live on one device")
+    edges = _tbbin_dev.get(src.device)
+    if edges is None:
+        edges = _tbbin_dev[src.device] = torch.from_numpy(tbbin_edges()[TBBIN_POS + 1:].copy()).to(src.device)
+    check(_L().mi355_tbbin_hist(ptr(src), src.numel(), ptr(items), items.shape[0], hist.shape[0], ptr(edges), edges.numel(), ptr(hist), ptr(partial),
+                                cur_stream()))
+
+
 # ---- BResNet-50 variant blocks (include/mi355rn.h, csrc/variant.hip) ---------------------------------------------------
 def blurpool_fwd(x):
     _need_cuda(x)

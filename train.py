@@ -68,6 +68,13 @@ class Logger:
                 f.write(line + "\n")
 
 
+def histogram_callback(cfg):
+    """train.py:140 of the reference: `WeightDistributionTB() if cfg.log.histogram else NoClbk()` — the per-epoch weight histograms"""
+    from sota_imagenet_amd.callbacks import WeightDistributionTB
+
+    return WeightDistributionTB() if cfg.log.histogram else fw.Callback()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-c", "--config", default=None, help="experiment YAML (Hydra or legacy schema)")
@@ -175,7 +182,7 @@ def main(argv=None):
         fw.Timer(),
         fw.ConsoleLogger(),
         fw.TensorBoard(run_dir, log_every=50),
-        fw.Callback(),  # WeightDistributionTB is a research add-on outside the hot path
+        histogram_callback(cfg),
     ]
     callbacks += [C.call(clb_cfg) for clb_cfg in cfg.run.extra_callbacks]
 
