@@ -536,6 +536,27 @@ int mi355_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tenso
 int mi355_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges, uint32_t* hist,
                      double* partial, void* stream);
 
+/* Backward centred weight normalisation: the reference's `src.callbacks.WeightNorm` (sota_imagenet/callbacks.py:104-123; recipes 9, 10, 14, 37-39),
+ * which after every optimizer step takes every module weight of 64 elements or more as a [size(0), -1] matrix, subtracts each row's mean and divides
+ * each row by its L2 norm — csrc/weight_norm.hip.  One launch over a table of rows of a flat fp32 array, in place:
+ *   items[]  { int64 first; int32 row_len; int32 n_rows }   16 bytes: n_rows consecutive rows of row_len elements, the first one at w[first] (ANY
+ *            element offset: the stem's rows are 147 long); a conv weight in KRSC memory and an FC weight alike, a row is one contiguous run
+ * Per row x[0..L), every operation rounded on its own:
+ *   S1 = sum (double)x_i;   m = (float)(S1 / (double)L);   c_i = x_i - m (float);   S2 = sum (double)c_i * (double)c_i;   nrm = (float)sqrt(S2);
+ *   x_i = c_i / nrm (float division)
+ *   the sums: per thread in element order, then a fixed tree; no floating-point atomics, nothing summed across workgroups — a row's result depends
+ *   on its elements alone (not on the item that holds it), and two runs on the same input agree bit for bit.  A constant row gives 0 / 0: the whole
+ *   row becomes NaN, as in the reference, and nothing outside it changes.
+ * One 256-thread workgroup per item; rows of at most mi355_wnorm_wave_row_max() elements take one wave each, longer rows the whole workgroup (the
+ * result does not depend on which, beyond the order of the sums).  Items must not overlap.  Elements outside the items (alignment gaps, BatchNorm
+ * tensors, biases, the FC padding rows) are neither read nor written.  status[i] (device, n_items ints), written with ordinary stores:
+ *   0  done
+ *   2  the item does not fit: first >= 0, row_len >= 1, n_rows >= 1 and first + row_len*n_rows <= n are tested before anything is accessed through
+ *      it; such an item is skipped and its memory untouched
+ * Fails (-1) before the launch on a null or misaligned pointer (16 bytes for w and items[], 4 for status[]), n == 0 or an empty table. */
+int mi355_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, void* stream);
+int mi355_wnorm_wave_row_max(void);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

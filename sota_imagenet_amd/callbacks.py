@@ -5,7 +5,7 @@ Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `
 `self.mixup(*input)` with Beta(alpha, alpha) samplers) and the un-vendored pt_clb.Cutmix / pt_clb.Mixup bases as
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
-over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip.
+over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip, WeightNorm :104-123 over csrc/weight_norm.hip.
 """
 
 import logging
@@ -241,6 +241,73 @@ class OrthoInitClb(Callback):
             self.fill()
             self.orthogonalise()
         self.has_been_init = True
+
+
+class WeightNorm(Callback):
+    """sota_imagenet/callbacks.py:104-123 (recipes 9, 10, 14, 37-39), the reference's "backward centered weight normalization": after every
+    optimizer step each conv filter and each FC row — a weight [O, ...] taken as an O x (numel / O) matrix — is centred on its mean and scaled
+    to unit L2 norm, in place.  It runs at the end of every training batch (the micro-batches of accumulate_steps > 1 included), on every rank
+    (each applies the same deterministic kernel to identical weights), and the first forward sees the initial weights as they are.  Listed among
+    run.extra_callbacks it comes after ModelEma, as in the reference: an average fused into the optimizer's step kernel takes the weights after
+    the step and before the normalisation.
+
+    The reference walks model.modules() with several torch calls per weight; here the model is a flat-array model (models._FlatModel:
+    models.resnet50, bresnet.BResNet50) on a CUDA device, anything else raises NotImplementedError (there is no CPU path), the plan
+    (item_plan.wnorm_records, wnorm_items) and its packed table are built once at on_begin, and on_batch_end is ONE launch of
+    ops.weight_norm_rows_ over the flat parameter array on the current stream (csrc/weight_norm.hip), nothing read back.
+    `records` is the planned table [(off, rows, row_len)], `names` the tensors' names, `items` the work items, `status` the last launch's status
+    tensor (all zero for a plan built from the model's own table), `launches` the launches so far.  A filter whose elements are all equal
+    becomes NaN (0 / 0), as in the reference.
+
+    Three deliberate departures from the reference:
+      1. Tensors with fewer than two dimensions are not selected.  The reference takes every module with a .weight of 64 elements or more; its
+         view(C, -1) of a BatchNorm weight with C >= 64 is C x 1, each row's mean is the element itself and its norm 0, so it writes NaN into
+         every such BatchNorm weight (it only ever ran on norm-free nets).  The planner takes parameters with ndim >= 2 and numel >= 64: Conv2d
+         and Linear weights.  The ECA Conv1d weights of BResNet-50 fall under numel < 64, exactly as in the reference.
+      2. It runs only while state.is_train.  The Runner fires on_batch_end during validation too, where the reference would rewrite the weights
+         being evaluated — under ModelEma the swapped-in average.
+      3. The constructor takes no arguments, like the reference's class as it stands.  Recipes 9, 10 and 14 still pass gamma / use_std from an
+         older signature (whose helpers lived in pytorch_tools); those keys raise TypeError here, as they would there."""
+
+    def __init__(self):
+        super().__init__()
+        self.records, self.names, self.items, self.status = [], [], [], None
+        self.launches = 0
+        self._flat = self._items_dev = None
+
+    def _flat_model(self):
+        from .models import _FlatModel
+
+        m = _unwrap(self.state.model)
+        if not isinstance(m, _FlatModel) or not m.flat_params.is_cuda:
+            raise NotImplementedError("WeightNorm runs on a flat-array model (models.resnet50) on a CUDA device: there is no CPU path and no "
+                                      f"module walk (got {type(m).__name__} on {getattr(getattr(m, 'flat_params', None), 'device', 'no flat array')})")
+        return m
+
+    def on_begin(self):
+        m = self._flat_model()
+        logging.getLogger(__name__).info("Using backward Centered Weight Normalization for weights")
+        self.build_plan(m)
+
+    def build_plan(self, m):
+        """the records, the work items and the packed table for the flat model m"""
+        self.records = item_plan.wnorm_records(m._table)
+        by_off = {off: f"{m._name_of(leaf)}.{attr}" for leaf, attr, kind, off, _ in m._entries if kind == 0}
+        self.names = [by_off[r[0]] for r in self.records]
+        self.items = item_plan.wnorm_items(self.records, ops.WNORM_ITEM_ELEMS)
+        ops.wnorm_check_items(self.items)  # once: the launches below pass no host table
+        self._items_dev = pack_records(self.items, m.flat_params.device)
+        self._flat = m.flat_params
+
+    @torch.no_grad()
+    def on_batch_end(self):
+        if not self.state.is_train:
+            return
+        m = self._flat_model()
+        if m.flat_params is not self._flat:  # the model moved since on_begin: the table lives where the array does
+            self.build_plan(m)
+        self.status = ops.weight_norm_rows_(self._flat.detach(), None, self._items_dev)
+        self.launches += 1
 
 
 class GradDistributionTB(Callback):

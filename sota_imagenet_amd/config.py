@@ -80,6 +80,13 @@ LOGGING_CALLBACK_TARGET_ALIASES = {"src.callbacks.GradDistributionTB": "sota_ima
 # existing test pins the table above to its one key
 WEIGHT_HISTOGRAM_TARGET_ALIASES = {"src.callbacks.WeightDistributionTB": "sota_imagenet_amd.callbacks.WeightDistributionTB"}
 
+# callbacks that rewrite the weights after every step (sota_imagenet/callbacks.py:104-123; recipes 9, 10, 14, 37-39), consulted last, after the
+# seven tables above, whose contents existing tests pin
+WEIGHT_CALLBACK_TARGET_ALIASES = {
+    "src.callbacks.WeightNorm": "sota_imagenet_amd.callbacks.WeightNorm",
+    "sota_imagenet.callbacks.WeightNorm": "sota_imagenet_amd.callbacks.WeightNorm",
+}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -318,7 +325,7 @@ def validate(cfg):
 def resolve_target(path):
     path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
             or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path) or LOGGING_CALLBACK_TARGET_ALIASES.get(path)
-            or WEIGHT_HISTOGRAM_TARGET_ALIASES.get(path, path))
+            or WEIGHT_HISTOGRAM_TARGET_ALIASES.get(path) or WEIGHT_CALLBACK_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

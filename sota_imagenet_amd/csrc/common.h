@@ -393,6 +393,9 @@ int launch_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tens
 // optim_wdist.hip: per-tensor histograms over TensorBoard's default bins and the items' min / max / sums (the WeightDistributionTB callback)
 int launch_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges,
                       uint32_t* hist, double* partial, hipStream_t st);
+// weight_norm.hip: every row of a table of items { first, row_len, n_rows } of one flat array centred and scaled to unit norm (the WeightNorm callback)
+int launch_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, hipStream_t st);
+int wnorm_wave_row_max();
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

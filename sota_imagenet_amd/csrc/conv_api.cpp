@@ -694,4 +694,9 @@ int mi355_tbbin_hist(const float* src, size_t n, const void* items, size_t n_ite
   return launch_tbbin_hist(src, n, items, n_items, n_tensors, edges, n_edges, hist, partial, (hipStream_t)stream);
 }
 
+int mi355_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, void* stream) {
+  return launch_weight_norm_rows(w, n, items, n_items, status, (hipStream_t)stream);
+}
+int mi355_wnorm_wave_row_max(void) { return wnorm_wave_row_max(); }
+
 }  // extern "C"

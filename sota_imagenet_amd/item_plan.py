@@ -2,7 +2,8 @@
 (callbacks.SAMOriginal, callbacks.SAM) run on.  Which parameters fit the flat kernels (place), the parameters grouped by pair of parameter /
 gradient storage with every tensor cut into work items of at most W elements (plan_items, storage_pairs), the 16-byte records the kernels read
 (pack_records) and a storage as flat arrays (flat_views); for the statistics taken per output unit (callbacks.SAM, the unit-wise optimizers of
-optim.py) the unit rule (unit_len) and the tables of pieces, slots and tensor records (plan_units).  Everything up to pack_records is pure Python on plain tuples, so a planner is pinned
+optim.py) the unit rule (unit_len) and the tables of pieces, slots and tensor records (plan_units); for the callbacks that run on a flat model's own
+table the matrices of OrthoInitClb (ortho_records) and the rows of WeightNorm with their work items (wnorm_records, wnorm_items).  Everything up to pack_records is pure Python on plain tuples, so a planner is pinned
 without a GPU (tests/test_item_plan_host.py); the device side of the records is csrc/optim_items.h.  The merged-range planner of SGD / Adam /
 MADGRAD / AdaiS (optim._merged_ranges) takes place and flat_views only."""
 import numpy as np
@@ -147,6 +148,33 @@ def ortho_records(table):
         elif kind == 0 and len(shape) == 2:
             out.append((off, shape[0], shape[1], 1))
     return out
+
+
+def wnorm_records(table):
+    """the rows the WeightNorm callback normalises.  table: a flat model's [(name, kind, offset, shape)]; returns [(off, rows, row_len)] for every
+    parameter (kind 0) with two or more dimensions and 64 elements or more, in table order: rows = shape[0], row_len = numel / rows — a conv
+    weight [O, I, kh, kw] is KRSC in memory, a row is still one contiguous run of I*kh*kw elements; an FC weight [O, I] gives (off, O, I), without
+    the padding rows behind it.  BatchNorm tensors and biases (one dimension: the reference's view(C, -1) of them has rows of ONE element, whose
+    norm after centring is 0), buffers and the ECA Conv1d weights (numel < 64, sota_imagenet/callbacks.py:118) are not selected."""
+    out = []
+    for _, kind, off, shape in table:
+        n = int(np.prod(shape)) if len(shape) else 1
+        if kind == 0 and len(shape) >= 2 and n >= 64:
+            out.append((off, shape[0], n // shape[0]))
+    return out
+
+
+def wnorm_items(records, W):
+    """the work items of ops.weight_norm_rows_.  records: [(off, rows, row_len)]; returns [(first element, row_len, n_rows)]: every record's rows
+    cut, from its first row, into runs of max(1, W // row_len) rows — whole rows only, a row longer than W is an item of its own; the cuts depend
+    on (rows, row_len, W) alone, the items of one record are consecutive and cover exactly its rows"""
+    items = []
+    for off, rows, row_len in records:
+        if rows < 1 or row_len < 1:
+            raise ValueError(f"record at offset {off}: rows={rows}, row_len={row_len} must be >= 1")
+        per = max(1, W // row_len)
+        items.extend((off + r * row_len, row_len, min(per, rows - r)) for r in range(0, rows, per))
+    return items
 
 
 def hist_records(t):

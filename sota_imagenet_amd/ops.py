@@ -729,6 +729,41 @@ def ortho_init_(flat, records_host, records_dev, gain=1.0):
     return status
 
 
+# ---- backward centred weight normalisation (include/mi355rn.h, csrc/weight_norm.hip): the WeightNorm callback of the reference ----------------------
+# stated once for the host; csrc/weight_norm.hip states the first for the kernel (mi355_wnorm_wave_row_max) and tests/test_weight_norm_host.py holds
+# the two together
+WNORM_WAVE_ROW_MAX = 1024  # rows up to this length take one wave, four rows at a time; longer rows the whole workgroup
+WNORM_ITEM_ELEMS = 4096    # W: an item holds max(1, W // row_len) rows (item_plan.wnorm_items).  Host side only: the kernel takes any n_rows
+
+
+def wnorm_check_items(items_host):
+    """ValueError if two of the items [(first, row_len, n_rows)] overlap: two workgroups would rewrite the same elements"""
+    end = None
+    for first, row_len, n_rows in sorted(items_host):
+        if end is not None and first < end:
+            raise ValueError(f"weight_norm_rows_: the item at offset {first} overlaps the one before it (which ends at {end})")
+        end = first + max(row_len, 0) * max(n_rows, 0)
+
+
+def weight_norm_rows_(flat, items_host, items_dev):
+    """replaces the loop of sota_imagenet/callbacks.py:116-123: every row of the table is centred on its mean and scaled to unit L2 norm, in place
+    and in ONE launch.  flat: the fp32 array the offsets count from; items_host: [(first element, row_len, n_rows)] (item_plan.wnorm_items),
+    items_dev: the same table packed for the device (item_plan.pack_records, CUDA int64 [n, 2]).  Items that overlap would race and raise here
+    (wnorm_check_items); a caller that launches one table every step checks it once and passes items_host=None afterwards.  An item that does
+    not fit the array is the kernel's to refuse.  Returns status (CUDA int32 per item: 0 done, 2 the item does not fit), not read back."""
+    _flat_f32(flat.numel(), flat=flat)
+    _lw_table("items_dev", items_dev)
+    if items_dev.device != flat.device:
+        raise ValueError("weight_norm_rows_: the items and the array must live on one device")
+    if items_host is not None:
+        if len(items_host) != items_dev.shape[0]:
+            raise ValueError(f"items_dev: expected {len(items_host)} records, got {items_dev.shape[0]}")
+        wnorm_check_items(items_host)
+    status = torch.empty(items_dev.shape[0], dtype=torch.int32, device=flat.device)
+    check(_L().mi355_weight_norm_rows(ptr(flat), flat.numel(), ptr(items_dev), items_dev.shape[0], ptr(status), cur_stream()))
+    return status
+
+
 # ---- the log histogram of |x| (include/mi355rn.h, csrc/optim_hist.hip): the GradDistributionTB callback of the reference ----------------------------
 # the bins, stated once for the host; csrc/absbin.h states them for the kernels and tests/test_grad_dist_host.py holds the two together
 ABSBIN_BINS, ABSBIN_SHIFT, ABSBIN_K0 = 512, 20, (77 << 3) + 2
