@@ -6,6 +6,9 @@ Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
 over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip, WeightNorm :104-123 over csrc/weight_norm.hip.
+What these share is stated once at module level: the flat model a callback runs on and its parameters by offset (_flat_model_of, _params_by_offset:
+OrthoInitClb, WeightNorm), and for the two histogram callbacks the re-plan key of a tensor (_tensor_key), the one-device check (_one_device) and the
+way out to state.tb_logger (_log_histograms); their launches per storage come from item_plan.dist_plan over item_plan.storage_array.
 """
 
 import logging
@@ -169,6 +172,44 @@ class CutmixMixup(Cutmix):
             self.state.input = self.mixup(*self.state.input)
 
 
+def _flat_model_of(state, who):
+    """state.model unwrapped, if it is a flat-array model on a CUDA device: what callback `who` runs on; NotImplementedError in its name otherwise"""
+    from .models import _FlatModel
+
+    m = _unwrap(state.model)
+    if not isinstance(m, _FlatModel) or not m.flat_params.is_cuda:
+        raise NotImplementedError(f"{who} runs on a flat-array model (models.resnet50) on a CUDA device: there is no CPU path and no "
+                                  f"module walk (got {type(m).__name__} on {getattr(getattr(m, 'flat_params', None), 'device', 'no flat array')})")
+    return m
+
+
+def _params_by_offset(m):
+    """{offset in the flat array: (name, parameter)} of the flat model m"""
+    return {off: (f"{m._name_of(leaf)}.{attr}", leaf._parameters[attr]) for leaf, attr, kind, off, _ in m._entries if kind == 0}
+
+
+def _tensor_key(t):
+    """what a histogram callback's plan depends on of a tensor: a change of any of these rebuilds it"""
+    return t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, t.device
+
+
+def _one_device(who, what, tensors):
+    """the device that all `tensors` live on; RuntimeError in the name of callback `who` if there is more than one"""
+    devs = {t.device for t in tensors}
+    if len(devs) != 1:
+        raise RuntimeError(f"{who}: {what} must live on one device (got {sorted(map(str, devs))})")
+    return devs.pop()
+
+
+def _log_histograms(state, last, raw):
+    """a callback's `last` to state.tb_logger at state.global_sample_step, if there is one: raw(value of a tag) -> (min, max, num, sum, sum_squares,
+    bucket_limits, bucket_counts), the arguments of add_histogram_raw"""
+    if state.tb_logger is not None:
+        for tag, v in last.items():
+            *stats, limits, counts = raw(v)
+            state.tb_logger.add_histogram_raw(tag, *stats, bucket_limits=limits, bucket_counts=counts, global_step=state.global_sample_step)
+
+
 class OrthoInitClb(Callback):
     """sota_imagenet/callbacks.py:250-266 (recipes 46-48, 50-53, 55): orthogonal initialisation of every conv and FC weight, once per process at the
     first on_begin (`has_been_init`: fit runs once per stage).  For a weight [O, I, kh, kw] or [O, I], rows = O and cols = I*kh*kw: a rows x cols
@@ -193,25 +234,16 @@ class OrthoInitClb(Callback):
         self.has_been_init = False
         self.records, self.names, self.status = [], [], None
 
-    def _flat_model(self):
-        from .models import _FlatModel
-
-        m = _unwrap(self.state.model)
-        if not isinstance(m, _FlatModel) or not m.flat_params.is_cuda:
-            raise NotImplementedError("OrthoInitClb runs on a flat-array model (models.resnet50) on a CUDA device: there is no CPU path and no "
-                                      f"module walk (got {type(m).__name__} on {getattr(getattr(m, 'flat_params', None), 'device', 'no flat array')})")
-        return m
-
     def _plan(self, m):
         self.records = item_plan.ortho_records(m._table)
-        by_off = {off: (f"{m._name_of(leaf)}.{attr}", leaf._parameters[attr]) for leaf, attr, kind, off, _ in m._entries if kind == 0}
+        by_off = _params_by_offset(m)
         self.names = [by_off[r[0]][0] for r in self.records]
         return [by_off[r[0]][1] for r in self.records]
 
     @torch.no_grad()
     def fill(self):
         """the planned tensors filled with N(0,1) draws, in table order"""
-        m = self._flat_model()
+        m = _flat_model_of(self.state, "OrthoInitClb")
         dev = m.flat_params.device
         g = torch.Generator(device=dev).manual_seed(int(getattr(self.state, "random_seed", 0) or 0))
         for p in self._plan(m):
@@ -220,7 +252,7 @@ class OrthoInitClb(Callback):
     @torch.no_grad()
     def orthogonalise(self):
         """one launch over the planned matrices, one readback; RuntimeError for a matrix the kernel could not orthogonalise"""
-        m = self._flat_model()
+        m = _flat_model_of(self.state, "OrthoInitClb")
         self._plan(m)
         dev = m.flat_params.device
         self.status = ops.ortho_init_(m.flat_params, self.records, pack_records(self.records, dev, item_plan.ORTHO_FIELDS), self.gain)
@@ -232,7 +264,7 @@ class OrthoInitClb(Callback):
     def on_begin(self):
         if self.has_been_init:
             return
-        self._flat_model()
+        _flat_model_of(self.state, "OrthoInitClb")
         start = int(getattr(self.state, "start_epoch", 0) or 0)
         if start > 0:
             logging.getLogger(__name__).info(f"OrthoInitClb: the fit starts at epoch {start}: the loaded weights are kept, no orthogonal initialisation")
@@ -275,25 +307,16 @@ class WeightNorm(Callback):
         self.launches = 0
         self._flat = self._items_dev = None
 
-    def _flat_model(self):
-        from .models import _FlatModel
-
-        m = _unwrap(self.state.model)
-        if not isinstance(m, _FlatModel) or not m.flat_params.is_cuda:
-            raise NotImplementedError("WeightNorm runs on a flat-array model (models.resnet50) on a CUDA device: there is no CPU path and no "
-                                      f"module walk (got {type(m).__name__} on {getattr(getattr(m, 'flat_params', None), 'device', 'no flat array')})")
-        return m
-
     def on_begin(self):
-        m = self._flat_model()
+        m = _flat_model_of(self.state, "WeightNorm")
         logging.getLogger(__name__).info("Using backward Centered Weight Normalization for weights")
         self.build_plan(m)
 
     def build_plan(self, m):
         """the records, the work items and the packed table for the flat model m"""
         self.records = item_plan.wnorm_records(m._table)
-        by_off = {off: f"{m._name_of(leaf)}.{attr}" for leaf, attr, kind, off, _ in m._entries if kind == 0}
-        self.names = [by_off[r[0]] for r in self.records]
+        by_off = _params_by_offset(m)
+        self.names = [by_off[r[0]][0] for r in self.records]
         self.items = item_plan.wnorm_items(self.records, ops.WNORM_ITEM_ELEMS)
         ops.wnorm_check_items(self.items)  # once: the launches below pass no host table
         self._items_dev = pack_records(self.items, m.flat_params.device)
@@ -303,7 +326,7 @@ class WeightNorm(Callback):
     def on_batch_end(self):
         if not self.state.is_train:
             return
-        m = self._flat_model()
+        m = _flat_model_of(self.state, "WeightNorm")
         if m.flat_params is not self._flat:  # the model moved since on_begin: the table lives where the array does
             self.build_plan(m)
         self.status = ops.weight_norm_rows_(self._flat.detach(), None, self._items_dev)
@@ -369,27 +392,17 @@ class GradDistributionTB(Callback):
         """tagged: [(tag, [tensor])]; the tables on the device, one launch per storage and tag"""
         recs = [(tag, ts, [item_plan.hist_records(t) for t in ts]) for tag, ts in tagged]
         W = ops.lw_item_elems()
-        devs = {t.device for _, ts, _ in recs for t in ts}
-        if len(devs) != 1:
-            raise RuntimeError(f"GradDistributionTB: all parameters and states must live on one device (got {sorted(map(str, devs))})")
-        dev = devs.pop()
+        dev = _one_device("GradDistributionTB", "all parameters and states", [t for _, ts, _ in recs for t in ts])
         rows = sum(len(ts) for _, ts, _ in recs)
         self._hist = torch.zeros(rows, ops.ABSBIN_BINS, dtype=torch.int32, device=dev)
         self._counts = torch.zeros(len(recs), ops.ABSBIN_BINS, dtype=torch.int64, device=dev)
         self._tags, row0 = [], 0
         for tag, ts, rs in recs:
-            by_storage = {}  # storage base -> tensor indices, in order of first appearance
-            for i, r in enumerate(rs):
-                by_storage.setdefault(r[0], []).append(i)
-            launches = []
-            for base, idx in by_storage.items():
+            launches = []  # a row of the plan is the tensor's position in its tag
+            for base, lo, hi, items, _ in item_plan.dist_plan([r[:3] for r in rs], W)[1]:
                 if base % 16:
                     raise RuntimeError(f"GradDistributionTB: a storage of {tag} does not start on a 16-byte boundary")
-                lo = min(rs[i][1] for i in idx) & ~3  # the flat array starts on a 16-byte boundary of the storage
-                hi = max(rs[i][1] + rs[i][2] for i in idx)
-                src = torch.empty(0, dtype=torch.float32, device=dev).set_(ts[idx[0]].untyped_storage(), lo, (hi - lo,))
-                items, _ = item_plan.plan_items([(rs[i][1] - lo, rs[i][2]) for i in idx], W, idx)
-                launches.append((src, pack_records(items, dev)))
+                launches.append((item_plan.storage_array(ts[items[0][2]], lo, hi), pack_records(items, dev)))
             rep = [r[3] for r in rs]
             if max(rep) >= 1 << 31:
                 raise RuntimeError(f"GradDistributionTB: a tensor of {tag} has 2^31 elements or more")
@@ -400,7 +413,7 @@ class GradDistributionTB(Callback):
     def log(self):
         """one logged step: `last`, and the histograms to state.tb_logger if there is one"""
         tagged = self._tensors()
-        key = tuple((tag, tuple((t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, t.device) for t in ts)) for tag, ts in tagged)
+        key = tuple((tag, tuple(map(_tensor_key, ts))) for tag, ts in tagged)
         if key != self._key:
             self.build_plan(tagged)
             self._key = key
@@ -414,11 +427,7 @@ class GradDistributionTB(Callback):
             raise RuntimeError("GradDistributionTB: the counting kernel refused its table (a multiplicity below 1)")
         self.last = {tag: (self._limits, counts[k].copy()) for k, (tag, *_) in enumerate(self._tags)}
         self.logged += 1
-        tb = self.state.tb_logger
-        if tb is not None:
-            for tag, (limits, c) in self.last.items():
-                tb.add_histogram_raw(tag, *self.raw_stats(limits, c), bucket_limits=limits.tolist(), bucket_counts=c.tolist(),
-                                     global_step=self.state.global_sample_step)
+        _log_histograms(self.state, self.last, lambda v: (*self.raw_stats(*v), v[0].tolist(), v[1].tolist()))
 
     @staticmethod
     def raw_stats(limits, counts):
@@ -499,10 +508,7 @@ class WeightDistributionTB(Callback):
                 raise NotImplementedError(f"WeightDistributionTB: {name} is not a CUDA tensor (there is no CPU path)")
             if t.numel() < 1:
                 raise ValueError(f"WeightDistributionTB: {name} has no element")
-        devs = {t.device for _, t in named}
-        if len(devs) != 1:
-            raise RuntimeError(f"WeightDistributionTB: the state_dict must live on one device (got {sorted(map(str, devs))})")
-        dev = devs.pop()
+        dev = _one_device("WeightDistributionTB", "the state_dict", [t for _, t in named])
         records = []
         for _, t in named:
             rec = None
@@ -529,10 +535,8 @@ class WeightDistributionTB(Callback):
             g[0], g[1] = min(g[0], r[1]), max(g[1], r[1] + r[2])
             g[2].append((k, r[1], r[2]))
         P.gathers, P.where, n_other = [], {}, 0
-        for (_, dtype), (lo, hi, members) in groups.items():
-            t0 = named[members[0][0]][1]
-            flat = torch.empty(0, dtype=dtype, device=dev).set_(t0.untyped_storage(), lo, (hi - lo,))
-            P.gathers.append((flat, n_other, n_other + hi - lo))
+        for lo, hi, members in groups.values():
+            P.gathers.append((item_plan.storage_array(named[members[0][0]][1], lo, hi), n_other, n_other + hi - lo))
             for k, first, n in members:
                 P.where[k] = (n_other + first - lo, n)
             n_other += hi - lo
@@ -549,8 +553,7 @@ class WeightDistributionTB(Callback):
         P.other = P.buf[h + p:].view(torch.float64)
         P.launches = []
         for base, lo, hi, items, i0 in launches:
-            t0 = named[P.rows[items[0][2]]][1]
-            src = torch.empty(0, dtype=torch.float32, device=dev).set_(t0.untyped_storage(), lo, (hi - lo,))
+            src = item_plan.storage_array(named[P.rows[items[0][2]]][1], lo, hi)
             P.launches.append((src, pack_records(items, dev), (i0, i0 + len(items))))
         return P
 
@@ -558,8 +561,7 @@ class WeightDistributionTB(Callback):
     def log(self):
         """one logged epoch: `last`, and the histograms to state.tb_logger if there is one"""
         named = list(self.state.model.state_dict().items())
-        key = tuple((name, t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, t.device) if torch.is_tensor(t) else (name, None)
-                    for name, t in named)
+        key = tuple((name, _tensor_key(t) if torch.is_tensor(t) else None) for name, t in named)
         if key != self._key:
             self._plan = self.build_plan(named)
             self._key = key
@@ -600,11 +602,7 @@ class WeightDistributionTB(Callback):
             last["model/" + name] = dict(stats, bucket_limits=limits, bucket_counts=kept)
         self.last = last
         self.logged += 1
-        tb = self.state.tb_logger
-        if tb is not None:
-            for tag, d in last.items():
-                tb.add_histogram_raw(tag, d["min"], d["max"], d["num"], d["sum"], d["sum_squares"], bucket_limits=d["bucket_limits"],
-                                     bucket_counts=d["bucket_counts"], global_step=self.state.global_sample_step)
+        _log_histograms(self.state, last, lambda d: [d[k] for k in ("min", "max", "num", "sum", "sum_squares", "bucket_limits", "bucket_counts")])
 
     def on_epoch_begin(self):
         if self.state.rank != 0 or env_rank() != 0:

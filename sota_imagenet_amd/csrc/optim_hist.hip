@@ -7,10 +7,8 @@
 //   absbin_hist_kernel, one workgroup per work item { first element, length, tensor } (the table of optim_items.h, at ANY element offset: a
 //     state of the layer-wise optimizers is one element per tensor): bin (absbin.h) of every element of the item — a scalar head up to the next
 //     16-byte boundary, an f32x4 body, a scalar tail (piece_walk) — counted in a 512-entry histogram in LDS, then the non-zero bins ADDED to
-//     hist[tensor][512] with integer atomicAdd.  A trained network's values sit in a handful of bins, an all-equal array in one, and same-address
-//     LDS atomics serialise: a thread first merges the equal neighbours among the four bins of its vector, and a wave whose active lanes all hold
-//     ONE bin adds its whole count once, from one lane (profiles/grad_dist.json: the all-equal array beside the ResNet-50 arrays).  Elements outside
-//     the items (alignment gaps, the FC padding rows) are never read into a count; a record that does not lie inside [0, n) is skipped.
+//     hist[tensor][512] with integer atomicAdd: the workgroup histogram of hist_count.h, which says why a wave on ONE bin adds once.  Elements
+//     outside the items (alignment gaps, the FC padding rows) are never read into a count; a record that does not lie inside [0, n) is skipped.
 //   subsample_counts_kernel, one workgroup of 512 threads: c_t(k) = rep[t] * (elements of tensor t in bins below k), C(k) = sum_t ceil(c_t(k) / s),
 //     counts[k] = ceil(C(k+1) / s) - ceil(C(k) / s), all in 64 bits.  A wave takes every eighth tensor, a lane eight consecutive bins: the prefix
 //     inside the lane, a shuffle scan over the lanes' totals; the eight waves' sums meet in LDS.  rep[t] counts a state that is stored once and
@@ -18,6 +16,7 @@
 //     without a read-back: the kernel then writes ~0 into every counts[k], which no count can be.
 #include "absbin.h"
 #include "common.h"
+#include "hist_count.h"
 #include "optim_items.h"
 
 namespace mi355 {
@@ -40,34 +39,10 @@ __global__ __launch_bounds__(256) void absbin_hist_kernel(const float* __restric
       it, (int)threadIdx.x, [&](int i) { atomicAdd(&sh[absbin(sp[i])], 1u); },
       [&](int head, int i) {
         const f32x4 v = reinterpret_cast<const f32x4*>(sp + head)[i];
-        const int b0 = absbin(v[0]), b1 = absbin(v[1]), b2 = absbin(v[2]), b3 = absbin(v[3]);
-        const int first = __builtin_amdgcn_readfirstlane(b0);
-        if (__all((b0 == first) & (b1 == first) & (b2 == first) & (b3 == first))) {  // one bin in the whole wave: one add
-          const unsigned long long act = __ballot(1);
-          if ((int)__lane_id() == __ffsll((long long)act) - 1) atomicAdd(&sh[first], 4u * (unsigned)__popcll(act));
-          return;
-        }
-        int cur = b0;
-        unsigned c = 1u;
-        const int rest[3] = {b1, b2, b3};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          if (rest[k] == cur) {
-            ++c;
-          } else {
-            atomicAdd(&sh[cur], c);
-            cur = rest[k], c = 1u;
-          }
-        }
-        atomicAdd(&sh[cur], c);
+        count_four(sh, absbin(v[0]), absbin(v[1]), absbin(v[2]), absbin(v[3]));
       });
   __syncthreads();
-  unsigned* __restrict__ row = hist + (size_t)it.slot * kNB;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const unsigned c = sh[threadIdx.x + 256 * k];
-    if (c) atomicAdd(&row[threadIdx.x + 256 * k], c);
-  }
+  flush_counts<kNB>(sh, hist + (size_t)it.slot * kNB);
 }
 
 __device__ __forceinline__ unsigned long long ceil_div(unsigned long long a, unsigned long long s) { return a / s + (a % s != 0); }

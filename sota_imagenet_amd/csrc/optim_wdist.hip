@@ -8,9 +8,8 @@
 //           number of edges <= |x| (x >= 0, -0.0 too) or < |x| (x < 0: the half-open side flips, e_k < |x| <= e_k+1), found by a binary search
 //           of 10 steps on exact double comparisons; the bin is 774 + c or 773 - c.  c = 774 lies outside the table — except x equal to the
 //           last edge, which np.histogram puts into the last bin — and is counted, like NaN, in the row's entry 1548: "in no bin".
-//   counts  a workgroup histogram of 1548 bins + that entry in LDS, its non-zero entries then ADDED to hist[tensor][1552] with integer atomicAdd.
-//           A thread first merges the equal neighbours among the four bins of its vector, and a wave whose active lanes all hold ONE bin adds its
-//           whole count once, from one lane: a BatchNorm weight at its initial value is an all-equal array.
+//   counts  a workgroup histogram of 1548 bins + that entry in LDS, its non-zero entries then ADDED to hist[tensor][1552] with integer atomicAdd:
+//           the workgroup histogram of hist_count.h, which says why a wave on ONE bin adds once.
 //   stats   partial[item] = { min, max, sum, sum of squares, NaN seen } of the item's elements, in double.  A thread adds its elements in array
 //           order, the lanes of a wave meet in a shuffle tree, the four waves are added in their order by thread 0: the same bits in every run.
 //           min and max skip NaN (the caller makes them NaN where the flag is set, as numpy does); the sums take every element, so NaN and
@@ -18,6 +17,7 @@
 // Elements outside the items (alignment gaps, the FC padding rows) are never read; a record that does not lie inside [0, n) is skipped by the
 // whole workgroup before any barrier, and its partial[] entry stays as it was.
 #include "common.h"
+#include "hist_count.h"
 #include "optim_items.h"
 
 namespace mi355 {
@@ -97,26 +97,7 @@ __global__ __launch_bounds__(256) void tbbin_hist_kernel(const float* __restrict
         const f32x4 v = reinterpret_cast<const f32x4*>(sp + head)[i];
 #pragma unroll
         for (int k = 0; k < 4; ++k) take(st, v[k]);
-        const int b0 = tbbin(v[0], pos), b1 = tbbin(v[1], pos), b2 = tbbin(v[2], pos), b3 = tbbin(v[3], pos);
-        const int first = __builtin_amdgcn_readfirstlane(b0);
-        if (__all((b0 == first) & (b1 == first) & (b2 == first) & (b3 == first))) {  // one bin in the whole wave: one add
-          const unsigned long long act = __ballot(1);
-          if ((int)__lane_id() == __ffsll((long long)act) - 1) atomicAdd(&sh[first], 4u * (unsigned)__popcll(act));
-          return;
-        }
-        int cur = b0;
-        unsigned c = 1u;
-        const int rest[3] = {b1, b2, b3};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          if (rest[k] == cur) {
-            ++c;
-          } else {
-            atomicAdd(&sh[cur], c);
-            cur = rest[k], c = 1u;
-          }
-        }
-        atomicAdd(&sh[cur], c);
+        count_four(sh, tbbin(v[0], pos), tbbin(v[1], pos), tbbin(v[2], pos), tbbin(v[3], pos));
       });
   // the statistics: a shuffle tree over the wave (every lane takes part; a lane without elements holds the neutral values), then the waves in order
 #pragma unroll
@@ -140,11 +121,7 @@ __global__ __launch_bounds__(256) void tbbin_hist_kernel(const float* __restrict
     double* __restrict__ out = partial + (size_t)blockIdx.x * kStats;
     out[0] = st.mn, out[1] = st.mx, out[2] = st.sum, out[3] = st.sq, out[4] = st.nan ? 1.0 : 0.0;
   }
-  unsigned* __restrict__ row = hist + (size_t)it.slot * kRow;
-  for (int i = threadIdx.x; i < kRow; i += 256) {
-    const unsigned c = sh[i];
-    if (c) atomicAdd(&row[i], c);
-  }
+  flush_counts<kRow>(sh, hist + (size_t)it.slot * kRow);
 }
 
 }  // namespace

@@ -1,9 +1,10 @@
 """The host side of the work-item plan, written once: what the layer-wise optimizers (optim._Layerwise) and the sharpness-aware callbacks
 (callbacks.SAMOriginal, callbacks.SAM) run on.  Which parameters fit the flat kernels (place), the parameters grouped by pair of parameter /
 gradient storage with every tensor cut into work items of at most W elements (plan_items, storage_pairs), the 16-byte records the kernels read
-(pack_records) and a storage as flat arrays (flat_views); for the statistics taken per output unit (callbacks.SAM, the unit-wise optimizers of
+(pack_records) and a storage as a flat array (storage_array; flat_views for a parameter and its gradient); for the statistics taken per output unit (callbacks.SAM, the unit-wise optimizers of
 optim.py) the unit rule (unit_len) and the tables of pieces, slots and tensor records (plan_units); for the callbacks that run on a flat model's own
-table the matrices of OrthoInitClb (ortho_records) and the rows of WeightNorm with their work items (wnorm_records, wnorm_items).  Everything up to pack_records is pure Python on plain tuples, so a planner is pinned
+table the matrices of OrthoInitClb (ortho_records) and the rows of WeightNorm with their work items (wnorm_records, wnorm_items); for the two
+histogram callbacks what to read of a tensor (hist_records) and the launches, one per storage (dist_plan).  Everything up to pack_records is pure Python on plain tuples, so a planner is pinned
 without a GPU (tests/test_item_plan_host.py); the device side of the records is csrc/optim_items.h.  The merged-range planner of SGD / Adam /
 MADGRAD / AdaiS (optim._merged_ranges) takes place and flat_views only."""
 import numpy as np
@@ -204,8 +205,9 @@ def hist_records(t):
 
 
 def dist_plan(records, W):
-    """the launches of callbacks.WeightDistributionTB.  records: per entry of a state_dict, in its order, (storage base ptr, first element, numel)
-    for a tensor the counting kernel reads, None for one it does not.  The tensors are numbered in that order (their rows of the histogram table)
+    """the launches of the two histogram callbacks.  records: (storage base ptr, first element, elements to read) for a tensor the counting kernel
+    reads, None for one it does not — callbacks.WeightDistributionTB: per entry of a state_dict, in its order; callbacks.GradDistributionTB: per
+    tensor of one tag (hist_records' source elements), none of them None.  The tensors are numbered in that order (their rows of the histogram table)
     and grouped by storage, one launch per storage in order of first appearance.  Returns (rows, launches, spans, n_items): rows[r] = the entry of
     row r; launches = [(base, lo, hi, items, first item)], [lo, hi) the element range of the storage that the launch's flat array covers (lo a
     multiple of 4 elements), items = plan_items' table with offsets relative to lo and the row as tensor index, first item = the launch's place
@@ -236,6 +238,11 @@ def pack_records(records, device=None, fields=ITEM_FIELDS):
     return t if device is None else t.to(device)
 
 
+def storage_array(t, lo, hi):
+    """the storage of the tensor t, in t's dtype and on its device, as a flat array over the elements [lo, hi)"""
+    return torch.empty(0, dtype=t.dtype, device=t.device).set_(t.untyped_storage(), lo, (hi - lo,))
+
+
 def flat_views(p, lo, hi):
-    """the storages of the parameter p and of its gradient as flat fp32 arrays over the elements [lo, hi)"""
-    return tuple(torch.empty(0, dtype=torch.float32, device=p.device).set_(t.untyped_storage(), lo, (hi - lo,)) for t in (p.data, p.grad))
+    """the storages of the parameter p and of its gradient (fp32 under the placement rule) as flat arrays over the elements [lo, hi)"""
+    return storage_array(p.data, lo, hi), storage_array(p.grad, lo, hi)

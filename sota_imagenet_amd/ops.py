@@ -705,6 +705,16 @@ def sam_lw_perturb(p, g, eps, items, tensors, coef, rho, grad_scale=1.0):
                                     coef.numel(), float(rho), float(grad_scale), cur_stream()))
 
 
+def _check_disjoint(what, spans):
+    """ValueError if one of the spans [(first element, length)], given in sorted order, begins before the one in front of it ends: two workgroups
+    would rewrite the same elements.  what: "<op>: the record" or "<op>: the item", as the message names it"""
+    end = None
+    for first, length in spans:
+        if end is not None and first < end:
+            raise ValueError(f"{what} at offset {first} overlaps the one before it (which ends at {end})")
+        end = first + length
+
+
 # ---- orthogonal initialisation (include/mi355rn.h, csrc/init_ortho.hip): the OrthoInitClb callback of the reference ---------------------------------
 def ortho_init_(flat, records_host, records_dev, gain=1.0):
     """replaces the nn.init.orthogonal_ calls of sota_imagenet/callbacks.py:260-265: every matrix of the table, filled with N(0,1) draws by the
@@ -719,11 +729,7 @@ def ortho_init_(flat, records_host, records_dev, gain=1.0):
         raise ValueError(f"records_dev: expected a CUDA int64 tensor [{n_mats}, 3] of 24-byte records, got {records_dev.dtype} {tuple(records_dev.shape)}")
     if records_dev.device != flat.device:
         raise ValueError("ortho_init_: the records and the array must live on one device")
-    end = None
-    for off, rows, chans, taps in sorted(records_host):
-        if end is not None and off < end:
-            raise ValueError(f"ortho_init_: the record at offset {off} overlaps the one before it (which ends at {end})")
-        end = off + max(rows, 0) * max(chans, 0) * max(taps, 0)
+    _check_disjoint("ortho_init_: the record", ((off, max(rows, 0) * max(chans, 0) * max(taps, 0)) for off, rows, chans, taps in sorted(records_host)))
     status = torch.empty(n_mats, dtype=torch.int32, device=flat.device)
     check(_L().mi355_ortho_init(ptr(flat), flat.numel(), ptr(records_dev), n_mats, float(gain), ptr(status), cur_stream()))
     return status
@@ -738,11 +744,7 @@ WNORM_ITEM_ELEMS = 4096    # W: an item holds max(1, W // row_len) rows (item_pl
 
 def wnorm_check_items(items_host):
     """ValueError if two of the items [(first, row_len, n_rows)] overlap: two workgroups would rewrite the same elements"""
-    end = None
-    for first, row_len, n_rows in sorted(items_host):
-        if end is not None and first < end:
-            raise ValueError(f"weight_norm_rows_: the item at offset {first} overlaps the one before it (which ends at {end})")
-        end = first + max(row_len, 0) * max(n_rows, 0)
+    _check_disjoint("weight_norm_rows_: the item", ((first, max(row_len, 0) * max(n_rows, 0)) for first, row_len, n_rows in sorted(items_host)))
 
 
 def weight_norm_rows_(flat, items_host, items_dev):
@@ -770,6 +772,12 @@ ABSBIN_BINS, ABSBIN_SHIFT, ABSBIN_K0 = 512, 20, (77 << 3) + 2
 ABSBIN_BAD_REP = 2 ** 64 - 1  # what mi355_subsample_counts writes into every count when a rep[t] < 1
 
 
+def _hist_table(hist, row):
+    """the table both counting kernels add into: int32 [n_tensors, row]"""
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != row or hist.shape[0] < 1:
+        raise ValueError(f"hist: expected a contiguous CUDA int32 tensor [n_tensors, {row}], got {hist.dtype} {tuple(hist.shape)}")
+
+
 def absbin_edges():
     """float32 [511]: the lower edges of bins 1..511 (= the upper edges of bins 0..510), the floats with bits (K0 + b) << SHIFT"""
     return ((np.arange(1, ABSBIN_BINS, dtype=np.int64) + ABSBIN_K0) << ABSBIN_SHIFT).astype(np.uint32).view(np.float32)
@@ -788,8 +796,7 @@ def absbin_hist(src, items, hist):
     _flat_f32(src.numel(), src=src)
     _lw_table("items", items)
     _need_cuda(hist)
-    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != ABSBIN_BINS or hist.shape[0] < 1:
-        raise ValueError(f"hist: expected a contiguous CUDA int32 tensor [n_tensors, {ABSBIN_BINS}], got {hist.dtype} {tuple(hist.shape)}")
+    _hist_table(hist, ABSBIN_BINS)
     if not (src.device == items.device == hist.device):
         raise ValueError("absbin_hist: the array, the table and the histograms must live on one device")
     check(_L().mi355_absbin_hist(ptr(src), src.numel(), ptr(items), items.shape[0], hist.shape[0], ptr(hist), cur_stream()))
@@ -801,8 +808,7 @@ def subsample_counts(hist, rep, subsample, counts, rep_host=None):
     per counted element, >= 1).  rep lives on the device: a rep < 1 makes the kernel write -1 (ABSBIN_BAD_REP unsigned) into every count; rep_host,
     the same numbers on the host where the caller has them, is tested here and raises ValueError."""
     _need_cuda(hist, rep, counts)
-    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != ABSBIN_BINS or hist.shape[0] < 1:
-        raise ValueError(f"hist: expected a contiguous CUDA int32 tensor [n_tensors, {ABSBIN_BINS}], got {hist.dtype} {tuple(hist.shape)}")
+    _hist_table(hist, ABSBIN_BINS)
     if rep.dtype != torch.int32 or rep.dim() != 1 or rep.numel() != hist.shape[0]:
         raise ValueError(f"rep: expected {hist.shape[0]} int32 elements, got {rep.dtype} {tuple(rep.shape)}")
     if counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != ABSBIN_BINS:
@@ -844,8 +850,7 @@ def tbbin_hist(src, items, hist, partial):
     _flat_f32(src.numel(), src=src)
     _lw_table("items", items)
     _need_cuda(hist, partial)
-    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != TBBIN_ROW or hist.shape[0] < 1:
-        raise ValueError(f"hist: expected a contiguous CUDA int32 tensor [n_tensors, {TBBIN_ROW}], got {hist.dtype} {tuple(hist.shape)}")
+    _hist_table(hist, TBBIN_ROW)
     if partial.dtype != torch.float64 or tuple(partial.shape) != (items.shape[0], TBBIN_STATS):
         raise ValueError(f"partial: expected a float64 tensor [{items.shape[0]}, {TBBIN_STATS}], got {partial.dtype} {tuple(partial.shape)}")
     if not (src.device == items.device == hist.device == partial.device):

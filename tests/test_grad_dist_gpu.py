@@ -12,39 +12,22 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import flat_layout  # noqa: E402
 import grad_dist_common as G  # noqa: E402
+from flat_layout import _ops  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
 GAP = 7.0e3  # fills everything between the records; no record below holds a value of its bin, which must stay empty
 
 
-def _ops():
-    from sota_imagenet_amd import item_plan, ops
-
-    return ops, item_plan
-
-
 def _draw(rng, n):
-    """|x| = 10^u, u uniform over [-18, 2] (so nothing reaches GAP's bin), signs mixed, some exact zeros"""
-    x = (10.0 ** rng.uniform(-18.0, 2.0, n)).astype(np.float32) * rng.choice(np.float32([-1, 1]), n)
-    x[rng.uniform(size=n) < 0.05] = 0.0
-    return x
+    """u uniform over [-18, 2], so nothing reaches GAP's bin"""
+    return flat_layout._draw(rng, n, -18.0, 2.0)
 
 
 def _layout(arrays, offsets=None, fill=GAP, tail=9):
-    """the arrays laid into one flat array at `offsets` (default: each at the next multiple of 4 behind a gap of 4), `fill` everywhere else;
-    returns (flat numpy, [(offset, numel)])"""
-    recs, end = [], 0
-    for i, a in enumerate(arrays):
-        off = offsets[i] if offsets else (end + 4 + 3) // 4 * 4
-        assert off >= end
-        recs.append((off, a.size))
-        end = off + a.size
-    flat = np.full(end + tail, fill, dtype=np.float32)
-    for (off, n), a in zip(recs, arrays):
-        flat[off:off + n] = a.ravel()
-    return flat, recs
+    return flat_layout._layout(arrays, offsets, fill, tail)
 
 
 def _hist_of(dev, flat, recs, hist=None, index=None, n_tensors=None):

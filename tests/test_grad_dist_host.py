@@ -166,6 +166,32 @@ def test_hist_records_errors(as_cuda):
         item_plan.hist_records(0.5)
 
 
+def test_dist_plan_gives_the_launches_build_plan_had_inline():
+    """the grouping GradDistributionTB.build_plan spelled out before it took its launches from item_plan.dist_plan, restated on tuples: per
+    storage, in order of first appearance, (lo, hi, items) and the packed table byte for byte.  W = 64; two storages interleaved in tensor order;
+    first elements at 0, 1, 2, 3 mod 4; tensors of W, W + 1 and 1 element (a broadcast state); the lowest first element of storage A is no multiple
+    of 4, so lo & ~3 matters"""
+    W, A, B = 64, 0x7000, 0x9000
+    rs = [(A, 6, W, 1), (B, 0, W + 1, 1), (A, 75, 1, 4608), (B, 69, 30, 1), (A, 80, 2 * W + 2, 1)]  # hist_records: (base, first, elements, rep)
+    assert sorted(r[1] % 4 for r in rs[:4]) == [0, 1, 2, 3] and min(r[1] for r in rs if r[0] == A) % 4
+    by_storage = {}  # storage base -> tensor indices, in order of first appearance
+    for i, r in enumerate(rs):
+        by_storage.setdefault(r[0], []).append(i)
+    want = []
+    for base, idx in by_storage.items():
+        lo = min(rs[i][1] for i in idx) & ~3
+        hi = max(rs[i][1] + rs[i][2] for i in idx)
+        items, _ = item_plan.plan_items([(rs[i][1] - lo, rs[i][2]) for i in idx], W, idx)
+        want.append((base, lo, hi, items))
+    rows, launches, spans, n_items = item_plan.dist_plan([r[:3] for r in rs], W)
+    assert rows == list(range(len(rs)))  # a row is the tensor's position in its tag
+    assert [l[:4] for l in launches] == want and [b for b, *_ in want] == [A, B] and [w[1:3] for w in want] == [(4, 210), (0, 99)]
+    assert want[0][3] == [(2, 64, 0), (71, 1, 2), (76, 64, 4), (140, 64, 4), (204, 2, 4)] and want[1][3] == [(0, 64, 1), (64, 1, 1), (69, 30, 3)]
+    for (_, _, _, items, i0), (_, _, _, items_want) in zip(launches, want):
+        assert torch.equal(item_plan.pack_records(items), item_plan.pack_records(items_want))
+    assert n_items == 8 and [l[4] for l in launches] == [0, 5] and spans == [(0, 1), (5, 2), (1, 1), (7, 1), (2, 3)]
+
+
 # ---- alias, configs, gates ---------------------------------------------------------------------------------------------------------------------------
 def test_the_alias_resolves():
     assert C.LOGGING_CALLBACK_TARGET_ALIASES == {"src.callbacks.GradDistributionTB": "sota_imagenet_amd.callbacks.GradDistributionTB"}

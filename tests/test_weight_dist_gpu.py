@@ -14,38 +14,23 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import flat_layout  # noqa: E402
 import weight_dist_common as WD  # noqa: E402
+from flat_layout import _ops  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
 U = 2.0 ** -53
 
 
-def _ops():
-    from sota_imagenet_amd import item_plan, ops
-
-    return ops, item_plan
-
-
 def _draw(rng, n):
-    """magnitudes 10^u, u uniform over [-14, 3], signs mixed, some exact zeros: both sides of the smallest edges, nothing outside the table"""
-    x = (10.0 ** rng.uniform(-14.0, 3.0, n)).astype(np.float32) * rng.choice(np.float32([-1, 1]), n)
-    x[rng.uniform(size=n) < 0.05] = 0.0
-    return x
+    """u uniform over [-14, 3]: both sides of the smallest edges, nothing outside the table"""
+    return flat_layout._draw(rng, n, -14.0, 3.0)
 
 
 def _layout(arrays, offsets=None, tail=9):
-    """the arrays laid into one flat array at `offsets` (default: each at the next multiple of 4 behind a gap of 4), NaN everywhere else"""
-    recs, end = [], 0
-    for i, a in enumerate(arrays):
-        off = offsets[i] if offsets else (end + 4 + 3) // 4 * 4
-        assert off >= end
-        recs.append((off, a.size))
-        end = off + a.size
-    flat = np.full(end + tail, NAN, dtype=np.float32)
-    for (off, n), a in zip(recs, arrays):
-        flat[off:off + n] = a.ravel()
-    return flat, recs
+    """NaN everywhere between the arrays"""
+    return flat_layout._layout(arrays, offsets, NAN, tail)
 
 
 def _run(dev, flat, recs):
