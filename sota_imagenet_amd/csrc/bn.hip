@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "dispatch.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -721,8 +722,7 @@ __global__ __launch_bounds__(256, 4) void stem_bwd_apply_kernel(const StemBwdArg
   }
 }
 
-int reduce_grid(int dtype, int M, int C, dim3* grid) {
-  const int V = 16 / (int)dtype_size(dtype);
+dim3 reduce_grid(int V, int M, int C, int* nblk_out) {  // V: elements per 16-byte vector (Vec16<T>::N); *nblk_out: the partial rows written
   const int tpr_full = C / V;
   const int tpr = tpr_full < 256 ? tpr_full : 256;
   const int rpp = 256 / tpr;
@@ -732,8 +732,8 @@ int reduce_grid(int dtype, int M, int C, dim3* grid) {
   const int cap = MAXBLK;
   if (nblk > cap / gy) nblk = cap / gy;
   if (nblk < 1) nblk = 1;
-  *grid = dim3(nblk, gy);
-  return nblk;
+  *nblk_out = nblk;
+  return dim3(nblk, gy);
 }
 
 int elementwise_blocks(size_t nvec, int cvecs) {
@@ -749,6 +749,14 @@ int elementwise_blocks(size_t nvec, int cvecs) {
   b = (b + 3) / 4 * 4;
   (void)cvecs;
   return (int)b;
+}
+
+// sizes an elementwise pass (ApplyArgs, BwdApplyArgs) for V elements per 16-byte vector; returns its workgroups
+template <typename Args>
+int size_elementwise(Args& a, int M, int C, int V) {
+  a.nvec = (size_t)M * C / V;
+  a.cvecs = C / V;
+  return elementwise_blocks(a.nvec, a.cvecs);
 }
 
 int check_c(int dtype, int C) {
@@ -770,14 +778,12 @@ int launch_bn_stats(int dtype, const void* x, float* partial, float* pivot, int*
   a.pivot = pivot;
   a.M = M;
   a.C = C;
-  dim3 grid;
-  *nblk_out = reduce_grid(dtype, M, C, &grid);
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL((bn_reduce_kernel<float, 0, 0, false>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((bn_reduce_kernel<bf16_t, 0, 0, false>), grid, dim3(256), 0, s, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "bn_stats", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((bn_reduce_kernel<T, 0, 0, false>), reduce_grid(Vec16<T>::N, M, C, nblk_out), dim3(256), 0, s, a);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_bn_finalize(const float* partial, const float* pivot, int nblk, int M, int C, const float* gamma,
@@ -819,7 +825,6 @@ int launch_bn_apply(int dtype, const void* x, const float* scale, const float* s
                     const void* x2, const float* scale2, const float* shift2, void* out, int M, int C, int relu,
                     hipStream_t s, uint8_t* relu_bits, QuantOut qo) {
   MI355_TRY(check_c(dtype, C));
-  const int V = 16 / (int)dtype_size(dtype);
   ApplyArgs a{};
   a.x = x;
   a.scale = scale;
@@ -830,51 +835,45 @@ int launch_bn_apply(int dtype, const void* x, const float* scale, const float* s
   a.shift2 = shift2;
   a.out = out;
   a.bits = relu_bits;
-  a.nvec = (size_t)M * C / V;
-  a.cvecs = C / V;
   a.relu = relu;
   a.slope = relu == 2 ? 0.01f : 0.f;  // activation code 2 = leaky ReLU (per-op path; the bit-mask path is ReLU)
   a.qo = qo;
-  const int blocks = elementwise_blocks(a.nvec, a.cvecs);
   if (qo.q) {  // fp8 training step: bf16, ReLU with bit mask (the executor's training forward)
     MI355_ARG(dtype == MI355_BF16 && relu == 1 && relu_bits && qo.scale && qo.amax && !(residual && x2), "bn_apply: the e4m3 twin needs bf16 + ReLU bit mask");
-    if (residual) hipLaunchKernelGGL((bn_apply_kernel<bf16_t, true, false, 2, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (x2) hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, true, 2, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (qo.only) hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, false, 2, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, false, 2, true>), dim3(blocks), dim3(256), 0, s, a);
-    MI355_LAUNCH_CHECK();
-    return 0;
+    const int blocks = size_elementwise(a, M, C, Vec16<bf16_t>::N);
+    const int form = residual ? 1 : x2 ? 2 : qo.only ? 3 : 0;  // 1: + residual, 2: + second branch, 3: the twin alone (no addend), 0: plain
+    return with_int<1, 2, 3, 0>(form, "bn_apply", [&](auto f) -> int {
+      constexpr bool RES = f == 1, X2 = f == 2, QONLY = f == 3;
+      hipLaunchKernelGGL((bn_apply_kernel<bf16_t, RES, X2, 2, true, QONLY>), dim3(blocks), dim3(256), 0, s, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
   }
-  const int rl = relu ? (relu_bits ? 2 : 1) : 0;
-  const int variant = (residual ? 6 : 0) + (x2 ? 3 : 0) + rl;
   MI355_ARG(!(residual && x2), "bn_apply: residual and second branch together are not supported");
   if (relu == 2 && relu_bits) {  // leaky ReLU + bit mask
     MI355_ARG(!residual && !x2, "bn_apply: the leaky bit-mask form has no residual / second-branch variant");
-    if (dtype == MI355_F32) hipLaunchKernelGGL((bn_apply_kernel<float, false, false, 3>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, false, 3>), dim3(blocks), dim3(256), 0, s, a);
-    MI355_LAUNCH_CHECK();
-    return 0;
+    return with_elem(dtype, "bn_apply", [&](auto e) -> int {
+      using T = typename decltype(e)::type;
+      const int blocks = size_elementwise(a, M, C, Vec16<T>::N);
+      hipLaunchKernelGGL((bn_apply_kernel<T, false, false, 3>), dim3(blocks), dim3(256), 0, s, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
   }
-#define MI355_BN_APPLY(TT)                                                                                      \
-  switch (variant) {                                                                                            \
-    case 0: hipLaunchKernelGGL((bn_apply_kernel<TT, false, false, 0>), dim3(blocks), dim3(256), 0, s, a); break; \
-    case 1: hipLaunchKernelGGL((bn_apply_kernel<TT, false, false, 1>), dim3(blocks), dim3(256), 0, s, a); break; \
-    case 2: hipLaunchKernelGGL((bn_apply_kernel<TT, false, false, 2>), dim3(blocks), dim3(256), 0, s, a); break; \
-    case 3: hipLaunchKernelGGL((bn_apply_kernel<TT, false, true, 0>), dim3(blocks), dim3(256), 0, s, a); break;  \
-    case 4: hipLaunchKernelGGL((bn_apply_kernel<TT, false, true, 1>), dim3(blocks), dim3(256), 0, s, a); break;  \
-    case 5: hipLaunchKernelGGL((bn_apply_kernel<TT, false, true, 2>), dim3(blocks), dim3(256), 0, s, a); break;  \
-    case 6: hipLaunchKernelGGL((bn_apply_kernel<TT, true, false, 0>), dim3(blocks), dim3(256), 0, s, a); break;  \
-    case 7: hipLaunchKernelGGL((bn_apply_kernel<TT, true, false, 1>), dim3(blocks), dim3(256), 0, s, a); break;  \
-    default: hipLaunchKernelGGL((bn_apply_kernel<TT, true, false, 2>), dim3(blocks), dim3(256), 0, s, a); break; \
-  }
-  if (dtype == MI355_F32) {
-    MI355_BN_APPLY(float)
-  } else {
-    MI355_BN_APPLY(bf16_t)
-  }
-#undef MI355_BN_APPLY
-  MI355_LAUNCH_CHECK();
-  return 0;
+  const int addend = residual ? 2 : x2 ? 1 : 0;  // 2: + residual, 1: + second branch, 0: none
+  const int rl = relu ? (relu_bits ? 2 : 1) : 0;
+  return with_elem(dtype, "bn_apply", [&](auto e) -> int {
+    return with_int<0, 1, 2>(addend, "bn_apply", [&](auto ad) -> int {
+      return with_int<0, 1, 2>(rl, "bn_apply", [&](auto RELU) -> int {
+        using T = typename decltype(e)::type;
+        constexpr bool RES = ad == 2, X2 = ad == 1;
+        const int blocks = size_elementwise(a, M, C, Vec16<T>::N);
+        hipLaunchKernelGGL((bn_apply_kernel<T, RES, X2, RELU>), dim3(blocks), dim3(256), 0, s, a);
+        MI355_LAUNCH_CHECK();
+        return 0;
+      });
+    });
+  });
 }
 
 int launch_bn_bwd_reduce(int dtype, const void* g, const void* mask_src, const void* x, const float* mean,
@@ -894,36 +893,27 @@ int launch_bn_bwd_reduce(int dtype, const void* g, const void* mask_src, const v
   a.partial = partial;
   a.M = M;
   a.C = C;
-  dim3 grid;
-  *nblk_out = reduce_grid(dtype, M, C, &grid);
   const int mask = relu_bits ? (slope != 0.f ? 3 : 2) : mask_src ? 1 : 0;
   if (eg) {  // the gradient comes out of an ECA backward on the fly: identity activation, nothing else stored
     MI355_ARG(mask == 0 && !dz_out && eg->gate && eg->dpool && eg->hw > 0, "bn_bwd_reduce: the ECA gradient source takes no mask / dz output");
-    if (dtype == MI355_F32) hipLaunchKernelGGL((bn_reduce_kernel<float, 1, 4, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bn_reduce_kernel<bf16_t, 1, 4, false>), grid, dim3(256), 0, s, a);
-    MI355_LAUNCH_CHECK();
-    return 0;
+    return with_elem(dtype, "bn_bwd_reduce", [&](auto e) -> int {
+      using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((bn_reduce_kernel<T, 1, 4, false>), reduce_grid(Vec16<T>::N, M, C, nblk_out), dim3(256), 0, s, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
   }
-  const int variant = mask * 2 + (dz_out ? 1 : 0);
-#define MI355_BN_REDUCE(TT)                                                                                     \
-  switch (variant) {                                                                                            \
-    case 0: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 0, false>), grid, dim3(256), 0, s, a); break;           \
-    case 1: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 0, true>), grid, dim3(256), 0, s, a); break;            \
-    case 2: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 1, false>), grid, dim3(256), 0, s, a); break;           \
-    case 3: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 1, true>), grid, dim3(256), 0, s, a); break;            \
-    case 4: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 2, false>), grid, dim3(256), 0, s, a); break;           \
-    case 5: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 2, true>), grid, dim3(256), 0, s, a); break;            \
-    case 6: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 3, false>), grid, dim3(256), 0, s, a); break;           \
-    default: hipLaunchKernelGGL((bn_reduce_kernel<TT, 1, 3, true>), grid, dim3(256), 0, s, a); break;           \
-  }
-  if (dtype == MI355_F32) {
-    MI355_BN_REDUCE(float)
-  } else {
-    MI355_BN_REDUCE(bf16_t)
-  }
-#undef MI355_BN_REDUCE
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "bn_bwd_reduce", [&](auto e) -> int {
+    return with_int<0, 1, 2, 3>(mask, "bn_bwd_reduce", [&](auto MASK) -> int {
+      return with_bool(dz_out == nullptr, [&](auto NO_DZ) -> int {
+        using T = typename decltype(e)::type;
+        constexpr bool DZ = !NO_DZ;
+        hipLaunchKernelGGL((bn_reduce_kernel<T, 1, MASK, DZ>), reduce_grid(Vec16<T>::N, M, C, nblk_out), dim3(256), 0, s, a);
+        MI355_LAUNCH_CHECK();
+        return 0;
+      });
+    });
+  });
 }
 
 int launch_bn_bwd_finalize(const float* partial, int nblk, int M, int C, const float* gamma, const float* invstd,
@@ -950,7 +940,6 @@ int launch_bn_bwd_apply(int dtype, const void* g, const void* mask_src, const vo
                         const float* invstd, const float* coef, void* dx, int M, int C, hipStream_t s,
                         const uint8_t* relu_bits, float slope, QuantOut qo, const EcaGrad* eg) {
   MI355_TRY(check_c(dtype, C));
-  const int V = 16 / (int)dtype_size(dtype);
   BwdApplyArgs a{};
   if (eg) a.eg = *eg;
   a.slope = slope;
@@ -962,50 +951,44 @@ int launch_bn_bwd_apply(int dtype, const void* g, const void* mask_src, const vo
   a.invstd = invstd;
   a.coef = coef;
   a.dx = dx;
-  a.nvec = (size_t)M * C / V;
-  a.cvecs = C / V;
   a.C = C;
-  const int blocks = elementwise_blocks(a.nvec, a.cvecs);
-  const int mask = relu_bits ? (slope != 0.f ? 3 : 2) : mask_src ? 1 : 0;
   a.qo = qo;
+  const int mask = relu_bits ? (slope != 0.f ? 3 : 2) : mask_src ? 1 : 0;
   if (eg) {
     MI355_ARG(mask == 0 && !qo.q && eg->gate && eg->dpool && eg->hw > 0, "bn_bwd_apply: the ECA gradient source takes no mask / twin");
-    if (dtype == MI355_F32) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, 4>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, 4>), dim3(blocks), dim3(256), 0, s, a);
-    MI355_LAUNCH_CHECK();
-    return 0;
+    return with_elem(dtype, "bn_bwd_apply", [&](auto e) -> int {
+      using T = typename decltype(e)::type;
+      const int blocks = size_elementwise(a, M, C, Vec16<T>::N);
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 4>), dim3(blocks), dim3(256), 0, s, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
   }
   if (qo.q) {
     MI355_ARG(dtype == MI355_BF16 && mask != 1 && mask != 3 && qo.scale && qo.amax, "bn_bwd_apply: the e4m3 twin needs bf16 and a ReLU bit mask (or none)");
-    if (mask == 2 && qo.only) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, 2, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (mask == 2) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, 2, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (qo.only) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, 0, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, 0, true>), dim3(blocks), dim3(256), 0, s, a);
-    MI355_LAUNCH_CHECK();
-    return 0;
+    const int blocks = size_elementwise(a, M, C, Vec16<bf16_t>::N);
+    return with_int<2, 0>(mask, "bn_bwd_apply", [&](auto MASK) -> int {
+      return with_bool(qo.only, [&](auto QONLY) -> int {
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, MASK, true, QONLY>), dim3(blocks), dim3(256), 0, s, a);
+        MI355_LAUNCH_CHECK();
+        return 0;
+      });
+    });
   }
-#define MI355_BN_BWD_APPLY(TT)                                                                                  \
-  switch (mask) {                                                                                               \
-    case 0: hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, 0>), dim3(blocks), dim3(256), 0, s, a); break;          \
-    case 1: hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, 1>), dim3(blocks), dim3(256), 0, s, a); break;          \
-    case 2: hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, 2>), dim3(blocks), dim3(256), 0, s, a); break;          \
-    default: hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, 3>), dim3(blocks), dim3(256), 0, s, a); break;         \
-  }
-  if (dtype == MI355_F32) {
-    MI355_BN_BWD_APPLY(float)
-  } else {
-    MI355_BN_BWD_APPLY(bf16_t)
-  }
-#undef MI355_BN_BWD_APPLY
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "bn_bwd_apply", [&](auto e) -> int {
+    return with_int<0, 1, 2, 3>(mask, "bn_bwd_apply", [&](auto MASK) -> int {
+      using T = typename decltype(e)::type;
+      const int blocks = size_elementwise(a, M, C, Vec16<T>::N);
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, MASK>), dim3(blocks), dim3(256), 0, s, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
+  });
 }
 
 static int stem_bwd_args(StemBwdArgs& a, int dtype, const void* dp, const uint8_t* idx, const uint8_t* bits, const void* y, const float* mean,
                          const float* invstd, int N, int H, int W, int C) {
   MI355_TRY(check_c(dtype, C));
-  const int V = 16 / (int)dtype_size(dtype);
-  (void)V;
   MI355_ARG(dp && idx && bits && y && H % 2 == 0 && W % 2 == 0 && C == SC, "stem_bwd: N=%d H=%d W=%d C=%d (64 channels)", N, H, W, C);
   MI355_ARG((unsigned long long)N * H * W * C * dtype_size(dtype) < 0xfffffff0ull, "stem_bwd: tensor beyond 32-bit offsets");
   a = StemBwdArgs{};
@@ -1020,16 +1003,17 @@ int launch_stem_bwd_reduce(int dtype, const void* dp, const uint8_t* idx, const 
   StemBwdArgs a;
   MI355_TRY(stem_bwd_args(a, dtype, dp, idx, bits, y, mean, invstd, N, H, W, C));
   a.partial = partial;
-  const int V = 16 / (int)dtype_size(dtype);
-  const int rpp = 256 / (C / V);
-  int nblk = cdiv(N * a.Ho * a.Wo, rpp * 4);
-  const int cap = std::min(2 * MAXBLK, 2 * device_cus());  // one resident round of 2 workgroups per CU (<= bn_max_blocks() partial rows)
-  if (nblk > cap) nblk = cap;
-  *nblk_out = nblk;
-  if (dtype == MI355_F32) hipLaunchKernelGGL(stem_bwd_reduce_kernel<float>, dim3(nblk), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(stem_bwd_reduce_kernel<bf16_t>, dim3(nblk), dim3(256), 0, s, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "stem_bwd_reduce", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    const int rpp = 256 / (C / Vec16<T>::N);
+    int nblk = cdiv(N * a.Ho * a.Wo, rpp * 4);
+    const int cap = std::min(2 * MAXBLK, 2 * device_cus());  // one resident round of 2 workgroups per CU (<= bn_max_blocks() partial rows)
+    if (nblk > cap) nblk = cap;
+    *nblk_out = nblk;
+    hipLaunchKernelGGL(stem_bwd_reduce_kernel<T>, dim3(nblk), dim3(256), 0, s, a);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // ... and the gradient wrt the raw conv output, dx [N][H][W][C]
@@ -1038,12 +1022,14 @@ int launch_stem_bwd_apply(int dtype, const void* dp, const uint8_t* idx, const u
   StemBwdArgs a;
   MI355_TRY(stem_bwd_args(a, dtype, dp, idx, bits, y, mean, invstd, N, H, W, C));
   a.coef = coef; a.dx = dx;
-  const int V = 16 / (int)dtype_size(dtype);
-  const int blocks = elementwise_blocks((size_t)N * a.Ho * a.Wo * (C / V), C / V);
-  if (dtype == MI355_F32) hipLaunchKernelGGL(stem_bwd_apply_kernel<float>, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(stem_bwd_apply_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "stem_bwd_apply", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    constexpr int V = Vec16<T>::N;
+    const int blocks = elementwise_blocks((size_t)N * a.Ho * a.Wo * (C / V), C / V);
+    hipLaunchKernelGGL(stem_bwd_apply_kernel<T>, dim3(blocks), dim3(256), 0, s, a);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // namespace mi355

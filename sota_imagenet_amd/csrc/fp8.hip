@@ -9,6 +9,7 @@
 #include <hip/hip_fp8.h>
 
 #include "common.h"
+#include "dispatch.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -58,18 +59,13 @@ extern "C" {
 int mi355_quantize_fp8(int src_dtype, const void* x, void* q, float scale, size_t n, void* stream) {
   MI355_ARG(x && q && n % 8 == 0 && scale > 0.f, "quantize_fp8: n=%zu must be a multiple of 8, scale > 0", n);
   hipStream_t s = (hipStream_t)stream;
-  if (src_dtype == MI355_F32) {
-    const size_t nvec = n / 4;
-    hipLaunchKernelGGL(quantize_fp8_kernel<float>, dim3((unsigned)std::min<size_t>((nvec + 255) / 256, 2048)), dim3(256), 0, s, (const float*)x, (unsigned char*)q, scale, nvec);
-  } else if (src_dtype == MI355_BF16) {
-    const size_t nvec = n / 8;
-    hipLaunchKernelGGL(quantize_fp8_kernel<bf16_t>, dim3((unsigned)std::min<size_t>((nvec + 255) / 256, 2048)), dim3(256), 0, s, (const bf16_t*)x, (unsigned char*)q, scale, nvec);
-  } else {
-    set_error("quantize_fp8: bad source dtype %d", src_dtype);
-    return MI355_E_ARG;
-  }
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(src_dtype, "quantize_fp8", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    const size_t nvec = n / Vec16<T>::N;
+    hipLaunchKernelGGL(quantize_fp8_kernel<T>, dim3((unsigned)std::min<size_t>((nvec + 255) / 256, 2048)), dim3(256), 0, s, (const T*)x, (unsigned char*)q, scale, nvec);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 // Reference call sites: sota_imagenet/dali_dataloader.py:113-123 (tensor contract of the batch),
 // sota_imagenet/callbacks.py:316-317 (model / criterion / backward), arg_parser.py:136-142 (SGD, CE).
 #include "common.h"
+#include "dispatch.h"
 #include "optim_sweep.h"
 #include "vec.h"
 
@@ -599,115 +600,94 @@ int grid_for(size_t total, int cap = 8192) {
   return (int)b;
 }
 
-#define DISPATCH_T(dtype, KERNEL, grid, ...)                                                    \
-  do {                                                                                          \
-    if ((dtype) == MI355_F32)                                                                   \
-      hipLaunchKernelGGL(KERNEL<float>, dim3(grid), dim3(256), 0, s, __VA_ARGS__);              \
-    else if ((dtype) == MI355_BF16)                                                             \
-      hipLaunchKernelGGL(KERNEL<bf16_t>, dim3(grid), dim3(256), 0, s, __VA_ARGS__);             \
-    else {                                                                                      \
-      set_error("bad dtype %d", (dtype));                                                       \
-      return MI355_E_ARG;                                                                       \
-    }                                                                                           \
-    MI355_LAUNCH_CHECK();                                                                       \
-  } while (0)
-
 }  // namespace
 
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s) {
   const int Hp = stem_hp(H), Wp = stem_wp(W);
   const int grid = grid_for((size_t)N * H * W);
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(stem_ingest_kernel<float>, dim3(grid), dim3(256), 0, s, x, (float*)xpad, N, H, W, Hp, Wp);
-  else
-    hipLaunchKernelGGL(stem_ingest_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, x, (bf16_t*)xpad, N, H, W, Hp, Wp);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "stem_ingest", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(stem_ingest_kernel<T>, dim3(grid), dim3(256), 0, s, x, (T*)xpad, N, H, W, Hp, Wp);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, hipStream_t s) {
   MI355_ARG(H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "maxpool: H=%d W=%d C=%d", H, W, C);
   const int Ho = H / 2, Wo = W / 2;
-  const int V = 16 / (int)dtype_size(dtype);
-  const int grid = grid_for((size_t)N * Ho * Wo * (C / V));
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, idx, N, H, W,
-                       C, Ho, Wo);
-  else
-    hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, idx, N,
-                       H, W, C, Ho, Wo);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "maxpool_fwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    const int grid = grid_for((size_t)N * Ho * Wo * (C / Vec16<T>::N));
+    hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, (T*)y, idx, N, H, W, C, Ho, Wo);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_bn_relu_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* p, uint8_t* idx,
                            uint8_t* bits, int N, int H, int W, int C, hipStream_t s) {
   MI355_ARG(H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "bn_relu_maxpool: H=%d W=%d C=%d", H, W, C);
   const int Ho = H / 2, Wo = W / 2;
-  const int V = 16 / (int)dtype_size(dtype);
-  if (Ho % 2 == 0 && Wo % 2 == 0) {  // 2 x 2 output blocks (every size the network is run at: H, W multiples of 32)
-    const int grid = grid_for((size_t)N * (Ho / 2) * (Wo / 2) * (C / V));
-    if (dtype == MI355_F32)
-      hipLaunchKernelGGL(bn_relu_maxpool2_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)y, scale, shift, (float*)p, idx, bits, N, H, W,
-                         C, Ho, Wo);
-    else if (knobs().pool_keys)
-      hipLaunchKernelGGL(bn_relu_maxpool3_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift, (bf16_t*)p, idx, bits, N, H, W, C, Ho, Wo);
-    else
-      hipLaunchKernelGGL(bn_relu_maxpool2_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift, (bf16_t*)p, idx, bits, N,
-                         H, W, C, Ho, Wo);
+  const bool blocks2 = Ho % 2 == 0 && Wo % 2 == 0;  // 2 x 2 output blocks (every size the network is run at: H, W multiples of 32)
+  if (blocks2 && dtype == MI355_BF16 && knobs().pool_keys) {  // packed (value, tap) keys: bf16 only
+    const int grid = grid_for((size_t)N * (Ho / 2) * (Wo / 2) * (C / Vec16<bf16_t>::N));
+    hipLaunchKernelGGL(bn_relu_maxpool3_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift, (bf16_t*)p, idx, bits, N, H, W, C, Ho, Wo);
     MI355_LAUNCH_CHECK();
     return 0;
   }
-  const int grid = grid_for((size_t)N * Ho * Wo * (C / V));
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)y, scale, shift, (float*)p,
-                       idx, bits, N, H, W, C, Ho, Wo);
-  else
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift,
-                       (bf16_t*)p, idx, bits, N, H, W, C, Ho, Wo);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  if (blocks2)
+    return with_elem(dtype, "bn_relu_maxpool", [&](auto e) -> int {
+      using T = typename decltype(e)::type;
+      const int grid = grid_for((size_t)N * (Ho / 2) * (Wo / 2) * (C / Vec16<T>::N));
+      hipLaunchKernelGGL(bn_relu_maxpool2_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)y, scale, shift, (T*)p, idx, bits, N, H, W, C, Ho, Wo);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
+  return with_elem(dtype, "bn_relu_maxpool", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    const int grid = grid_for((size_t)N * Ho * Wo * (C / Vec16<T>::N));
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)y, scale, shift, (T*)p, idx, bits, N, H, W, C, Ho, Wo);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C,
                        hipStream_t s) {
   MI355_ARG(H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "maxpool: H=%d W=%d C=%d", H, W, C);
   const int Ho = H / 2, Wo = W / 2;
-  const int V = 16 / (int)dtype_size(dtype);
-  const int grid = grid_for((size_t)N * Ho * Wo * (C / V));
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)dy, idx, (float*)dx, N, H,
-                       W, C, Ho, Wo);
-  else
-    hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)dy, idx, (bf16_t*)dx, N,
-                       H, W, C, Ho, Wo);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "maxpool_bwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    const int grid = grid_for((size_t)N * Ho * Wo * (C / Vec16<T>::N));
+    hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)dy, idx, (T*)dx, N, H, W, C, Ho, Wo);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_gap_fwd(int dtype, const void* x, float* pooled, int N, int HW, int C, hipStream_t s) {
   MI355_ARG(C % 8 == 0, "gap: C=%d", C);
-  const int V = 16 / (int)dtype_size(dtype);
-  MI355_ARG(C % (8 * V) == 0, "gap: C=%d must be a multiple of %d", C, 8 * V);
-  const int grid = N * (C / (8 * V));
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(gap_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, pooled, N, HW, C);
-  else
-    hipLaunchKernelGGL(gap_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, pooled, N, HW, C);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "gap_fwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    constexpr int V = Vec16<T>::N;
+    MI355_ARG(C % (8 * V) == 0, "gap: C=%d must be a multiple of %d", C, 8 * V);
+    const int grid = N * (C / (8 * V));
+    hipLaunchKernelGGL(gap_fwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, pooled, N, HW, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_gap_bwd(int dtype, const float* dpooled, void* dx, int N, int HW, int C, hipStream_t s) {
   MI355_ARG(C % 8 == 0, "gap: C=%d", C);
-  const int V = 16 / (int)dtype_size(dtype);
-  const int grid = grid_for((size_t)N * HW * (C / V));
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(gap_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, dpooled, (float*)dx, N, HW, C);
-  else
-    hipLaunchKernelGGL(gap_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, dpooled, (bf16_t*)dx, N, HW, C);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "gap_bwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    const int grid = grid_for((size_t)N * HW * (C / Vec16<T>::N));
+    hipLaunchKernelGGL(gap_bwd_kernel<T>, dim3(grid), dim3(256), 0, s, dpooled, (T*)dx, N, HW, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_ce(const float* logits, const float* target, float smoothing, float grad_scale, float* loss,
@@ -728,10 +708,11 @@ int launch_sgd(float* p, const float* g, float* m, size_t n, float lr, float mom
             "sgd: pointers must be 16-byte aligned");
   MI355_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "sgd: ema_decay=%g outside [0, 1]", (double)ema_decay);
   const size_t n4 = n / 4;
-  if (ema) hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for(n4, 4096)), dim3(256), 0, s, p, g, m, ema, n4, n, lr, mom, wd, gscale, 1.f - ema_decay);
-  else hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for(n4, 4096)), dim3(256), 0, s, p, g, m, ema, n4, n, lr, mom, wd, gscale, 0.f);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_bool(ema != nullptr, [&](auto EMA) -> int {
+    hipLaunchKernelGGL(sgd_kernel<EMA>, dim3(grid_for(n4, 4096)), dim3(256), 0, s, p, g, m, ema, n4, n, lr, mom, wd, gscale, EMA ? 1.f - ema_decay : 0.f);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s) {

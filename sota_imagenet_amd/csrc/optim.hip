@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "dispatch.h"
 #include "optim_sum.h"
 #include "optim_sweep.h"
 #include "vec.h"
@@ -93,15 +94,13 @@ int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double b
   a.ema_w = ema ? 1.f - ema_decay : 0.f;
   const size_t n4 = n / 4;
   const dim3 grid(adam_grid(n4)), block(256);
-  if (decoupled) {
-    if (ema) hipLaunchKernelGGL((adam_kernel<true, true>), grid, block, 0, s, p, g, m, v, ema, n4, n, a);
-    else hipLaunchKernelGGL((adam_kernel<true, false>), grid, block, 0, s, p, g, m, v, ema, n4, n, a);
-  } else {
-    if (ema) hipLaunchKernelGGL((adam_kernel<false, true>), grid, block, 0, s, p, g, m, v, ema, n4, n, a);
-    else hipLaunchKernelGGL((adam_kernel<false, false>), grid, block, 0, s, p, g, m, v, ema, n4, n, a);
-  }
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_bool(decoupled != 0, [&](auto DECOUPLED) -> int {
+    return with_bool(ema != nullptr, [&](auto EMA) -> int {
+      hipLaunchKernelGGL((adam_kernel<DECOUPLED, EMA>), grid, block, 0, s, p, g, m, v, ema, n4, n, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
+  });
 }
 
 // ---- MADGRAD: src.optimizers.MADGRAD.step of the reference (sota_imagenet/optimizers.py:726-767), in its operation order --------------------
@@ -165,10 +164,11 @@ int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* 
   a.ema_w = ema ? 1.f - ema_decay : 0.f;
   const size_t n4 = n / 4;
   const dim3 grid(adam_grid(n4)), block(256);
-  if (ema) hipLaunchKernelGGL((madgrad_kernel<true>), grid, block, 0, st, p, g, gss, s, x0, ema, n4, n, a);
-  else hipLaunchKernelGGL((madgrad_kernel<false>), grid, block, 0, st, p, g, gss, s, x0, ema, n4, n, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_bool(ema != nullptr, [&](auto EMA) -> int {
+    hipLaunchKernelGGL((madgrad_kernel<EMA>), grid, block, 0, st, p, g, gss, s, x0, ema, n4, n, a);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // ---- AdaiS: src.optimizers.AdaiS.step of the reference (sota_imagenet/optimizers.py:569-639) as three device stages on one stream ----------------
@@ -296,10 +296,11 @@ int launch_adais_step(float* p, const float* g, float* m, const float* v, float*
   a.ema_w = ema ? 1.f - ema_decay : 0.f;
   const size_t n4 = n / 4;
   const dim3 grid(adam_grid(n4)), block(256);
-  if (ema) hipLaunchKernelGGL((adais_step_kernel<true>), grid, block, 0, st, p, g, m, v, b1prod, ema, mean, n4, n, a);
-  else hipLaunchKernelGGL((adais_step_kernel<false>), grid, block, 0, st, p, g, m, v, b1prod, ema, mean, n4, n, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_bool(ema != nullptr, [&](auto EMA) -> int {
+    hipLaunchKernelGGL((adais_step_kernel<EMA>), grid, block, 0, st, p, g, m, v, b1prod, ema, mean, n4, n, a);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // namespace mi355

@@ -31,6 +31,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "dispatch.h"
 #include "optim_items.h"
 #include "optim_sum.h"
 #include "optim_sweep.h"
@@ -261,14 +262,12 @@ int launch_adamp_update(float* p, const float* g, float* m, float* v, float* ema
   if (!adamp_args("adamp_update", beta1, beta2, eps, lr, step, nesterov, gscale, a)) return MI355_E_ARG;
   a.ema_w = ema ? 1.f - ema_decay : 0.f;
   const dim3 grid((unsigned)n_items);
-  if (ema)
-    hipLaunchKernelGGL((adamp_update_kernel<true>), grid, dim3(256), 0, st, p, g, m, v, ema, n, (const LwItem*)items, (const UnitTensor*)tensors,
+  return with_bool(ema != nullptr, [&](auto EMA) -> int {
+    hipLaunchKernelGGL((adamp_update_kernel<EMA>), grid, dim3(256), 0, st, p, g, m, v, ema, n, (const LwItem*)items, (const UnitTensor*)tensors,
                        n_tensors, coef, (int)n_slots, wdf, a);
-  else
-    hipLaunchKernelGGL((adamp_update_kernel<false>), grid, dim3(256), 0, st, p, g, m, v, ema, n, (const LwItem*)items, (const UnitTensor*)tensors,
-                       n_tensors, coef, (int)n_slots, wdf, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // namespace mi355

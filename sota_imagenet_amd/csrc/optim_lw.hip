@@ -36,6 +36,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "dispatch.h"
 #include "optim_items.h"
 #include "optim_sum.h"
 #include "optim_sweep.h"
@@ -153,13 +154,6 @@ __global__ __launch_bounds__(256) void lw_update_kernel(float* __restrict__ p, c
   item_sweep(it.len, rule, upd(p + it.off), last(g + it.off), upd(m + it.off), upd_if<EMA>(ema + it.off));
 }
 
-template <int RULE>
-void lw_update_launch(bool ema_on, dim3 grid, hipStream_t st, float* p, const float* g, float* m, float* ema, size_t n, const LwItem* items,
-                      const float* coef, int n_tensors, const LwUpdArgs& a) {
-  if (ema_on) hipLaunchKernelGGL((lw_update_kernel<RULE, true>), grid, dim3(256), 0, st, p, g, m, ema, n, items, coef, n_tensors, a);
-  else hipLaunchKernelGGL((lw_update_kernel<RULE, false>), grid, dim3(256), 0, st, p, g, m, ema, n, items, coef, n_tensors, a);
-}
-
 __global__ __launch_bounds__(256) void lw_unit_sumsq_kernel(const float* __restrict__ src, size_t n, const UnitPiece* __restrict__ pieces,
                                                             size_t n_pieces, int n_slots, double* __restrict__ partial, float scale) {
   const auto add = [&](double(&acc)[1], float x) {
@@ -208,15 +202,6 @@ __global__ __launch_bounds__(256) void lw_unit_update_kernel(float* __restrict__
   };
   const auto elem = [&](const f32x4& c, float& pk, float& gk, float& mk, float& ek) { lw_elem<RULE, EMA>(pk, gk, mk, ek, c, a); };
   unit_item_sweep(it.len, sp, coef_of, elem, upd(p + it.off), last(g + it.off), upd(m + it.off), upd_if<EMA>(ema + it.off));
-}
-
-template <int RULE>
-void lw_unit_update_launch(bool ema_on, dim3 grid, hipStream_t st, float* p, const float* g, float* m, float* ema, size_t n, const LwItem* items,
-                           const UnitTensor* tens, int n_tensors, const float* den, int n_slots, const f32x4& c0, const LwUpdArgs& a) {
-  if (ema_on)
-    hipLaunchKernelGGL((lw_unit_update_kernel<RULE, true>), grid, dim3(256), 0, st, p, g, m, ema, n, items, tens, n_tensors, den, n_slots, c0, a);
-  else
-    hipLaunchKernelGGL((lw_unit_update_kernel<RULE, false>), grid, dim3(256), 0, st, p, g, m, ema, n, items, tens, n_tensors, den, n_slots, c0, a);
 }
 
 }  // namespace
@@ -268,11 +253,13 @@ int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, s
   const LwUpdArgs a = lw_upd_args(lr, soft_wd, wd_eps, gscale, ema, ema_decay);
   const dim3 grid((unsigned)n_items);
   const LwItem* it = (const LwItem*)items;
-  if (rule == 0) lw_update_launch<0>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
-  else if (rule == 1) lw_update_launch<1>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
-  else lw_update_launch<2>(ema != nullptr, grid, st, p, g, m, ema, n, it, coef, n_tensors, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_int<0, 1, 2>(rule, "lw_update", [&](auto RULE) -> int {
+    return with_bool(ema != nullptr, [&](auto EMA) -> int {
+      hipLaunchKernelGGL((lw_update_kernel<RULE, EMA>), grid, dim3(256), 0, st, p, g, m, ema, n, it, coef, n_tensors, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
+  });
 }
 
 int launch_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, double* partial,
@@ -324,10 +311,13 @@ int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* e
   const dim3 grid((unsigned)n_items);
   const LwItem* it = (const LwItem*)items;
   const UnitTensor* tn = (const UnitTensor*)tensors;
-  if (rule == 0) lw_unit_update_launch<0>(ema != nullptr, grid, st, p, g, m, ema, n, it, tn, n_tensors, den, (int)n_slots, c0, a);
-  else lw_unit_update_launch<1>(ema != nullptr, grid, st, p, g, m, ema, n, it, tn, n_tensors, den, (int)n_slots, c0, a);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_int<0, 1>(rule, "lw_unit_update", [&](auto RULE) -> int {
+    return with_bool(ema != nullptr, [&](auto EMA) -> int {
+      hipLaunchKernelGGL((lw_unit_update_kernel<RULE, EMA>), grid, dim3(256), 0, st, p, g, m, ema, n, it, tn, n_tensors, den, (int)n_slots, c0, a);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
+  });
 }
 
 }  // namespace mi355

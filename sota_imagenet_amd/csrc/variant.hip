@@ -13,6 +13,7 @@
 //   dropout        on the pooled features
 // All tensors NHWC; one thread handles one 16-byte channel vector (HBM-bound streaming, coalesced over channels).
 #include "common.h"
+#include "dispatch.h"
 #include "vec.h"
 
 namespace mi355 {
@@ -983,25 +984,31 @@ __global__ __launch_bounds__(256) void axpby_kernel(const float* __restrict__ sr
 namespace mi355 {
 int launch_nchw_pad64(int dtype, const float* x, void* h, int N, int HW, hipStream_t s) {
   const size_t total = (size_t)N * HW * 64;
-  if (dtype == MI355_F32) hipLaunchKernelGGL(nchw_pad64_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, x, (float*)h, N, HW);
-  else hipLaunchKernelGGL(nchw_pad64_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, x, (bf16_t*)h, N, HW);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "nchw_pad64", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(nchw_pad64_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, x, (T*)h, N, HW);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int launch_nchw_im2col3s2(int dtype, const float* x, void* h, int N, int H, int W, hipStream_t s) {
   MI355_ARG(H % 2 == 0 && W % 2 == 0, "nchw_im2col3s2: H=%d W=%d (even)", H, W);
   const size_t total = (size_t)N * (H / 2) * (W / 2) * 64;
-  if (dtype == MI355_F32) hipLaunchKernelGGL(nchw_im2col3s2_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, x, (float*)h, N, H, W);
-  else hipLaunchKernelGGL(nchw_im2col3s2_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, x, (bf16_t*)h, N, H, W);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "nchw_im2col3s2", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(nchw_im2col3s2_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, x, (T*)h, N, H, W);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int launch_weight_pad_cast(int dtype, const float* w, void* wp, int Cout, int taps, int Cin, int Coutp, int Cinp, hipStream_t s) {
   const size_t total = (size_t)Coutp * taps * Cinp;
-  if (dtype == MI355_F32) hipLaunchKernelGGL(weight_pad_cast_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, (float*)wp, Cout, taps, Cin, Coutp, Cinp);
-  else hipLaunchKernelGGL(weight_pad_cast_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w, (bf16_t*)wp, Cout, taps, Cin, Coutp, Cinp);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "weight_pad_cast", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(weight_pad_cast_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, w, (T*)wp, Cout, taps, Cin, Coutp, Cinp);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int launch_keep_scale_batch(const KeepBatch& kb, unsigned long long seed, hipStream_t s) {
   if (kb.count <= 0) return 0;
@@ -1013,15 +1020,19 @@ int launch_keep_scale_batch(const KeepBatch& kb, unsigned long long seed, hipStr
 }
 int launch_bres_weight_prep(int dtype, const BPrepDesc* table, int nconv, int total_rows, int total_tiles, float eps, bool transposed, hipStream_t s) {
   MI355_ARG(table && nconv > 0 && total_rows > 0, "bres_weight_prep: empty table");
-  if (dtype == MI355_F32) hipLaunchKernelGGL(bres_weight_rows_kernel<float>, dim3(total_rows), dim3(256), 0, s, table, nconv, eps);
-  else hipLaunchKernelGGL(bres_weight_rows_kernel<bf16_t>, dim3(total_rows), dim3(256), 0, s, table, nconv, eps);
-  MI355_LAUNCH_CHECK();
-  if (transposed) {
-    if (dtype == MI355_F32) hipLaunchKernelGGL(bres_weight_transpose_kernel<float>, dim3(total_tiles), dim3(256), 0, s, table, nconv);
-    else hipLaunchKernelGGL(bres_weight_transpose_kernel<bf16_t>, dim3(total_tiles), dim3(256), 0, s, table, nconv);
+  MI355_TRY(with_elem(dtype, "bres_weight_prep", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(bres_weight_rows_kernel<T>, dim3(total_rows), dim3(256), 0, s, table, nconv, eps);
     MI355_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  }));
+  if (!transposed) return 0;
+  return with_elem(dtype, "bres_weight_prep", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(bres_weight_transpose_kernel<T>, dim3(total_tiles), dim3(256), 0, s, table, nconv);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int launch_weight_unpad(const float* dwp, float* dw, float beta, int Cout, int taps, int Cin, int Cinp, hipStream_t s) {
   hipLaunchKernelGGL(weight_unpad_kernel, dim3(grid_for((size_t)Cout * taps * Cin)), dim3(256), 0, s, dwp, dw, beta, Cout, taps, Cin, Cinp);
@@ -1042,12 +1053,12 @@ int launch_eca_residual_fwd(int dtype, const void* x, const float* w, int k, con
   }
   const Affine af{xs, xh, ss, sh2};
   const size_t total = (size_t)N * HW * C;
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(eca_residual_fwd_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)x, gate, keep, (const float*)shortcut, (float*)out, N, HW, C, act, af, out_bits);
-  else
-    hipLaunchKernelGGL(eca_residual_fwd_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)x, gate, keep, (const bf16_t*)shortcut, (bf16_t*)out, N, HW, C, act, af, out_bits);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "eca_residual_fwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(eca_residual_fwd_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)x, gate, keep, (const T*)shortcut, (T*)out, N, HW, C, act, af, out_bits);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 // its backward from dout: dshortcut (the shortcut operand's gradient), dx (the ECA input's), dw[k] (beta 0 / 1); ws: 2*N*C + 1152 floats
 int launch_eca_residual_bwd(int dtype, const void* dout, const void* out, const void* x, const float* keep, const float* w, int k, const float* pooled,
@@ -1062,21 +1073,14 @@ int launch_eca_residual_bwd(int dtype, const void* dout, const void* out, const 
   float *sprod = ws, *dpool = ws + (size_t)N * C, *dwpart = ws + (size_t)2 * N * C, *sums = ws + (size_t)2 * N * C + 1152;
   MI355_ARG(!bn_row || (!dx && xs && xh && bn_mean && bn_invstd), "eca_residual_bwd: the BatchNorm sums need the raw tensor form and no stored dx");
   MI355_ARG(!ds_row || (bn_row && ds_y && ds_mean && ds_invstd), "eca_residual_bwd: the downsample sums come with the bn3 sums");
-  if (dtype == MI355_F32) {
-    if (bn_row)
-      hipLaunchKernelGGL((eca_residual_bwd_reduce_kernel<float, true>), dim3(N * (C / 32)), dim3(256), 0, s, (const float*)dout, (const float*)out, (const float*)x, keep,
-                         (float*)dshortcut, sprod, N, HW, C, act, xs, xh, sums, out_bits, (const float*)(ds_row ? ds_y : nullptr));
-    else
-      hipLaunchKernelGGL((eca_residual_bwd_reduce_kernel<float, false>), dim3(N * (C / 32)), dim3(256), 0, s, (const float*)dout, (const float*)out, (const float*)x, keep,
-                         (float*)dshortcut, sprod, N, HW, C, act, xs, xh, nullptr, out_bits, nullptr);
-  } else {
-    if (bn_row)
-      hipLaunchKernelGGL((eca_residual_bwd_reduce_kernel<bf16_t, true>), dim3(N * (C / 64)), dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, (const bf16_t*)x,
-                         keep, (bf16_t*)dshortcut, sprod, N, HW, C, act, xs, xh, sums, out_bits, (const bf16_t*)(ds_row ? ds_y : nullptr));
-    else
-      hipLaunchKernelGGL((eca_residual_bwd_reduce_kernel<bf16_t, false>), dim3(N * (C / 64)), dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, (const bf16_t*)x,
-                         keep, (bf16_t*)dshortcut, sprod, N, HW, C, act, xs, xh, nullptr, out_bits, nullptr);
-  }
+  MI355_TRY(with_elem(dtype, "eca_residual_bwd", [&](auto e) -> int {
+    return with_bool(bn_row != nullptr, [&](auto SUMS) -> int {  // the per-image sums of the BatchNorm backward ride along (ds_y only with them)
+      using T = typename decltype(e)::type;
+      hipLaunchKernelGGL((eca_residual_bwd_reduce_kernel<T, SUMS>), dim3(N * (C / (8 * Vec16<T>::N))), dim3(256), 0, s, (const T*)dout, (const T*)out, (const T*)x, keep,
+                         (T*)dshortcut, sprod, N, HW, C, act, xs, xh, SUMS ? sums : nullptr, out_bits, (const T*)(SUMS && ds_row ? ds_y : nullptr));
+      return 0;
+    });
+  }));
   hipLaunchKernelGGL(eca_gate_bwd_kernel, dim3(ECA_GB), dim3(ECA_BT), 0, s, sprod, gate, pooled, w, k, dpool, dwpart, N, C, 1.f / (float)HW);
   hipLaunchKernelGGL(eca_dw_finish_kernel, dim3(1), dim3(64), 0, s, dwpart, dw, k, beta);
   if (bn_row) hipLaunchKernelGGL(eca_bn_sums_kernel, dim3(C / 16), dim3(16 * ECA_SL), 0, s, sums, gate, dpool, keep, bn_mean, bn_invstd, bn_row, N, C, HW);
@@ -1086,12 +1090,12 @@ int launch_eca_residual_bwd(int dtype, const void* dout, const void* out, const 
     return 0;
   }
   const size_t total = (size_t)N * HW * C;
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(eca_residual_bwd_apply_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)dshortcut, gate, dpool, keep, (float*)dx, N, HW, C);
-  else
-    hipLaunchKernelGGL(eca_residual_bwd_apply_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)dshortcut, gate, dpool, keep, (bf16_t*)dx, N, HW, C);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "eca_residual_bwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(eca_residual_bwd_apply_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)dshortcut, gate, dpool, keep, (T*)dx, N, HW, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int launch_axpby(const float* src, float* dst, float beta, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n)), dim3(256), 0, s, src, dst, beta, n);
@@ -1102,50 +1106,51 @@ int launch_axpby(const float* src, float* dst, float beta, size_t n, hipStream_t
 
 using namespace mi355;
 
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16)                  \
-  do {                                                          \
-    if ((dtype) == MI355_F32) { CALL_F32; }                     \
-    else if ((dtype) == MI355_BF16) { CALL_BF16; }              \
-    else { set_error("bad dtype %d", (dtype)); return MI355_E_ARG; } \
-  } while (0)
-
 extern "C" {
 
 int mi355_blurpool_fwd(int dtype, const void* x, void* y, int N, int H, int W, int C, void* stream) {
   MI355_ARG(x && y && N > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "blurpool: H=%d W=%d (even) C=%d (multiple of 8)", H, W, C);
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)N * (H / 2) * (W / 2) * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(blurpool_fwd_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)x, (float*)y, N, H, W, C),
-             hipLaunchKernelGGL(blurpool_fwd_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, N, H, W, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "blurpool", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(blurpool_fwd_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int mi355_blurpool_bwd(int dtype, const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
   MI355_ARG(dy && dx && N > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "blurpool: H=%d W=%d (even) C=%d (multiple of 8)", H, W, C);
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)N * H * W * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(blurpool_bwd_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)dy, (float*)dx, N, H, W, C),
-             hipLaunchKernelGGL(blurpool_bwd_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)dy, (bf16_t*)dx, N, H, W, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "blurpool", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(blurpool_bwd_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)dy, (T*)dx, N, H, W, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int mi355_avgpool2_fwd(int dtype, const void* x, void* y, int N, int H, int W, int C, void* stream) {
   MI355_ARG(x && y && N > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "avgpool2: H=%d W=%d (even) C=%d (multiple of 8)", H, W, C);
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)N * (H / 2) * (W / 2) * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((avgpool2_kernel<float, false>), dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)x, (float*)y, N, H, W, C),
-             hipLaunchKernelGGL((avgpool2_kernel<bf16_t, false>), dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, N, H, W, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "avgpool2", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((avgpool2_kernel<T, false>), dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int mi355_avgpool2_bwd(int dtype, const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
   MI355_ARG(dy && dx && N > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "avgpool2: H=%d W=%d (even) C=%d (multiple of 8)", H, W, C);
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)N * H * W * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((avgpool2_kernel<float, true>), dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)dy, (float*)dx, N, H, W, C),
-             hipLaunchKernelGGL((avgpool2_kernel<bf16_t, true>), dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)dy, (bf16_t*)dx, N, H, W, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "avgpool2", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((avgpool2_kernel<T, true>), dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)dy, (T*)dx, N, H, W, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int mi355_maxpool3s1_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
   MI355_ARG(x && y && idx && N > 0 && H > 0 && W > 0 && C % 8 == 0, "maxpool3s1: C=%d (multiple of 8)", C);
@@ -1154,15 +1159,19 @@ int mi355_maxpool3s1_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N,
   if (W >= 16 && (size_t)N * H * C / 8 >= 16384 && pool_seg(W) > 0) {  // enough rows to fill the chip: the row-walking form (3 loads per pixel instead of 9)
     const int SEG = pool_seg(W);
     const size_t rows = (size_t)N * H * ((W + SEG - 1) / SEG) * C;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool3s1_fwd_rows_kernel<float>, dim3(grid_for(rows / 4)), dim3(256), 0, s, (const float*)x, (float*)y, idx, N, H, W, C, SEG),
-               hipLaunchKernelGGL(maxpool3s1_fwd_rows_kernel<bf16_t>, dim3(grid_for(rows / 8)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, idx, N, H, W, C, SEG));
+    return with_elem(dtype, "maxpool3s1", [&](auto e) -> int {
+      using T = typename decltype(e)::type;
+      hipLaunchKernelGGL(maxpool3s1_fwd_rows_kernel<T>, dim3(grid_for(rows / Vec16<T>::N)), dim3(256), 0, s, (const T*)x, (T*)y, idx, N, H, W, C, SEG);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
+  }
+  return with_elem(dtype, "maxpool3s1", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(maxpool3s1_fwd_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)x, (T*)y, idx, N, H, W, C);
     MI355_LAUNCH_CHECK();
     return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool3s1_fwd_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)x, (float*)y, idx, N, H, W, C),
-             hipLaunchKernelGGL(maxpool3s1_fwd_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, idx, N, H, W, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  });
 }
 int mi355_maxpool3s1_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C, void* stream) {
   MI355_ARG(dy && dx && idx && N > 0 && H > 0 && W > 0 && C % 8 == 0, "maxpool3s1: C=%d (multiple of 8)", C);
@@ -1171,15 +1180,19 @@ int mi355_maxpool3s1_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx
   if (W >= 16 && (size_t)N * H * C / 8 >= 16384 && pool_seg(W) > 0) {
     const int SEG = pool_seg(W);
     const size_t rows = (size_t)N * H * ((W + SEG - 1) / SEG) * C;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool3s1_bwd_rows_kernel<float>, dim3(grid_for(rows / 4)), dim3(256), 0, s, (const float*)dy, idx, (float*)dx, N, H, W, C, SEG),
-               hipLaunchKernelGGL(maxpool3s1_bwd_rows_kernel<bf16_t>, dim3(grid_for(rows / 8)), dim3(256), 0, s, (const bf16_t*)dy, idx, (bf16_t*)dx, N, H, W, C, SEG));
+    return with_elem(dtype, "maxpool3s1", [&](auto e) -> int {
+      using T = typename decltype(e)::type;
+      hipLaunchKernelGGL(maxpool3s1_bwd_rows_kernel<T>, dim3(grid_for(rows / Vec16<T>::N)), dim3(256), 0, s, (const T*)dy, idx, (T*)dx, N, H, W, C, SEG);
+      MI355_LAUNCH_CHECK();
+      return 0;
+    });
+  }
+  return with_elem(dtype, "maxpool3s1", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(maxpool3s1_bwd_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)dy, idx, (T*)dx, N, H, W, C);
     MI355_LAUNCH_CHECK();
     return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool3s1_bwd_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)dy, idx, (float*)dx, N, H, W, C),
-             hipLaunchKernelGGL(maxpool3s1_bwd_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)dy, idx, (bf16_t*)dx, N, H, W, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  });
 }
 
 int mi355_eca_fwd(int dtype, const void* x, const float* w, int k, void* y, float* pooled, float* gate, int N, int HW, int C, void* stream) {
@@ -1188,10 +1201,12 @@ int mi355_eca_fwd(int dtype, const void* x, const float* w, int k, void* y, floa
   MI355_TRY(launch_gap_fwd(dtype, x, pooled, N, HW, C, s));
   hipLaunchKernelGGL(eca_gate_kernel, dim3(grid_for((size_t)N * C)), dim3(256), 0, s, pooled, w, k, gate, N, C);
   const size_t total = (size_t)N * HW * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((eca_scale_kernel<float, false>), dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)x, gate, nullptr, (float*)y, N, HW, C),
-             hipLaunchKernelGGL((eca_scale_kernel<bf16_t, false>), dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)x, gate, nullptr, (bf16_t*)y, N, HW, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "eca", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((eca_scale_kernel<T, false>), dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)x, gate, nullptr, (T*)y, N, HW, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int mi355_eca_bwd(int dtype, const void* dy, const void* x, const float* w, int k, const float* pooled, const float* gate, void* dx, float* dw,
                   float beta, float* ws, int N, int HW, int C, void* stream) {
@@ -1200,15 +1215,20 @@ int mi355_eca_bwd(int dtype, const void* dy, const void* x, const float* w, int 
   float* sprod = ws;                    // [N][C]
   float* dpool = ws + (size_t)N * C;    // [N][C]
   float* dwpart = ws + (size_t)2 * N * C;  // [ECA_GB][9]
-  DISPATCH_T(dtype, hipLaunchKernelGGL(eca_prod_reduce_kernel<float>, dim3(N * (C / 32)), dim3(256), 0, s, (const float*)dy, (const float*)x, sprod, N, HW, C),
-             hipLaunchKernelGGL(eca_prod_reduce_kernel<bf16_t>, dim3(N * (C / 64)), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, sprod, N, HW, C));
+  MI355_TRY(with_elem(dtype, "eca_bwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(eca_prod_reduce_kernel<T>, dim3(N * (C / (8 * Vec16<T>::N))), dim3(256), 0, s, (const T*)dy, (const T*)x, sprod, N, HW, C);
+    return 0;
+  }));
   hipLaunchKernelGGL(eca_gate_bwd_kernel, dim3(ECA_GB), dim3(ECA_BT), 0, s, sprod, gate, pooled, w, k, dpool, dwpart, N, C, 1.f / (float)HW);
   hipLaunchKernelGGL(eca_dw_finish_kernel, dim3(1), dim3(64), 0, s, dwpart, dw, k, beta);
   const size_t total = (size_t)N * HW * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((eca_scale_kernel<float, true>), dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)dy, gate, dpool, (float*)dx, N, HW, C),
-             hipLaunchKernelGGL((eca_scale_kernel<bf16_t, true>), dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)dy, gate, dpool, (bf16_t*)dx, N, HW, C));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "eca_bwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((eca_scale_kernel<T, true>), dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)dy, gate, dpool, (T*)dx, N, HW, C);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int mi355_weight_std_fwd(const float* w, float* w_hat, float* mean, float* invstd, int Cout, int K, float eps, void* stream) {
@@ -1228,20 +1248,24 @@ int mi355_residual_act_fwd(int dtype, const void* branch, const float* scale_n, 
   MI355_ARG(branch && out && N > 0 && HWC % 8 == 0 && act >= 0 && act <= 2, "residual_act: HWC=%zu (multiple of 8) act=%d", HWC, act);
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)N * HWC;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(residual_act_fwd_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)branch, scale_n, (const float*)shortcut, (float*)out, N, HWC, act),
-             hipLaunchKernelGGL(residual_act_fwd_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)branch, scale_n, (const bf16_t*)shortcut, (bf16_t*)out, N, HWC, act));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "residual_act", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(residual_act_fwd_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)branch, scale_n, (const T*)shortcut, (T*)out, N, HWC, act);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int mi355_residual_act_bwd(int dtype, const void* dout, const void* out, const float* scale_n, void* dbranch, void* dshortcut, int N, size_t HWC, int act,
                            void* stream) {
   MI355_ARG(dout && out && dbranch && N > 0 && HWC % 8 == 0 && act >= 0 && act <= 2, "residual_act_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const size_t total = (size_t)N * HWC;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(residual_act_bwd_kernel<float>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const float*)dout, (const float*)out, scale_n, (float*)dbranch, (float*)dshortcut, N, HWC, act),
-             hipLaunchKernelGGL(residual_act_bwd_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, scale_n, (bf16_t*)dbranch, (bf16_t*)dshortcut, N, HWC, act));
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "residual_act_bwd", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(residual_act_bwd_kernel<T>, dim3(grid_for(total / Vec16<T>::N)), dim3(256), 0, s, (const T*)dout, (const T*)out, scale_n, (T*)dbranch, (T*)dshortcut, N, HWC, act);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int mi355_keep_scale(float* keep, size_t n, float p, unsigned long long seed, unsigned long long counter, void* stream) {

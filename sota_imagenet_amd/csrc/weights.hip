@@ -8,6 +8,7 @@
 #include <hip/hip_fp8.h>
 
 #include "common.h"
+#include "dispatch.h"
 
 namespace mi355 {
 namespace {
@@ -108,47 +109,43 @@ int launch_weight_prep(int dtype, const float* w, void* w_cast, void* w_tr, int 
   MI355_ARG(Cout % 32 == 0 && Cin % 32 == 0, "weight_prep: Cout=%d Cin=%d must be multiples of 32", Cout, Cin);
   if (!w_cast && !w_tr) return 0;
   dim3 grid(Cin / 32, Cout / 32, taps);
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL((weight_prep_kernel<float, float>), grid, dim3(256), 0, stream, w, (float*)w_cast, (float*)w_tr, Cout,
-                       taps, Cin);
-  else
-    hipLaunchKernelGGL((weight_prep_kernel<bf16_t, float>), grid, dim3(256), 0, stream, w, (bf16_t*)w_cast, (bf16_t*)w_tr,
-                       Cout, taps, Cin);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "weight_prep", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((weight_prep_kernel<T, float>), grid, dim3(256), 0, stream, w, (T*)w_cast, (T*)w_tr, Cout, taps, Cin);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_transpose_any(int dtype, const void* w, void* wt, int Cout, int taps, int Cin, hipStream_t stream) {
   MI355_ARG(Cout % 32 == 0 && Cin % 32 == 0, "transpose: Cout=%d Cin=%d must be multiples of 32", Cout, Cin);
   dim3 grid(Cin / 32, Cout / 32, taps);
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL((weight_prep_kernel<float, float>), grid, dim3(256), 0, stream, (const float*)w,
-                       (float*)nullptr, (float*)wt, Cout, taps, Cin);
-  else
-    hipLaunchKernelGGL((weight_prep_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, stream, (const bf16_t*)w,
-                       (bf16_t*)nullptr, (bf16_t*)wt, Cout, taps, Cin);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "transpose", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL((weight_prep_kernel<T, T>), grid, dim3(256), 0, stream, (const T*)w, (T*)nullptr, (T*)wt, Cout, taps, Cin);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_weight_prep_batch(int dtype, const PrepDesc* table, int nlayers, int total_tiles, const float* params,
                              hipStream_t stream) {
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(weight_prep_batch_kernel<float>, dim3(total_tiles), dim3(256), 0, stream, table, nlayers, params);
-  else
-    hipLaunchKernelGGL(weight_prep_batch_kernel<bf16_t>, dim3(total_tiles), dim3(256), 0, stream, table, nlayers, params);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "weight_prep_batch", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(weight_prep_batch_kernel<T>, dim3(total_tiles), dim3(256), 0, stream, table, nlayers, params);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_stem_pack(int dtype, const float* w, void* packed, hipStream_t stream) {
   const int n = 64 * 4 * 64;
-  if (dtype == MI355_F32)
-    hipLaunchKernelGGL(stem_pack_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, stream, w, (float*)packed);
-  else
-    hipLaunchKernelGGL(stem_pack_kernel<bf16_t>, dim3(cdiv(n, 256)), dim3(256), 0, stream, w, (bf16_t*)packed);
-  MI355_LAUNCH_CHECK();
-  return 0;
+  return with_elem(dtype, "stem_pack", [&](auto e) -> int {
+    using T = typename decltype(e)::type;
+    hipLaunchKernelGGL(stem_pack_kernel<T>, dim3(cdiv(n, 256)), dim3(256), 0, stream, w, (T*)packed);
+    MI355_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // namespace mi355

@@ -70,6 +70,24 @@ def test_bad_arguments_return_status_not_crash():
     assert "Cin" in native.last_error()
 
 
+@pytest.mark.skipif(torch.cuda.is_available(), reason="host-side refusal, called with dummy pointers: never sent to a GPU")
+@pytest.mark.parametrize("dtype", [7, native.FP8])
+def test_elementwise_entry_points_refuse_a_dtype_outside_their_set(dtype):
+    """The launchers directly behind the C-ABI accept MI355_F32 and MI355_BF16 only: any other code (a stray integer, or MI355_FP8, which other
+    calls do take) is refused with MI355_E_ARG before anything is launched — not run as the bf16 instance over a grid sized for fp32."""
+    L = native.lib()
+    p = torch.zeros(64).data_ptr()  # non-null, never dereferenced
+    N, H, W, C, HW = 1, 8, 8, 64, 64
+    calls = {"mi355_stem_ingest": (dtype, p, p, N, H, W, None),
+             "mi355_maxpool_fwd": (dtype, p, p, p, N, H, W, C, None),
+             "mi355_maxpool_bwd": (dtype, p, p, p, N, H, W, C, None),
+             "mi355_gap_fwd": (dtype, p, p, N, HW, C, None),
+             "mi355_gap_bwd": (dtype, p, p, N, HW, C, None)}
+    for name, args in calls.items():
+        rc = getattr(L, name)(*args)
+        assert rc == -1 and "dtype" in native.last_error(), (name, rc, native.last_error())
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the GPU-less failure mode")
 def test_no_cpu_fallback_without_gpu():
     L = native.lib()
