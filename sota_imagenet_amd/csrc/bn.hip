@@ -1033,3 +1033,66 @@ int launch_stem_bwd_apply(int dtype, const void* dp, const uint8_t* idx, const u
 }
 
 }  // namespace mi355
+
+using namespace mi355;
+
+extern "C" {
+
+size_t mi355_bn_workspace_bytes(int C) { return ((size_t)bn_max_blocks() * 2 * C + 8 * (size_t)C) * 4; }
+
+int mi355_bn_fwd_train(int dtype, const void* x, const void* residual, void* out, const float* gamma,
+                       const float* beta, float* running_mean, float* running_var, float* save_mean,
+                       float* save_invstd, int M, int C, float eps, float momentum, int relu, void* ws,
+                       size_t ws_bytes, void* stream) {
+  MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = (float*)ws;
+  float* scale = partial + (size_t)bn_max_blocks() * 2 * C;
+  float* shift = scale + C;
+  float* pivot = shift + C;
+  int nblk = 0;
+  MI355_TRY(launch_bn_stats(dtype, x, partial, pivot, &nblk, M, C, s));
+  MI355_TRY(launch_bn_finalize(partial, pivot, nblk, M, C, gamma, beta, running_mean, running_var, save_mean, save_invstd,
+                               scale, shift, eps, momentum, s));
+  return launch_bn_apply(dtype, x, scale, shift, residual, nullptr, nullptr, nullptr, out, M, C, relu, s);
+}
+
+int mi355_bn_fwd_train_partial(int dtype, const void* x, const void* residual, void* out, const float* gamma, const float* beta,
+                               float* running_mean, float* running_var, float* save_mean, float* save_invstd, int M, int C, float eps,
+                               float momentum, int relu, const float* partial, int nblk, void* ws, size_t ws_bytes, void* stream) {
+  MI355_ARG(ws && ws_bytes >= (size_t)2 * C * 4 && partial && nblk >= 1, "bn_fwd_train_partial: nblk=%d, workspace of 2*C floats", nblk);
+  hipStream_t s = (hipStream_t)stream;
+  float* scale = (float*)ws;
+  float* shift = scale + C;
+  MI355_TRY(launch_bn_finalize(partial, nullptr, nblk, M, C, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale,
+                               shift, eps, momentum, s));
+  return launch_bn_apply(dtype, x, scale, shift, residual, nullptr, nullptr, nullptr, out, M, C, relu, s);
+}
+
+int mi355_bn_fwd_eval(int dtype, const void* x, const void* residual, void* out, const float* gamma,
+                      const float* beta, const float* running_mean, const float* running_var, int M, int C, float eps,
+                      int relu, void* ws, size_t ws_bytes, void* stream) {
+  MI355_ARG(ws && ws_bytes >= (size_t)2 * C * 4, "bn_eval: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* scale = (float*)ws;
+  float* shift = scale + C;
+  MI355_TRY(launch_bn_eval_coeffs(gamma, beta, running_mean, running_var, scale, shift, C, eps, s));
+  return launch_bn_apply(dtype, x, scale, shift, residual, nullptr, nullptr, nullptr, out, M, C, relu, s);
+}
+
+int mi355_bn_bwd(int dtype, const void* dout, const void* out, const void* x, const float* gamma,
+                 const float* save_mean, const float* save_invstd, void* dx, void* dz_out, float* dgamma,
+                 float* dbeta, float beta_acc, int M, int C, int relu, void* ws, size_t ws_bytes, void* stream) {
+  MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = (float*)ws;
+  float* coef = partial + (size_t)bn_max_blocks() * 2 * C;
+  int nblk = 0;
+  const void* mask = relu ? out : nullptr;
+  const float slope = relu == 2 ? 0.01f : 0.f;  // activation code 2: leaky ReLU
+  MI355_TRY(launch_bn_bwd_reduce(dtype, dout, mask, x, save_mean, save_invstd, dz_out, partial, &nblk, M, C, s, nullptr, slope));
+  MI355_TRY(launch_bn_bwd_finalize(partial, nblk, M, C, gamma, save_invstd, dgamma, dbeta, beta_acc, coef, s));
+  return launch_bn_bwd_apply(dtype, dout, mask, x, save_mean, save_invstd, coef, dx, M, C, s, nullptr, slope);
+}
+
+}  // extern "C"

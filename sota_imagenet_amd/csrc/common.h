@@ -318,8 +318,7 @@ int launch_eca_residual_bwd(int dtype, const void* dout, const void* out, const 
 // fp8 step: scale[i] = amax[i] > 0 ? 448 / (headroom * amax[i]) : scale[i];  amax[i] = 0   (delayed per-tensor scaling)
 int launch_fp8_scale_update(float* scale, unsigned* amax, int n, float headroom, hipStream_t s);
 
-// pooling / head / loss / optimizer
-int launch_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, hipStream_t s);
+// pooling / head
 // p = maxpool3x3/2(relu(y*scale+shift)) + argmax + the ReLU bit mask of the (never stored) full-resolution activation
 int launch_bn_relu_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* p, uint8_t* idx,
                            uint8_t* bits, int N, int H, int W, int C, hipStream_t s);
@@ -328,74 +327,6 @@ int launch_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, 
 int launch_gap_fwd(int dtype, const void* x, float* pooled, int N, int HW, int C, hipStream_t s);
 int launch_fc(const float* x, const float* w, float* out, int M, int N, int K, hipStream_t s);  // fc.hip: out = x * w^T, fp32
 int launch_gap_bwd(int dtype, const float* dpooled, void* dx, int N, int HW, int C, hipStream_t s);
-int launch_ce(const float* logits, const float* target, float smoothing, float grad_scale, float* loss,
-              float* row_loss, float* dlogits, int N, int C, hipStream_t s);
-int launch_sgd(float* p, const float* g, float* m, size_t n, float lr, float mom, float wd, float gscale,
-               hipStream_t s, float* ema = nullptr, float ema_decay = 0.f);
-// optim.hip: fused Adam (decoupled = 0) / AdamW (decoupled = 1) step, + the parameter average when ema != nullptr
-int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps, float step_size,
-                float bc2_sqrt, double lr, double wd, int decoupled, float gscale, hipStream_t s, float* ema = nullptr,
-                float ema_decay = 0.f);
-// optim.hip: fused MADGRAD step (lamb = (lr + eps) * sqrt(k + 1) is formed here in double), + the parameter average when ema != nullptr
-int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* x0, size_t n, double lr, double momentum, double wd,
-                   double eps, int k, float gscale, hipStream_t st, float* ema = nullptr, float ema_decay = 0.f);
-// optim.hip: the three AdaiS stages; adais_partials(n) = the doubles launch_adais_moments writes for a range of n elements
-size_t adais_partials(size_t n);
-int launch_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float gscale, double* partial, hipStream_t st);
-int launch_adais_mean(const double* partial, size_t count, size_t param_size, float* mean, hipStream_t st);
-int launch_adais_step(float* p, const float* g, float* m, const float* v, float* b1prod, const float* mean, size_t n, double lr, double beta0,
-                      double beta2, double eps, double wd, int step, float gscale, hipStream_t st, float* ema = nullptr,
-                      float ema_decay = 0.f);
-// optim_lw.hip: the layer-wise optimizers' three stages over a work-item table (items / tensors: 16-byte records, see there)
-size_t lw_item_elems();
-int launch_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, double* partial, hipStream_t st);
-int launch_lw_coef(int rule, int flags, const double* partial, size_t n_partial, const void* tensors, size_t n_tensors, void* v, float* coef,
-                   double* sums, double beta1, double beta2, double eps, double lr, double wd, double mean, hipStream_t st);
-int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
-                     int n_tensors, double lr, int soft_wd, double wd_eps, float gscale, float ema_decay, hipStream_t st);
-// the unit-wise form (unitwise_norm=True): one statistic, the norm, per slot (optim_items.h: pieces, slots, tensor records)
-int launch_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, double* partial,
-                         hipStream_t st);
-int launch_lw_unit_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, double* sums,
-                        double beta2, double eps, hipStream_t st);
-int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
-                          const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double wd, int soft_wd,
-                          double wd_eps, float gscale, float ema_decay, hipStream_t st);
-// optim_adamp.hip: AdamP's three stages over the same tables plus one record { slot0, n_slots, unit_len, kind } per tensor for the decision
-int launch_adamp_unit_sums(const float* p, const float* g, const float* m, const float* v, size_t n, const void* pieces, size_t n_pieces,
-                           int n_slots, double beta1, double beta2, double eps, int step, int nesterov, float gscale, double* partial,
-                           hipStream_t st);
-int launch_adamp_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, const void* tensors, size_t n_tensors,
-                      float* coef, float* wdf, int* mode, double lr, double wd, double eps, double delta, double wd_ratio, hipStream_t st);
-int launch_adamp_update(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
-                        const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1,
-                        double beta2, double eps, int step, int nesterov, float gscale, float ema_decay, hipStream_t st);
-// optim_sam.hip: the four stages of the SAMOriginal callback over the same work-item table (kind[tensor]: 1 = weight, 0 = other)
-int launch_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
-                     float gscale, double* partial, hipStream_t st);
-int launch_sam_scale(const double* partial, size_t n_partial, double rho, float* out, hipStream_t st);
-int launch_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
-                       const float* out, float eta, float gscale, hipStream_t st);
-int launch_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, hipStream_t st);
-// optim_sam_lw.hip: the stages of the SAM callback, one norm pair per slot (a whole tensor, or one output unit of it); tables: see there
-int launch_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, int n_tensors, float gscale, double* partial,
-                        hipStream_t st);
-int launch_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* pieces, size_t n_pieces, int n_slots, float gscale,
-                          double* partial, int threads_per_piece, hipStream_t st);
-int launch_sam_lw_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms, hipStream_t st);
-int launch_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
-                          const float* coef, size_t n_slots, double rho, float gscale, hipStream_t st);
-// init_ortho.hip: Gram-Schmidt, in place, over a table of matrices { off, rows, chans, taps } of one flat array (the OrthoInitClb callback)
-int launch_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, hipStream_t st);
-// optim_hist.hip: per-tensor histograms of |x| over the bins of absbin.h and the bin counts of the twice-subsampled set (the GradDistributionTB callback)
-int launch_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, hipStream_t st);
-int launch_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, hipStream_t st);
-// optim_wdist.hip: per-tensor histograms over TensorBoard's default bins and the items' min / max / sums (the WeightDistributionTB callback)
-int launch_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges,
-                      uint32_t* hist, double* partial, hipStream_t st);
-// weight_norm.hip: every row of a table of items { first, row_len, n_rows } of one flat array centred and scaled to unit norm (the WeightNorm callback)
-int launch_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, hipStream_t st);
-int wnorm_wave_row_max();
 int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int W, hipStream_t s);
 // logits[n][o] = tmp[n*ld + o] + bias[o]
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s);

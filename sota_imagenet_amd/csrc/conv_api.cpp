@@ -1,4 +1,5 @@
-// conv_api.cpp — geometry builders and the per-op C-ABI entry points declared in include/mi355rn.h.
+// conv_api.cpp — the library's process-wide state (error string, knobs, CU count), the conv geometry builders, and the C-ABI entry points
+// of the convolutions and the stem (include/mi355rn.h).  Every other op's entry point is in the file that implements it.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -428,11 +429,6 @@ size_t mi355_stem_workspace_bytes(int dtype, int N, int H, int W) {
   return align_up((size_t)64 * 4 * 64 * dtype_size(dtype), 256) + (size_t)splits * 64 * 4 * 64 * 4;
 }
 
-int mi355_stem_ingest(int dtype, const float* x_nchw, void* xpad, int N, int H, int W, void* stream) {
-  MI355_ARG(x_nchw && xpad && H % 2 == 0 && W % 2 == 0, "stem_ingest: bad arguments");
-  return launch_stem_ingest(dtype, x_nchw, xpad, N, H, W, (hipStream_t)stream);
-}
-
 int mi355_stem_fwd(int dtype, const void* xpad, const float* w_krsc, void* y, int N, int H, int W, void* ws,
                    size_t ws_bytes, void* stream) {
   const size_t pk = (size_t)64 * 4 * 64 * dtype_size(dtype);
@@ -456,247 +452,5 @@ int mi355_stem_wgrad(int dtype, const void* dy, const void* xpad, float* dw, flo
   MI355_TRY(launch_wgrad(dtype, a, splits, s));
   return launch_stem_unpack((float*)ws, splits, dw, beta, s);
 }
-
-size_t mi355_bn_workspace_bytes(int C) { return ((size_t)bn_max_blocks() * 2 * C + 8 * (size_t)C) * 4; }
-
-int mi355_bn_fwd_train(int dtype, const void* x, const void* residual, void* out, const float* gamma,
-                       const float* beta, float* running_mean, float* running_var, float* save_mean,
-                       float* save_invstd, int M, int C, float eps, float momentum, int relu, void* ws,
-                       size_t ws_bytes, void* stream) {
-  MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* partial = (float*)ws;
-  float* scale = partial + (size_t)bn_max_blocks() * 2 * C;
-  float* shift = scale + C;
-  float* pivot = shift + C;
-  int nblk = 0;
-  MI355_TRY(launch_bn_stats(dtype, x, partial, pivot, &nblk, M, C, s));
-  MI355_TRY(launch_bn_finalize(partial, pivot, nblk, M, C, gamma, beta, running_mean, running_var, save_mean, save_invstd,
-                               scale, shift, eps, momentum, s));
-  return launch_bn_apply(dtype, x, scale, shift, residual, nullptr, nullptr, nullptr, out, M, C, relu, s);
-}
-
-int mi355_bn_fwd_train_partial(int dtype, const void* x, const void* residual, void* out, const float* gamma, const float* beta,
-                               float* running_mean, float* running_var, float* save_mean, float* save_invstd, int M, int C, float eps,
-                               float momentum, int relu, const float* partial, int nblk, void* ws, size_t ws_bytes, void* stream) {
-  MI355_ARG(ws && ws_bytes >= (size_t)2 * C * 4 && partial && nblk >= 1, "bn_fwd_train_partial: nblk=%d, workspace of 2*C floats", nblk);
-  hipStream_t s = (hipStream_t)stream;
-  float* scale = (float*)ws;
-  float* shift = scale + C;
-  MI355_TRY(launch_bn_finalize(partial, nullptr, nblk, M, C, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale,
-                               shift, eps, momentum, s));
-  return launch_bn_apply(dtype, x, scale, shift, residual, nullptr, nullptr, nullptr, out, M, C, relu, s);
-}
-
-int mi355_bn_fwd_eval(int dtype, const void* x, const void* residual, void* out, const float* gamma,
-                      const float* beta, const float* running_mean, const float* running_var, int M, int C, float eps,
-                      int relu, void* ws, size_t ws_bytes, void* stream) {
-  MI355_ARG(ws && ws_bytes >= (size_t)2 * C * 4, "bn_eval: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* scale = (float*)ws;
-  float* shift = scale + C;
-  MI355_TRY(launch_bn_eval_coeffs(gamma, beta, running_mean, running_var, scale, shift, C, eps, s));
-  return launch_bn_apply(dtype, x, scale, shift, residual, nullptr, nullptr, nullptr, out, M, C, relu, s);
-}
-
-int mi355_bn_bwd(int dtype, const void* dout, const void* out, const void* x, const float* gamma,
-                 const float* save_mean, const float* save_invstd, void* dx, void* dz_out, float* dgamma,
-                 float* dbeta, float beta_acc, int M, int C, int relu, void* ws, size_t ws_bytes, void* stream) {
-  MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* partial = (float*)ws;
-  float* coef = partial + (size_t)bn_max_blocks() * 2 * C;
-  int nblk = 0;
-  const void* mask = relu ? out : nullptr;
-  const float slope = relu == 2 ? 0.01f : 0.f;  // activation code 2: leaky ReLU
-  MI355_TRY(launch_bn_bwd_reduce(dtype, dout, mask, x, save_mean, save_invstd, dz_out, partial, &nblk, M, C, s, nullptr, slope));
-  MI355_TRY(launch_bn_bwd_finalize(partial, nblk, M, C, gamma, save_invstd, dgamma, dbeta, beta_acc, coef, s));
-  return launch_bn_bwd_apply(dtype, dout, mask, x, save_mean, save_invstd, coef, dx, M, C, s, nullptr, slope);
-}
-
-int mi355_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
-  return launch_maxpool_fwd(dtype, x, y, idx, N, H, W, C, (hipStream_t)stream);
-}
-int mi355_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C,
-                      void* stream) {
-  return launch_maxpool_bwd(dtype, dy, idx, dx, N, H, W, C, (hipStream_t)stream);
-}
-int mi355_gap_fwd(int dtype, const void* x, float* pooled, int N, int HW, int C, void* stream) {
-  return launch_gap_fwd(dtype, x, pooled, N, HW, C, (hipStream_t)stream);
-}
-int mi355_gap_bwd(int dtype, const float* dpooled, void* dx, int N, int HW, int C, void* stream) {
-  return launch_gap_bwd(dtype, dpooled, dx, N, HW, C, (hipStream_t)stream);
-}
-int mi355_ce_loss(const float* logits, const float* target, float smoothing, float grad_scale, float* loss,
-                  float* row_loss, float* dlogits, int N, int C, void* stream) {
-  return launch_ce(logits, target, smoothing, grad_scale, loss, row_loss, dlogits, N, C, (hipStream_t)stream);
-}
-int mi355_sgd_step(float* p, const float* g, float* m, size_t n, float lr, float momentum, float weight_decay,
-                   float grad_scale, void* stream) {
-  return launch_sgd(p, g, m, n, lr, momentum, weight_decay, grad_scale, (hipStream_t)stream);
-}
-int mi355_sgd_step_ema(float* p, const float* g, float* m, float* ema, size_t n, float lr, float momentum, float weight_decay,
-                       float grad_scale, float ema_decay, void* stream) {
-  MI355_ARG(ema, "sgd_step_ema: null ema");
-  return launch_sgd(p, g, m, n, lr, momentum, weight_decay, grad_scale, (hipStream_t)stream, ema, ema_decay);
-}
-int mi355_adam_step(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps,
-                    float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled, float grad_scale,
-                    void* stream) {
-  return launch_adam(p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lr, weight_decay, decoupled, grad_scale,
-                     (hipStream_t)stream);
-}
-int mi355_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, double beta1, double beta2,
-                        float eps, float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled,
-                        float grad_scale, float ema_decay, void* stream) {
-  MI355_ARG(ema, "adam_step_ema: null ema");
-  return launch_adam(p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lr, weight_decay, decoupled, grad_scale,
-                     (hipStream_t)stream, ema, ema_decay);
-}
-int mi355_madgrad_step(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, size_t n, double lr, double momentum,
-                       double weight_decay, double eps, int k, float grad_scale, void* stream) {
-  return launch_madgrad(p, g, grad_sum_sq, s, x0, n, lr, momentum, weight_decay, eps, k, grad_scale, (hipStream_t)stream);
-}
-int mi355_madgrad_step_ema(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, float* ema, size_t n, double lr,
-                           double momentum, double weight_decay, double eps, int k, float grad_scale, float ema_decay, void* stream) {
-  MI355_ARG(ema, "madgrad_step_ema: null ema");
-  return launch_madgrad(p, g, grad_sum_sq, s, x0, n, lr, momentum, weight_decay, eps, k, grad_scale, (hipStream_t)stream, ema, ema_decay);
-}
-size_t mi355_adais_workspace_bytes(size_t n) { return adais_partials(n) * sizeof(double); }
-int mi355_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float grad_scale, void* workspace, void* stream) {
-  return launch_adais_moments(g, v, n, beta2, step, grad_scale, (double*)workspace, (hipStream_t)stream);
-}
-int mi355_adais_mean(const void* workspace, size_t workspace_bytes, size_t param_size, float* mean, void* stream) {
-  MI355_ARG(workspace_bytes % sizeof(double) == 0, "adais_mean: workspace_bytes=%zu is not a whole number of partial sums", workspace_bytes);
-  return launch_adais_mean((const double*)workspace, workspace_bytes / sizeof(double), param_size, mean, (hipStream_t)stream);
-}
-int mi355_adais_step(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, size_t n, double lr,
-                     double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale, void* stream) {
-  return launch_adais_step(p, g, m, v, beta1_prod, mean, n, lr, beta0, beta2, eps, weight_decay, step, grad_scale, (hipStream_t)stream);
-}
-int mi355_adais_step_ema(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, float* ema, size_t n,
-                         double lr, double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale,
-                         float ema_decay, void* stream) {
-  MI355_ARG(ema, "adais_step_ema: null ema");
-  return launch_adais_step(p, g, m, v, beta1_prod, mean, n, lr, beta0, beta2, eps, weight_decay, step, grad_scale, (hipStream_t)stream, ema,
-                           ema_decay);
-}
-
-size_t mi355_lw_item_elems(void) { return lw_item_elems(); }
-int mi355_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, void* partial, void* stream) {
-  return launch_lw_sumsq(src, n, items, n_items, n_tensors, scale, (double*)partial, (hipStream_t)stream);
-}
-int mi355_lw_coef(int rule, int flags, const void* partial, size_t n_partial, const void* tensors, size_t n_tensors, void* v, float* coef,
-                  void* sums, double beta1, double beta2, double eps, double lr, double weight_decay, double mean, void* stream) {
-  return launch_lw_coef(rule, flags, (const double*)partial, n_partial, tensors, n_tensors, v, coef, (double*)sums, beta1, beta2, eps, lr,
-                        weight_decay, mean, (hipStream_t)stream);
-}
-int mi355_lw_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const float* coef, int n_tensors,
-                    double lr, int soft_wd, double wd_eps, float grad_scale, void* stream) {
-  return launch_lw_update(rule, p, g, m, nullptr, n, items, n_items, coef, n_tensors, lr, soft_wd, wd_eps, grad_scale, 0.f, (hipStream_t)stream);
-}
-int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
-                        int n_tensors, double lr, int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream) {
-  MI355_ARG(ema, "lw_update_ema: null ema");
-  return launch_lw_update(rule, p, g, m, ema, n, items, n_items, coef, n_tensors, lr, soft_wd, wd_eps, grad_scale, ema_decay,
-                          (hipStream_t)stream);
-}
-
-int mi355_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, void* partial, void* stream) {
-  return launch_lw_unit_sumsq(src, n, pieces, n_pieces, n_slots, scale, (double*)partial, (hipStream_t)stream);
-}
-int mi355_lw_unit_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, void* sums, double beta2,
-                       double eps, void* stream) {
-  return launch_lw_unit_coef((const double*)partial, n_partial, slots, n_slots, v, den, (double*)sums, beta2, eps, (hipStream_t)stream);
-}
-int mi355_lw_unit_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const void* tensors,
-                         int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay, int soft_wd, double wd_eps,
-                         float grad_scale, void* stream) {
-  return launch_lw_unit_update(rule, p, g, m, nullptr, n, items, n_items, tensors, n_tensors, den, n_slots, beta1, lr, weight_decay, soft_wd,
-                               wd_eps, grad_scale, 0.f, (hipStream_t)stream);
-}
-int mi355_lw_unit_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
-                             const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay,
-                             int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream) {
-  MI355_ARG(ema, "lw_unit_update_ema: null ema");
-  return launch_lw_unit_update(rule, p, g, m, ema, n, items, n_items, tensors, n_tensors, den, n_slots, beta1, lr, weight_decay, soft_wd, wd_eps,
-                               grad_scale, ema_decay, (hipStream_t)stream);
-}
-
-int mi355_adamp_unit_sums(const float* p, const float* g, const float* m, const float* v, size_t n, const void* pieces, size_t n_pieces,
-                          int n_slots, double beta1, double beta2, double eps, int step, int nesterov, float grad_scale, void* partial,
-                          void* stream) {
-  return launch_adamp_unit_sums(p, g, m, v, n, pieces, n_pieces, n_slots, beta1, beta2, eps, step, nesterov, grad_scale, (double*)partial,
-                                (hipStream_t)stream);
-}
-int mi355_adamp_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, const void* decide, size_t n_tensors, float* coef,
-                     float* wdf, int* mode, double lr, double weight_decay, double eps, double delta, double wd_ratio, void* stream) {
-  return launch_adamp_coef((const double*)partial, n_partial, slots, n_slots, decide, n_tensors, coef, wdf, mode, lr, weight_decay, eps, delta,
-                           wd_ratio, (hipStream_t)stream);
-}
-int mi355_adamp_update(float* p, const float* g, float* m, float* v, size_t n, const void* items, size_t n_items, const void* tensors,
-                       int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1, double beta2, double eps,
-                       int step, int nesterov, float grad_scale, void* stream) {
-  return launch_adamp_update(p, g, m, v, nullptr, n, items, n_items, tensors, n_tensors, coef, n_slots, wdf, lr, beta1, beta2, eps, step,
-                             nesterov, grad_scale, 0.f, (hipStream_t)stream);
-}
-int mi355_adamp_update_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
-                           const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1,
-                           double beta2, double eps, int step, int nesterov, float grad_scale, float ema_decay, void* stream) {
-  MI355_ARG(ema, "adamp_update_ema: null ema");
-  return launch_adamp_update(p, g, m, v, ema, n, items, n_items, tensors, n_tensors, coef, n_slots, wdf, lr, beta1, beta2, eps, step, nesterov,
-                             grad_scale, ema_decay, (hipStream_t)stream);
-}
-
-int mi355_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
-                    float grad_scale, void* partial, void* stream) {
-  return launch_sam_sumsq(p, g, n, items, n_items, kind, n_tensors, eta, grad_scale, (double*)partial, (hipStream_t)stream);
-}
-int mi355_sam_scale(const void* partial, size_t n_partial, double rho, float* out, void* stream) {
-  return launch_sam_scale((const double*)partial, n_partial, rho, out, (hipStream_t)stream);
-}
-int mi355_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
-                      const float* out, float eta, float grad_scale, void* stream) {
-  return launch_sam_perturb(p, g, eps, n, items, n_items, kind, n_tensors, out, eta, grad_scale, (hipStream_t)stream);
-}
-int mi355_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, void* stream) {
-  return launch_sam_restore(p, eps, n, items, n_items, n_tensors, (hipStream_t)stream);
-}
-
-int mi355_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, int n_tensors, float grad_scale, void* partial,
-                       void* stream) {
-  return launch_sam_lw_sumsq(p, g, n, items, n_items, n_tensors, grad_scale, (double*)partial, (hipStream_t)stream);
-}
-int mi355_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* pieces, size_t n_pieces, int n_slots, float grad_scale,
-                         void* partial, int threads_per_piece, void* stream) {
-  return launch_sam_unit_sumsq(p, g, n, pieces, n_pieces, n_slots, grad_scale, (double*)partial, threads_per_piece, (hipStream_t)stream);
-}
-int mi355_sam_lw_coef(const void* partial, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms, void* stream) {
-  return launch_sam_lw_coef((const double*)partial, n_partial, slots, n_slots, coef, norms, (hipStream_t)stream);
-}
-int mi355_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
-                         const float* coef, size_t n_slots, double rho, float grad_scale, void* stream) {
-  return launch_sam_lw_perturb(p, g, eps, n, items, n_items, tensors, n_tensors, coef, n_slots, rho, grad_scale, (hipStream_t)stream);
-}
-
-int mi355_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, void* stream) {
-  return launch_ortho_init(w, n, mats, n_mats, gain, status, (hipStream_t)stream);
-}
-
-int mi355_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, void* stream) {
-  return launch_absbin_hist(src, n, items, n_items, n_tensors, hist, (hipStream_t)stream);
-}
-int mi355_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, void* stream) {
-  return launch_subsample_counts(hist, rep, n_tensors, subsample, counts, (hipStream_t)stream);
-}
-int mi355_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges,
-                     uint32_t* hist, double* partial, void* stream) {
-  return launch_tbbin_hist(src, n, items, n_items, n_tensors, edges, n_edges, hist, partial, (hipStream_t)stream);
-}
-
-int mi355_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, void* stream) {
-  return launch_weight_norm_rows(w, n, items, n_items, status, (hipStream_t)stream);
-}
-int mi355_wnorm_wave_row_max(void) { return wnorm_wave_row_max(); }
 
 }  // extern "C"

@@ -191,7 +191,8 @@ __global__ __launch_bounds__(kT) void ortho_init_kernel(float* w, size_t n, cons
 
 }  // namespace
 
-int launch_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, hipStream_t st) {
+extern "C" int mi355_ortho_init(float* w, size_t n, const void* mats, size_t n_mats, float gain, int* status, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(w && mats && status, "ortho_init: null pointer");
   MI355_ARG((uintptr_t)w % 4 == 0 && (uintptr_t)mats % 8 == 0 && (uintptr_t)status % 4 == 0,
             "ortho_init: misaligned pointer (8 bytes for the records, 4 for the array and status[])");

@@ -613,7 +613,8 @@ int launch_stem_ingest(int dtype, const float* x, void* xpad, int N, int H, int 
   });
 }
 
-int launch_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, hipStream_t s) {
+extern "C" int mi355_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   MI355_ARG(H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "maxpool: H=%d W=%d C=%d", H, W, C);
   const int Ho = H / 2, Wo = W / 2;
   return with_elem(dtype, "maxpool_fwd", [&](auto e) -> int {
@@ -690,8 +691,9 @@ int launch_gap_bwd(int dtype, const float* dpooled, void* dx, int N, int HW, int
   });
 }
 
-int launch_ce(const float* logits, const float* target, float smoothing, float grad_scale, float* loss,
-              float* row_loss, float* dlogits, int N, int C, hipStream_t s) {
+extern "C" int mi355_ce_loss(const float* logits, const float* target, float smoothing, float grad_scale, float* loss,
+                             float* row_loss, float* dlogits, int N, int C, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   MI355_ARG(logits && target && loss && row_loss, "ce: null pointer");
   hipLaunchKernelGGL(ce_row_kernel, dim3(N), dim3(256), 0, s, logits, target, smoothing, grad_scale, row_loss, dlogits,
                      N, C);
@@ -701,8 +703,8 @@ int launch_ce(const float* logits, const float* target, float smoothing, float g
   return 0;
 }
 
-int launch_sgd(float* p, const float* g, float* m, size_t n, float lr, float mom, float wd, float gscale,
-               hipStream_t s, float* ema, float ema_decay) {
+static int launch_sgd(float* p, const float* g, float* m, size_t n, float lr, float mom, float wd, float gscale,
+                      hipStream_t s, float* ema = nullptr, float ema_decay = 0.f) {
   MI355_ARG(p && g && m, "sgd: null pointer");
   MI355_ARG(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)ema % 16 == 0),
             "sgd: pointers must be 16-byte aligned");
@@ -713,6 +715,15 @@ int launch_sgd(float* p, const float* g, float* m, size_t n, float lr, float mom
     MI355_LAUNCH_CHECK();
     return 0;
   });
+}
+extern "C" int mi355_sgd_step(float* p, const float* g, float* m, size_t n, float lr, float momentum, float weight_decay,
+                              float grad_scale, void* stream) {
+  return launch_sgd(p, g, m, n, lr, momentum, weight_decay, grad_scale, (hipStream_t)stream);
+}
+extern "C" int mi355_sgd_step_ema(float* p, const float* g, float* m, float* ema, size_t n, float lr, float momentum, float weight_decay,
+                                  float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "sgd_step_ema: null ema");
+  return launch_sgd(p, g, m, n, lr, momentum, weight_decay, grad_scale, (hipStream_t)stream, ema, ema_decay);
 }
 
 int launch_bias_slice(const float* tmp, int ld, const float* bias, float* out, int N, int O, hipStream_t s) {
@@ -732,3 +743,24 @@ int launch_pad_dlogits(const float* src, float* dst, int ld, float* dbias, float
 }
 
 }  // namespace mi355
+
+using namespace mi355;
+
+extern "C" {
+
+int mi355_stem_ingest(int dtype, const float* x_nchw, void* xpad, int N, int H, int W, void* stream) {
+  MI355_ARG(x_nchw && xpad && H % 2 == 0 && W % 2 == 0, "stem_ingest: bad arguments");
+  return launch_stem_ingest(dtype, x_nchw, xpad, N, H, W, (hipStream_t)stream);
+}
+int mi355_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C,
+                      void* stream) {
+  return launch_maxpool_bwd(dtype, dy, idx, dx, N, H, W, C, (hipStream_t)stream);
+}
+int mi355_gap_fwd(int dtype, const void* x, float* pooled, int N, int HW, int C, void* stream) {
+  return launch_gap_fwd(dtype, x, pooled, N, HW, C, (hipStream_t)stream);
+}
+int mi355_gap_bwd(int dtype, const float* dpooled, void* dx, int N, int HW, int C, void* stream) {
+  return launch_gap_bwd(dtype, dpooled, dx, N, HW, C, (hipStream_t)stream);
+}
+
+}  // extern "C"

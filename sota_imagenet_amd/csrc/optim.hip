@@ -69,8 +69,10 @@ int adam_grid(size_t n4) {
 
 }  // namespace
 
-int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps, float step_size,
-                float bc2_sqrt, double lr, double wd, int decoupled, float gscale, hipStream_t s, float* ema, float ema_decay) {
+// decoupled = 0: Adam, 1: AdamW; + the parameter average when ema != nullptr
+static int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps, float step_size,
+                       float bc2_sqrt, double lr, double wd, int decoupled, float gscale, hipStream_t s, float* ema = nullptr,
+                       float ema_decay = 0.f) {
   MI355_ARG(p && g && m && v, "adam: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema), "adam: pointers must be 16-byte aligned");
   MI355_ARG(beta1 >= 0.0 && beta1 < 1.0, "adam: beta1=%g outside [0, 1)", beta1);
@@ -101,6 +103,19 @@ int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double b
       return 0;
     });
   });
+}
+extern "C" int mi355_adam_step(float* p, const float* g, float* m, float* v, size_t n, double beta1, double beta2, float eps,
+                               float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled, float grad_scale,
+                               void* stream) {
+  return launch_adam(p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lr, weight_decay, decoupled, grad_scale,
+                     (hipStream_t)stream);
+}
+extern "C" int mi355_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, double beta1, double beta2,
+                                   float eps, float step_size, float bc2_sqrt, double lr, double weight_decay, int decoupled,
+                                   float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "adam_step_ema: null ema");
+  return launch_adam(p, g, m, v, n, beta1, beta2, eps, step_size, bc2_sqrt, lr, weight_decay, decoupled, grad_scale,
+                     (hipStream_t)stream, ema, ema_decay);
 }
 
 // ---- MADGRAD: src.optimizers.MADGRAD.step of the reference (sota_imagenet/optimizers.py:726-767), in its operation order --------------------
@@ -141,8 +156,8 @@ __global__ __launch_bounds__(256) void madgrad_kernel(float* __restrict__ p, con
 
 }  // namespace
 
-int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* x0, size_t n, double lr, double momentum, double wd,
-                   double eps, int k, float gscale, hipStream_t st, float* ema, float ema_decay) {
+static int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* x0, size_t n, double lr, double momentum, double wd,
+                          double eps, int k, float gscale, hipStream_t st, float* ema = nullptr, float ema_decay = 0.f) {
   MI355_ARG(p && g && gss && s && x0, "madgrad: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(gss) && aligned16(s) && aligned16(x0) && aligned16(ema),
             "madgrad: pointers must be 16-byte aligned");
@@ -169,6 +184,16 @@ int launch_madgrad(float* p, const float* g, float* gss, float* s, const float* 
     MI355_LAUNCH_CHECK();
     return 0;
   });
+}
+extern "C" int mi355_madgrad_step(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, size_t n, double lr, double momentum,
+                                  double weight_decay, double eps, int k, float grad_scale, void* stream) {
+  return launch_madgrad(p, g, grad_sum_sq, s, x0, n, lr, momentum, weight_decay, eps, k, grad_scale, (hipStream_t)stream);
+}
+extern "C" int mi355_madgrad_step_ema(float* p, const float* g, float* grad_sum_sq, float* s, const float* x0, float* ema, size_t n, double lr,
+                                      double momentum, double weight_decay, double eps, int k, float grad_scale, float ema_decay,
+                                      void* stream) {
+  MI355_ARG(ema, "madgrad_step_ema: null ema");
+  return launch_madgrad(p, g, grad_sum_sq, s, x0, n, lr, momentum, weight_decay, eps, k, grad_scale, (hipStream_t)stream, ema, ema_decay);
 }
 
 // ---- AdaiS: src.optimizers.AdaiS.step of the reference (sota_imagenet/optimizers.py:569-639) as three device stages on one stream ----------------
@@ -248,9 +273,12 @@ int adais_bc2(const char* who, double beta2, int step, float* bc2) {
 
 }  // namespace
 
-size_t adais_partials(size_t n) { return (size_t)adam_grid(n / 4); }
+// the doubles mi355_adais_moments writes for a range of n elements: one per workgroup
+extern "C" size_t mi355_adais_workspace_bytes(size_t n) { return (size_t)adam_grid(n / 4) * sizeof(double); }
 
-int launch_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float gscale, double* partial, hipStream_t st) {
+extern "C" int mi355_adais_moments(const float* g, float* v, size_t n, double beta2, int step, float gscale, void* workspace, void* stream) {
+  double* partial = (double*)workspace;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(g && v && partial, "adais_moments: null pointer");
   MI355_ARG(aligned16(g) && aligned16(v), "adais_moments: g and v must be 16-byte aligned");
   MI355_ARG((uintptr_t)partial % 8 == 0, "adais_moments: the workspace must be 8-byte aligned");
@@ -264,7 +292,11 @@ int launch_adais_moments(const float* g, float* v, size_t n, double beta2, int s
   return 0;
 }
 
-int launch_adais_mean(const double* partial, size_t count, size_t param_size, float* mean, hipStream_t st) {
+extern "C" int mi355_adais_mean(const void* workspace, size_t workspace_bytes, size_t param_size, float* mean, void* stream) {
+  const double* partial = (const double*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  MI355_ARG(workspace_bytes % sizeof(double) == 0, "adais_mean: workspace_bytes=%zu is not a whole number of partial sums", workspace_bytes);
+  const size_t count = workspace_bytes / sizeof(double);
   MI355_ARG(partial && mean, "adais_mean: null pointer");
   MI355_ARG((uintptr_t)partial % 8 == 0 && (uintptr_t)mean % 4 == 0, "adais_mean: misaligned pointer");
   MI355_ARG(count >= 1 && param_size >= 1, "adais_mean: count=%zu and param_size=%zu must be >= 1", count, param_size);
@@ -273,8 +305,9 @@ int launch_adais_mean(const double* partial, size_t count, size_t param_size, fl
   return 0;
 }
 
-int launch_adais_step(float* p, const float* g, float* m, const float* v, float* b1prod, const float* mean, size_t n, double lr, double beta0,
-                      double beta2, double eps, double wd, int step, float gscale, hipStream_t st, float* ema, float ema_decay) {
+static int launch_adais_step(float* p, const float* g, float* m, const float* v, float* b1prod, const float* mean, size_t n, double lr,
+                             double beta0, double beta2, double eps, double wd, int step, float gscale, hipStream_t st, float* ema = nullptr,
+                             float ema_decay = 0.f) {
   MI355_ARG(p && g && m && v && b1prod && mean, "adais_step: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(b1prod) && aligned16(ema),
             "adais_step: pointers must be 16-byte aligned");
@@ -301,6 +334,17 @@ int launch_adais_step(float* p, const float* g, float* m, const float* v, float*
     MI355_LAUNCH_CHECK();
     return 0;
   });
+}
+extern "C" int mi355_adais_step(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, size_t n, double lr,
+                                double beta0, double beta2, double eps, double weight_decay, int step, float grad_scale, void* stream) {
+  return launch_adais_step(p, g, m, v, beta1_prod, mean, n, lr, beta0, beta2, eps, weight_decay, step, grad_scale, (hipStream_t)stream);
+}
+extern "C" int mi355_adais_step_ema(float* p, const float* g, float* m, const float* v, float* beta1_prod, const float* mean, float* ema,
+                                    size_t n, double lr, double beta0, double beta2, double eps, double weight_decay, int step,
+                                    float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "adais_step_ema: null ema");
+  return launch_adais_step(p, g, m, v, beta1_prod, mean, n, lr, beta0, beta2, eps, weight_decay, step, grad_scale, (hipStream_t)stream, ema,
+                           ema_decay);
 }
 
 }  // namespace mi355

@@ -213,9 +213,11 @@ bool adamp_args(const char* who, double beta1, double beta2, double eps, double 
 
 }  // namespace
 
-int launch_adamp_unit_sums(const float* p, const float* g, const float* m, const float* v, size_t n, const void* pieces, size_t n_pieces,
-                           int n_slots, double beta1, double beta2, double eps, int step, int nesterov, float gscale, double* partial,
-                           hipStream_t st) {
+extern "C" int mi355_adamp_unit_sums(const float* p, const float* g, const float* m, const float* v, size_t n, const void* pieces,
+                                     size_t n_pieces, int n_slots, double beta1, double beta2, double eps, int step, int nesterov, float gscale,
+                                     void* partial_, void* stream) {
+  double* partial = (double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(p && g && m && v && pieces && partial, "adamp_unit_sums: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(pieces) && (uintptr_t)partial % 8 == 0,
             "adamp_unit_sums: misaligned pointer (16 bytes for the arrays and the table, 8 for partial[])");
@@ -228,8 +230,11 @@ int launch_adamp_unit_sums(const float* p, const float* g, const float* m, const
   return 0;
 }
 
-int launch_adamp_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, const void* tensors, size_t n_tensors,
-                      float* coef, float* wdf, int* mode, double lr, double wd, double eps, double delta, double wd_ratio, hipStream_t st) {
+extern "C" int mi355_adamp_coef(const void* partial_, size_t n_partial, const void* slots, size_t n_slots, const void* tensors, size_t n_tensors,
+                                float* coef, float* wdf, int* mode, double lr, double wd, double eps, double delta, double wd_ratio,
+                                void* stream) {
+  const double* partial = (const double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(partial && slots && tensors && coef && wdf && mode, "adamp_coef: null pointer");
   MI355_ARG((uintptr_t)partial % 8 == 0 && (uintptr_t)slots % 8 == 0 && aligned16(tensors) && (uintptr_t)coef % 8 == 0 && (uintptr_t)wdf % 4 == 0 &&
                 (uintptr_t)mode % 4 == 0,
@@ -248,9 +253,9 @@ int launch_adamp_coef(const double* partial, size_t n_partial, const void* slots
   return 0;
 }
 
-int launch_adamp_update(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
-                        const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1,
-                        double beta2, double eps, int step, int nesterov, float gscale, float ema_decay, hipStream_t st) {
+static int launch_adamp_update(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
+                               const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1,
+                               double beta2, double eps, int step, int nesterov, float gscale, float ema_decay, hipStream_t st) {
   MI355_ARG(p && g && m && v && items && tensors && coef && wdf, "adamp_update: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema) && aligned16(items) && aligned16(tensors) &&
                 (uintptr_t)coef % 8 == 0 && (uintptr_t)wdf % 4 == 0,
@@ -268,6 +273,20 @@ int launch_adamp_update(float* p, const float* g, float* m, float* v, float* ema
     MI355_LAUNCH_CHECK();
     return 0;
   });
+}
+extern "C" int mi355_adamp_update(float* p, const float* g, float* m, float* v, size_t n, const void* items, size_t n_items, const void* tensors,
+                                  int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr, double beta1, double beta2,
+                                  double eps, int step, int nesterov, float grad_scale, void* stream) {
+  return launch_adamp_update(p, g, m, v, nullptr, n, items, n_items, tensors, n_tensors, coef, n_slots, wdf, lr, beta1, beta2, eps, step,
+                             nesterov, grad_scale, 0.f, (hipStream_t)stream);
+}
+extern "C" int mi355_adamp_update_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, const void* items, size_t n_items,
+                                      const void* tensors, int n_tensors, const float* coef, size_t n_slots, const float* wdf, double lr,
+                                      double beta1, double beta2, double eps, int step, int nesterov, float grad_scale, float ema_decay,
+                                      void* stream) {
+  MI355_ARG(ema, "adamp_update_ema: null ema");
+  return launch_adamp_update(p, g, m, v, ema, n, items, n_items, tensors, n_tensors, coef, n_slots, wdf, lr, beta1, beta2, eps, step, nesterov,
+                             grad_scale, ema_decay, (hipStream_t)stream);
 }
 
 }  // namespace mi355

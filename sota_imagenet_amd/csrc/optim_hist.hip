@@ -95,7 +95,8 @@ __global__ __launch_bounds__(kNB) void subsample_counts_kernel(const unsigned* _
 
 }  // namespace
 
-int launch_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, hipStream_t st) {
+extern "C" int mi355_absbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, uint32_t* hist, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(src && items && hist, "absbin_hist: null pointer");
   MI355_ARG(aligned16(src) && aligned16(items) && aligned16(hist), "absbin_hist: misaligned pointer (16 bytes for the array, the table and hist[])");
   MI355_ARG(n_items >= 1 && n_items <= kLwMaxGrid && n_tensors >= 1, "absbin_hist: n_items=%zu, n_tensors=%d out of range", n_items, n_tensors);
@@ -104,7 +105,8 @@ int launch_absbin_hist(const float* src, size_t n, const void* items, size_t n_i
   return 0;
 }
 
-int launch_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, hipStream_t st) {
+extern "C" int mi355_subsample_counts(const uint32_t* hist, const int32_t* rep, int n_tensors, int subsample, uint64_t* counts, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(hist && rep && counts, "subsample_counts: null pointer");
   MI355_ARG(aligned16(hist) && (uintptr_t)rep % 4 == 0 && (uintptr_t)counts % 8 == 0,
             "subsample_counts: misaligned pointer (16 bytes for hist[], 4 for rep[], 8 for counts[])");

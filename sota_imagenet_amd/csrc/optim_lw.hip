@@ -2,7 +2,7 @@
 // AdamLayerwise :293-397, MyAdai :400-519) on flat fp32 arrays (gfx950).  Each of them needs one statistic PER PARAMETER TENSOR — the sum of
 // squares of its gradient, or of the parameter itself for MyNovograd — and uses it as a per-tensor scalar in the update.  A step is three
 // stages on one stream, nothing read back by the host, over a work-item table the host builds once per plan:
-//   item   = (element offset, length <= lw_item_elems(), tensor index), cut from one tensor's own dense range: never across two tensors,
+//   item   = (element offset, length <= mi355_lw_item_elems(), tensor index), cut from one tensor's own dense range: never across two tensors,
 //            never in padding, the cuts a function of the tensor's numel alone; the items of one tensor are consecutive.
 //   (a) lw_sumsq_kernel, one workgroup per item: x = src * scale in float, x * x summed in double — per thread in element order, then the
 //       fixed LDS tree of optim_sum.h — into partial[item].  No floating-point atomics: partial[] does not depend on scheduling.
@@ -206,9 +206,12 @@ __global__ __launch_bounds__(256) void lw_unit_update_kernel(float* __restrict__
 
 }  // namespace
 
-size_t lw_item_elems() { return kLwItemElems; }
+extern "C" size_t mi355_lw_item_elems(void) { return kLwItemElems; }
 
-int launch_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, double* partial, hipStream_t st) {
+extern "C" int mi355_lw_sumsq(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, float scale, void* partial_,
+                              void* stream) {
+  double* partial = (double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(src && items && partial, "lw_sumsq: null pointer");
   MI355_ARG(aligned16(src) && aligned16(items) && (uintptr_t)partial % 8 == 0, "lw_sumsq: misaligned pointer (16 bytes for the array and the table)");
   MI355_ARG(n_items >= 1 && n_items <= kLwMaxGrid && n_tensors >= 1, "lw_sumsq: n_items=%zu, n_tensors=%d out of range", n_items, n_tensors);
@@ -218,8 +221,11 @@ int launch_lw_sumsq(const float* src, size_t n, const void* items, size_t n_item
   return 0;
 }
 
-int launch_lw_coef(int rule, int flags, const double* partial, size_t n_partial, const void* tensors, size_t n_tensors, void* v, float* coef,
-                   double* sums, double beta1, double beta2, double eps, double lr, double wd, double mean, hipStream_t st) {
+extern "C" int mi355_lw_coef(int rule, int flags, const void* partial_, size_t n_partial, const void* tensors, size_t n_tensors, void* v,
+                             float* coef, void* sums_, double beta1, double beta2, double eps, double lr, double wd, double mean, void* stream) {
+  const double* partial = (const double*)partial_;
+  double* sums = (double*)sums_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(partial && tensors && v && coef && sums, "lw_coef: null pointer");
   MI355_ARG((uintptr_t)partial % 8 == 0 && aligned16(tensors) && aligned16(coef) && (uintptr_t)sums % 8 == 0 &&
                 (uintptr_t)v % (rule == 2 ? 8 : 4) == 0,
@@ -239,8 +245,9 @@ int launch_lw_coef(int rule, int flags, const double* partial, size_t n_partial,
   return 0;
 }
 
-int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items, const float* coef,
-                     int n_tensors, double lr, int soft_wd, double wd_eps, float gscale, float ema_decay, hipStream_t st) {
+static int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                            const float* coef, int n_tensors, double lr, int soft_wd, double wd_eps, float gscale, float ema_decay,
+                            hipStream_t st) {
   MI355_ARG(p && g && m && items && coef, "lw_update: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(ema) && aligned16(items) && aligned16(coef),
             "lw_update: pointers must be 16-byte aligned");
@@ -261,9 +268,22 @@ int launch_lw_update(int rule, float* p, const float* g, float* m, float* ema, s
     });
   });
 }
+extern "C" int mi355_lw_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const float* coef,
+                               int n_tensors, double lr, int soft_wd, double wd_eps, float grad_scale, void* stream) {
+  return launch_lw_update(rule, p, g, m, nullptr, n, items, n_items, coef, n_tensors, lr, soft_wd, wd_eps, grad_scale, 0.f, (hipStream_t)stream);
+}
+extern "C" int mi355_lw_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                                   const float* coef, int n_tensors, double lr, int soft_wd, double wd_eps, float grad_scale, float ema_decay,
+                                   void* stream) {
+  MI355_ARG(ema, "lw_update_ema: null ema");
+  return launch_lw_update(rule, p, g, m, ema, n, items, n_items, coef, n_tensors, lr, soft_wd, wd_eps, grad_scale, ema_decay,
+                          (hipStream_t)stream);
+}
 
-int launch_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, double* partial,
-                         hipStream_t st) {
+extern "C" int mi355_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t n_pieces, int n_slots, float scale, void* partial_,
+                                   void* stream) {
+  double* partial = (double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(src && pieces && partial, "lw_unit_sumsq: null pointer");
   MI355_ARG(aligned16(src) && aligned16(pieces) && (uintptr_t)partial % 8 == 0,
             "lw_unit_sumsq: misaligned pointer (16 bytes for the array and the table, 8 for partial[])");
@@ -275,8 +295,11 @@ int launch_lw_unit_sumsq(const float* src, size_t n, const void* pieces, size_t 
   return 0;
 }
 
-int launch_lw_unit_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, double* sums,
-                        double beta2, double eps, hipStream_t st) {
+extern "C" int mi355_lw_unit_coef(const void* partial_, size_t n_partial, const void* slots, size_t n_slots, float* v, float* den, void* sums_,
+                                  double beta2, double eps, void* stream) {
+  const double* partial = (const double*)partial_;
+  double* sums = (double*)sums_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(partial && slots && v && den && sums, "lw_unit_coef: null pointer");
   MI355_ARG((uintptr_t)partial % 8 == 0 && (uintptr_t)slots % 8 == 0 && (uintptr_t)v % 4 == 0 && (uintptr_t)den % 4 == 0 && (uintptr_t)sums % 8 == 0,
             "lw_unit_coef: misaligned pointer (8 bytes for partial[], slots[] and sums[], 4 for v[] and den[])");
@@ -290,9 +313,9 @@ int launch_lw_unit_coef(const double* partial, size_t n_partial, const void* slo
   return 0;
 }
 
-int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
-                          const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double wd, int soft_wd,
-                          double wd_eps, float gscale, float ema_decay, hipStream_t st) {
+static int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                                 const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double wd,
+                                 int soft_wd, double wd_eps, float gscale, float ema_decay, hipStream_t st) {
   MI355_ARG(p && g && m && items && tensors && den, "lw_unit_update: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(ema) && aligned16(items) && aligned16(tensors) && (uintptr_t)den % 4 == 0,
             "lw_unit_update: misaligned pointer (16 bytes for the arrays and the tables, 4 for den[])");
@@ -318,6 +341,19 @@ int launch_lw_unit_update(int rule, float* p, const float* g, float* m, float* e
       return 0;
     });
   });
+}
+extern "C" int mi355_lw_unit_update(int rule, float* p, const float* g, float* m, size_t n, const void* items, size_t n_items, const void* tensors,
+                                    int n_tensors, const float* den, size_t n_slots, double beta1, double lr, double weight_decay, int soft_wd,
+                                    double wd_eps, float grad_scale, void* stream) {
+  return launch_lw_unit_update(rule, p, g, m, nullptr, n, items, n_items, tensors, n_tensors, den, n_slots, beta1, lr, weight_decay, soft_wd,
+                               wd_eps, grad_scale, 0.f, (hipStream_t)stream);
+}
+extern "C" int mi355_lw_unit_update_ema(int rule, float* p, const float* g, float* m, float* ema, size_t n, const void* items, size_t n_items,
+                                        const void* tensors, int n_tensors, const float* den, size_t n_slots, double beta1, double lr,
+                                        double weight_decay, int soft_wd, double wd_eps, float grad_scale, float ema_decay, void* stream) {
+  MI355_ARG(ema, "lw_unit_update_ema: null ema");
+  return launch_lw_unit_update(rule, p, g, m, ema, n, items, n_items, tensors, n_tensors, den, n_slots, beta1, lr, weight_decay, soft_wd, wd_eps,
+                               grad_scale, ema_decay, (hipStream_t)stream);
 }
 
 }  // namespace mi355

@@ -83,8 +83,10 @@ __global__ __launch_bounds__(256) void sam_restore_kernel(float* __restrict__ p,
 
 }  // namespace
 
-int launch_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors, float eta,
-                     float gscale, double* partial, hipStream_t st) {
+extern "C" int mi355_sam_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
+                               float eta, float gscale, void* partial_, void* stream) {
+  double* partial = (double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(p && g && items && kind && partial, "sam_sumsq: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(items) && (uintptr_t)kind % 4 == 0 && (uintptr_t)partial % 8 == 0,
             "sam_sumsq: misaligned pointer (16 bytes for the arrays and the table, 8 for the partial sums)");
@@ -97,7 +99,9 @@ int launch_sam_sumsq(const float* p, const float* g, size_t n, const void* items
   return 0;
 }
 
-int launch_sam_scale(const double* partial, size_t n_partial, double rho, float* out, hipStream_t st) {
+extern "C" int mi355_sam_scale(const void* partial_, size_t n_partial, double rho, float* out, void* stream) {
+  const double* partial = (const double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(partial && out, "sam_scale: null pointer");
   MI355_ARG((uintptr_t)partial % 8 == 0 && (uintptr_t)out % 8 == 0, "sam_scale: misaligned pointer (8 bytes for the partial sums and the result)");
   MI355_ARG(n_partial >= 1 && n_partial <= kLwMaxGrid, "sam_scale: n_partial=%zu out of range", n_partial);
@@ -107,8 +111,9 @@ int launch_sam_scale(const double* partial, size_t n_partial, double rho, float*
   return 0;
 }
 
-int launch_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind, int n_tensors,
-                       const float* out, float eta, float gscale, hipStream_t st) {
+extern "C" int mi355_sam_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const int* kind,
+                                 int n_tensors, const float* out, float eta, float gscale, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(p && g && eps && items && kind && out, "sam_perturb: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(eps) && aligned16(items) && (uintptr_t)kind % 4 == 0 && (uintptr_t)out % 8 == 0,
             "sam_perturb: misaligned pointer (16 bytes for the arrays and the table, 8 for the result of sam_scale)");
@@ -121,7 +126,8 @@ int launch_sam_perturb(float* p, const float* g, float* eps, size_t n, const voi
   return 0;
 }
 
-int launch_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, hipStream_t st) {
+extern "C" int mi355_sam_restore(float* p, const float* eps, size_t n, const void* items, size_t n_items, int n_tensors, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(p && eps && items, "sam_restore: null pointer");
   MI355_ARG(aligned16(p) && aligned16(eps) && aligned16(items), "sam_restore: misaligned pointer (16 bytes for the arrays and the table)");
   MI355_ARG(n_items >= 1 && n_items <= kLwMaxGrid && n_tensors >= 1, "sam_restore: n_items=%zu, n_tensors=%d out of range", n_items, n_tensors);

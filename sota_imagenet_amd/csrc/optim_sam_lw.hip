@@ -104,8 +104,10 @@ __global__ __launch_bounds__(256) void sam_lw_perturb_kernel(float* __restrict__
 
 }  // namespace
 
-int launch_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, int n_tensors, float gscale, double* partial,
-                        hipStream_t st) {
+extern "C" int mi355_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* items, size_t n_items, int n_tensors, float gscale,
+                                  void* partial_, void* stream) {
+  double* partial = (double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(p && g && items && partial, "sam_lw_sumsq: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(items) && aligned16(partial),
             "sam_lw_sumsq: misaligned pointer (16 bytes for the arrays, the table and the pairs of partial sums)");
@@ -116,8 +118,10 @@ int launch_sam_lw_sumsq(const float* p, const float* g, size_t n, const void* it
   return 0;
 }
 
-int launch_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* pieces, size_t n_pieces, int n_slots, float gscale,
-                          double* partial, int threads_per_piece, hipStream_t st) {
+extern "C" int mi355_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* pieces, size_t n_pieces, int n_slots, float gscale,
+                                    void* partial_, int threads_per_piece, void* stream) {
+  double* partial = (double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(p && g && pieces && partial, "sam_unit_sumsq: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(pieces) && aligned16(partial),
             "sam_unit_sumsq: misaligned pointer (16 bytes for the arrays, the table and the pairs of partial sums)");
@@ -134,7 +138,10 @@ int launch_sam_unit_sumsq(const float* p, const float* g, size_t n, const void* 
   return 0;
 }
 
-int launch_sam_lw_coef(const double* partial, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms, hipStream_t st) {
+extern "C" int mi355_sam_lw_coef(const void* partial_, size_t n_partial, const void* slots, size_t n_slots, float* coef, float* norms,
+                                 void* stream) {
+  const double* partial = (const double*)partial_;
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(partial && slots && coef && norms, "sam_lw_coef: null pointer");
   MI355_ARG(aligned16(partial) && (uintptr_t)slots % 8 == 0 && (uintptr_t)coef % 4 == 0 && (uintptr_t)norms % 8 == 0,
             "sam_lw_coef: misaligned pointer (16 bytes for the pairs of partial sums, 8 for the slot table and norms[], 4 for coef[])");
@@ -146,8 +153,9 @@ int launch_sam_lw_coef(const double* partial, size_t n_partial, const void* slot
   return 0;
 }
 
-int launch_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors, int n_tensors,
-                          const float* coef, size_t n_slots, double rho, float gscale, hipStream_t st) {
+extern "C" int mi355_sam_lw_perturb(float* p, const float* g, float* eps, size_t n, const void* items, size_t n_items, const void* tensors,
+                                    int n_tensors, const float* coef, size_t n_slots, double rho, float gscale, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(p && g && eps && items && tensors && coef, "sam_lw_perturb: null pointer");
   MI355_ARG(aligned16(p) && aligned16(g) && aligned16(eps) && aligned16(items) && aligned16(tensors) && (uintptr_t)coef % 4 == 0,
             "sam_lw_perturb: misaligned pointer (16 bytes for the arrays and the tables, 4 for coef[])");

@@ -126,8 +126,9 @@ __global__ __launch_bounds__(256) void tbbin_hist_kernel(const float* __restrict
 
 }  // namespace
 
-int launch_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges,
-                      uint32_t* hist, double* partial, hipStream_t st) {
+extern "C" int mi355_tbbin_hist(const float* src, size_t n, const void* items, size_t n_items, int n_tensors, const double* edges, int n_edges,
+                                uint32_t* hist, double* partial, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(src && items && edges && hist && partial, "tbbin_hist: null pointer");
   MI355_ARG(aligned16(src) && aligned16(items) && aligned16(hist) && (uintptr_t)edges % 8 == 0 && (uintptr_t)partial % 8 == 0,
             "tbbin_hist: misaligned pointer (16 bytes for the array, the table and hist[], 8 for edges[] and partial[])");

@@ -127,9 +127,10 @@ __global__ __launch_bounds__(256) void weight_norm_rows_kernel(float* w, size_t 
 
 }  // namespace
 
-int wnorm_wave_row_max() { return kWaveRowMax; }
+extern "C" int mi355_wnorm_wave_row_max(void) { return kWaveRowMax; }
 
-int launch_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, hipStream_t st) {
+extern "C" int mi355_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   MI355_ARG(w && items && status, "weight_norm_rows: null pointer");
   MI355_ARG(aligned16(w) && aligned16(items) && (uintptr_t)status % 4 == 0,
             "weight_norm_rows: misaligned pointer (16 bytes for the array and the table, 4 for status[])");
