@@ -557,6 +557,29 @@ int mi355_tbbin_hist(const float* src, size_t n, const void* items, size_t n_ite
 int mi355_weight_norm_rows(float* w, size_t n, const void* items, size_t n_items, int* status, void* stream);
 int mi355_wnorm_wave_row_max(void);
 
+/* Forward weight transform per output filter: the reference's `weight_standardization: True` (train.py:66-67) and its ForwardWeightNorm callback
+ * (sota_imagenet/callbacks.py:62-84) — csrc/weight_std.hip.  The plain ResNet-50 executor runs these itself once
+ * mi355_resnet50_set_weight_transform has switched it on; the entry points serve the per-row tests and the callback's bake.
+ *   rows[]  { int64 off; int32 len; int32 reserved }   16 bytes: one filter, len contiguous elements from element `off` of the flat fp32 arrays
+ *           (ANY element offset: the stem's rows are 147 long); row k of the table owns invstd[k]
+ *   mode    1 standardise, 2 centre
+ * Forward, per row w[0..L), every operation rounded on its own:
+ *   S1 = sum (double)w_i;  S2 = sum (double)w_i * (double)w_i;  mu = S1 / L;  var = max(S2 / L - mu * mu, 0);
+ *   is = (float)(1 / sqrt(var + eps)) (mode 1) or 1 (mode 2);  w_hat_i = (w_i - (float)mu) * is (float);  invstd[k] = is
+ *   the sums: per lane in element order, then a fixed tree; no floating-point atomics, nothing summed across waves — two runs on the same input
+ *   agree bit for bit.  A constant row gives zeros and a finite invstd, never NaN.  w_hat may be w itself (the transform baked in place).
+ * Backward, per row of the slice [row_begin, row_end) of the table, g = the gradient wrt w_hat:
+ *   m1 = (float)(sum (double)g_i / L);  m2 = (float)(sum (double)g_i * (double)w_hat_i / L) (mode 1) or 0 (mode 2);
+ *   dw_i = (beta != 0 ? beta * dw_i : 0) + invstd[k] * (g_i - m1 - w_hat_i * m2)          (mode 2: invstd[k] * (g_i - m1))
+ * One wave per row, one launch per call.  A record that does not lie inside [0, n) is skipped (nothing read or written through it); elements
+ * outside the rows are neither read nor written.  The table must hold every row the call names.  Fails (MI355_E_ARG) before the launch on a
+ * null or misaligned pointer (16 bytes for the arrays and rows[], 4 for invstd[]), a mode other than 1 or 2, n == 0, an empty table or slice,
+ * eps < 0, or (backward) dw being the array g or w_hat is read from. */
+int mi355_weight_std_rows_fwd(const float* w, float* w_hat, float* invstd, size_t n, const void* rows, size_t n_rows, int mode, float eps,
+                              void* stream);
+int mi355_weight_std_rows_bwd(const float* g, const float* w_hat, const float* invstd, float* dw, size_t n, const void* rows, size_t row_begin,
+                              size_t row_end, int mode, float beta, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —
@@ -813,10 +836,24 @@ int mi355_resnet50_kernel_table(const mi355_ctx* ctx, char* out, size_t cap, siz
  *   "<conv>.y" raw conv output, "<block>.a1|a2|out" post-activation tensors (e.g. "layer1.0.out"),
  *   "<bn>.save_mean|save_invstd", "stem.p0" (the stem's BN+ReLU+maxpool output; the 112x112 activation itself
  *   is never stored), "pooled", "dpooled", "gG0".."gG1" (block-output gradients of the last backward),
- *   "grad.cur" (between two backward segments: the gradient the next segment starts from).
+ *   "grad.cur" (between two backward segments: the gradient the next segment starts from);
+ *   with a weight transform on: "<conv>.w_hat" (fp32 [Cout,K,K,Cin], what the last forward convolved with) and "<conv>.ws_invstd" ([Cout]).
  * shape is NHWC (ndim 4) or [n] / [N,C]; dtype is MI355_F32 or the ctx dtype.  Read-only use.     */
 int mi355_resnet50_debug_tensor(const mi355_ctx* ctx, const char* name, void** ptr, int* dtype, int* ndim,
                                 int shape[4]);
+/* Per-filter forward weight transform of every convolution (the FC is left alone): mode 0 off (the default), 1 standardise — the reference's
+ * `weight_standardization: True` (train.py:66-67), w_hat = (w - mean) / sqrt(var + 1e-5) per output filter over K*K*Cin, biased variance —,
+ * 2 centre — ForwardWeightNorm(use_std=False), sota_imagenet/callbacks.py:62-84: w_hat = w - mean.  The bound parameters and gradients stay
+ * those of the raw w.  With a mode on, every forward (training and inference) starts with ONE launch of the forward kernel of
+ * csrc/weight_std.hip over all 53 convolutions and convolves with w_hat; every weight gradient is formed wrt w_hat in a scratch array and one
+ * backward launch per backward segment (a bottleneck's three or four convolutions, or the stem) writes beta*dw + the gradient wrt w into the
+ * bound gradients, behind that segment's weight gradients on their stream: 17 launches per backward, and a segment's gradients are complete when
+ * the backward call that ran it returns.  The scratch (w_hat and the gradient wrt it, each the size of the flat parameter array, one invstd
+ * per filter, the row table) is allocated when a mode other than 0 is first set and kept until the context is destroyed; mode 0 launches
+ * nothing and reads the parameters as before.  Fails with MI355_E_ARG on a mode outside 0..2 or any mode other than 0 on a MI355_FP8
+ * context, MI355_E_STATE on a layout-only context or between a training forward and the end of its backward, MI355_E_NOMEM if the scratch
+ * cannot be allocated.                                                                                                                  */
+int mi355_resnet50_set_weight_transform(mi355_ctx* ctx, int mode);
 /* Test hook (teacher forcing): between two calls of mi355_resnet50_backward() that split the segments, replace the gradient the next
  * segment starts from ("grad.cur": wrt that block's output, or wrt the stem's pooled output before the last segment) by `g` (device
  * memory, the ctx dtype, exactly the tensor's bytes).  The BN-backward sums the producing kernel's epilogue left for that tensor are

@@ -5,7 +5,8 @@ Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `
 `self.mixup(*input)` with Beta(alpha, alpha) samplers) and the un-vendored pt_clb.Cutmix / pt_clb.Mixup bases as
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
-over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip, WeightNorm :104-123 over csrc/weight_norm.hip.
+over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip, WeightNorm :104-123 over csrc/weight_norm.hip,
+ForwardWeightNorm :62-84 over csrc/weight_std.hip and the executor's weight transform.
 What these share is stated once at module level: the flat model a callback runs on and its parameters by offset (_flat_model_of, _params_by_offset:
 OrthoInitClb, WeightNorm), and for the two histogram callbacks the re-plan key of a tensor (_tensor_key), the one-device check (_one_device) and the
 way out to state.tb_logger (_log_histograms); their launches per storage come from item_plan.dist_plan over item_plan.storage_array.
@@ -331,6 +332,57 @@ class WeightNorm(Callback):
             self.build_plan(m)
         self.status = ops.weight_norm_rows_(self._flat.detach(), None, self._items_dev)
         self.launches += 1
+
+
+class ForwardWeightNorm(Callback):
+    """sota_imagenet/callbacks.py:62-84, the forward form of the idea WeightNorm applies after the step: on_begin registers a per-filter
+    parametrisation on every non-depthwise Conv2d — with use_std=False pt.utils.misc.zero_mean_conv_weight, w_hat = w - mean over each output
+    filter (restated from memory of pytorch_tools) — so that forward convolves with w_hat while the optimizer keeps the
+    raw w, and on_end removes it, which leaves the parametrised weight behind as the parameter.
+
+    Here on_begin switches the plain ResNet-50 executor's weight transform to "centre" (models.ResNet50.set_weight_transform: one launch of
+    csrc/weight_std.hip at the head of every forward, one per backward segment), and on_end bakes w_hat into the flat
+    parameter array — ONE launch of the same forward kernel with the parameters as source and destination (ops.weight_std_rows_fwd over
+    item_plan.ws_rows) — and switches the transform off: an eval forward after on_end gives the bits of one before it (a centred filter's mean
+    rounds to zero only approximately, but the executor no longer subtracts it).  A model built with weight_standardization=True keeps that
+    mode: the callback refuses it (RuntimeError) instead of replacing one transform by the other.
+    use_std=True needs pt.utils.misc.normalize_conv_weight(gamma=...), which is not in the reference tree: NotImplementedError.  gamma without
+    use_std is ignored, as in the reference.  A model that is not the plain flat ResNet-50 on a CUDA device raises NotImplementedError."""
+
+    def __init__(self, gamma=None, use_std=False):
+        super().__init__()
+        if use_std:
+            raise NotImplementedError("ForwardWeightNorm(use_std=True): pt.utils.misc.normalize_conv_weight is not part of the reference tree; "
+                                      "use_std=False (zero_mean_conv_weight) is what is built")
+        self.gamma, self.use_std = gamma, False
+        self.rows, self.invstd = [], None
+
+    def _model(self):
+        from .models import ResNet50
+
+        m = _flat_model_of(self.state, "ForwardWeightNorm")
+        if not isinstance(m, ResNet50):
+            raise NotImplementedError(f"ForwardWeightNorm runs on the plain ResNet-50 executor (models.resnet50 without variant keys), got {type(m).__name__}")
+        return m
+
+    def on_begin(self):
+        m = self._model()
+        if m.weight_transform not in (0, ops.WS_CENTRE):
+            raise RuntimeError("ForwardWeightNorm: the model already standardises its weights (weight_standardization=True)")
+        logging.getLogger(__name__).info("Using forward Centered Weight Normalization for weights")
+        m.set_weight_transform("centre")
+
+    @torch.no_grad()
+    def on_end(self):
+        m = self._model()
+        if m.weight_transform != ops.WS_CENTRE:  # (on_begin never ran, or something else switched it off: nothing to leave behind)
+            return
+        self.rows = item_plan.ws_rows(m._table)
+        rows_dev = pack_records(self.rows, m.flat_params.device)
+        self.invstd = torch.empty(len(self.rows), dtype=torch.float32, device=m.flat_params.device)
+        flat = m.flat_params.detach()
+        ops.weight_std_rows_fwd(flat, flat, self.invstd, rows_dev, ops.WS_CENTRE)
+        m.set_weight_transform("off")
 
 
 class GradDistributionTB(Callback):

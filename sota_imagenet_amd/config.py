@@ -87,6 +87,13 @@ WEIGHT_CALLBACK_TARGET_ALIASES = {
     "sota_imagenet.callbacks.WeightNorm": "sota_imagenet_amd.callbacks.WeightNorm",
 }
 
+# callbacks that transform the weights inside the forward pass (sota_imagenet/callbacks.py:62-84), consulted last, after the eight tables above,
+# whose contents existing tests pin
+FORWARD_WEIGHT_CALLBACK_TARGET_ALIASES = {
+    "src.callbacks.ForwardWeightNorm": "sota_imagenet_amd.callbacks.ForwardWeightNorm",
+    "sota_imagenet.callbacks.ForwardWeightNorm": "sota_imagenet_amd.callbacks.ForwardWeightNorm",
+}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -325,7 +332,8 @@ def validate(cfg):
 def resolve_target(path):
     path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
             or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path) or LOGGING_CALLBACK_TARGET_ALIASES.get(path)
-            or WEIGHT_HISTOGRAM_TARGET_ALIASES.get(path) or WEIGHT_CALLBACK_TARGET_ALIASES.get(path, path))
+            or WEIGHT_HISTOGRAM_TARGET_ALIASES.get(path) or WEIGHT_CALLBACK_TARGET_ALIASES.get(path)
+            or FORWARD_WEIGHT_CALLBACK_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

@@ -40,6 +40,7 @@ struct ConvBN {
   int bwd_rows = 0;   // partial rows of THIS layer's BN-backward sums left in bn_partial by the dgrad that produced its
                       // activation gradient (0: none, bn_backward runs the standalone reduce kernel)
   bool is_stem = false;
+  size_t ws_row0 = 0;  // the layer's first row (filter) in the weight-transform row table (mi355_ctx::ws_rows)
   // fp8 training step (ctx dtype MI355_FP8): forward / dgrad of this layer on e4m3 operands where the geometry allows it
   bool fp8_fwd = false, fp8_dgrad = false, fp8_wgrad = false;
   void* w_q = nullptr;          // e4m3 [Cout][taps][Cin]
@@ -61,7 +62,15 @@ struct Block {
   uint8_t *a1_q = nullptr, *a2_q = nullptr, *out_q = nullptr;           // e4m3 twins (fp8 step; null where no fp8 conv reads them)
   int qid_a1 = -1, qid_a2 = -1, qid_out = -1;
   int Hin, Win, Hout, Wout, Cin, Cout;
+  size_t ws_row_begin = 0, ws_row_end = 0;  // the rows of the block's convolutions in the weight-transform row table: one contiguous run
 };
+
+// one output filter in the row table of csrc/weight_std.hip
+struct WsRow {
+  long long off;
+  int len, reserved;
+};
+constexpr float WS_EPS = 1e-5f;  // oracle/bresnet50_ref.py::ws
 
 }  // namespace
 }  // namespace mi355
@@ -127,6 +136,13 @@ struct mi355_ctx : FlatModel {
   int next_seg = 0;
   void* cur_dout = nullptr;  // gradient wrt the current block output during backward
   double fwd_flops = 0, train_flops = 0;
+
+  // per-filter forward weight transform (mi355_resnet50_set_weight_transform; csrc/weight_std.hip): 0 off, 1 standardise, 2 centre.  The row table
+  // is laid out at creation in parameter order (a block's convolutions are one run of it); the device copies exist once a mode has been set
+  int ws_mode = 0;
+  std::vector<WsRow> ws_rows;
+  float *w_hat = nullptr, *dw_hat = nullptr, *ws_invstd = nullptr;  // w_hat / dw_hat: param_elems floats, at the parameters' offsets
+  WsRow* ws_rows_dev = nullptr;
 
   // profiling
   unsigned prof_mask = 0;
@@ -206,6 +222,16 @@ inline void* sk_ws_of(mi355_ctx* c, hipStream_t s) {
   return c->stream_k ? c->sk_ws[(c->wstream && s == c->wstream) ? 1 : 0] : nullptr;
 }
 inline float* bn_coef_of(mi355_ctx* c, hipStream_t s) { return (c->wstream && s == c->wstream) ? c->bn_coef2 : c->bn_coef; }
+// what the convolutions read as their fp32 weights, and where their weight gradients land: the parameters and the bound gradients, or with a
+// weight transform on w_hat and the gradient wrt it (ws_backward then writes the bound gradients)
+inline const float* conv_weights(const mi355_ctx* c) { return c->ws_mode ? c->w_hat : c->params; }
+inline float* conv_wgrad_dst(mi355_ctx* c) { return c->ws_mode ? c->dw_hat : c->grads; }
+inline float conv_wgrad_beta(const mi355_ctx* c, float beta_acc) { return c->ws_mode ? 0.f : beta_acc; }
+// grads = beta_acc * grads + (the gradient wrt w of the rows [r0, r1), from the gradient wrt w_hat their weight-gradient launches left on `s`)
+int ws_backward(mi355_ctx* c, size_t r0, size_t r1, float beta_acc, hipStream_t s) {
+  Prof p(c, PC_OTHER, 0, 0, s);
+  return mi355_weight_std_rows_bwd(c->dw_hat, c->w_hat, c->ws_invstd, c->grads, c->param_elems, c->ws_rows_dev, r0, r1, c->ws_mode, beta_acc, s);
+}
 double conv_flops(const mi355_ctx* c, const ConvBN& l) {
   return 2.0 * c->N * l.Hout * l.Wout * (double)l.Cout * l.Cin * l.K * l.K;
 }
@@ -227,7 +253,7 @@ int conv_forward(mi355_ctx* c, ConvBN& l, const void* in, int training, float mo
   a.stat_partial = training ? bn_partial_of(c, s) : nullptr;
   a.stat_rows_cap = (int)((size_t)bn_max_blocks() * c->max_c / l.Cout);  // the scratch holds bn_max_blocks() rows of the widest layer
   a.sk_ws = sk_ws_of(c, s);
-  a.wt = c->dtype == MI355_F32 ? (const void*)(c->params + l.w_off) : (const void*)l.w_cast;
+  a.wt = c->dtype == MI355_F32 ? (const void*)(conv_weights(c) + l.w_off) : (const void*)l.w_cast;
   a.out = l.y;
   const double fl = conv_flops(c, l);
   const bool q = training && c->fp8_fwd_on && l.fp8_fwd;
@@ -351,7 +377,7 @@ int conv_wgrad(mi355_ctx* c, ConvBN& l, const void* dy, const void* x, float bet
     MI355_TRY(launch_wgrad(c->dtype, a, l.splits, s));
   }
   snprintf(l.k_wgrad, sizeof(l.k_wgrad), "%s", mi355_last_conv_kernel());
-  return launch_splitk_reduce(c->wg_partial, l.splits, n, c->grads + l.w_off, n, beta_acc, s);
+  return launch_splitk_reduce(c->wg_partial, l.splits, n, conv_wgrad_dst(c) + l.w_off, n, conv_wgrad_beta(c, beta_acc), s);
 }
 
 // dx = dgrad(dy) (+ addend under its mask).  bn (optional): the conv+BN layer whose post-ReLU activation dx is the
@@ -577,9 +603,11 @@ void plan_fp8(mi355_ctx* c, const char** bad) {
 
 int weight_prep_all(mi355_ctx* c, bool need_tr, hipStream_t s) {
   Prof p(c, PC_OTHER, 0, 0, s);
-  MI355_TRY(launch_stem_pack(c->dtype, c->params + c->stem.w_off, c->stem_pack, s));
+  if (c->ws_mode)  // w_hat and invstd of all 53 convolutions, one launch
+    MI355_TRY(mi355_weight_std_rows_fwd(c->params, c->w_hat, c->ws_invstd, c->param_elems, c->ws_rows_dev, c->ws_rows.size(), c->ws_mode, WS_EPS, s));
+  MI355_TRY(launch_stem_pack(c->dtype, conv_weights(c) + c->stem.w_off, c->stem_pack, s));
   if (need_tr || c->dtype != MI355_F32)
-    MI355_TRY(launch_weight_prep_batch(c->dtype, c->prep_table[need_tr ? 1 : 0], c->prep_layers, c->prep_tiles, c->params, s));
+    MI355_TRY(launch_weight_prep_batch(c->dtype, c->prep_table[need_tr ? 1 : 0], c->prep_layers, c->prep_tiles, conv_weights(c), s));
   if (need_tr)
     MI355_TRY(launch_weight_prep(MI355_F32, c->params + c->fc_w_off, nullptr, c->fc_wtr, c->fc_pad, 1, 2048, s));
   return 0;
@@ -671,6 +699,8 @@ int backward_block(mi355_ctx* c, Block& b, Block* prev, float beta_acc, hipStrea
   MI355_TRY(bn_backward(c, b.c1, B4, b.a1_bits, nullptr, B4, beta_acc, s));  // B4 = dy1
   MI355_TRY(c->fork(s, &ws));
   MI355_TRY(conv_wgrad(c, b.c1, B4, b.in, beta_acc, ws));
+  // (every weight gradient of the block went to ws, in order: one launch behind the last turns them into the gradients wrt w)
+  if (c->ws_mode) MI355_TRY(ws_backward(c, b.ws_row_begin, b.ws_row_end, beta_acc, ws));
   if (b.has_ds) {
     if (c->overlap) MI355_HIP(hipStreamWaitEvent(s, c->ds_done, 0));
     // Gn = dx_in = conv1 dgrad + shortcut gradient (+ the sums of the previous block's bn3)
@@ -722,7 +752,8 @@ int backward_stem(mi355_ctx* c, float beta_acc, hipStream_t s) {
     MI355_TRY(launch_wgrad(c->dtype, a, l.splits, ws));
     snprintf(l.k_wgrad, sizeof(l.k_wgrad), "%s", mi355_last_conv_kernel());
   }
-  MI355_TRY(launch_stem_unpack(c->wg_partial, l.splits, c->grads + l.w_off, beta_acc, ws));
+  MI355_TRY(launch_stem_unpack(c->wg_partial, l.splits, conv_wgrad_dst(c) + l.w_off, conv_wgrad_beta(c, beta_acc), ws));
+  if (c->ws_mode) MI355_TRY(ws_backward(c, l.ws_row0, l.ws_row0 + l.Cout, beta_acc, ws));
   return release_set(c, par);
 }
 
@@ -776,19 +807,28 @@ int mi355_resnet50_create(mi355_ctx** out, int device, int dtype, int N, int H, 
     c->segs.push_back({seg_begin, c->param_elems});
     seg_begin = c->param_elems;
   };
+  auto add_rows = [&](ConvBN& l) {  // after register_convbn: the layer's filters, in parameter order
+    l.ws_row0 = c->ws_rows.size();
+    const int len = l.K * l.K * l.Cin;
+    for (int r = 0; r < l.Cout; ++r) c->ws_rows.push_back({(long long)(l.w_off + (size_t)r * len), len, 0});
+  };
   add_param(c, rev, "fc.bias", &c->fc_b_off, 1, num_classes);
   add_param(c, rev, "fc.weight", &c->fc_w_off, 2, num_classes, 2048, 0, 0,
             (size_t)(c->fc_pad - num_classes) * 2048);
   end_segment();
   for (int i = (int)c->blocks.size() - 1; i >= 0; --i) {
     Block& b = c->blocks[i];
-    if (b.has_ds) register_convbn(c, rev, b.ds);
-    register_convbn(c, rev, b.c3);
-    register_convbn(c, rev, b.c2);
-    register_convbn(c, rev, b.c1);
+    b.ws_row_begin = c->ws_rows.size();
+    for (ConvBN* l : {&b.ds, &b.c3, &b.c2, &b.c1}) {
+      if (l == &b.ds && !b.has_ds) continue;
+      register_convbn(c, rev, *l);
+      add_rows(*l);
+    }
+    b.ws_row_end = c->ws_rows.size();
     end_segment();
   }
   register_convbn(c, rev, c->stem);
+  add_rows(c->stem);
   end_segment();
   // expose tensors in torchvision (forward) order
   c->tensors.assign(rev.rbegin(), rev.rend());
@@ -931,6 +971,8 @@ int mi355_resnet50_destroy(mi355_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   if (c->ds_done) (void)hipEventDestroy(c->ds_done);
   if (c->sk_err_host) (void)hipHostFree(c->sk_err_host);
+  for (void* p : {(void*)c->w_hat, (void*)c->dw_hat, (void*)c->ws_invstd, (void*)c->ws_rows_dev})
+    if (p) (void)hipFree(p);
   delete c;  // (FlatModel: side stream, its events, the arena)
   return 0;
 }
@@ -1114,6 +1156,14 @@ int mi355_resnet50_debug_tensor(const mi355_ctx* c, const char* name, void** ptr
       if (n == l.conv_name + ".sdy" && l.fp8_dgrad) return set1(c->q_scale + l.qid_dy, 1);
       if (n == l.conv_name + ".amax_w") return set1(reinterpret_cast<float*>(c->q_amax + l.qid_w), 1);
     }
+    if (c->ws_mode) {  // what the last forward convolved with
+      if (n == l.conv_name + ".w_hat") {
+        *ptr = c->w_hat + l.w_off; *dtype = MI355_F32; *ndim = 4;
+        shape[0] = l.Cout; shape[1] = shape[2] = l.K; shape[3] = l.Cin;
+        return 0;
+      }
+      if (n == l.conv_name + ".ws_invstd") return set1(c->ws_invstd + l.ws_row0, l.Cout);
+    }
     if (n == l.conv_name + ".y") return set4(l.y, c->dtype, l.Hout, l.Wout, l.Cout);
     if (n == l.bn_name + ".save_mean") return set1(l.stat, l.Cout);
     if (n == l.bn_name + ".save_invstd") return set1(l.stat + l.Cout, l.Cout);
@@ -1168,6 +1218,39 @@ int mi355_resnet50_force_grad(mi355_ctx* c, const void* g, size_t bytes, void* s
   }
   MI355_ARG(bytes == want, "force_grad: %zu bytes given, the pending gradient has %zu", bytes, want);
   MI355_HIP(hipMemcpyAsync(c->cur_dout, g, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+int mi355_resnet50_set_weight_transform(mi355_ctx* c, int mode) {
+  MI355_ARG(c, "set_weight_transform: null ctx");
+  MI355_ARG(mode >= 0 && mode <= 2, "set_weight_transform: mode %d (0 off, 1 standardise, 2 centre)", mode);
+  MI355_ARG(mode == 0 || !c->fp8, "set_weight_transform: the fp8 step has no weight transform (mode %d)", mode);
+  if (c->fwd_training_done) {
+    set_error("set_weight_transform: a training forward is waiting for its backward");
+    return MI355_E_STATE;
+  }
+  if (mode != 0 && !c->w_hat) {
+    if (c->device < 0) {
+      set_error("set_weight_transform: layout-only context");
+      return MI355_E_STATE;
+    }
+    MI355_HIP(hipSetDevice(c->device));
+    const size_t nb = c->param_elems * sizeof(float), rb = c->ws_rows.size() * sizeof(WsRow);
+    bool ok = hipMalloc((void**)&c->w_hat, nb) == hipSuccess && hipMalloc((void**)&c->dw_hat, nb) == hipSuccess &&
+              hipMalloc((void**)&c->ws_invstd, c->ws_rows.size() * sizeof(float)) == hipSuccess && hipMalloc((void**)&c->ws_rows_dev, rb) == hipSuccess;
+    // (the gaps between the rows are never read; zeros keep a debugging copy of the whole array finite)
+    ok = ok && hipMemset(c->w_hat, 0, nb) == hipSuccess && hipMemset(c->dw_hat, 0, nb) == hipSuccess &&
+         hipMemcpy(c->ws_rows_dev, c->ws_rows.data(), rb, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+      set_error("set_weight_transform: scratch of %zu bytes -> %s", 2 * nb + rb, hipGetErrorString(hipGetLastError()));
+      for (void** p : {(void**)&c->w_hat, (void**)&c->dw_hat, (void**)&c->ws_invstd, (void**)&c->ws_rows_dev}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+      }
+      return MI355_E_NOMEM;
+    }
+  }
+  c->ws_mode = mode;
   return 0;
 }
 

@@ -165,6 +165,18 @@ def wnorm_records(table):
     return out
 
 
+def ws_rows(table):
+    """the rows of the forward weight transform (ops.weight_std_rows_fwd): [(first element, row_len)], one per output filter of every conv
+    weight — a parameter (kind 0) with four dimensions — of a flat model's [(name, kind, offset, shape)], in table order.  An FC weight is not
+    a conv: the transform leaves it alone.  A conv weight [O, I, kh, kw] is KRSC in memory, a filter is one contiguous run of I*kh*kw elements."""
+    rows = []
+    for _, kind, off, shape in table:
+        if kind == 0 and len(shape) == 4:
+            L = int(np.prod(shape[1:]))
+            rows.extend((off + r * L, L) for r in range(shape[0]))
+    return rows
+
+
 def wnorm_items(records, W):
     """the work items of ops.weight_norm_rows_.  records: [(off, rows, row_len)]; returns [(first element, row_len, n_rows)]: every record's rows
     cut, from its first row, into runs of max(1, W // row_len) rows — whole rows only, a row longer than W is an item of its own; the cuts depend

@@ -317,10 +317,13 @@ class ResNet50(_FlatModel):
     _prefix = "resnet50"
     _max_ctxs = 3  # progressive resize / val batch: keep the 3 most recent shapes
 
-    def __init__(self, num_classes=1000, dtype=None, pretrained=None, **unsupported):
+    WEIGHT_TRANSFORMS = {"off": 0, "standardise": 1, "centre": 2}  # mi355_resnet50_set_weight_transform
+
+    def __init__(self, num_classes=1000, dtype=None, pretrained=None, weight_standardization=False, **unsupported):
         super().__init__()
         if pretrained:
             raise ValueError("pretrained weights are not available offline")
+        self._ws_mode = 0
         # architecture kwargs of pytorch_tools.models.resnet50 that would change the graph are rejected loudly
         for k, v in unsupported.items():
             if v not in (None, False, "", 0, 0.0, "relu", "abn"):
@@ -331,9 +334,37 @@ class ResNet50(_FlatModel):
         self._dt = native.FP8 if self.fp8 else native.dtype_code(self.compute_dtype)
         self._init_flat_state()
         self.reset_parameters()
+        # the reference's conv_to_ws_conv (train.py:66-67): the parameters stay raw, every forward convolves with the standardised filters
+        self.set_weight_transform("standardise" if weight_standardization else "off")
 
     def _create(self, out, device, N, H, W):
         return native.lib().mi355_resnet50_create(out, device, self._dt, N, H, W, self.num_classes)
+
+    @property
+    def weight_transform(self):
+        """the per-filter forward weight transform in force: 0 off, 1 standardise, 2 centre"""
+        return self._ws_mode
+
+    def set_weight_transform(self, mode):
+        """the per-filter forward weight transform of every convolution (mi355_resnet50_set_weight_transform): "off" / 0, "standardise" / 1 —
+        w_hat = (w - mean) / sqrt(var + 1e-5) per output filter —, "centre" / 2 — w_hat = w - mean.  parameters(), state_dict() and the
+        optimizer keep the raw weights; forward (training and eval) convolves with w_hat and backward leaves the gradients wrt the raw weights.
+        Applies to every native context, existing and future.  The fp8 step has none: ValueError."""
+        mode = self.WEIGHT_TRANSFORMS.get(mode, mode)
+        if isinstance(mode, bool) or mode not in (0, 1, 2):
+            raise ValueError(f"set_weight_transform: mode {mode!r} (one of {sorted(self.WEIGHT_TRANSFORMS)} or 0, 1, 2)")
+        if mode and self.fp8:
+            raise ValueError("resnet50(dtype='fp8') has no weight transform (weight_standardization / ForwardWeightNorm): use bf16 or fp32")
+        for c in self._ctxs.values():
+            check(native.lib().mi355_resnet50_set_weight_transform(c, mode))
+        self._ws_mode = mode
+
+    def _ctx(self, N, H, W):
+        new = (N, H, W) not in self._ctxs
+        c = super()._ctx(N, H, W)
+        if new and self._ws_mode:
+            check(native.lib().mi355_resnet50_set_weight_transform(c, self._ws_mode))
+        return c
 
     # ---- module tree with torchvision names --------------------------------------------------------------
     def _canonical_order(self):
@@ -456,7 +487,8 @@ _VARIANT_KEYS = ("stem_type", "antialias", "attn_type", "norm_layer", "norm_act"
 
 
 def _is_variant(kw):
-    return any(kw.get(k) not in (None, False, "", 0, 0.0, "relu", "abn") for k in _VARIANT_KEYS)
+    """a key that changes the graph is set.  weight_standardization alone does not: both models take it"""
+    return any(kw.get(k) not in (None, False, "", 0, 0.0, "relu", "abn") for k in _VARIANT_KEYS if k != "weight_standardization")
 
 
 def _bresnet50(**kw):
@@ -476,7 +508,8 @@ def _bresnet50(**kw):
 
 def resnet50(**kwargs):
     """plugin entry point — same name as the reference's `_target_: pytorch_tools.models.resnet50`.  Plain kwargs give the
-    torchvision-layout ResNet-50 on the static executor; the BResNet-50 model_params give the variant graph (bresnet.py)."""
+    torchvision-layout ResNet-50 on the static executor, with or without weight_standardization; the BResNet-50 model_params give the variant
+    graph (bresnet.py)."""
     if _is_variant(kwargs):
         return _bresnet50(**kwargs)
     return ResNet50(**kwargs)

@@ -766,6 +766,43 @@ def weight_norm_rows_(flat, items_host, items_dev):
     return status
 
 
+# ---- forward weight transform per filter (include/mi355rn.h, csrc/weight_std.hip): weight_standardization / the ForwardWeightNorm callback ---------
+WS_STANDARDISE, WS_CENTRE = 1, 2
+WS_EPS = 1e-5  # oracle/bresnet50_ref.py::ws
+
+
+def _ws_args(who, n_rows, rows_dev, invstd, **arrays):
+    n = next(iter(arrays.values())).numel()
+    _flat_f32(n, **arrays)
+    _lw_table("rows_dev", rows_dev)
+    _need_cuda(invstd)
+    if invstd.dtype != torch.float32 or invstd.numel() != rows_dev.shape[0]:
+        raise ValueError(f"invstd: expected {rows_dev.shape[0]} float32 elements (one per row of the table), got {invstd.dtype} with {invstd.numel()}")
+    if len({t.device for t in (rows_dev, invstd, *arrays.values())}) != 1:
+        raise ValueError(f"{who}: the table, invstd and the arrays must live on one device")
+    return n
+
+
+def weight_std_rows_fwd(w, w_hat, invstd, rows_dev, mode, eps=WS_EPS):
+    """w_hat = the per-row transform of w (mode WS_STANDARDISE: (w - mean) / sqrt(var + eps), WS_CENTRE: w - mean), invstd[k] = row k's factor,
+    in ONE launch.  w, w_hat: flat fp32 arrays of one size the row offsets count from — the same tensor bakes the transform in place —;
+    rows_dev: [(first element, row_len)] packed for the device (item_plan.ws_rows, pack_records; CUDA int64 [n, 2]); a row that does not fit
+    the array is skipped by the kernel.  Elements outside the rows are neither read nor written."""
+    n = _ws_args("weight_std_rows_fwd", rows_dev.shape[0], rows_dev, invstd, w=w, w_hat=w_hat)
+    check(_L().mi355_weight_std_rows_fwd(ptr(w), ptr(w_hat), ptr(invstd), n, ptr(rows_dev), rows_dev.shape[0], int(mode), float(eps), cur_stream()))
+
+
+def weight_std_rows_bwd(g, w_hat, invstd, dw, rows_dev, mode, beta=0.0, row_begin=0, row_end=None):
+    """dw = beta * dw + (the gradient wrt w of the rows [row_begin, row_end) of the table, from g = the gradient wrt w_hat), in ONE launch:
+    invstd * (g - mean(g) - w_hat * mean(g * w_hat)) per row (WS_CENTRE: invstd * (g - mean(g)), invstd as the forward left it: 1)"""
+    row_end = rows_dev.shape[0] if row_end is None else int(row_end)
+    if not 0 <= int(row_begin) < row_end <= rows_dev.shape[0]:
+        raise ValueError(f"weight_std_rows_bwd: rows [{row_begin}, {row_end}) of a table of {rows_dev.shape[0]}")
+    n = _ws_args("weight_std_rows_bwd", rows_dev.shape[0], rows_dev, invstd, g=g, w_hat=w_hat, dw=dw)
+    check(_L().mi355_weight_std_rows_bwd(ptr(g), ptr(w_hat), ptr(invstd), ptr(dw), n, ptr(rows_dev), int(row_begin), row_end, int(mode), float(beta),
+                                         cur_stream()))
+
+
 # ---- the log histogram of |x| (include/mi355rn.h, csrc/optim_hist.hip): the GradDistributionTB callback of the reference ----------------------------
 # the bins, stated once for the host; csrc/absbin.h states them for the kernels and tests/test_grad_dist_host.py holds the two together
 ABSBIN_BINS, ABSBIN_SHIFT, ABSBIN_K0 = 512, 20, (77 << 3) + 2
