@@ -562,7 +562,7 @@ int mi355_wnorm_wave_row_max(void);
  * mi355_resnet50_set_weight_transform has switched it on; the entry points serve the per-row tests and the callback's bake.
  *   rows[]  { int64 off; int32 len; int32 reserved }   16 bytes: one filter, len contiguous elements from element `off` of the flat fp32 arrays
  *           (ANY element offset: the stem's rows are 147 long); row k of the table owns invstd[k]
- *   mode    1 standardise, 2 centre
+ *   mode    1 standardise (MI355_WS_STANDARDISE), 2 centre (MI355_WS_CENTRE)
  * Forward, per row w[0..L), every operation rounded on its own:
  *   S1 = sum (double)w_i;  S2 = sum (double)w_i * (double)w_i;  mu = S1 / L;  var = max(S2 / L - mu * mu, 0);
  *   is = (float)(1 / sqrt(var + eps)) (mode 1) or 1 (mode 2);  w_hat_i = (w_i - (float)mu) * is (float);  invstd[k] = is
@@ -575,6 +575,9 @@ int mi355_wnorm_wave_row_max(void);
  * outside the rows are neither read nor written.  The table must hold every row the call names.  Fails (MI355_E_ARG) before the launch on a
  * null or misaligned pointer (16 bytes for the arrays and rows[], 4 for invstd[]), a mode other than 1 or 2, n == 0, an empty table or slice,
  * eps < 0, or (backward) dw being the array g or w_hat is read from. */
+#define MI355_WS_STANDARDISE 1
+#define MI355_WS_CENTRE 2
+#define MI355_WS_EPS 1e-5f /* the eps of the executor's own forward: oracle/bresnet50_ref.py::ws */
 int mi355_weight_std_rows_fwd(const float* w, float* w_hat, float* invstd, size_t n, const void* rows, size_t n_rows, int mode, float eps,
                               void* stream);
 int mi355_weight_std_rows_bwd(const float* g, const float* w_hat, const float* invstd, float* dw, size_t n, const void* rows, size_t row_begin,

@@ -1,7 +1,8 @@
 // optim_items.h — the tables that the kernels of optim_lw.hip, optim_adamp.hip, optim_sam.hip and optim_sam_lw.hip walk: the work items, and
 // for the statistics taken per output unit the pieces, slots and tensor records; the test every kernel makes before it touches memory through a
-// record; and the three loops over them that the unit-wise families share: the sums of a piece (piece_sums), the gather of a slot's partial
-// sums (slot_gather) and the update of an item whose elements take a coefficient per slot (unit_item_sweep).
+// record; the walk of a run of elements that starts at any element offset, bare (piece_walk) and with one element rule (piece_sweep: the row
+// kernels of weight_norm.hip and weight_std.hip); and the three loops that the unit-wise families share: the sums of a piece (piece_sums), the
+// gather of a slot's partial sums (slot_gather) and the update of an item whose elements take a coefficient per slot (unit_item_sweep).
 #pragma once
 #include <cstddef>
 
@@ -64,6 +65,16 @@ __device__ __forceinline__ void piece_walk(const UnitPiece& pc, int l, One one, 
   if (l < head) one(l);
   for (int i = l; i < n4; i += G) four(head, i);
   if (l < tail) one(head + 4 * n4 + l);
+}
+
+// piece_walk with the element rule stated once (optim_sweep.h): rule(float&...) gets one reference per array, the head element, then the four
+// lanes of every vector in order, then the tail element.  The arrays, named by use (rd, upd, wr, ...), are already offset to the piece's first
+// element; the rows of weight_norm.hip and weight_std.hip are walked this way.
+template <int G, typename Rule, typename... A>
+__device__ __forceinline__ void piece_sweep(const UnitPiece& pc, int l, Rule rule, const A&... a) {
+  constexpr std::index_sequence_for<A...> js;
+  piece_walk<G>(
+      pc, l, [&](int i) { sweep_element(i, rule, js, a...); }, [&](int head, int i) { sweep_vector(i, rule, js, a.at(head)...); });
 }
 
 // K sums per piece, one group of G threads per piece, 256 / G pieces per workgroup: add(acc, x...) takes one element of every array of src, in

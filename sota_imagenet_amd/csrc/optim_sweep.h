@@ -5,8 +5,13 @@
 //   upd(q)   read, and written back after the rule (float*); an array the rule overwrites without reading it costs no load
 //   upd_if<ON>(q)  upd(q) where ON; an array that is not there otherwise (the moving average of a step without one): nothing is loaded or
 //            stored through q and the rule gets a zero, so a kernel names the array once and only its element rule asks whether it exists
+//   wr(q)    written after the rule, never read: the rule gets a zero   (float*)
+//   rd_when(q, on)   rd(q) where the run-time flag `on` holds; otherwise nothing is loaded through q and the rule gets a zero   (const float*)
+//   upd_when(q, on)  upd(q) where `on` holds, wr(q) otherwise: an accumulation beta * old + new whose beta may be zero, old then being anything
 // rule(float&...) gets one reference per array, in the same order; it is called four times per vector and once per tail element, so a reduction
-// that adds into a captured variable sees a thread's elements in array order.  Stores cover the upd() arrays only.  The arrays must not overlap.
+// that adds into a captured variable sees a thread's elements in array order.  Stores cover the upd() and wr() arrays only.  The arrays must not
+// overlap, except that a wr() array may be an rd() array of the same sweep: a thread has read its elements of every array before it writes any.
+// a.at(e) is the same kind of array e elements further on (piece_sweep of optim_items.h: the vectors behind a scalar head).
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -15,19 +20,20 @@
 
 namespace mi355 {
 
-template <typename T, bool NONTEMPORAL, bool ON = true>
+template <typename T, bool NONTEMPORAL, bool ON = true, bool LOAD = ON>
 struct SweepArray {
   T* q;
   static constexpr bool kStore = ON && !std::is_const<T>::value;
+  __device__ __forceinline__ SweepArray at(int e) const { return {q + e}; }
   template <typename I>
   __device__ __forceinline__ f32x4 load4(I i) const {
-    if constexpr (!ON) return f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (!LOAD) return f32x4{0.f, 0.f, 0.f, 0.f};
     else if constexpr (NONTEMPORAL) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q) + i);
     else return reinterpret_cast<const f32x4*>(q)[i];
   }
   template <typename I>
   __device__ __forceinline__ float load1(I i) const {
-    if constexpr (ON) return q[i];
+    if constexpr (LOAD) return q[i];
     else return 0.f;
   }
   template <typename I>
@@ -45,6 +51,36 @@ __device__ __forceinline__ SweepArray<const float, true> last(const float* q) { 
 __device__ __forceinline__ SweepArray<float, false> upd(float* q) { return {q}; }
 template <bool ON>
 __device__ __forceinline__ SweepArray<float, false, ON> upd_if(float* q) { return {q}; }
+__device__ __forceinline__ SweepArray<float, false, true, false> wr(float* q) { return {q}; }
+
+// rd(q) / upd(q) whose load is decided at run time (the same for every element of the sweep)
+template <typename T>
+struct SweepArrayWhen {
+  T* q;
+  bool on;
+  __device__ __forceinline__ SweepArrayWhen at(int e) const { return {q + e, on}; }
+  template <typename I>
+  __device__ __forceinline__ f32x4 load4(I i) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (on) v = reinterpret_cast<const f32x4*>(q)[i];
+    return v;
+  }
+  template <typename I>
+  __device__ __forceinline__ float load1(I i) const {
+    return on ? q[i] : 0.f;
+  }
+  template <typename I>
+  __device__ __forceinline__ void store4(I i, const f32x4& x) const {
+    if constexpr (!std::is_const<T>::value) reinterpret_cast<f32x4*>(q)[i] = x;
+  }
+  template <typename I>
+  __device__ __forceinline__ void store1(I i, float x) const {
+    if constexpr (!std::is_const<T>::value) q[i] = x;
+  }
+};
+
+__device__ __forceinline__ SweepArrayWhen<const float> rd_when(const float* q, bool on) { return {q, on}; }
+__device__ __forceinline__ SweepArrayWhen<float> upd_when(float* q, bool on) { return {q, on}; }
 
 // vector i of every array
 template <typename I, typename Rule, size_t... J, typename... A>

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "flat_model.h"
+#include "rows.h"
 
 namespace mi355 {
 
@@ -64,13 +65,6 @@ struct Block {
   int Hin, Win, Hout, Wout, Cin, Cout;
   size_t ws_row_begin = 0, ws_row_end = 0;  // the rows of the block's convolutions in the weight-transform row table: one contiguous run
 };
-
-// one output filter in the row table of csrc/weight_std.hip
-struct WsRow {
-  long long off;
-  int len, reserved;
-};
-constexpr float WS_EPS = 1e-5f;  // oracle/bresnet50_ref.py::ws
 
 }  // namespace
 }  // namespace mi355
@@ -140,9 +134,9 @@ struct mi355_ctx : FlatModel {
   // per-filter forward weight transform (mi355_resnet50_set_weight_transform; csrc/weight_std.hip): 0 off, 1 standardise, 2 centre.  The row table
   // is laid out at creation in parameter order (a block's convolutions are one run of it); the device copies exist once a mode has been set
   int ws_mode = 0;
-  std::vector<WsRow> ws_rows;
+  std::vector<RowRecord> ws_rows;  // one output filter per record (rows.h)
   float *w_hat = nullptr, *dw_hat = nullptr, *ws_invstd = nullptr;  // w_hat / dw_hat: param_elems floats, at the parameters' offsets
-  WsRow* ws_rows_dev = nullptr;
+  RowRecord* ws_rows_dev = nullptr;
 
   // profiling
   unsigned prof_mask = 0;
@@ -604,7 +598,7 @@ void plan_fp8(mi355_ctx* c, const char** bad) {
 int weight_prep_all(mi355_ctx* c, bool need_tr, hipStream_t s) {
   Prof p(c, PC_OTHER, 0, 0, s);
   if (c->ws_mode)  // w_hat and invstd of all 53 convolutions, one launch
-    MI355_TRY(mi355_weight_std_rows_fwd(c->params, c->w_hat, c->ws_invstd, c->param_elems, c->ws_rows_dev, c->ws_rows.size(), c->ws_mode, WS_EPS, s));
+    MI355_TRY(mi355_weight_std_rows_fwd(c->params, c->w_hat, c->ws_invstd, c->param_elems, c->ws_rows_dev, c->ws_rows.size(), c->ws_mode, MI355_WS_EPS, s));
   MI355_TRY(launch_stem_pack(c->dtype, conv_weights(c) + c->stem.w_off, c->stem_pack, s));
   if (need_tr || c->dtype != MI355_F32)
     MI355_TRY(launch_weight_prep_batch(c->dtype, c->prep_table[need_tr ? 1 : 0], c->prep_layers, c->prep_tiles, conv_weights(c), s));
@@ -1223,7 +1217,7 @@ int mi355_resnet50_force_grad(mi355_ctx* c, const void* g, size_t bytes, void* s
 
 int mi355_resnet50_set_weight_transform(mi355_ctx* c, int mode) {
   MI355_ARG(c, "set_weight_transform: null ctx");
-  MI355_ARG(mode >= 0 && mode <= 2, "set_weight_transform: mode %d (0 off, 1 standardise, 2 centre)", mode);
+  MI355_ARG(mode == 0 || mode == MI355_WS_STANDARDISE || mode == MI355_WS_CENTRE, "set_weight_transform: mode %d (0 off, 1 standardise, 2 centre)", mode);
   MI355_ARG(mode == 0 || !c->fp8, "set_weight_transform: the fp8 step has no weight transform (mode %d)", mode);
   if (c->fwd_training_done) {
     set_error("set_weight_transform: a training forward is waiting for its backward");
@@ -1235,7 +1229,7 @@ int mi355_resnet50_set_weight_transform(mi355_ctx* c, int mode) {
       return MI355_E_STATE;
     }
     MI355_HIP(hipSetDevice(c->device));
-    const size_t nb = c->param_elems * sizeof(float), rb = c->ws_rows.size() * sizeof(WsRow);
+    const size_t nb = c->param_elems * sizeof(float), rb = c->ws_rows.size() * sizeof(RowRecord);
     bool ok = hipMalloc((void**)&c->w_hat, nb) == hipSuccess && hipMalloc((void**)&c->dw_hat, nb) == hipSuccess &&
               hipMalloc((void**)&c->ws_invstd, c->ws_rows.size() * sizeof(float)) == hipSuccess && hipMalloc((void**)&c->ws_rows_dev, rb) == hipSuccess;
     // (the gaps between the rows are never read; zeros keep a debugging copy of the whole array finite)

@@ -767,6 +767,7 @@ def weight_norm_rows_(flat, items_host, items_dev):
 
 
 # ---- forward weight transform per filter (include/mi355rn.h, csrc/weight_std.hip): weight_standardization / the ForwardWeightNorm callback ---------
+# stated once for the host; include/mi355rn.h states them for the library (MI355_WS_*) and tests/test_weight_std_host.py holds the two together
 WS_STANDARDISE, WS_CENTRE = 1, 2
 WS_EPS = 1e-5  # oracle/bresnet50_ref.py::ws
 

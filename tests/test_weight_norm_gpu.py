@@ -159,6 +159,28 @@ def test_a_constant_row_becomes_nan_and_its_neighbours_do_not(kernel_run):
     assert N[1, 0] == 0 and WN.worst_ratio(got[[0, 2]].numpy(), Y[[0, 2]], WN.native_bound(M[[0, 2]], N[[0, 2]], Y[[0, 2]])) <= 1.0
 
 
+def test_the_recorded_bits(dev):
+    """tests/golden/row_kernels_bits.npz (make_row_kernels_golden.py): the same call on the stored input gives the stored bits — rows shorter than
+    the scalar head, every head and tail, both sides of WNORM_WAVE_ROW_MAX, items of one, three and six rows —, NaN rows and sentinel gaps included.
+    A difference means the arithmetic or the order of a sum has changed; the file is not made again from the kernel it tests."""
+    import row_bits_common as R
+
+    z = np.load(R.FIXTURE)
+    recs = [tuple(int(v) for v in r) for r in z["records"]]
+    assert recs == R.layout()[0]
+    got = R.run_weight_norm(recs, z["w"].copy(), dev)
+    want = z["wnorm/out"]
+    assert got["wnorm/status"].tolist() == z["wnorm/status"].tolist() == [0] * len(recs)
+    mask = R.row_mask(want.size, R.rows_of(recs))
+    o, rows, L = recs[R.CONST_RECORD]
+    const = slice(o + R.CONST_ROW * L, o + (R.CONST_ROW + 1) * L)
+    assert np.isnan(want[const]).all() and np.isfinite(want[o:o + L]).all() and np.isfinite(want[o + 2 * L:o + 3 * L]).all()
+    assert np.array_equal(np.isnan(got["wnorm/out"]), np.isnan(want)), "the NaN pattern: the constant row, the row of one element, the gaps"
+    assert np.array_equal(got["wnorm/out"][const].view(np.int32), want[const].view(np.int32))
+    assert (want.view(np.int32)[~mask] == SENTINEL).all() and (got["wnorm/out"].view(np.int32)[~mask] == SENTINEL).all()
+    assert R.same_bits(got["wnorm/out"], want)
+
+
 # ---- 2. items that do not fit --------------------------------------------------------------------------------------------------------------------
 def test_items_that_do_not_fit_are_refused_and_their_memory_untouched(dev):
     """an item that ends past n, one that starts before 0 and two with an empty shape in one launch with two valid items, which come out right.

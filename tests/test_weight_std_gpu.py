@@ -132,6 +132,48 @@ def test_rows_backward_against_float64(dev, rows_case, mode_name, beta):
     assert _same_bits(again[m], dw[m])
 
 
+# ---- the recorded bits ---------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def recorded(dev):
+    """tests/golden/row_kernels_bits.npz (make_row_kernels_golden.py) and what the same calls give on its stored inputs, computed once"""
+    import row_bits_common as R
+
+    z = np.load(R.FIXTURE)
+    recs = [tuple(int(v) for v in r) for r in z["records"]]
+    assert recs == R.layout()[0] and tuple(z["bwd_slice"]) == R.BWD_SLICE
+    return R, z, recs, R.run_weight_std(recs, z["w"].copy(), z["g"].copy(), z["dw_old"].copy(), dev)
+
+
+@pytest.mark.parametrize("mode_name", MODE_IDS)
+def test_rows_forward_gives_the_recorded_bits(recorded, mode_name):
+    """rows shorter than the scalar head, every head and tail, one lane short of a wave and one past: a difference means the arithmetic or the
+    order of a sum has changed.  Out of place into sentinels and in place give the same array, gaps included."""
+    R, z, recs, got = recorded
+    mode = WS.MODES[mode_name]
+    want, inv = z[f"fwd/{mode}/w_hat"], z[f"fwd/{mode}/invstd"]
+    mask = R.row_mask(want.size, R.rows_of(recs))
+    assert (want.view(np.int32)[~mask] == R.SENTINEL).all() and np.isfinite(want[mask]).all()
+    for name in (f"fwd/{mode}/w_hat", f"fwd/{mode}/in_place"):
+        assert np.array_equal(np.isnan(got[name]), ~mask) and (got[name].view(np.int32)[~mask] == R.SENTINEL).all(), name
+        assert R.same_bits(got[name], want), name
+    assert R.same_bits(got[f"fwd/{mode}/invstd"], inv) and R.same_bits(got[f"fwd/{mode}/in_place_invstd"], inv)
+
+
+@pytest.mark.parametrize("beta", [0.0, 0.5])
+@pytest.mark.parametrize("mode_name", MODE_IDS)
+def test_rows_backward_gives_the_recorded_bits(recorded, mode_name, beta):
+    """a slice that starts and ends inside a group of four rows; with beta == 0 dw starts as NaN, which is never read"""
+    R, z, recs, got = recorded
+    mode = WS.MODES[mode_name]
+    want, have = z[f"bwd/{mode}/{beta}/dw"], got[f"bwd/{mode}/{beta}/dw"]
+    rows = R.rows_of(recs)
+    sl = R.row_mask(want.size, rows[R.BWD_SLICE[0]: R.BWD_SLICE[1]])
+    assert np.isfinite(want[sl]).all() and np.isfinite(have[sl]).all()
+    outside = z["dw_old"][~sl] if beta else np.full(int((~sl).sum()), np.nan, dtype=np.float32)
+    assert R.same_bits(want[~sl], outside) and R.same_bits(have[~sl], outside), "rows outside the slice and the gaps keep their bits"
+    assert R.same_bits(have, want)
+
+
 # ---- the model tests -----------------------------------------------------------------------------------------------------------------------------
 def _model(dtype, **kw):
     from sota_imagenet_amd.models import resnet50

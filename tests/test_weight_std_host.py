@@ -133,6 +133,23 @@ def test_header_declares_the_entry_points():
     assert re.search(r"^SRCS\s*:=.*\bweight_std\.hip\b", src, re.M)
 
 
+def test_the_constants_of_host_and_header_agree():
+    """the mode codes and the epsilon are stated once per side: ops for the host, include/mi355rn.h for the library and the executor"""
+    from sota_imagenet_amd import ops
+
+    text = open(os.path.join(ROOT, "include", "mi355rn.h")).read()
+    macros = dict(re.findall(r"^#define\s+(MI355_WS_\w+)\s+(\S+)", text, re.M))
+    assert set(macros) == {"MI355_WS_STANDARDISE", "MI355_WS_CENTRE", "MI355_WS_EPS"}
+    assert int(macros["MI355_WS_STANDARDISE"]) == ops.WS_STANDARDISE == WS.STANDARDISE == 1
+    assert int(macros["MI355_WS_CENTRE"]) == ops.WS_CENTRE == WS.CENTRE == 2
+    assert macros["MI355_WS_EPS"].endswith("f") and float(macros["MI355_WS_EPS"][:-1]) == ops.WS_EPS == WS.EPS
+    # nothing in the library's sources restates them
+    csrc = os.path.join(ROOT, "sota_imagenet_amd", "csrc")
+    for name in ("weight_std.hip", "resnet_exec.cpp"):
+        src = open(os.path.join(csrc, name)).read()
+        assert "MI355_WS_STANDARDISE" in src and not re.search(r"\bWS_EPS\s*=|mode\s*==\s*[12]\b", src), name
+
+
 def test_layout_only_and_argument_refusals_of_the_entry_points():
     import ctypes
 
