@@ -583,6 +583,36 @@ int mi355_weight_std_rows_fwd(const float* w, float* w_hat, float* invstd, size_
 int mi355_weight_std_rows_bwd(const float* g, const float* w_hat, const float* invstd, float* dw, size_t n, const void* rows, size_t row_begin,
                               size_t row_end, int mode, float beta, void* stream);
 
+/* Forward spectral normalisation per convolution: the reference's ForwardSpectralNorm callback (sota_imagenet/callbacks.py:87-101), i.e.
+ * torch.nn.utils.parametrizations.spectral_norm with dim 0, one power iteration and eps 1e-12 — csrc/spectral_norm.hip.  The plain ResNet-50
+ * executor runs these itself once mi355_resnet50_set_spectral_norm has switched it on; the entry points serve the per-matrix tests, the warm
+ * start and the callback's bake.
+ *   mats[]  { int64 off; int32 len; int32 rows; int64 u0; int64 v0 }   32 bytes: `rows` rows of `len` contiguous elements from element `off` of
+ *           the flat fp32 arrays (ANY element offset); the matrix owns u[u0 .. u0 + rows), v[v0 .. v0 + len) (v in memory order: (K,K,Cin) for
+ *           a conv filter) and sigma[its index].  u0 and v0 are the running sums of rows and len: they ascend with the index.
+ * One power iteration, every sum in double and in a fixed order, every operation rounded on its own:
+ *   t_r = sum_c W_rc v_c;  u_r = (float)(t_r / max(sqrt(sum_r t_r^2), eps));  s_c = sum_r W_rc u_r;  v_c = (float)(s_c / max(sqrt(sum_c s_c^2), eps));
+ *   sigma = (float) sum_c s_c v_c
+ * mi355_spectral_fwd runs `iters` of them (1: a training forward; up to MI355_SN_WARM_ITERS: the warm start); iters == 0 is the eval rule: u and v
+ * are left as they are and sigma = (float) sum_r u_r t_r.  Then, unless w_hat is NULL, w_hat_rc = W_rc / sigma (w_hat == w: in place).  A zero
+ * matrix has sigma = 0 and becomes NaN, as in torch.  4 launches per iteration (2 for eval) and one for the division, over all matrices.
+ * mi355_spectral_bwd, from g = the gradient wrt w_hat, for the matrices whose rows are the slice [row_begin, row_end) of u[] (whole matrices:
+ * one that the slice cuts is skipped), u, v, sigma constants:   d = sum_rc g_rc w_hat_rc;
+ *   dw_rc = (beta != 0 ? beta * dw_rc : 0) + (g_rc - ((float)d * u_r) * v_c) / sigma                                   2 launches.
+ * No floating-point atomics; no workgroup waits on another: every sum across workgroups is taken by one owner from what an earlier launch on
+ * the same stream left in `scratch` (mi355_spectral_scratch_doubles(n_u, n_v) doubles).  A record that does not lie inside [0, n), [0, n_u) and
+ * [0, n_v) is skipped (nothing read or written through it); elements outside the matrices are neither read nor written.  Fails (MI355_E_ARG)
+ * before any launch on a null or misaligned pointer (16 bytes for the arrays, mats[] and scratch, 4 for u, v, sigma), n, n_u, n_v or n_mats
+ * of 0, n_mats > 65535, iters outside 0 .. MI355_SN_WARM_ITERS, an empty slice or one beyond n_u, or (backward) dw being g or w_hat. */
+#define MI355_SN_EPS 1e-12f
+#define MI355_SN_WARM_ITERS 15 /* power iterations torch runs when the parametrisation is registered */
+#define MI355_SN_SLABS 16      /* row slabs per matrix of the column sums */
+size_t mi355_spectral_scratch_doubles(size_t n_u, size_t n_v);
+int mi355_spectral_fwd(const float* w, float* w_hat, float* u, float* v, float* sigma, double* scratch, size_t n, size_t n_u, size_t n_v,
+                       const void* mats, size_t n_mats, int iters, void* stream);
+int mi355_spectral_bwd(const float* g, const float* w_hat, const float* u, const float* v, const float* sigma, float* dw, double* scratch, size_t n,
+                       size_t n_u, size_t n_v, const void* mats, size_t n_mats, size_t row_begin, size_t row_end, float beta, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —
@@ -857,6 +887,17 @@ int mi355_resnet50_debug_tensor(const mi355_ctx* ctx, const char* name, void** p
  * context, MI355_E_STATE on a layout-only context or between a training forward and the end of its backward, MI355_E_NOMEM if the scratch
  * cannot be allocated.                                                                                                                  */
 int mi355_resnet50_set_weight_transform(mi355_ctx* ctx, int mode);
+/* Forward spectral normalisation of every convolution (csrc/spectral_norm.hip; the reference's ForwardSpectralNorm callback): on != 0 — every
+ * forward runs mi355_spectral_fwd over the 53 conv filters at its head (training: one power iteration, which advances u and v; eval: none) and
+ * convolves with w_hat = w / sigma; every backward segment runs mi355_spectral_bwd on the weight-gradient stream behind that segment's weight
+ * gradients and leaves the gradients wrt the raw weights in the bound array.  u (one float per filter of the model, 26 560) and v (one per
+ * filter element of each convolution, sum of K*K*Cin over the 53, in (K,K,Cin) order) are caller-owned device arrays that must outlive the
+ * switch: every context of a model is given the same two and advances one state.  A switch of its own, not a mode of
+ * mi355_resnet50_set_weight_transform, and the two exclude each other: MI355_E_ARG when the other one is in force (from either call), on
+ * null u or v with on != 0, or on a MI355_FP8 context; MI355_E_STATE on a layout-only context or between a training forward and the end of its
+ * backward; MI355_E_NOMEM if the scratch (w_hat, the gradient wrt it, sigma, the table, the sums' scratch) cannot be allocated.  It is
+ * allocated at the first on != 0 and kept; on == 0 launches nothing and reads the parameters as before. */
+int mi355_resnet50_set_spectral_norm(mi355_ctx* ctx, int on, float* u, float* v);
 /* Test hook (teacher forcing): between two calls of mi355_resnet50_backward() that split the segments, replace the gradient the next
  * segment starts from ("grad.cur": wrt that block's output, or wrt the stem's pooled output before the last segment) by `g` (device
  * memory, the ctx dtype, exactly the tensor's bytes).  The BN-backward sums the producing kernel's epilogue left for that tensor are

@@ -6,7 +6,7 @@ Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
 over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip, WeightNorm :104-123 over csrc/weight_norm.hip,
-ForwardWeightNorm :62-84 over csrc/weight_std.hip and the executor's weight transform.
+ForwardWeightNorm :62-84 over csrc/weight_std.hip and the executor's weight transform, ForwardSpectralNorm :87-101 over csrc/spectral_norm.hip.
 What these share is stated once at module level: the flat model a callback runs on and its parameters by offset (_flat_model_of, _params_by_offset:
 OrthoInitClb, WeightNorm), and for the two histogram callbacks the re-plan key of a tensor (_tensor_key), the one-device check (_one_device) and the
 way out to state.tb_logger (_log_histograms); their launches per storage come from item_plan.dist_plan over item_plan.storage_array.
@@ -383,6 +383,55 @@ class ForwardWeightNorm(Callback):
         flat = m.flat_params.detach()
         ops.weight_std_rows_fwd(flat, flat, self.invstd, rows_dev, ops.WS_CENTRE)
         m.set_weight_transform("off")
+
+
+class ForwardSpectralNorm(Callback):
+    """sota_imagenet/callbacks.py:87-101 (recipe 29): on_begin calls torch.nn.utils.parametrizations.spectral_norm on every nn.Conv2d — forward
+    convolves with w / sigma(w), sigma from one power iteration per training forward on the buffers u, v (dim 0, eps 1e-12; 15 iterations at
+    registration) — and on_end removes the parametrisations, which leaves w / sigma behind as the parameter.
+
+    Here on_begin switches the plain ResNet-50 executor's spectral normalisation on (models.ResNet50.set_spectral_norm: csrc/spectral_norm.hip
+    over all 53 convolutions at the head of every forward and behind every backward segment), and on_end bakes
+    w <- w / sigma into the flat parameter array with the eval rule — no power iteration, ops.spectral_fwd with the parameters as source and
+    destination — and switches it off: an eval forward after on_end gives the bits of one before it.  A second on_begin leaves a warmed state
+    alone.  The model must be the plain flat ResNet-50 on a CUDA device (NotImplementedError otherwise: BResNet-50, a torch model of
+    nn.Conv2d, a CPU model), not fp8 (ValueError) and without a weight transform (RuntimeError); ForwardWeightNorm.on_begin on a model that
+    already has spectral normalisation raises RuntimeError likewise.
+
+    Deviations from torch, deliberate:
+      * parameters(), state_dict(), the optimizer, EMA, checkpoints and the histogram callbacks see the raw weights under torchvision names;
+        torch would expose parametrizations.weight.original and the buffers _u, _v.  u and v are not saved: a resumed run warms anew
+        (models.ResNet50.spectral_state / load_spectral_state carry them by hand);
+      * the start vectors come from a CPU generator of their own seeded with `seed` (per conv in parameter order, u then v), not from the
+        global generator: every rank draws the same state without communication and the deterministic kernels keep the ranks equal bit for
+        bit, where the reference relies on DDP's per-forward buffer broadcast;
+      * the sums of the power iteration are taken in double and rounded once; torch takes them in float32."""
+
+    def __init__(self, seed=0):
+        super().__init__()
+        self.seed = int(seed)
+
+    def _model(self):
+        from .models import ResNet50
+
+        m = _flat_model_of(self.state, "ForwardSpectralNorm")
+        if not isinstance(m, ResNet50):
+            raise NotImplementedError(f"ForwardSpectralNorm runs on the plain ResNet-50 executor (models.resnet50 without variant keys), got {type(m).__name__}")
+        return m
+
+    def on_begin(self):
+        m = self._model()
+        logging.getLogger(__name__).info("Adding spectral norm parametrization for weights")
+        m.set_spectral_norm(True, seed=self.seed)
+
+    @torch.no_grad()
+    def on_end(self):
+        m = self._model()
+        if not m.spectral_norm:  # (on_begin never ran, or something else switched it off: nothing to leave behind)
+            return
+        sn, flat = m._sn, m.flat_params.detach()
+        ops.spectral_fwd(flat, flat, sn["u"], sn["v"], sn["sigma"], sn["scratch"], sn["mats_dev"], 0)
+        m.set_spectral_norm(False)
 
 
 class GradDistributionTB(Callback):

@@ -94,6 +94,13 @@ FORWARD_WEIGHT_CALLBACK_TARGET_ALIASES = {
     "sota_imagenet.callbacks.ForwardWeightNorm": "sota_imagenet_amd.callbacks.ForwardWeightNorm",
 }
 
+# the other callback that parametrises the weights inside the forward pass (sota_imagenet/callbacks.py:87-101; recipe 29), consulted last, after
+# the nine tables above, whose contents existing tests pin
+FORWARD_SPECTRAL_CALLBACK_TARGET_ALIASES = {
+    "src.callbacks.ForwardSpectralNorm": "sota_imagenet_amd.callbacks.ForwardSpectralNorm",
+    "sota_imagenet.callbacks.ForwardSpectralNorm": "sota_imagenet_amd.callbacks.ForwardSpectralNorm",
+}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -333,7 +340,7 @@ def resolve_target(path):
     path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
             or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path) or LOGGING_CALLBACK_TARGET_ALIASES.get(path)
             or WEIGHT_HISTOGRAM_TARGET_ALIASES.get(path) or WEIGHT_CALLBACK_TARGET_ALIASES.get(path)
-            or FORWARD_WEIGHT_CALLBACK_TARGET_ALIASES.get(path, path))
+            or FORWARD_WEIGHT_CALLBACK_TARGET_ALIASES.get(path) or FORWARD_SPECTRAL_CALLBACK_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

@@ -8,6 +8,7 @@
 //   wr(q)    written after the rule, never read: the rule gets a zero   (float*)
 //   rd_when(q, on)   rd(q) where the run-time flag `on` holds; otherwise nothing is loaded through q and the rule gets a zero   (const float*)
 //   upd_when(q, on)  upd(q) where `on` holds, wr(q) otherwise: an accumulation beta * old + new whose beta may be zero, old then being anything
+//   rd_any(q)        read, q at any 4-byte phase against the sweep's vectors: scalar loads   (const float*)
 // rule(float&...) gets one reference per array, in the same order; it is called four times per vector and once per tail element, so a reduction
 // that adds into a captured variable sees a thread's elements in array order.  Stores cover the upd() and wr() arrays only.  The arrays must not
 // overlap, except that a wr() array may be an rd() array of the same sweep: a thread has read its elements of every array before it writes any.
@@ -81,6 +82,28 @@ struct SweepArrayWhen {
 
 __device__ __forceinline__ SweepArrayWhen<const float> rd_when(const float* q, bool on) { return {q, on}; }
 __device__ __forceinline__ SweepArrayWhen<float> upd_when(float* q, bool on) { return {q, on}; }
+
+// rd(q) of an array that does not share the sweep's 16-byte phase (the vector v next to a matrix row that starts at any element: spectral_norm.hip):
+// four scalar loads per vector, nothing stored
+struct SweepArrayAny {
+  const float* q;
+  __device__ __forceinline__ SweepArrayAny at(int e) const { return {q + e}; }
+  template <typename I>
+  __device__ __forceinline__ f32x4 load4(I i) const {
+    const float* p = q + 4 * (size_t)i;
+    return f32x4{p[0], p[1], p[2], p[3]};
+  }
+  template <typename I>
+  __device__ __forceinline__ float load1(I i) const {
+    return q[i];
+  }
+  template <typename I>
+  __device__ __forceinline__ void store4(I, const f32x4&) const {}
+  template <typename I>
+  __device__ __forceinline__ void store1(I, float) const {}
+};
+
+__device__ __forceinline__ SweepArrayAny rd_any(const float* q) { return {q}; }
 
 // vector i of every array
 template <typename I, typename Rule, size_t... J, typename... A>

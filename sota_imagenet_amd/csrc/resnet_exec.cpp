@@ -137,6 +137,15 @@ struct mi355_ctx : FlatModel {
   std::vector<RowRecord> ws_rows;  // one output filter per record (rows.h)
   float *w_hat = nullptr, *dw_hat = nullptr, *ws_invstd = nullptr;  // w_hat / dw_hat: param_elems floats, at the parameters' offsets
   RowRecord* ws_rows_dev = nullptr;
+  // forward spectral normalisation (mi355_resnet50_set_spectral_norm; csrc/spectral_norm.hip): a switch of its own that shares w_hat / dw_hat
+  // and the rows' order with the transform above and excludes it.  One record per convolution, in the order of ws_rows (sn_mats[i].u0 = the
+  // layer's ws_row0); u and v belong to the caller, who gives every context of a model the same two
+  bool sn_on = false;
+  std::vector<SpectralMat> sn_mats;
+  size_t sn_nv = 0;  // sum of the row lengths: the elements of v
+  float *sn_u = nullptr, *sn_v = nullptr, *sn_sigma = nullptr;
+  double* sn_scratch = nullptr;
+  SpectralMat* sn_mats_dev = nullptr;
 
   // profiling
   unsigned prof_mask = 0;
@@ -217,14 +226,33 @@ inline void* sk_ws_of(mi355_ctx* c, hipStream_t s) {
 }
 inline float* bn_coef_of(mi355_ctx* c, hipStream_t s) { return (c->wstream && s == c->wstream) ? c->bn_coef2 : c->bn_coef; }
 // what the convolutions read as their fp32 weights, and where their weight gradients land: the parameters and the bound gradients, or with a
-// weight transform on w_hat and the gradient wrt it (ws_backward then writes the bound gradients)
-inline const float* conv_weights(const mi355_ctx* c) { return c->ws_mode ? c->w_hat : c->params; }
-inline float* conv_wgrad_dst(mi355_ctx* c) { return c->ws_mode ? c->dw_hat : c->grads; }
-inline float conv_wgrad_beta(const mi355_ctx* c, float beta_acc) { return c->ws_mode ? 0.f : beta_acc; }
+// weight transform or spectral normalisation on w_hat and the gradient wrt it (ws_backward then writes the bound gradients)
+inline bool hat_on(const mi355_ctx* c) { return c->ws_mode || c->sn_on; }
+inline const float* conv_weights(const mi355_ctx* c) { return hat_on(c) ? c->w_hat : c->params; }
+inline float* conv_wgrad_dst(mi355_ctx* c) { return hat_on(c) ? c->dw_hat : c->grads; }
+inline float conv_wgrad_beta(const mi355_ctx* c, float beta_acc) { return hat_on(c) ? 0.f : beta_acc; }
 // grads = beta_acc * grads + (the gradient wrt w of the rows [r0, r1), from the gradient wrt w_hat their weight-gradient launches left on `s`)
 int ws_backward(mi355_ctx* c, size_t r0, size_t r1, float beta_acc, hipStream_t s) {
   Prof p(c, PC_OTHER, 0, 0, s);
+  if (c->sn_on)  // (a segment's rows are whole convolutions)
+    return mi355_spectral_bwd(c->dw_hat, c->w_hat, c->sn_u, c->sn_v, c->sn_sigma, c->grads, c->sn_scratch, c->param_elems, c->ws_rows.size(), c->sn_nv,
+                              c->sn_mats_dev, c->sn_mats.size(), r0, r1, beta_acc, s);
   return mi355_weight_std_rows_bwd(c->dw_hat, c->w_hat, c->ws_invstd, c->grads, c->param_elems, c->ws_rows_dev, r0, r1, c->ws_mode, beta_acc, s);
+}
+// a device array a weight parametrisation needs, allocated at its first use and kept until the context is destroyed
+template <typename T>
+bool dev_array(T** p, size_t bytes, bool zero) {
+  if (*p) return true;
+  if (hipMalloc((void**)p, bytes) != hipSuccess) {
+    *p = nullptr;
+    return false;
+  }
+  return !zero || hipMemset(*p, 0, bytes) == hipSuccess;
+}
+// w_hat and the gradient wrt it (the gaps between the rows are never read; zeros keep a debugging copy of the whole array finite)
+bool hat_arrays(mi355_ctx* c) {
+  const size_t nb = c->param_elems * sizeof(float);
+  return dev_array(&c->w_hat, nb, true) && dev_array(&c->dw_hat, nb, true);
 }
 double conv_flops(const mi355_ctx* c, const ConvBN& l) {
   return 2.0 * c->N * l.Hout * l.Wout * (double)l.Cout * l.Cin * l.K * l.K;
@@ -599,6 +627,9 @@ int weight_prep_all(mi355_ctx* c, bool need_tr, hipStream_t s) {
   Prof p(c, PC_OTHER, 0, 0, s);
   if (c->ws_mode)  // w_hat and invstd of all 53 convolutions, one launch
     MI355_TRY(mi355_weight_std_rows_fwd(c->params, c->w_hat, c->ws_invstd, c->param_elems, c->ws_rows_dev, c->ws_rows.size(), c->ws_mode, MI355_WS_EPS, s));
+  if (c->sn_on)  // sigma and w_hat of all 53 convolutions; a training forward advances u and v by one power iteration
+    MI355_TRY(mi355_spectral_fwd(c->params, c->w_hat, c->sn_u, c->sn_v, c->sn_sigma, c->sn_scratch, c->param_elems, c->ws_rows.size(), c->sn_nv,
+                                 c->sn_mats_dev, c->sn_mats.size(), need_tr ? 1 : 0, s));  // (need_tr: a training forward)
   MI355_TRY(launch_stem_pack(c->dtype, conv_weights(c) + c->stem.w_off, c->stem_pack, s));
   if (need_tr || c->dtype != MI355_F32)
     MI355_TRY(launch_weight_prep_batch(c->dtype, c->prep_table[need_tr ? 1 : 0], c->prep_layers, c->prep_tiles, conv_weights(c), s));
@@ -694,7 +725,7 @@ int backward_block(mi355_ctx* c, Block& b, Block* prev, float beta_acc, hipStrea
   MI355_TRY(c->fork(s, &ws));
   MI355_TRY(conv_wgrad(c, b.c1, B4, b.in, beta_acc, ws));
   // (every weight gradient of the block went to ws, in order: one launch behind the last turns them into the gradients wrt w)
-  if (c->ws_mode) MI355_TRY(ws_backward(c, b.ws_row_begin, b.ws_row_end, beta_acc, ws));
+  if (hat_on(c)) MI355_TRY(ws_backward(c, b.ws_row_begin, b.ws_row_end, beta_acc, ws));
   if (b.has_ds) {
     if (c->overlap) MI355_HIP(hipStreamWaitEvent(s, c->ds_done, 0));
     // Gn = dx_in = conv1 dgrad + shortcut gradient (+ the sums of the previous block's bn3)
@@ -747,7 +778,7 @@ int backward_stem(mi355_ctx* c, float beta_acc, hipStream_t s) {
     snprintf(l.k_wgrad, sizeof(l.k_wgrad), "%s", mi355_last_conv_kernel());
   }
   MI355_TRY(launch_stem_unpack(c->wg_partial, l.splits, conv_wgrad_dst(c) + l.w_off, conv_wgrad_beta(c, beta_acc), ws));
-  if (c->ws_mode) MI355_TRY(ws_backward(c, l.ws_row0, l.ws_row0 + l.Cout, beta_acc, ws));
+  if (hat_on(c)) MI355_TRY(ws_backward(c, l.ws_row0, l.ws_row0 + l.Cout, beta_acc, ws));
   return release_set(c, par);
 }
 
@@ -805,6 +836,8 @@ int mi355_resnet50_create(mi355_ctx** out, int device, int dtype, int N, int H, 
     l.ws_row0 = c->ws_rows.size();
     const int len = l.K * l.K * l.Cin;
     for (int r = 0; r < l.Cout; ++r) c->ws_rows.push_back({(long long)(l.w_off + (size_t)r * len), len, 0});
+    c->sn_mats.push_back({{(long long)l.w_off, len, l.Cout}, (long long)l.ws_row0, (long long)c->sn_nv});
+    c->sn_nv += (size_t)len;
   };
   add_param(c, rev, "fc.bias", &c->fc_b_off, 1, num_classes);
   add_param(c, rev, "fc.weight", &c->fc_w_off, 2, num_classes, 2048, 0, 0,
@@ -965,7 +998,8 @@ int mi355_resnet50_destroy(mi355_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   if (c->ds_done) (void)hipEventDestroy(c->ds_done);
   if (c->sk_err_host) (void)hipHostFree(c->sk_err_host);
-  for (void* p : {(void*)c->w_hat, (void*)c->dw_hat, (void*)c->ws_invstd, (void*)c->ws_rows_dev})
+  for (void* p : {(void*)c->w_hat, (void*)c->dw_hat, (void*)c->ws_invstd, (void*)c->ws_rows_dev, (void*)c->sn_sigma, (void*)c->sn_scratch,
+                  (void*)c->sn_mats_dev})
     if (p) (void)hipFree(p);
   delete c;  // (FlatModel: side stream, its events, the arena)
   return 0;
@@ -1150,13 +1184,24 @@ int mi355_resnet50_debug_tensor(const mi355_ctx* c, const char* name, void** ptr
       if (n == l.conv_name + ".sdy" && l.fp8_dgrad) return set1(c->q_scale + l.qid_dy, 1);
       if (n == l.conv_name + ".amax_w") return set1(reinterpret_cast<float*>(c->q_amax + l.qid_w), 1);
     }
-    if (c->ws_mode) {  // what the last forward convolved with
+    if (hat_on(c)) {  // what the last forward convolved with
       if (n == l.conv_name + ".w_hat") {
         *ptr = c->w_hat + l.w_off; *dtype = MI355_F32; *ndim = 4;
         shape[0] = l.Cout; shape[1] = shape[2] = l.K; shape[3] = l.Cin;
         return 0;
       }
-      if (n == l.conv_name + ".ws_invstd") return set1(c->ws_invstd + l.ws_row0, l.Cout);
+      if (c->ws_mode && n == l.conv_name + ".ws_invstd") return set1(c->ws_invstd + l.ws_row0, l.Cout);
+      if (c->sn_on) {  // the layer's record is found by its first row
+        size_t i = 0;
+        while (i + 1 < c->sn_mats.size() && (size_t)c->sn_mats[i].u0 != l.ws_row0) ++i;
+        if (n == l.conv_name + ".sn_sigma") return set1(c->sn_sigma + i, 1);
+        if (n == l.conv_name + ".sn_u") return set1(c->sn_u + l.ws_row0, l.Cout);
+        if (n == l.conv_name + ".sn_v") {
+          *ptr = c->sn_v + c->sn_mats[i].v0; *dtype = MI355_F32; *ndim = 3;
+          shape[0] = shape[1] = l.K; shape[2] = l.Cin; shape[3] = 0;
+          return 0;
+        }
+      }
     }
     if (n == l.conv_name + ".y") return set4(l.y, c->dtype, l.Hout, l.Wout, l.Cout);
     if (n == l.bn_name + ".save_mean") return set1(l.stat, l.Cout);
@@ -1223,28 +1268,48 @@ int mi355_resnet50_set_weight_transform(mi355_ctx* c, int mode) {
     set_error("set_weight_transform: a training forward is waiting for its backward");
     return MI355_E_STATE;
   }
-  if (mode != 0 && !c->w_hat) {
+  MI355_ARG(mode == 0 || !c->sn_on, "set_weight_transform: spectral normalisation is on (mode %d); the two exclude each other", mode);
+  if (mode != 0 && !(c->w_hat && c->dw_hat && c->ws_invstd && c->ws_rows_dev)) {
     if (c->device < 0) {
       set_error("set_weight_transform: layout-only context");
       return MI355_E_STATE;
     }
     MI355_HIP(hipSetDevice(c->device));
-    const size_t nb = c->param_elems * sizeof(float), rb = c->ws_rows.size() * sizeof(RowRecord);
-    bool ok = hipMalloc((void**)&c->w_hat, nb) == hipSuccess && hipMalloc((void**)&c->dw_hat, nb) == hipSuccess &&
-              hipMalloc((void**)&c->ws_invstd, c->ws_rows.size() * sizeof(float)) == hipSuccess && hipMalloc((void**)&c->ws_rows_dev, rb) == hipSuccess;
-    // (the gaps between the rows are never read; zeros keep a debugging copy of the whole array finite)
-    ok = ok && hipMemset(c->w_hat, 0, nb) == hipSuccess && hipMemset(c->dw_hat, 0, nb) == hipSuccess &&
-         hipMemcpy(c->ws_rows_dev, c->ws_rows.data(), rb, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-      set_error("set_weight_transform: scratch of %zu bytes -> %s", 2 * nb + rb, hipGetErrorString(hipGetLastError()));
-      for (void** p : {(void**)&c->w_hat, (void**)&c->dw_hat, (void**)&c->ws_invstd, (void**)&c->ws_rows_dev}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-      }
-      return MI355_E_NOMEM;
+    const size_t rb = c->ws_rows.size() * sizeof(RowRecord);
+    if (!(hat_arrays(c) && dev_array(&c->ws_invstd, c->ws_rows.size() * sizeof(float), false) && dev_array(&c->ws_rows_dev, rb, false) &&
+          hipMemcpy(c->ws_rows_dev, c->ws_rows.data(), rb, hipMemcpyHostToDevice) == hipSuccess)) {
+      set_error("set_weight_transform: scratch of %zu bytes -> %s", 2 * c->param_elems * sizeof(float) + rb, hipGetErrorString(hipGetLastError()));
+      return MI355_E_NOMEM;  // (what was allocated stays for the next attempt and goes with the context)
     }
   }
   c->ws_mode = mode;
+  return 0;
+}
+
+int mi355_resnet50_set_spectral_norm(mi355_ctx* c, int on, float* u, float* v) {
+  MI355_ARG(c, "set_spectral_norm: null ctx");
+  MI355_ARG(!on || !c->fp8, "set_spectral_norm: the fp8 step has no spectral normalisation");
+  MI355_ARG(!on || c->ws_mode == 0, "set_spectral_norm: weight transform %d is in force; the two exclude each other", c->ws_mode);
+  MI355_ARG(!on || (u && v), "set_spectral_norm: null u or v");
+  if (c->fwd_training_done) {
+    set_error("set_spectral_norm: a training forward is waiting for its backward");
+    return MI355_E_STATE;
+  }
+  if (on && !(c->w_hat && c->dw_hat && c->sn_sigma && c->sn_scratch && c->sn_mats_dev)) {
+    if (c->device < 0) {
+      set_error("set_spectral_norm: layout-only context");
+      return MI355_E_STATE;
+    }
+    MI355_HIP(hipSetDevice(c->device));
+    const size_t mb = c->sn_mats.size() * sizeof(SpectralMat), sb = mi355_spectral_scratch_doubles(c->ws_rows.size(), c->sn_nv) * sizeof(double);
+    if (!(hat_arrays(c) && dev_array(&c->sn_sigma, c->sn_mats.size() * sizeof(float), true) && dev_array(&c->sn_scratch, sb, false) &&
+          dev_array(&c->sn_mats_dev, mb, false) && hipMemcpy(c->sn_mats_dev, c->sn_mats.data(), mb, hipMemcpyHostToDevice) == hipSuccess)) {
+      set_error("set_spectral_norm: scratch of %zu bytes -> %s", 2 * c->param_elems * sizeof(float) + sb + mb, hipGetErrorString(hipGetLastError()));
+      return MI355_E_NOMEM;
+    }
+  }
+  c->sn_on = on != 0;
+  c->sn_u = on ? u : nullptr, c->sn_v = on ? v : nullptr;
   return 0;
 }
 

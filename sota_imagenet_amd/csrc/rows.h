@@ -1,5 +1,5 @@
-// rows.h — the 16-byte record of the row tables (csrc/weight_norm.hip, csrc/weight_std.hip and the executor that builds the latter's table) and
-// the test a kernel makes before it touches memory through one.  Plain C++ for host and device.
+// rows.h — the 16-byte record of the row tables (csrc/weight_norm.hip, csrc/weight_std.hip and the executor that builds the latter's table), the
+// test a kernel makes before it touches memory through one, and the matrix record csrc/spectral_norm.hip builds on it.  Plain C++ for host and device.
 #pragma once
 #include <cstddef>
 
@@ -20,5 +20,14 @@ __host__ __device__ inline bool rows_ok(long long off, int len, int count, size_
   const size_t total = (size_t)len * (size_t)count;  // < 2^62
   return total <= n && (size_t)off <= n - total;
 }
+
+// a matrix of the spectral normalisation (csrc/spectral_norm.hip and the executor that builds its table): a run of rows and its places in the
+// vectors of the power iteration
+struct SpectralMat {
+  RowRecord run;  // count = R rows of len = L elements
+  long long u0;   // the matrix owns u[u0 .. u0 + R)
+  long long v0;   // and v[v0 .. v0 + L); u0 and v0 ascend with the index in the table
+};
+static_assert(sizeof(SpectralMat) == 32, "matrix records are 32 bytes");
 
 }  // namespace mi355

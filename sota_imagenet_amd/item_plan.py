@@ -13,6 +13,7 @@ import torch
 ITEM_FIELDS = ("<i8", "<i4", "<i4")    # work items, SAM's pieces { first element, length, tensor or slot } and tensor records { start, unit_len, slot0 }
 TENSOR_FIELDS = ("<i4", "<i4", "<f8")  # the tensor records of lw_coef { first item, item count, numel }
 ORTHO_FIELDS = ("<i8", "<i4", "<i4", "<i4", "<i4")  # the matrices of ortho_init_ { first element, rows, chans, taps, pad }: 24 bytes
+SPECTRAL_FIELDS = ("<i8", "<i4", "<i4", "<i8", "<i8")  # the matrices of ops.spectral_fwd { first element, row_len, rows, u0, v0 }: 32 bytes
 
 
 def dense_range(t):
@@ -175,6 +176,21 @@ def ws_rows(table):
             L = int(np.prod(shape[1:]))
             rows.extend((off + r * L, L) for r in range(shape[0]))
     return rows
+
+
+def spectral_mats(table):
+    """the matrices of the forward spectral normalisation (ops.spectral_fwd / spectral_bwd): ([(first element, row_len, rows, u0, v0)], n_u, n_v),
+    one record per conv weight — a parameter (kind 0) with four dimensions — of a flat model's [(name, kind, offset, shape)], in the order of
+    their offsets in the flat array, which is the order the executor lays out its own table in: u0 is the running sum of the rows (one
+    element of u per filter), v0 the running sum of the row lengths (one element of v per filter element, in memory order (K,K,Cin)); n_u and
+    n_v are the sizes of u and v.  An FC weight is not a conv.  Pack with pack_records(records, device, SPECTRAL_FIELDS)."""
+    mats, u0, v0 = [], 0, 0
+    for _, kind, off, shape in sorted(table, key=lambda t: t[2]):
+        if kind == 0 and len(shape) == 4:
+            L = int(np.prod(shape[1:]))
+            mats.append((off, L, shape[0], u0, v0))
+            u0, v0 = u0 + shape[0], v0 + L
+    return mats, u0, v0
 
 
 def wnorm_items(records, W):

@@ -15,10 +15,11 @@ import contextlib
 import ctypes
 from collections import OrderedDict
 
+import numpy as np
 import torch
 import torch.nn as nn
 
-from . import native
+from . import item_plan, native, ops
 from .native import check, ptr
 
 _DTYPES = {
@@ -324,6 +325,7 @@ class ResNet50(_FlatModel):
         if pretrained:
             raise ValueError("pretrained weights are not available offline")
         self._ws_mode = 0
+        self._sn = None  # spectral normalisation: dict(mats, mats_dev, u, v, sigma, scratch, seed) while it is on
         # architecture kwargs of pytorch_tools.models.resnet50 that would change the graph are rejected loudly
         for k, v in unsupported.items():
             if v not in (None, False, "", 0, 0.0, "relu", "abn"):
@@ -355,6 +357,8 @@ class ResNet50(_FlatModel):
             raise ValueError(f"set_weight_transform: mode {mode!r} (one of {sorted(self.WEIGHT_TRANSFORMS)} or 0, 1, 2)")
         if mode and self.fp8:
             raise ValueError("resnet50(dtype='fp8') has no weight transform (weight_standardization / ForwardWeightNorm): use bf16 or fp32")
+        if mode and self._sn is not None:
+            raise RuntimeError("set_weight_transform: spectral normalisation is on; the two exclude each other")
         for c in self._ctxs.values():
             check(native.lib().mi355_resnet50_set_weight_transform(c, mode))
         self._ws_mode = mode
@@ -364,7 +368,114 @@ class ResNet50(_FlatModel):
         c = super()._ctx(N, H, W)
         if new and self._ws_mode:
             check(native.lib().mi355_resnet50_set_weight_transform(c, self._ws_mode))
+        if new and self._sn is not None:
+            check(native.lib().mi355_resnet50_set_spectral_norm(c, 1, ptr(self._sn["u"]), ptr(self._sn["v"])))
         return c
+
+    def _apply(self, fn, recurse=True):
+        out = super()._apply(fn, recurse)  # (the native contexts are gone: new ones are given the moved vectors)
+        if self._sn is not None:
+            for k in ("mats_dev", "u", "v", "sigma", "scratch"):
+                self._sn[k] = fn(self._sn[k])
+        return out
+
+    # ---- forward spectral normalisation (csrc/spectral_norm.hip; callbacks.ForwardSpectralNorm) -------------------------------------------
+    @property
+    def spectral_norm(self):
+        """whether every convolution reads w / sigma(w) (set_spectral_norm)"""
+        return self._sn is not None
+
+    def _conv_names(self):
+        return {off: name[: -len(".weight")] for name, kind, off, shape in self._table if kind == 0 and len(shape) == 4}
+
+    @staticmethod
+    def spectral_draws(table, seed):
+        """the start vectors before the warm-up, as torch's spectral_norm draws them: {conv name: (u [Cout], v [Cin, K, K])}, N(0, 1) normalised,
+        from a CPU generator of their own seeded with `seed`, per conv in the table's (torchvision) order, u then v — the global generator is not
+        touched, and every rank draws the same"""
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        out = {}
+        for name, kind, _, shape in table:
+            if kind == 0 and len(shape) == 4:
+                u = torch.nn.functional.normalize(torch.randn(shape[0], generator=gen), dim=0, eps=ops.SN_EPS)
+                v = torch.nn.functional.normalize(torch.randn(int(np.prod(shape[1:])), generator=gen), dim=0, eps=ops.SN_EPS)
+                out[name[: -len(".weight")]] = (u, v.view(*shape[1:]))
+        return out
+
+    def set_spectral_norm(self, on, seed=0):
+        """forward spectral normalisation of every convolution (mi355_resnet50_set_spectral_norm): forward convolves with w / sigma, sigma from
+        one power iteration per training forward (none in eval) on the model's own `spectral_u` / `spectral_v`; parameters(), state_dict() and the
+        optimizer keep the raw weights, backward leaves the gradients wrt them.  Switching it on draws the vectors (spectral_draws(seed)) and
+        runs torch's ops.SN_WARM_ITERS iterations on the current weights; switching it on again keeps the state.  Applies to every native
+        context, existing and future.  Excludes a weight transform (RuntimeError), the fp8 step (ValueError) and a CPU model (RuntimeError)."""
+        if not on:
+            for c in self._ctxs.values():
+                check(native.lib().mi355_resnet50_set_spectral_norm(c, 0, None, None))
+            self._sn = None
+            return
+        if self._sn is not None:
+            return
+        if self.fp8:
+            raise ValueError("resnet50(dtype='fp8') has no spectral normalisation (ForwardSpectralNorm): use bf16 or fp32")
+        if self._ws_mode:
+            raise RuntimeError("set_spectral_norm: a weight transform is in force (weight_standardization / ForwardWeightNorm); the two exclude each other")
+        if not self._flat_params.is_cuda:
+            raise RuntimeError("set_spectral_norm: the MI355X hot path has no CPU fallback — call .cuda() first")
+        dev = self._flat_params.device
+        mats, n_u, n_v = item_plan.spectral_mats(self._table)
+        sn = dict(mats=mats, mats_dev=item_plan.pack_records(mats, dev, item_plan.SPECTRAL_FIELDS), seed=int(seed),
+                  u=torch.zeros(n_u, dtype=torch.float32, device=dev), v=torch.zeros(n_v, dtype=torch.float32, device=dev),
+                  sigma=torch.zeros(len(mats), dtype=torch.float32, device=dev))
+        sn["scratch"] = ops.spectral_scratch(sn["u"], sn["v"])
+        self._sn = sn
+        try:
+            self.load_spectral_state(self.spectral_draws(self._table, seed))
+            ops.spectral_fwd(self._flat_params.detach(), None, sn["u"], sn["v"], sn["sigma"], sn["scratch"], sn["mats_dev"], ops.SN_WARM_ITERS)
+            for c in self._ctxs.values():
+                check(native.lib().mi355_resnet50_set_spectral_norm(c, 1, ptr(sn["u"]), ptr(sn["v"])))
+        except Exception:
+            for c in self._ctxs.values():  # (best effort: the first error is the one to report)
+                native.lib().mi355_resnet50_set_spectral_norm(c, 0, None, None)
+            self._sn = None
+            raise
+
+    @property
+    def spectral_u(self):
+        return None if self._sn is None else self._sn["u"]
+
+    @property
+    def spectral_v(self):
+        return None if self._sn is None else self._sn["v"]
+
+    def _spectral_slots(self):
+        names = self._conv_names()
+        shapes = {off: shape for _, kind, off, shape in self._table if kind == 0 and len(shape) == 4}
+        for off, L, R, u0, v0 in self._sn["mats"]:
+            co, ci, kh, kw = shapes[off]
+            yield names[off], slice(u0, u0 + R), slice(v0, v0 + L), (kh, kw, ci)
+
+    def spectral_state(self):
+        """{conv name: (u [Cout], v [Cin, K, K])} in torch's layout (copies): what torch keeps as parametrizations.weight.0._u / _v"""
+        if self._sn is None:
+            raise RuntimeError("spectral_state: spectral normalisation is off")
+        return {name: (self._sn["u"][us].clone(), self._sn["v"][vs].view(*khwc).permute(2, 0, 1).clone(memory_format=torch.contiguous_format))
+                for name, us, vs, khwc in self._spectral_slots()}
+
+    @torch.no_grad()
+    def load_spectral_state(self, d):
+        """sets u and v from {conv name: (u [Cout], v [Cin, K, K] or flat in that order)}: teacher forcing, or a state carried across a resume"""
+        if self._sn is None:
+            raise RuntimeError("load_spectral_state: spectral normalisation is off")
+        slots = list(self._spectral_slots())
+        missing = [name for name, *_ in slots if name not in d]
+        if missing:
+            raise KeyError(f"load_spectral_state: no state for {missing[:3]}{'...' if len(missing) > 3 else ''}")
+        for name, us, vs, (kh, kw, ci) in slots:
+            u, v = d[name]
+            if u.numel() != us.stop - us.start or v.numel() != vs.stop - vs.start:
+                raise ValueError(f"load_spectral_state: {name}: u of {u.numel()} / v of {v.numel()} elements")
+            self._sn["u"][us] = u.detach().reshape(-1).to(self._sn["u"])
+            self._sn["v"][vs] = v.detach().reshape(ci, kh, kw).permute(1, 2, 0).reshape(-1).to(self._sn["v"])
 
     # ---- module tree with torchvision names --------------------------------------------------------------
     def _canonical_order(self):

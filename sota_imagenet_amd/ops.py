@@ -804,6 +804,59 @@ def weight_std_rows_bwd(g, w_hat, invstd, dw, rows_dev, mode, beta=0.0, row_begi
                                          cur_stream()))
 
 
+# ---- forward spectral normalisation per convolution (include/mi355rn.h, csrc/spectral_norm.hip): the ForwardSpectralNorm callback -------------------
+# stated once for the host; include/mi355rn.h states them for the library (MI355_SN_*) and tests/test_spectral_host.py holds the two together
+SN_EPS = 1e-12  # torch.nn.utils.parametrizations.spectral_norm's eps (rounded to float32 where it is used)
+SN_WARM_ITERS = 15  # the power iterations torch runs at registration
+SN_SLABS = 16  # row slabs per matrix of the column sums: the scratch holds one partial sum per slab and element of v
+
+
+def spectral_scratch(u, v):
+    """the float64 scratch spectral_fwd / spectral_bwd need for vectors of these sizes, on their device"""
+    return torch.empty(_L().mi355_spectral_scratch_doubles(u.numel(), v.numel()), dtype=torch.float64, device=u.device)
+
+
+def _sn_args(who, mats_dev, u, v, sigma, scratch, **arrays):
+    n = next(iter(arrays.values())).numel()
+    _flat_f32(n, **arrays)
+    _need_cuda(mats_dev, u, v, sigma, scratch)
+    if mats_dev.dtype != torch.int64 or mats_dev.dim() != 2 or mats_dev.shape[1] != 4 or mats_dev.shape[0] < 1:
+        raise ValueError(f"mats_dev: expected a CUDA int64 tensor [n, 4] of 32-byte records, got {mats_dev.dtype} {tuple(mats_dev.shape)}")
+    for name, t in (("u", u), ("v", v)):
+        if t.dtype != torch.float32 or t.numel() < 1:
+            raise ValueError(f"{name}: expected a non-empty float32 tensor, got {t.dtype} with {t.numel()}")
+    if sigma.dtype != torch.float32 or sigma.numel() != mats_dev.shape[0]:
+        raise ValueError(f"sigma: expected {mats_dev.shape[0]} float32 elements (one per matrix), got {sigma.dtype} with {sigma.numel()}")
+    need = _L().mi355_spectral_scratch_doubles(u.numel(), v.numel())
+    if scratch.dtype != torch.float64 or scratch.numel() < need:
+        raise ValueError(f"scratch: expected {need} float64 elements (spectral_scratch), got {scratch.dtype} with {scratch.numel()}")
+    if len({t.device for t in (mats_dev, u, v, sigma, scratch, *arrays.values())}) != 1:
+        raise ValueError(f"{who}: the table, u, v, sigma, the scratch and the arrays must live on one device")
+    return n
+
+
+def spectral_fwd(w, w_hat, u, v, sigma, scratch, mats_dev, iters):
+    """`iters` power iterations of every matrix of the table on (u, v) — 1: a training forward; 0: the eval rule, u and v untouched —, sigma[i] of
+    matrix i, and, unless w_hat is None, w_hat = w / sigma (w_hat is w: in place).  w, w_hat: flat fp32 arrays of one size the offsets count
+    from; mats_dev: item_plan.spectral_mats packed with SPECTRAL_FIELDS (CUDA int64 [n, 4]); u, v: the sizes spectral_mats returns.  A matrix
+    that does not fit the arrays is skipped by the kernels; elements outside the matrices are neither read nor written."""
+    arrays = dict(w=w) if w_hat is None else dict(w=w, w_hat=w_hat)
+    n = _sn_args("spectral_fwd", mats_dev, u, v, sigma, scratch, **arrays)
+    check(_L().mi355_spectral_fwd(ptr(w), ptr(w_hat), ptr(u), ptr(v), ptr(sigma), ptr(scratch), n, u.numel(), v.numel(), ptr(mats_dev),
+                                  mats_dev.shape[0], int(iters), cur_stream()))
+
+
+def spectral_bwd(g, w_hat, u, v, sigma, dw, scratch, mats_dev, beta=0.0, row_begin=0, row_end=None):
+    """dw = beta * dw + (the gradient wrt w, from g = the gradient wrt w_hat = w / sigma with u, v, sigma constants) for the matrices whose rows
+    are the slice [row_begin, row_end) of u — whole matrices —: (g - (sum g * w_hat) * u_r * v_c) / sigma"""
+    row_end = u.numel() if row_end is None else int(row_end)
+    if not 0 <= int(row_begin) < row_end <= u.numel():
+        raise ValueError(f"spectral_bwd: rows [{row_begin}, {row_end}) of u[{u.numel()}]")
+    n = _sn_args("spectral_bwd", mats_dev, u, v, sigma, scratch, g=g, w_hat=w_hat, dw=dw)
+    check(_L().mi355_spectral_bwd(ptr(g), ptr(w_hat), ptr(u), ptr(v), ptr(sigma), ptr(dw), ptr(scratch), n, u.numel(), v.numel(), ptr(mats_dev),
+                                  mats_dev.shape[0], int(row_begin), row_end, float(beta), cur_stream()))
+
+
 # ---- the log histogram of |x| (include/mi355rn.h, csrc/optim_hist.hip): the GradDistributionTB callback of the reference ----------------------------
 # the bins, stated once for the host; csrc/absbin.h states them for the kernels and tests/test_grad_dist_host.py holds the two together
 ABSBIN_BINS, ABSBIN_SHIFT, ABSBIN_K0 = 512, 20, (77 << 3) + 2
