@@ -214,6 +214,29 @@ int mi355_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, in
 int mi355_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W,
                       int C, void* stream);
 
+/* The stem tail of the ResNet-50 executor, per op (what forward / backward_stem of resnet_exec.cpp launch).
+ * Forward: p[N,H/2,W/2,C] = maxpool3x3/2/pad1(relu(y * scale[c] + shift[c])) from the raw conv output y[N,H,W,C] — the activation is
+ *   rounded to dtype before the maximum and never stored; idx[N,H/2,W/2,C] u8 = kh * 3 + kw of the first maximum of the window in
+ *   row-major scan order (in-image taps only, as mi355_maxpool_fwd); bits[N,H,W,C/V] u8, V = 16 / sizeof(element) values per byte:
+ *   bit e of byte (n, h, w, v) = (y * scale + shift > 0) of channel v * V + e.  H, W even, C a multiple of 8.
+ *   form  0: the launcher's own rule — what the executor runs (3 for bf16 with even H/2 and W/2 unless MI355_POOL_KEYS=0,
+ *            2 for any other dtype / knob at such a shape, else 1)
+ *         1: one thread per window;  2: one thread per 2 x 2 block of windows (H/2, W/2 even);
+ *         3: packed (value, tap) integer keys (bf16, H/2, W/2 even); its bit is (stored value != 0), which differs from forms
+ *            1 and 2 only for positive values below 2^-134.  NaN inputs: forms 1 and 2 propagate them, form 3 does not.
+ *   A form the shape or dtype does not allow is MI355_E_ARG before any launch (never silently another form).
+ * Backward: from dp[N,H/2,W/2,C], the gradient wrt p: g = the max pool's backward under idx (a pixel adds its windows in (oh, ow)
+ *   order in fp32, the sum is rounded to dtype), zeroed where its bit is clear; then BatchNorm backward on y with the saved
+ *   mean / invstd: dbeta = sum g, dgamma = sum g * x_hat (beta_acc = 0 overwrite / 1 accumulate), dx[N,H,W,C] = gamma * invstd *
+ *   (g - dbeta / M - x_hat * dgamma / M), M = N*H*W.  The pool gradient at full resolution is never stored.
+ *   C = 64, H, W even, N*H*W*C*sizeof(element) below 2^32 - 16 (32-bit buffer offsets); ws >= mi355_bn_workspace_bytes(C) bytes.
+ * replaces cuDNN BN fwd/bwd + ATen relu / max_pool2d_with_indices fwd/bwd on the stem — callbacks.py:316-317 (K3-K5, K8) */
+int mi355_bn_relu_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* p, uint8_t* idx, uint8_t* bits,
+                          int N, int H, int W, int C, int form, void* stream);
+int mi355_stem_bwd(int dtype, const void* dp, const uint8_t* idx, const uint8_t* bits, const void* y, const float* gamma,
+                   const float* mean, const float* invstd, void* dx, float* dgamma, float* dbeta, float beta_acc, int N, int H,
+                   int W, int C, void* ws, size_t ws_bytes, void* stream);
+
 /* global average pool x[N,HW,C] -> pooled[N,C] fp32, and its backward (broadcast of dpooled/HW).
  * replaces ATen mean / its backward — callbacks.py:316-317 (K6)                                     */
 int mi355_gap_fwd(int dtype, const void* x, float* pooled, int N, int HW, int C, void* stream);

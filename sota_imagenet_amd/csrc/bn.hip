@@ -1095,4 +1095,19 @@ int mi355_bn_bwd(int dtype, const void* dout, const void* out, const void* x, co
   return launch_bn_bwd_apply(dtype, dout, mask, x, save_mean, save_invstd, coef, dx, M, C, s, nullptr, slope);
 }
 
+// the executor's backward_stem sequence (resnet_exec.cpp), per op
+int mi355_stem_bwd(int dtype, const void* dp, const uint8_t* idx, const uint8_t* bits, const void* y, const float* gamma, const float* mean,
+                   const float* invstd, void* dx, float* dgamma, float* dbeta, float beta_acc, int N, int H, int W, int C, void* ws,
+                   size_t ws_bytes, void* stream) {
+  MI355_ARG(gamma && mean && invstd && dx && dgamma && dbeta && N >= 1, "stem_bwd: null pointer / N=%d", N);
+  MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = (float*)ws;
+  float* coef = partial + (size_t)bn_max_blocks() * 2 * C;
+  int nblk = 0;
+  MI355_TRY(launch_stem_bwd_reduce(dtype, dp, idx, bits, y, mean, invstd, partial, &nblk, N, H, W, C, s));
+  MI355_TRY(launch_bn_bwd_finalize(partial, nblk, N * H * W, C, gamma, invstd, dgamma, dbeta, beta_acc, coef, s));
+  return launch_stem_bwd_apply(dtype, dp, idx, bits, y, mean, invstd, coef, dx, N, H, W, C, s);
+}
+
 }  // extern "C"

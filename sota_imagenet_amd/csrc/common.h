@@ -321,7 +321,7 @@ int launch_fp8_scale_update(float* scale, unsigned* amax, int n, float headroom,
 // pooling / head
 // p = maxpool3x3/2(relu(y*scale+shift)) + argmax + the ReLU bit mask of the (never stored) full-resolution activation
 int launch_bn_relu_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* p, uint8_t* idx,
-                           uint8_t* bits, int N, int H, int W, int C, hipStream_t s);
+                           uint8_t* bits, int N, int H, int W, int C, int form /* 0: the launcher's rule */, hipStream_t s);
 int launch_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C,
                        hipStream_t s);
 int launch_gap_fwd(int dtype, const void* x, float* pooled, int N, int HW, int C, hipStream_t s);

@@ -626,18 +626,24 @@ extern "C" int mi355_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx
   });
 }
 
+// form: 0 the rule below (what the executor runs); 1 one thread per window, 2 one thread per 2 x 2 output block, 3 packed keys — forced, for the per-op
+// entry point (mi355_bn_relu_maxpool); a form the shape or dtype does not allow is refused, never replaced by another
 int launch_bn_relu_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* p, uint8_t* idx,
-                           uint8_t* bits, int N, int H, int W, int C, hipStream_t s) {
+                           uint8_t* bits, int N, int H, int W, int C, int form, hipStream_t s) {
   MI355_ARG(H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "bn_relu_maxpool: H=%d W=%d C=%d", H, W, C);
+  MI355_ARG(form >= 0 && form <= 3, "bn_relu_maxpool: form=%d outside 0..3", form);
   const int Ho = H / 2, Wo = W / 2;
   const bool blocks2 = Ho % 2 == 0 && Wo % 2 == 0;  // 2 x 2 output blocks (every size the network is run at: H, W multiples of 32)
-  if (blocks2 && dtype == MI355_BF16 && knobs().pool_keys) {  // packed (value, tap) keys: bf16 only
+  MI355_ARG(form < 2 || blocks2, "bn_relu_maxpool: form %d works on 2 x 2 output blocks, H/2=%d W/2=%d must be even", form, Ho, Wo);
+  MI355_ARG(form != 3 || dtype == MI355_BF16, "bn_relu_maxpool: form 3 (packed keys) is bf16 only, dtype %d", dtype);
+  if (form == 0) form = !blocks2 ? 1 : dtype == MI355_BF16 && knobs().pool_keys ? 3 : 2;
+  if (form == 3) {  // packed (value, tap) keys: bf16 only
     const int grid = grid_for((size_t)N * (Ho / 2) * (Wo / 2) * (C / Vec16<bf16_t>::N));
     hipLaunchKernelGGL(bn_relu_maxpool3_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift, (bf16_t*)p, idx, bits, N, H, W, C, Ho, Wo);
     MI355_LAUNCH_CHECK();
     return 0;
   }
-  if (blocks2)
+  if (form == 2)
     return with_elem(dtype, "bn_relu_maxpool", [&](auto e) -> int {
       using T = typename decltype(e)::type;
       const int grid = grid_for((size_t)N * (Ho / 2) * (Wo / 2) * (C / Vec16<T>::N));
@@ -751,6 +757,11 @@ extern "C" {
 int mi355_stem_ingest(int dtype, const float* x_nchw, void* xpad, int N, int H, int W, void* stream) {
   MI355_ARG(x_nchw && xpad && H % 2 == 0 && W % 2 == 0, "stem_ingest: bad arguments");
   return launch_stem_ingest(dtype, x_nchw, xpad, N, H, W, (hipStream_t)stream);
+}
+int mi355_bn_relu_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* p, uint8_t* idx, uint8_t* bits, int N, int H,
+                          int W, int C, int form, void* stream) {
+  MI355_ARG(y && scale && shift && p && idx && bits && N >= 1, "bn_relu_maxpool: null pointer / N=%d", N);
+  return launch_bn_relu_maxpool(dtype, y, scale, shift, p, idx, bits, N, H, W, C, form, (hipStream_t)stream);
 }
 int mi355_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C,
                       void* stream) {

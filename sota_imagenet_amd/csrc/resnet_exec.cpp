@@ -1056,7 +1056,7 @@ int mi355_resnet50_forward(mi355_ctx* c, const float* x_nchw, float* logits, int
     const int C = 64;
     Prof p(c, PC_BN_APPLY, 0, (double)N * c->stem.Hout * c->stem.Wout * C * c->es * 1.25, s);
     MI355_TRY(launch_bn_relu_maxpool(c->dtype, c->stem.y, c->stem.stat + 2 * C, c->stem.stat + 3 * C, c->p0, c->pool_idx,
-                                     c->a0_bits, N, c->stem.Hout, c->stem.Wout, C, s));
+                                     c->a0_bits, N, c->stem.Hout, c->stem.Wout, C, 0, s));
   }
   for (auto& b : c->blocks) {
     if (b.has_ds) {  // the downsample conv + its statistics run beside conv1..conv3

@@ -299,6 +299,44 @@ def maxpool_bwd(dy, idx, x_shape):
     return dx
 
 
+def bn_relu_maxpool(y, scale, shift, form=0):
+    """The stem's fused tail on the raw conv output y [N,H,W,C]: (p, idx, bits) = pooled relu(y * scale + shift), argmax codes, ReLU bits
+    [N,H,W,C/V] (V = 16 bytes of elements).  form: 0 the executor's rule, 1 / 2 / 3 one of the three kernels forced (mi355rn.h)."""
+    _need_cuda(y, scale, shift)
+    N, H, W, C = y.shape
+    V = 16 // y.element_size()
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t.dtype != torch.float32 or t.numel() != C:
+            raise ValueError(f"bn_relu_maxpool: {name} must be {C} fp32 values")
+    p = torch.empty((N, H // 2, W // 2, C), dtype=y.dtype, device=y.device)
+    idx = torch.empty((N, H // 2, W // 2, C), dtype=torch.uint8, device=y.device)
+    bits = torch.empty((N, H, W, C // V), dtype=torch.uint8, device=y.device)
+    check(_L().mi355_bn_relu_maxpool(dtype_code(y.dtype), ptr(y), ptr(scale), ptr(shift), ptr(p), ptr(idx), ptr(bits), N, H, W, C, int(form),
+                                     cur_stream()))
+    return p, idx, bits
+
+
+def stem_bwd(dp, idx, bits, y, gamma, mean, invstd, dgamma=None, dbeta=None, beta_acc=0.0):
+    """The executor's stem backward from the pooled gradient dp [N,H/2,W/2,64]: returns (dx wrt y, dgamma, dbeta).  dgamma / dbeta given:
+    written in place (beta_acc = 1 accumulates onto them)."""
+    _need_cuda(dp, idx, bits, y, gamma, mean, invstd, dgamma, dbeta)
+    N, H, W, C = y.shape
+    V = 16 // y.element_size()
+    if (tuple(dp.shape) != (N, H // 2, W // 2, C) or dp.dtype != y.dtype or tuple(idx.shape) != tuple(dp.shape) or idx.dtype != torch.uint8
+            or tuple(bits.shape) != (N, H, W, C // V) or bits.dtype != torch.uint8):
+        raise ValueError(f"stem_bwd: dp / idx [N,H/2,W/2,C] and bits [N,H,W,C/{V}] u8 do not match y {tuple(y.shape)} {y.dtype}")
+    for name, t in (("gamma", gamma), ("mean", mean), ("invstd", invstd), ("dgamma", dgamma), ("dbeta", dbeta)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != C):
+            raise ValueError(f"stem_bwd: {name} must be {C} fp32 values")
+    dx = torch.empty_like(y)
+    dg = dgamma if dgamma is not None else torch.zeros(C, dtype=torch.float32, device=y.device)
+    db = dbeta if dbeta is not None else torch.zeros(C, dtype=torch.float32, device=y.device)
+    ws, n = _bn_ws(C, y.device)
+    check(_L().mi355_stem_bwd(dtype_code(y.dtype), ptr(dp), ptr(idx), ptr(bits), ptr(y), ptr(gamma), ptr(mean), ptr(invstd), ptr(dx), ptr(dg),
+                              ptr(db), beta_acc, N, H, W, C, ptr(ws), n, cur_stream()))
+    return dx, dg, db
+
+
 def gap_fwd(x):
     _need_cuda(x)
     N, H, W, C = x.shape

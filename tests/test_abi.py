@@ -82,10 +82,43 @@ def test_elementwise_entry_points_refuse_a_dtype_outside_their_set(dtype):
              "mi355_maxpool_fwd": (dtype, p, p, p, N, H, W, C, None),
              "mi355_maxpool_bwd": (dtype, p, p, p, N, H, W, C, None),
              "mi355_gap_fwd": (dtype, p, p, N, HW, C, None),
-             "mi355_gap_bwd": (dtype, p, p, N, HW, C, None)}
+             "mi355_gap_bwd": (dtype, p, p, N, HW, C, None),
+             "mi355_bn_relu_maxpool": (dtype, p, p, p, p, p, p, N, H, W, C, 0, None),
+             "mi355_stem_bwd": (dtype, p, p, p, p, p, p, p, p, p, p, 0.0, N, H, W, C, p, 1 << 30, None)}
     for name, args in calls.items():
         rc = getattr(L, name)(*args)
         assert rc == -1 and "dtype" in native.last_error(), (name, rc, native.last_error())
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="host-side refusal, called with dummy pointers: never sent to a GPU")
+def test_stem_tail_entry_points_refuse_what_their_kernels_cannot_run():
+    """A forced form of the fused BN + ReLU + max pool that the shape or dtype does not allow is MI355_E_ARG before any launch — never another form in
+    its place; the stem backward keeps its launchers' refusals (64 channels, even H and W, 32-bit buffer offsets)."""
+    L = native.lib()
+    p = torch.zeros(64).data_ptr()  # non-null, never dereferenced
+
+    def pool(dtype, H, W, form, C=64):
+        return L.mi355_bn_relu_maxpool(dtype, p, p, p, p, p, p, 2, H, W, C, form, None)
+
+    def bwd(dtype, N, H, W, C):
+        return L.mi355_stem_bwd(dtype, p, p, p, p, p, p, p, p, p, p, 0.0, N, H, W, C, p, 1 << 30, None)
+
+    for dtype in (native.F32, native.BF16):
+        for H, W in ((4, 6), (6, 4), (6, 10)):  # an odd pooled height or width: one thread per window is the only form
+            for form in (2, 3):
+                assert pool(dtype, H, W, form) == -1 and "form %d" % form in native.last_error(), (dtype, H, W, form, native.last_error())
+        for form in (-1, 4):
+            assert pool(dtype, 8, 8, form) == -1 and "outside 0..3" in native.last_error()
+        assert pool(dtype, 7, 8, 0) == -1 and "H=7" in native.last_error()
+        assert pool(dtype, 8, 8, 1, C=60) == -1 and "C=60" in native.last_error()
+        assert bwd(dtype, 2, 8, 8, 128) == -1 and "64 channels" in native.last_error()
+        assert bwd(dtype, 2, 7, 8, 64) == -1 and "H=7" in native.last_error()
+        assert bwd(dtype, 2, 8, 6 + 1, 64) == -1 and "W=7" in native.last_error()
+    assert pool(native.F32, 8, 8, 3) == -1 and "bf16 only" in native.last_error()  # packed keys
+    assert bwd(native.F32, 1024, 128, 128, 64) == -1 and "32-bit offsets" in native.last_error()  # 2^32 bytes
+    assert bwd(native.BF16, 2048, 128, 128, 64) == -1 and "32-bit offsets" in native.last_error()
+    assert L.mi355_bn_relu_maxpool(native.F32, None, p, p, p, p, p, 2, 8, 8, 64, 0, None) == -1 and "null" in native.last_error()
+    assert L.mi355_stem_bwd(native.F32, p, p, p, p, p, p, p, p, p, p, 0.0, 2, 8, 8, 64, p, 16, None) == -1 and "workspace" in native.last_error()
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the GPU-less failure mode")

@@ -7,6 +7,7 @@ Tolerances (normalised max error  max|got-ref| / max|ref|):
 import pytest
 import torch
 
+import stem_tail_common as ST
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -187,15 +188,28 @@ def test_bn_eval(dev, dtype):
 def test_maxpool(dev, dtype):
     from sota_imagenet_amd import ops
 
-    N, H, W, C = 2, 16, 12, 64
-    x = torch.relu(rnd((N, H, W, C), 41, dtype))  # post-ReLU input: many exact ties at 0
-    y_ref, _ = R.maxpool(x)
-    dy = rnd(tuple(y_ref.shape), 42, dtype)
-    dx_ref = R.maxpool_bwd(x, dy)
-    y, idx = ops.maxpool_fwd(x.to(dev, dtype))
-    assert torch.equal(y.float().cpu(), y_ref)
-    dx = ops.maxpool_bwd(dy.to(dev, dtype), idx, (N, H, W, C))
-    assert nerr(dx, dx_ref) < TOL[dtype]
+    # one window per image; odd pooled sizes; two channel slabs
+    for N, H, W, C in [(2, 16, 12, 64), (1, 2, 2, 64), (2, 6, 10, 64), (3, 16, 12, 128)]:
+        x = torch.relu(rnd((N, H, W, C), 41, dtype))  # post-ReLU input: many exact ties at 0
+        y_ref, _ = R.maxpool(x)
+        dy = rnd(tuple(y_ref.shape), 42, dtype)
+        dx_ref = R.maxpool_bwd(x, dy)
+        y, idx = ops.maxpool_fwd(x.to(dev, dtype))
+        assert torch.equal(y.float().cpu(), y_ref)
+        assert torch.equal(idx.cpu(), ST.pool_codes(x)[1]), (N, H, W, C)  # the codes themselves: the first maximum of the window's in-image taps
+        dx = ops.maxpool_bwd(dy.to(dev, dtype), idx, (N, H, W, C))
+        assert nerr(dx, dx_ref) < TOL[dtype]
+        assert nerr(dx, ST.pool_scatter(dy, idx.cpu(), (N, H, W, C))) < TOL[dtype]  # teacher-forced on the returned codes
+        # dyadic data (k/4): plateaus at every level, and a pixel's sum of at most four gradients is exact in either dtype
+        g = torch.Generator().manual_seed(43)
+        xd = torch.randint(-6, 7, (N, H, W, C), generator=g).float() / 4
+        dyd = torch.randint(-8, 9, tuple(y_ref.shape), generator=g).float() / 4
+        yd, idxd = ops.maxpool_fwd(xd.to(dev, dtype))
+        pd, coded = ST.pool_codes(xd)
+        assert torch.equal(yd.double().cpu(), pd) and torch.equal(idxd.cpu(), coded), (N, H, W, C)
+        dxd = ops.maxpool_bwd(dyd.to(dev, dtype), idxd, (N, H, W, C))
+        assert torch.equal(dxd.float().cpu(), ST.pool_scatter(dyd, idxd.cpu(), (N, H, W, C))), (N, H, W, C)
+        assert torch.equal(dxd.float().cpu(), R.maxpool_bwd(xd, dyd)), (N, H, W, C)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
