@@ -206,6 +206,24 @@ int mi355_bn_bwd(int dtype, const void* dout, const void* out, const void* x, co
                  const float* save_mean, const float* save_invstd, void* dx, void* dz_out,
                  float* dgamma, float* dbeta, float beta_acc, int M, int C, int relu, void* ws,
                  size_t ws_bytes, void* stream);
+/* Every mi355_bn_* call refuses a null required pointer (residual, dz_out and the running statistics of the training forward, as a pair, are
+ * optional) and M < 1 with MI355_E_ARG before any launch.
+ *
+ * The two BatchNorm calls of the executors, per op (bn_apply / bn_backward of resnet_exec.cpp, without the e4m3 twin).
+ * mi355_bn_apply: out = act(x * scale[c] + shift[c] (+ residual | + x2 * scale2[c] + shift2[c])) on GIVEN fp32 coefficients, each product-sum one
+ *   fma, the sum rounded to dtype once.  relu: 0 / 1 / 2 as above.  bits (optional, relu != 0): [M][C/V] u8, V = 16 / sizeof(element) values per
+ *   byte, bit e of byte (m, v) = (the sum before the activation > 0) of channel v * V + e — clear for 0 and -0; the upper bits of an fp32
+ *   byte are zero.  MI355_E_ARG, never another form: residual together with x2; relu = 2 with bits and an addend; bits with relu = 0.
+ * mi355_bn_bwd_bits: dz = g where the bit is set, else g * slope (relu 1: slope 0; 2: 0.01; 0: no mask, bits NULL), rounded to dtype only where
+ *   dz_out stores it; dbeta = sum dz, dgamma = sum dz * x_hat (beta_acc as above); dx = gamma * invstd * (dz - dbeta / M - x_hat * dgamma / M).
+ *   partial / nblk: [nblk][2][C] fp32 rows of (sum dz, sum dz * x_hat) a fused data-gradient epilogue left (mi355_conv2d_dgrad_bn): the reduce
+ *   pass is skipped — unless dz_out is given, which needs that pass; NULL / 0: the call reduces itself.  dx may alias g, dz_out may alias g.
+ *   ws: >= mi355_bn_workspace_bytes(C) bytes.                                                                                               */
+int mi355_bn_apply(int dtype, const void* x, const float* scale, const float* shift, const void* residual, const void* x2,
+                   const float* scale2, const float* shift2, void* out, uint8_t* bits, int M, int C, int relu, void* stream);
+int mi355_bn_bwd_bits(int dtype, const void* g, const uint8_t* bits, const void* x, const float* gamma, const float* mean,
+                      const float* invstd, void* dx, void* dz_out, float* dgamma, float* dbeta, float beta_acc, int M, int C, int relu,
+                      const float* partial, int nblk, void* ws, size_t ws_bytes, void* stream);
 
 /* MaxPool 3x3 stride 2 pad 1 on NHWC; idx[N,Ho,Wo,C] uint8 = window position of the first maximum.
  * replaces ATen max_pool2d_with_indices fwd/bwd — callbacks.py:316-317 (K5)                         */

@@ -1044,6 +1044,8 @@ int mi355_bn_fwd_train(int dtype, const void* x, const void* residual, void* out
                        const float* beta, float* running_mean, float* running_var, float* save_mean,
                        float* save_invstd, int M, int C, float eps, float momentum, int relu, void* ws,
                        size_t ws_bytes, void* stream) {
+  MI355_TRY(check_c(dtype, C));
+  MI355_ARG(x && out && gamma && beta && save_mean && save_invstd && !running_mean == !running_var && M >= 1, "bn_fwd_train: null pointer / M=%d", M);
   MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)ws;
@@ -1060,6 +1062,9 @@ int mi355_bn_fwd_train(int dtype, const void* x, const void* residual, void* out
 int mi355_bn_fwd_train_partial(int dtype, const void* x, const void* residual, void* out, const float* gamma, const float* beta,
                                float* running_mean, float* running_var, float* save_mean, float* save_invstd, int M, int C, float eps,
                                float momentum, int relu, const float* partial, int nblk, void* ws, size_t ws_bytes, void* stream) {
+  MI355_TRY(check_c(dtype, C));
+  MI355_ARG(x && out && gamma && beta && save_mean && save_invstd && !running_mean == !running_var && M >= 1, "bn_fwd_train_partial: null pointer / M=%d",
+            M);
   MI355_ARG(ws && ws_bytes >= (size_t)2 * C * 4 && partial && nblk >= 1, "bn_fwd_train_partial: nblk=%d, workspace of 2*C floats", nblk);
   hipStream_t s = (hipStream_t)stream;
   float* scale = (float*)ws;
@@ -1072,6 +1077,8 @@ int mi355_bn_fwd_train_partial(int dtype, const void* x, const void* residual, v
 int mi355_bn_fwd_eval(int dtype, const void* x, const void* residual, void* out, const float* gamma,
                       const float* beta, const float* running_mean, const float* running_var, int M, int C, float eps,
                       int relu, void* ws, size_t ws_bytes, void* stream) {
+  MI355_TRY(check_c(dtype, C));
+  MI355_ARG(x && out && gamma && beta && running_mean && running_var && M >= 1, "bn_fwd_eval: null pointer / M=%d", M);
   MI355_ARG(ws && ws_bytes >= (size_t)2 * C * 4, "bn_eval: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* scale = (float*)ws;
@@ -1083,6 +1090,8 @@ int mi355_bn_fwd_eval(int dtype, const void* x, const void* residual, void* out,
 int mi355_bn_bwd(int dtype, const void* dout, const void* out, const void* x, const float* gamma,
                  const float* save_mean, const float* save_invstd, void* dx, void* dz_out, float* dgamma,
                  float* dbeta, float beta_acc, int M, int C, int relu, void* ws, size_t ws_bytes, void* stream) {
+  MI355_TRY(check_c(dtype, C));
+  MI355_ARG(dout && (out || !relu) && x && gamma && save_mean && save_invstd && dx && dgamma && dbeta && M >= 1, "bn_bwd: null pointer / M=%d", M);
   MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)ws;
@@ -1093,6 +1102,41 @@ int mi355_bn_bwd(int dtype, const void* dout, const void* out, const void* x, co
   MI355_TRY(launch_bn_bwd_reduce(dtype, dout, mask, x, save_mean, save_invstd, dz_out, partial, &nblk, M, C, s, nullptr, slope));
   MI355_TRY(launch_bn_bwd_finalize(partial, nblk, M, C, gamma, save_invstd, dgamma, dbeta, beta_acc, coef, s));
   return launch_bn_bwd_apply(dtype, dout, mask, x, save_mean, save_invstd, coef, dx, M, C, s, nullptr, slope);
+}
+
+// the executors' bn_apply (resnet_exec.cpp), per op: launch_bn_apply on given coefficients, without the e4m3 twin
+int mi355_bn_apply(int dtype, const void* x, const float* scale, const float* shift, const void* residual, const void* x2, const float* scale2,
+                   const float* shift2, void* out, uint8_t* bits, int M, int C, int relu, void* stream) {
+  MI355_TRY(check_c(dtype, C));
+  MI355_ARG(x && scale && shift && out && (!x2 || (scale2 && shift2)) && M >= 1, "bn_apply: null pointer / M=%d", M);
+  MI355_ARG(relu >= 0 && relu <= 2, "bn_apply: relu=%d outside 0..2", relu);
+  MI355_ARG(!bits || relu != 0, "bn_apply: a bit mask needs an activation (relu=0)");
+  return launch_bn_apply(dtype, x, scale, shift, residual, x2, scale2, shift2, out, M, C, relu, (hipStream_t)stream, bits);
+}
+
+// the executors' bn_backward sequence (resnet_exec.cpp), per op: reduce over the bit mask (or the partial rows a fused data-gradient epilogue
+// left), finalize, apply.  A masked write-back forces the reduce, as there: the rows of an epilogue come without it
+int mi355_bn_bwd_bits(int dtype, const void* g, const uint8_t* bits, const void* x, const float* gamma, const float* mean, const float* invstd,
+                      void* dx, void* dz_out, float* dgamma, float* dbeta, float beta_acc, int M, int C, int relu, const float* partial, int nblk,
+                      void* ws, size_t ws_bytes, void* stream) {
+  MI355_TRY(check_c(dtype, C));
+  MI355_ARG(g && x && gamma && mean && invstd && dx && dgamma && dbeta && M >= 1, "bn_bwd_bits: null pointer / M=%d", M);
+  MI355_ARG(relu >= 0 && relu <= 2, "bn_bwd_bits: relu=%d outside 0..2", relu);
+  MI355_ARG((relu != 0) == (bits != nullptr), "bn_bwd_bits: relu=%d %s bit mask", relu, relu ? "needs a" : "takes no");
+  MI355_ARG(partial ? nblk >= 1 : nblk == 0, "bn_bwd_bits: nblk=%d %s partial rows", nblk, partial ? "with" : "without");
+  MI355_ARG(ws && ws_bytes >= mi355_bn_workspace_bytes(C), "bn: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* own = (float*)ws;
+  float* coef = own + (size_t)bn_max_blocks() * 2 * C;
+  const float slope = relu == 2 ? 0.01f : 0.f;
+  const float* rows = partial;
+  if (!rows || dz_out) {
+    rows = own;
+    MI355_TRY(launch_bn_bwd_reduce(dtype, g, nullptr, x, mean, invstd, dz_out, own, &nblk, M, C, s, bits, slope));
+  }
+  MI355_TRY(launch_bn_bwd_finalize(rows, nblk, M, C, gamma, invstd, dgamma, dbeta, beta_acc, coef, s));
+  // after a masked write-back the mask is already applied
+  return launch_bn_bwd_apply(dtype, dz_out ? dz_out : g, nullptr, x, mean, invstd, coef, dx, M, C, s, dz_out ? nullptr : bits, slope);
 }
 
 // the executor's backward_stem sequence (resnet_exec.cpp), per op

@@ -267,19 +267,80 @@ def bn_fwd_eval(x, gamma, beta, running_mean, running_var, residual=None, relu=T
     return out
 
 
-def bn_bwd(dout, out, x, gamma, save_mean, save_invstd, relu=True, want_dz=False):
-    """Returns (dx, dgamma, dbeta, dz or None)."""
-    _need_cuda(dout, out, x, gamma, save_mean, save_invstd)
+def _bn_c_vectors(who, C, **named):
+    for name, t in named.items():
+        if t is not None and (t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be {C} contiguous fp32 values")
+
+
+def _bn_like(who, x, **named):
+    for name, t in named.items():
+        if t is not None and (t.shape != x.shape or t.dtype != x.dtype or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous {tuple(x.shape)} {x.dtype} tensor like x")
+
+
+def bn_bwd(dout, out, x, gamma, save_mean, save_invstd, relu=True, want_dz=False, dgamma=None, dbeta=None, beta_acc=0.0):
+    """Returns (dx, dgamma, dbeta, dz or None).  dgamma / dbeta given: written in place (beta_acc = 1 accumulates onto them)."""
+    _need_cuda(dout, out, x, gamma, save_mean, save_invstd, dgamma, dbeta)
     C = x.shape[-1]
     M = x.numel() // C
+    _bn_c_vectors("bn_bwd", C, dgamma=dgamma, dbeta=dbeta)
     dx = torch.empty_like(x)
     dz = torch.empty_like(x) if want_dz else None
-    dg = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    dg = dgamma if dgamma is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
+    db = dbeta if dbeta is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
     ws, n = _bn_ws(C, x.device)
     check(_L().mi355_bn_bwd(dtype_code(x.dtype), ptr(dout), ptr(out), ptr(x), ptr(gamma), ptr(save_mean), ptr(save_invstd), ptr(dx),
-                            ptr(dz), ptr(dg), ptr(db), 0.0, M, C, int(relu), ptr(ws), n, cur_stream()))
+                            ptr(dz), ptr(dg), ptr(db), float(beta_acc), M, C, int(relu), ptr(ws), n, cur_stream()))
     return dx, dg, db, dz
+
+
+def bn_apply(x, scale, shift, residual=None, x2=None, scale2=None, shift2=None, relu=1, want_bits=False):
+    """The executors' BatchNorm apply pass on given fp32 coefficients (mi355_bn_apply): act(x * scale + shift (+ residual | + x2 * scale2 + shift2)).
+    relu: 0 / 1 / 2 (leaky, slope 0.01).  Returns (out, bits): bits [..., C/V] u8 (V = 16 bytes of elements, bit e of byte v = the sum of channel
+    v * V + e was > 0) with want_bits, else None.  Combinations the kernels do not have raise (native.check)."""
+    _need_cuda(x, scale, shift, residual, x2, scale2, shift2)
+    C = x.shape[-1]
+    M = x.numel() // C
+    V = 16 // x.element_size()
+    if not x.is_contiguous():
+        raise ValueError("bn_apply: x must be contiguous")
+    _bn_c_vectors("bn_apply", C, scale=scale, shift=shift, scale2=scale2, shift2=shift2)
+    _bn_like("bn_apply", x, residual=residual, x2=x2)
+    out = torch.empty_like(x)
+    bits = torch.empty(tuple(x.shape[:-1]) + (C // V,), dtype=torch.uint8, device=x.device) if want_bits else None
+    check(_L().mi355_bn_apply(dtype_code(x.dtype), ptr(x), ptr(scale), ptr(shift), ptr(residual), ptr(x2), ptr(scale2), ptr(shift2), ptr(out),
+                              ptr(bits), M, C, int(relu), cur_stream()))
+    return out, bits
+
+
+def bn_bwd_bits(g, bits, x, gamma, mean, invstd, relu=1, dx=None, dz_out=None, dgamma=None, dbeta=None, beta_acc=0.0, partial=None):
+    """The executors' BatchNorm backward from the ReLU bit mask (mi355_bn_bwd_bits): returns (dx, dgamma, dbeta).  relu 0: bits None.  dx / dz_out
+    given: written in place, either may be g itself.  dgamma / dbeta given: written in place (beta_acc = 1 accumulates).  partial: fp32
+    [nblk, 2, C] rows of (sum dz, sum dz * x_hat) from a fused data-gradient epilogue, in place of the reduce pass (ignored, as in the executor, when
+    dz_out asks for the masked gradient)."""
+    _need_cuda(g, bits, x, gamma, mean, invstd, dx, dz_out, dgamma, dbeta, partial)
+    C = x.shape[-1]
+    M = x.numel() // C
+    V = 16 // x.element_size()
+    if not x.is_contiguous():
+        raise ValueError("bn_bwd_bits: x must be contiguous")
+    _bn_like("bn_bwd_bits", x, g=g, dx=dx, dz_out=dz_out)
+    _bn_c_vectors("bn_bwd_bits", C, gamma=gamma, mean=mean, invstd=invstd, dgamma=dgamma, dbeta=dbeta)
+    if bits is not None and (bits.dtype != torch.uint8 or bits.numel() != M * C // V or not bits.is_contiguous()):
+        raise ValueError(f"bn_bwd_bits: bits must be {M * C // V} contiguous u8 values (one per 16-byte vector)")
+    nblk = 0
+    if partial is not None:
+        if partial.dim() != 3 or partial.shape[1:] != (2, C) or partial.dtype != torch.float32 or not partial.is_contiguous():
+            raise ValueError(f"bn_bwd_bits: partial must be contiguous fp32 [nblk, 2, {C}] rows")
+        nblk = partial.shape[0]
+    dx = dx if dx is not None else torch.empty_like(x)
+    dg = dgamma if dgamma is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
+    db = dbeta if dbeta is not None else torch.zeros(C, dtype=torch.float32, device=x.device)
+    ws, n = _bn_ws(C, x.device)
+    check(_L().mi355_bn_bwd_bits(dtype_code(x.dtype), ptr(g), ptr(bits), ptr(x), ptr(gamma), ptr(mean), ptr(invstd), ptr(dx), ptr(dz_out), ptr(dg),
+                                 ptr(db), float(beta_acc), M, C, int(relu), ptr(partial), nblk, ptr(ws), n, cur_stream()))
+    return dx, dg, db
 
 
 def maxpool_fwd(x):

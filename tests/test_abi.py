@@ -84,7 +84,13 @@ def test_elementwise_entry_points_refuse_a_dtype_outside_their_set(dtype):
              "mi355_gap_fwd": (dtype, p, p, N, HW, C, None),
              "mi355_gap_bwd": (dtype, p, p, N, HW, C, None),
              "mi355_bn_relu_maxpool": (dtype, p, p, p, p, p, p, N, H, W, C, 0, None),
-             "mi355_stem_bwd": (dtype, p, p, p, p, p, p, p, p, p, p, 0.0, N, H, W, C, p, 1 << 30, None)}
+             "mi355_stem_bwd": (dtype, p, p, p, p, p, p, p, p, p, p, 0.0, N, H, W, C, p, 1 << 30, None),
+             "mi355_bn_fwd_train": (dtype, p, p, p, p, p, p, p, p, p, HW, C, 1e-5, 0.1, 1, p, 1 << 30, None),
+             "mi355_bn_fwd_train_partial": (dtype, p, p, p, p, p, p, p, p, p, HW, C, 1e-5, 0.1, 1, p, 1, p, 1 << 30, None),
+             "mi355_bn_fwd_eval": (dtype, p, p, p, p, p, p, p, HW, C, 1e-5, 1, p, 1 << 30, None),
+             "mi355_bn_bwd": (dtype, p, p, p, p, p, p, p, p, p, p, 0.0, HW, C, 1, p, 1 << 30, None),
+             "mi355_bn_apply": (dtype, p, p, p, None, None, None, None, p, p, HW, C, 1, None),
+             "mi355_bn_bwd_bits": (dtype, p, p, p, p, p, p, p, None, p, p, 0.0, HW, C, 1, p, 1, p, 1 << 30, None)}
     for name, args in calls.items():
         rc = getattr(L, name)(*args)
         assert rc == -1 and "dtype" in native.last_error(), (name, rc, native.last_error())
@@ -119,6 +125,81 @@ def test_stem_tail_entry_points_refuse_what_their_kernels_cannot_run():
     assert bwd(native.BF16, 2048, 128, 128, 64) == -1 and "32-bit offsets" in native.last_error()
     assert L.mi355_bn_relu_maxpool(native.F32, None, p, p, p, p, p, 2, 8, 8, 64, 0, None) == -1 and "null" in native.last_error()
     assert L.mi355_stem_bwd(native.F32, p, p, p, p, p, p, p, p, p, p, 0.0, 2, 8, 8, 64, p, 16, None) == -1 and "workspace" in native.last_error()
+
+
+def test_bn_per_op_prototypes():
+    """the two per-op BatchNorm calls that mirror the executors' bn_apply / bn_backward: argument order and types, as tests/test_bn_gpu.py and ops.py
+    pass them"""
+    protos = native.parse_header()
+    norm = lambda ps: [re.sub(r"\s+", " ", q) for q in ps]  # noqa: E731
+    assert protos["mi355_bn_apply"][0] == "int" and norm(protos["mi355_bn_apply"][1]) == [
+        "int dtype", "const void* x", "const float* scale", "const float* shift", "const void* residual", "const void* x2", "const float* scale2",
+        "const float* shift2", "void* out", "uint8_t* bits", "int M", "int C", "int relu", "void* stream"]
+    assert protos["mi355_bn_bwd_bits"][0] == "int" and norm(protos["mi355_bn_bwd_bits"][1]) == [
+        "int dtype", "const void* g", "const uint8_t* bits", "const void* x", "const float* gamma", "const float* mean", "const float* invstd",
+        "void* dx", "void* dz_out", "float* dgamma", "float* dbeta", "float beta_acc", "int M", "int C", "int relu", "const float* partial", "int nblk",
+        "void* ws", "size_t ws_bytes", "void* stream"]
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="host-side refusal, called with dummy pointers: never sent to a GPU")
+def test_bn_entry_points_refuse_before_any_launch():
+    """Every BatchNorm entry point refuses a null required pointer and M < 1 (M = 0 would divide by zero in the finalize); the two per-op calls refuse the
+    combinations their kernels do not have — never silently another form.  All MI355_E_ARG with a message, before anything is launched."""
+    L = native.lib()
+    p = torch.zeros(64).data_ptr()  # non-null, never dereferenced
+    C, BIG = 64, 1 << 30
+
+    def refused(rc, word):
+        assert rc == -1 and word in native.last_error(), (rc, word, native.last_error())
+
+    calls = {  # name -> (arguments as a list, indices of the required pointers, index of M)
+        "mi355_bn_fwd_train": ([native.F32, p, None, p, p, p, p, p, p, p, 8, C, 1e-5, 0.1, 1, p, BIG, None], (1, 3, 4, 5, 8, 9), 10),
+        "mi355_bn_fwd_train_partial": ([native.F32, p, None, p, p, p, p, p, p, p, 8, C, 1e-5, 0.1, 1, p, 1, p, BIG, None], (1, 3, 4, 5, 8, 9), 10),
+        "mi355_bn_fwd_eval": ([native.F32, p, None, p, p, p, p, p, 8, C, 1e-5, 1, p, BIG, None], (1, 3, 4, 5, 6, 7), 8),
+        "mi355_bn_bwd": ([native.F32, p, p, p, p, p, p, p, None, p, p, 0.0, 8, C, 1, p, BIG, None], (1, 2, 3, 4, 5, 6, 7, 9, 10), 12),
+        "mi355_bn_apply": ([native.F32, p, p, p, None, None, None, None, p, None, 8, C, 1, None], (1, 2, 3, 8), 10),
+        "mi355_bn_bwd_bits": ([native.F32, p, p, p, p, p, p, p, None, p, p, 0.0, 8, C, 1, None, 0, p, BIG, None], (1, 3, 4, 5, 6, 7, 9, 10), 12),
+    }
+    for name, (args, required, m_at) in calls.items():
+        fn = getattr(L, name)
+        for i in required:
+            a = list(args)
+            a[i] = None
+            refused(fn(*a), "null pointer")
+        for M in (0, -3):
+            a = list(args)
+            a[m_at] = M
+            refused(fn(*a), f"M={M}")
+        a = list(args)
+        a[m_at + 1] = 96  # C
+        refused(fn(*a), "C=96")
+    # a running mean without a running variance
+    a = list(calls["mi355_bn_fwd_train"][0])
+    a[6] = None
+    refused(L.mi355_bn_fwd_train(*a), "null pointer")
+
+    def apply(relu, residual=None, x2=None, sc2=None, sh2=None, bits=None, dtype=native.BF16):
+        return L.mi355_bn_apply(dtype, p, p, p, residual, x2, sc2, sh2, p, bits, 8, C, relu, None)
+
+    for dtype in (native.F32, native.BF16):
+        refused(apply(1, residual=p, x2=p, sc2=p, sh2=p, dtype=dtype), "residual and second branch together")
+        refused(apply(2, residual=p, bits=p, dtype=dtype), "leaky bit-mask form")
+        refused(apply(2, x2=p, sc2=p, sh2=p, bits=p, dtype=dtype), "leaky bit-mask form")
+        refused(apply(0, bits=p, dtype=dtype), "a bit mask needs an activation")
+        refused(apply(1, x2=p, sc2=None, sh2=p, dtype=dtype), "null pointer")
+        for relu in (-1, 3):
+            refused(apply(relu, dtype=dtype), "outside 0..2")
+
+    def bwd(relu, bits, partial=None, nblk=0, ws_bytes=BIG):
+        return L.mi355_bn_bwd_bits(native.BF16, p, bits, p, p, p, p, p, None, p, p, 0.0, 8, C, relu, partial, nblk, p, ws_bytes, None)
+
+    refused(bwd(0, p), "relu=0 takes no bit mask")
+    refused(bwd(1, None), "relu=1 needs a bit mask")
+    refused(bwd(2, None), "relu=2 needs a bit mask")
+    refused(bwd(3, p), "outside 0..2")
+    refused(bwd(1, p, partial=p, nblk=0), "nblk=0 with partial rows")
+    refused(bwd(1, p, partial=None, nblk=4), "nblk=4 without partial rows")
+    refused(bwd(1, p, ws_bytes=16), "workspace")
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the GPU-less failure mode")
