@@ -654,6 +654,51 @@ int mi355_spectral_fwd(const float* w, float* w_hat, float* u, float* v, float* 
 int mi355_spectral_bwd(const float* g, const float* w_hat, const float* u, const float* v, const float* sigma, float* dw, double* scratch, size_t n,
                        size_t n_u, size_t n_v, const void* mats, size_t n_mats, size_t row_begin, size_t row_end, float beta, void* stream);
 
+/* Weight penalties in the loss — csrc/ortho_loss.hip: the reference's OrthoLoss, type 1 (sota_imagenet/callbacks.py:126-156, appended to the
+ * criterion by OrthoLossClb, :191-203) and NormLoss (:206-221, NormLossClb :224-229), over the flat fp32 parameter array.  They always read the
+ * raw parameters (the reference penalises parametrizations.weight.original).
+ * OrthoLoss.  Per conv weight viewed as W [O, K] (O rows of K contiguous elements, O <= K):  G = W W^T - I,  F = |G|_F;  where F / O > min_norm
+ * the loss takes F and the gradient (2 / F) G W (0 where F == 0); elsewhere nothing.
+ *   mats[]   { int64 off; int32 len; int32 rows; int64 g0; int64 t0 }   32 bytes: `rows` = O rows of `len` = K elements from element `off` of the
+ *            flat arrays (ANY element offset); the matrix owns gram[g0 .. g0 + O*O) and, with nt = ceil(O / MI355_OL_TILE), the tiles
+ *            tiles[t0 .. t0 + nt (nt + 1) / 2): tile (ti, tj <= ti) at t0 + ti (ti + 1) / 2 + tj
+ *   tiles[]  { int32 mat; int32 ti | tj << 16; int32 item0; int32 n_slabs }   16 bytes: n_slabs = ceil(K / MI355_OL_KSLAB) consecutive items
+ *   items[]  { int32 tile; int32 slab }   8 bytes — item tiles[t].item0 + j is { t, j }
+ *   gitems[] { int32 mat; int32 ti; int32 tc; int32 0 }   16 bytes: row tile ti and the tile of MI355_OL_TILE columns tc of K
+ * mi355_ortho_loss_fwd, 3 launches: every item's partial tile (v_mfma_f32_32x32x2_f32: exact fp32, k ascending) -> partial[]; per tile, G = (the
+ * slab partials added in slab order) - I, stored with its mirror, and the tile's sum of G^2 in double -> tile_ss[]; ONE workgroup: per matrix, in
+ * tile order, F = (float)sqrt(sum), ratio = F / (float)O, gate = ratio > min_norm, coef = gate && F > 0 ? 2 / F : 0 ->
+ * stats[4m ..] = { F, ratio, gate, coef } and *loss = (float) sum_m gate F (double, matrix order).
+ * mi355_ortho_loss_bwd, 1 launch:  dw[r, c] = (accumulate ? dw[r, c] : 0) + (s[0] * coef) * sum_j G[r, j] W[j, c], j ascending inside one
+ * workgroup; s is a DEVICE scalar (the upstream gradient times the callback's weight).  gram[] and stats[] as mi355_ortho_loss_fwd left them.
+ * NormLoss.  Per tensor viewed as R rows:  loss += mean_r (1 - n_r)^2, n_r = |row r|_2 in double;  d/dw = (2 / R)(n_r - 1) / n_r w, 0 where n_r == 0.
+ *   items[]   { int64 off; int32 len; int32 count }   16 bytes: `count` consecutive whole rows of ONE tensor (the row record of the row kernels)
+ *   tensors[] { int64 item0; int32 n_items; int32 rows }   16 bytes: the tensor's consecutive items and its R; item0 ascends with the index
+ * mi355_norm_loss_fwd, 2 launches: part[item] = sum_r (1 - n_r)^2; ONE workgroup: tensor_loss[k] = (its parts in item order) / R and
+ * *loss = (float) sum_k tensor_loss[k] in tensor order.  mi355_norm_loss_bwd, 1 launch:
+ *   dw = (accumulate ? dw : 0) + (float)(s[0] (2 / R)(n_r - 1) / n_r) * w.
+ * Every sum across threads is double in a fixed order; no floating-point atomics, no workgroup waits on another, nothing is read back to the
+ * host; two runs agree bit for bit.  A record that does not lie inside its arrays ([0, n), gram[n_gram], the tables), that has rows > len, or that
+ * disagrees with the records it points to is SKIPPED, as mi355_spectral_fwd skips one: nothing is read or written through it and its
+ * statistics are 0 — an item that does not name its tile and slab writes no partial, and a tile with such an item writes no G and counts 0.  Elements outside the matrices / rows are neither read nor written.  Scratch: partial[mi355_ortho_loss_partial_floats(n_items)],
+ * tile_ss[n_tiles] doubles, stats[mi355_ortho_loss_stats_floats(n_mats)], gram[n_gram]; part[n_items] and tensor_loss[n_tensors] doubles.  All
+ * launches run on `stream`.  Fails (MI355_E_ARG) before any launch on a null or misaligned pointer (16 bytes for the arrays, the 16- and 32-byte
+ * tables and stats; 8 for items[] of the Gram pass and the doubles; 4 for loss and s), a size of 0, n_mats or n_tensors > 65535, a NaN
+ * min_norm, or dw being w. */
+#define MI355_OL_TILE 64   /* rows and columns of a Gram tile; columns of K per gradient item */
+#define MI355_OL_KSLAB 512 /* elements of K per Gram item */
+size_t mi355_ortho_loss_partial_floats(size_t n_items);
+size_t mi355_ortho_loss_stats_floats(size_t n_mats);
+int mi355_ortho_loss_fwd(const float* w, size_t n, float* gram, size_t n_gram, float* partial, double* tile_ss, float* stats, float* loss,
+                         const void* mats, size_t n_mats, const void* tiles, size_t n_tiles, const void* items, size_t n_items, float min_norm,
+                         void* stream);
+int mi355_ortho_loss_bwd(const float* w, float* dw, size_t n, const float* gram, size_t n_gram, const float* stats, const float* s,
+                         const void* mats, size_t n_mats, size_t n_tiles, const void* gitems, size_t n_gitems, int accumulate, void* stream);
+int mi355_norm_loss_fwd(const float* w, size_t n, double* part, double* tensor_loss, float* loss, const void* items, size_t n_items,
+                        const void* tensors, size_t n_tensors, void* stream);
+int mi355_norm_loss_bwd(const float* w, float* dw, size_t n, const float* s, const void* items, size_t n_items, const void* tensors,
+                        size_t n_tensors, int accumulate, void* stream);
+
 /* ---- BResNet-50 variant blocks (BASELINE configs[3]) ---------------------------------------------------------------
  * The reference builds that model as pytorch_tools.models.resnet50(stem_type="deep", antialias=True, attn_type="eca",
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —

@@ -6,7 +6,8 @@ Re-states sota_imagenet/callbacks.py:232-247 (`CutmixMixup`: coin flip between `
 SURVEY.md Appendix C records them (mix with the PREVIOUS batch, permuted; CutMix target weight = real box area).
 SAMOriginal re-states sota_imagenet/callbacks.py:279-337 over csrc/optim_sam.hip, SAM :339-420 over csrc/optim_sam_lw.hip, OrthoInitClb :250-266
 over csrc/init_ortho.hip, GradDistributionTB :30-60 over csrc/optim_hist.hip, WeightDistributionTB :11-17 over csrc/optim_wdist.hip, WeightNorm :104-123 over csrc/weight_norm.hip,
-ForwardWeightNorm :62-84 over csrc/weight_std.hip and the executor's weight transform, ForwardSpectralNorm :87-101 over csrc/spectral_norm.hip.
+ForwardWeightNorm :62-84 over csrc/weight_std.hip and the executor's weight transform, ForwardSpectralNorm :87-101 over csrc/spectral_norm.hip,
+OrthoLossClb :191-203 and NormLossClb :224-229 over losses.OrthoLoss / NormLoss and csrc/ortho_loss.hip.
 What these share is stated once at module level: the flat model a callback runs on and its parameters by offset (_flat_model_of, _params_by_offset:
 OrthoInitClb, WeightNorm), and for the two histogram callbacks the re-plan key of a tensor (_tensor_key), the one-device check (_one_device) and the
 way out to state.tb_logger (_log_histograms); their launches per storage come from item_plan.dist_plan over item_plan.storage_array.
@@ -432,6 +433,68 @@ class ForwardSpectralNorm(Callback):
         sn, flat = m._sn, m.flat_params.detach()
         ops.spectral_fwd(flat, flat, sn["u"], sn["v"], sn["sigma"], sn["scratch"], sn["mats_dev"], 0)
         m.set_spectral_norm(False)
+
+
+class _LossTermClb(Callback):
+    """what OrthoLossClb and NormLossClb share: on_begin sets state.criterion = state.criterion + term(model) * weight, ONCE per callback
+    object.  The criterion must be a losses.Loss (the `+` of the reference's pt.losses.Loss); the term needs a flat model on a CUDA device
+    (NotImplementedError otherwise).  The term stays in the criterion during validation, as in the reference."""
+
+    def __init__(self, weight):
+        super().__init__()
+        self.weight = weight
+        self.term = None
+
+    def _make_term(self):
+        raise NotImplementedError
+
+    def on_begin(self):
+        if self.term is not None:  # a later stage: train.py calls fit once per stage
+            return
+        from .losses import Loss
+
+        if not isinstance(self.state.criterion, Loss):
+            raise TypeError(f"{type(self).__name__}: state.criterion must be a losses.Loss to take another term, got {type(self.state.criterion).__name__}")
+        term = self._make_term()
+        self.state.criterion = self.state.criterion + term * self.weight
+        self.term = term
+
+
+class OrthoLossClb(_LossTermClb):
+    """sota_imagenet/callbacks.py:191-203 (recipes 24, 29, 30, 35, 39): on_begin appends OrthoLoss(model, **kwargs) * weight to the criterion —
+    losses.OrthoLoss on csrc/ortho_loss.hip; kwargs are its eps, min_filters, min_norm, debug.  type=2, the
+    convolutional form OrthoLoss2 (callbacks.py:159-188), raises NotImplementedError: no ResNet-50 recipe here uses it.
+
+    Deviations from the reference, deliberate:
+      * the term is appended once.  The reference's on_begin runs at every fit, and its train.py calls fit once per stage, so there a run of
+        k stages ends with k copies of the penalty, the effective weight growing stage by stage;
+      * the Gram products are always fp32 (the reference's run in half precision under autocast) and the gate F / O > min_norm is decided on the
+        device (losses.OrthoLoss)."""
+
+    def __init__(self, weight=0.01, type=1, **kwargs):
+        super().__init__(weight)
+        if type != 1:
+            raise NotImplementedError(f"OrthoLossClb(type={type!r}): only type 1 (kernel orthogonalisation, OrthoLoss) is built; type 2 is the "
+                                      "convolutional form OrthoLoss2")
+        self.type, self.kwargs = type, kwargs
+
+    def _make_term(self):
+        from .losses import OrthoLoss
+
+        return OrthoLoss(_flat_model_of(self.state, "OrthoLossClb"), **self.kwargs)
+
+
+class NormLossClb(_LossTermClb):
+    """sota_imagenet/callbacks.py:224-229: on_begin appends NormLoss(model) * weight to the criterion — losses.NormLoss on csrc/ortho_loss.hip.
+    Appended once, not once per stage (see OrthoLossClb)."""
+
+    def __init__(self, weight=1e-4):
+        super().__init__(weight)
+
+    def _make_term(self):
+        from .losses import NormLoss
+
+        return NormLoss(_flat_model_of(self.state, "NormLossClb"))
 
 
 class GradDistributionTB(Callback):

@@ -101,6 +101,15 @@ FORWARD_SPECTRAL_CALLBACK_TARGET_ALIASES = {
     "sota_imagenet.callbacks.ForwardSpectralNorm": "sota_imagenet_amd.callbacks.ForwardSpectralNorm",
 }
 
+# callbacks that append a parameter-only term to the criterion (sota_imagenet/callbacks.py:191-203, :224-229; recipes 24, 29, 30, 35, 39),
+# consulted last, after the ten tables above, whose contents existing tests pin
+LOSS_CALLBACK_TARGET_ALIASES = {
+    "src.callbacks.OrthoLossClb": "sota_imagenet_amd.callbacks.OrthoLossClb",
+    "sota_imagenet.callbacks.OrthoLossClb": "sota_imagenet_amd.callbacks.OrthoLossClb",
+    "src.callbacks.NormLossClb": "sota_imagenet_amd.callbacks.NormLossClb",
+    "sota_imagenet.callbacks.NormLossClb": "sota_imagenet_amd.callbacks.NormLossClb",
+}
+
 
 def default_config():
     """StrictConfig defaults — sota_imagenet/arg_parser.py:13-156."""
@@ -340,7 +349,8 @@ def resolve_target(path):
     path = (TARGET_ALIASES.get(path) or LAYERWISE_TARGET_ALIASES.get(path) or CALLBACK_TARGET_ALIASES.get(path)
             or ADAMP_TARGET_ALIASES.get(path) or INIT_CALLBACK_TARGET_ALIASES.get(path) or LOGGING_CALLBACK_TARGET_ALIASES.get(path)
             or WEIGHT_HISTOGRAM_TARGET_ALIASES.get(path) or WEIGHT_CALLBACK_TARGET_ALIASES.get(path)
-            or FORWARD_WEIGHT_CALLBACK_TARGET_ALIASES.get(path) or FORWARD_SPECTRAL_CALLBACK_TARGET_ALIASES.get(path, path))
+            or FORWARD_WEIGHT_CALLBACK_TARGET_ALIASES.get(path) or FORWARD_SPECTRAL_CALLBACK_TARGET_ALIASES.get(path)
+            or LOSS_CALLBACK_TARGET_ALIASES.get(path, path))
     mod, _, attr = path.rpartition(".")
     return getattr(importlib.import_module(mod), attr)
 

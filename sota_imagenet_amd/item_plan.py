@@ -3,7 +3,8 @@
 gradient storage with every tensor cut into work items of at most W elements (plan_items, storage_pairs), the 16-byte records the kernels read
 (pack_records) and a storage as a flat array (storage_array; flat_views for a parameter and its gradient); for the statistics taken per output unit (callbacks.SAM, the unit-wise optimizers of
 optim.py) the unit rule (unit_len) and the tables of pieces, slots and tensor records (plan_units); for the callbacks that run on a flat model's own
-table the matrices of OrthoInitClb (ortho_records) and the rows of WeightNorm with their work items (wnorm_records, wnorm_items); for the two
+table the matrices of OrthoInitClb (ortho_records), the rows of WeightNorm with their work items (wnorm_records, wnorm_items) and the matrices,
+tiles and rows of the two loss penalties (ortho_loss_mats, ortho_loss_cut; norm_loss_rows, norm_loss_items); for the two
 histogram callbacks what to read of a tensor (hist_records) and the launches, one per storage (dist_plan).  Everything up to pack_records is pure Python on plain tuples, so a planner is pinned
 without a GPU (tests/test_item_plan_host.py); the device side of the records is csrc/optim_items.h.  The merged-range planner of SGD / Adam /
 MADGRAD / AdaiS (optim._merged_ranges) takes place and flat_views only."""
@@ -14,6 +15,9 @@ ITEM_FIELDS = ("<i8", "<i4", "<i4")    # work items, SAM's pieces { first elemen
 TENSOR_FIELDS = ("<i4", "<i4", "<f8")  # the tensor records of lw_coef { first item, item count, numel }
 ORTHO_FIELDS = ("<i8", "<i4", "<i4", "<i4", "<i4")  # the matrices of ortho_init_ { first element, rows, chans, taps, pad }: 24 bytes
 SPECTRAL_FIELDS = ("<i8", "<i4", "<i4", "<i8", "<i8")  # the matrices of ops.spectral_fwd { first element, row_len, rows, u0, v0 }: 32 bytes
+ORTHO_LOSS_FIELDS = SPECTRAL_FIELDS  # the matrices of ops.ortho_loss_fwd { first element, row_len, rows, g0, t0 }: 32 bytes
+OL_TILE_FIELDS = ("<i4", "<i4", "<i4", "<i4")  # its tiles { mat, ti | tj << 16, item0, n_slabs } and gradient items { mat, ti, tc, 0 }: 16 bytes
+OL_ITEM_FIELDS = ("<i4", "<i4")  # its Gram items { tile, slab }: 8 bytes
 
 
 def dense_range(t):
@@ -191,6 +195,73 @@ def spectral_mats(table):
             mats.append((off, L, shape[0], u0, v0))
             u0, v0 = u0 + shape[0], v0 + L
     return mats, u0, v0
+
+
+def ortho_loss_mats(table, min_filters):
+    """the matrices of the orthogonality penalty (losses.OrthoLoss; sota_imagenet/callbacks.py:138-146): ([(first element, row_len, rows, g0)],
+    n_gram) for every conv weight — a parameter (kind 0) with four dimensions — of a flat model's [(name, kind, offset, shape)] whose rows = O
+    and row_len = I*kh*kw have rows <= row_len and rows >= min_filters, in the order of their offsets; g0 is the running sum of rows^2 (the
+    place of its Gram matrix), n_gram the total.  A filter is one contiguous run of row_len elements (KRSC memory), and W W^T does not depend on
+    the order of the columns."""
+    mats, g0 = [], 0
+    for _, kind, off, shape in sorted(table, key=lambda t: t[2]):
+        if kind == 0 and len(shape) == 4:
+            O, L = shape[0], int(np.prod(shape[1:]))
+            if O <= L and O >= min_filters:
+                mats.append((off, L, O, g0))
+                g0 += O * O
+    return mats, g0
+
+
+def ortho_loss_cut(mats, tile, kslab):
+    """the work items of ops.ortho_loss_fwd / ortho_loss_bwd, a function of the records [(off, row_len, rows, g0)] and the two sizes alone.
+    Returns a dict of tables in the kernels' field order:
+      mats    [(off, row_len, rows, g0, t0)]: t0 the matrix's first tile (ORTHO_LOSS_FIELDS)
+      tiles   [(mat, ti | tj << 16, item0, n_slabs)]: per matrix the tiles of `tile` rows x `tile` rows on or below the diagonal, ti ascending and
+              tj <= ti ascending inside — tile (ti, tj) of a matrix sits at t0 + ti (ti + 1) / 2 + tj —, each with its n_slabs = ceil(row_len /
+              kslab) consecutive items (OL_TILE_FIELDS)
+      items   [(tile, slab)]: the Gram pass, item tiles[t].item0 + j = (t, j) (OL_ITEM_FIELDS)
+      gitems  [(mat, ti, tc, 0)]: the gradient pass, every row tile with every tile of `tile` columns of row_len (OL_TILE_FIELDS)
+    A record with rows > row_len has no Gram matrix to ask for and raises ValueError: it must never reach a kernel."""
+    out = dict(mats=[], tiles=[], items=[], gitems=[])
+    for m, (off, L, R, g0) in enumerate(mats):
+        if R < 1 or L < 1 or R > L:
+            raise ValueError(f"matrix at offset {off}: rows={R}, row_len={L} — 1 <= rows <= row_len is needed")
+        nt, n_slabs = -(-R // tile), -(-L // kslab)
+        if nt >= 1 << 15:
+            raise ValueError(f"matrix at offset {off}: {nt} row tiles do not fit the tile record")
+        out["mats"].append((off, L, R, g0, len(out["tiles"])))
+        for ti in range(nt):
+            for tj in range(ti + 1):
+                t = len(out["tiles"])
+                out["tiles"].append((m, ti | tj << 16, len(out["items"]), n_slabs))
+                out["items"].extend((t, j) for j in range(n_slabs))
+            out["gitems"].extend((m, ti, tc, 0) for tc in range(-(-L // tile)))
+    return out
+
+
+def norm_loss_rows(table):
+    """the rows of the norm penalty (losses.NormLoss; sota_imagenet/callbacks.py:213-217 walks every module with a .weight of 64 elements or
+    more): [(off, rows, row_len)] for every parameter (kind 0) of a flat model's [(name, kind, offset, shape)] whose name ends in ".weight" and
+    that has 64 elements or more, in table order; rows = shape[0], row_len = numel / rows.  Unlike wnorm_records the BatchNorm weights are in
+    (rows of ONE element: n_r = |gamma_r|) and so is the FC weight, without its padding rows; biases and buffers are not."""
+    out = []
+    for name, kind, off, shape in table:
+        n = int(np.prod(shape)) if len(shape) else 1
+        if kind == 0 and name.endswith(".weight") and n >= 64:
+            out.append((off, shape[0], n // shape[0]))
+    return out
+
+
+def norm_loss_items(records, W):
+    """the tables of ops.norm_loss_fwd / norm_loss_bwd from norm_loss_rows' records: (items, tensors) — items = wnorm_items(records, W), runs of
+    whole rows of one tensor; tensors = [(first item, item count, rows)] per record (ITEM_FIELDS)"""
+    items, tensors = [], []
+    for rec in records:
+        mine = wnorm_items([rec], W)
+        tensors.append((len(items), len(mine), rec[1]))
+        items.extend(mine)
+    return items, tensors
 
 
 def wnorm_items(records, W):

@@ -956,6 +956,117 @@ def spectral_bwd(g, w_hat, u, v, sigma, dw, scratch, mats_dev, beta=0.0, row_beg
                                   mats_dev.shape[0], int(row_begin), row_end, float(beta), cur_stream()))
 
 
+# ---- weight penalties in the loss (include/mi355rn.h, csrc/ortho_loss.hip): the OrthoLossClb and NormLossClb callbacks of the reference -------------
+# stated once for the host; include/mi355rn.h states the first two for the library (MI355_OL_*) and tests/test_ortho_loss_host.py holds them together
+OL_TILE = 64    # rows and columns of a Gram tile; columns of K per gradient item
+OL_KSLAB = 512  # elements of K per Gram item
+NL_ITEM_ELEMS = 16384  # W of the norm penalty's items (item_plan.norm_loss_items).  Host side only: the kernels take any run of whole rows
+_OL_TABLES = (("mats", 4), ("tiles", 2), ("items", 1), ("gitems", 2))  # int64 columns of the packed records
+
+
+def ortho_loss_scratch(n_gram, n_mats, n_tiles, n_items, device):
+    """what ortho_loss_fwd leaves and ortho_loss_bwd reads, on `device`: gram (every G, fp32), partial (the slab partials), tile_ss (float64 per
+    tile), stats ([n_mats, 4]: F, F / O, gate, coefficient) and loss (the 0-dim fp32 total)"""
+    L = _L()
+    return dict(gram=torch.empty(n_gram, dtype=torch.float32, device=device),
+                partial=torch.empty(L.mi355_ortho_loss_partial_floats(n_items), dtype=torch.float32, device=device),
+                tile_ss=torch.empty(n_tiles, dtype=torch.float64, device=device),
+                stats=torch.empty(L.mi355_ortho_loss_stats_floats(n_mats) // 4, 4, dtype=torch.float32, device=device),
+                loss=torch.empty((), dtype=torch.float32, device=device))
+
+
+def _ol_args(who, tables, scratch, **arrays):
+    n = next(iter(arrays.values())).numel()
+    _flat_f32(n, **arrays)
+    for name, cols in _OL_TABLES:
+        t = tables[name]
+        _need_cuda(t)
+        if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != cols or t.shape[0] < 1:
+            raise ValueError(f"{name}: expected a CUDA int64 tensor [n, {cols}] of {8 * cols}-byte records, got {t.dtype} {tuple(t.shape)}")
+    L = _L()
+    n_mats, n_tiles, n_items = (tables[k].shape[0] for k in ("mats", "tiles", "items"))
+    want = dict(gram=(torch.float32, 1), partial=(torch.float32, L.mi355_ortho_loss_partial_floats(n_items)), tile_ss=(torch.float64, n_tiles),
+                stats=(torch.float32, L.mi355_ortho_loss_stats_floats(n_mats)), loss=(torch.float32, 1))
+    for name, (dt, need) in want.items():
+        t = scratch[name]
+        _need_cuda(t)
+        if t.dtype != dt or t.numel() < need or (name in ("stats", "loss") and t.numel() != need):
+            raise ValueError(f"{name}: expected {need} {dt} elements (ortho_loss_scratch), got {t.dtype} with {t.numel()}")
+    if len({t.device for t in (*tables.values(), *scratch.values(), *arrays.values())}) != 1:
+        raise ValueError(f"{who}: the tables, the scratch and the arrays must live on one device")
+    return n
+
+
+def ortho_loss_fwd(w, tables, scratch, min_norm):
+    """replaces the loop of sota_imagenet/callbacks.py:138-156 in 3 launches: for every matrix of the tables G = W W^T - I (scratch["gram"]), its
+    Frobenius norm F, the gate F / O > min_norm and the gradient's coefficient (scratch["stats"]), and scratch["loss"] = sum of the gated F, which
+    is returned (a view, not read back).  w: the flat fp32 array the offsets count from; tables: item_plan.ortho_loss_cut(.., OL_TILE, OL_KSLAB)
+    packed for the device — mats (ORTHO_LOSS_FIELDS), tiles and gitems (OL_TILE_FIELDS), items (OL_ITEM_FIELDS).  A record that does not fit is
+    skipped by the kernels; elements outside the matrices are not read."""
+    n = _ol_args("ortho_loss_fwd", tables, scratch, w=w)
+    s = scratch
+    check(_L().mi355_ortho_loss_fwd(ptr(w), n, ptr(s["gram"]), s["gram"].numel(), ptr(s["partial"]), ptr(s["tile_ss"]), ptr(s["stats"]), ptr(s["loss"]),
+                                    ptr(tables["mats"]), tables["mats"].shape[0], ptr(tables["tiles"]), tables["tiles"].shape[0],
+                                    ptr(tables["items"]), tables["items"].shape[0], float(min_norm), cur_stream()))
+    return s["loss"]
+
+
+def _dev_scalar(name, s, like):
+    _need_cuda(s)
+    if s.dtype != torch.float32 or s.numel() != 1 or s.device != like.device:
+        raise ValueError(f"{name}: expected ONE float32 element on {like.device} (the upstream gradient stays on the device), got {s.dtype} with "
+                         f"{s.numel()} on {s.device}")
+
+
+def ortho_loss_bwd(w, dw, tables, scratch, s, accumulate=True):
+    """dw (+)= s * (2 / F) G W for every matrix whose gate ortho_loss_fwd left open, in ONE launch, from the gram and stats it left in `scratch`;
+    s: a 1-element CUDA fp32 tensor (the upstream gradient times the callback's weight); accumulate=False overwrites the matrices' elements
+    (zeros where the gate is closed) and leaves every other element of dw alone."""
+    n = _ol_args("ortho_loss_bwd", tables, scratch, w=w, dw=dw)
+    _dev_scalar("s", s, w)
+    check(_L().mi355_ortho_loss_bwd(ptr(w), ptr(dw), n, ptr(scratch["gram"]), scratch["gram"].numel(), ptr(scratch["stats"]), ptr(s),
+                                    ptr(tables["mats"]), tables["mats"].shape[0], tables["tiles"].shape[0], ptr(tables["gitems"]),
+                                    tables["gitems"].shape[0], int(bool(accumulate)), cur_stream()))
+
+
+def norm_loss_scratch(n_items, n_tensors, device):
+    """what norm_loss_fwd leaves: part (float64 per item), tensor_loss (float64 per tensor: its mean) and loss (the 0-dim fp32 total)"""
+    return dict(part=torch.empty(n_items, dtype=torch.float64, device=device), tensor_loss=torch.empty(n_tensors, dtype=torch.float64, device=device),
+                loss=torch.empty((), dtype=torch.float32, device=device))
+
+
+def _nl_args(who, items_dev, tensors_dev, **arrays):
+    n = next(iter(arrays.values())).numel()
+    _flat_f32(n, **arrays)
+    _lw_table("items_dev", items_dev)
+    _lw_table("tensors_dev", tensors_dev)
+    if len({t.device for t in (items_dev, tensors_dev, *arrays.values())}) != 1:
+        raise ValueError(f"{who}: the tables and the arrays must live on one device")
+    return n
+
+
+def norm_loss_fwd(w, items_dev, tensors_dev, scratch):
+    """replaces the loop of sota_imagenet/callbacks.py:213-221 in 2 launches: scratch["loss"] = sum over the tensors of mean_r (1 - |row r|)^2,
+    which is returned (a view, not read back).  items_dev, tensors_dev: item_plan.norm_loss_items packed for the device (CUDA int64 [n, 2])."""
+    n = _nl_args("norm_loss_fwd", items_dev, tensors_dev, w=w)
+    for name, dt, need in (("part", torch.float64, items_dev.shape[0]), ("tensor_loss", torch.float64, tensors_dev.shape[0]), ("loss", torch.float32, 1)):
+        t = scratch[name]
+        _need_cuda(t)
+        if t.dtype != dt or t.numel() != need or t.device != w.device:
+            raise ValueError(f"{name}: expected {need} {dt} elements on {w.device} (norm_loss_scratch), got {t.dtype} with {t.numel()} on {t.device}")
+    check(_L().mi355_norm_loss_fwd(ptr(w), n, ptr(scratch["part"]), ptr(scratch["tensor_loss"]), ptr(scratch["loss"]), ptr(items_dev), items_dev.shape[0],
+                                   ptr(tensors_dev), tensors_dev.shape[0], cur_stream()))
+    return scratch["loss"]
+
+
+def norm_loss_bwd(w, dw, items_dev, tensors_dev, s, accumulate=True):
+    """dw (+)= s * (2 / R)(n_r - 1) / n_r * w for every row of the tables (0 where n_r == 0), in ONE launch; s as in ortho_loss_bwd"""
+    n = _nl_args("norm_loss_bwd", items_dev, tensors_dev, w=w, dw=dw)
+    _dev_scalar("s", s, w)
+    check(_L().mi355_norm_loss_bwd(ptr(w), ptr(dw), n, ptr(s), ptr(items_dev), items_dev.shape[0], ptr(tensors_dev), tensors_dev.shape[0],
+                                   int(bool(accumulate)), cur_stream()))
+
+
 # ---- the log histogram of |x| (include/mi355rn.h, csrc/optim_hist.hip): the GradDistributionTB callback of the reference ----------------------------
 # the bins, stated once for the host; csrc/absbin.h states them for the kernels and tests/test_grad_dist_host.py holds the two together
 ABSBIN_BINS, ABSBIN_SHIFT, ABSBIN_K0 = 512, 20, (77 << 3) + 2

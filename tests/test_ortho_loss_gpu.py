@@ -1,0 +1,456 @@
+"""The weight penalties in the loss on the GPU: the kernels of csrc/ortho_loss.hip stage by stage against float64 on the matrices of
+tests/ortho_loss_common.py (whose bounds these are), an exact-integer case, NormLoss per op, determinism, the reference's own record
+(tests/golden/ortho_loss_ref.npz), the order of the two backward nodes on the ResNet-50 executor, evaluation, and three steps of Runner.fit."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ortho_loss_common as C
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+S_UP = 0.37  # the upstream scalar of the per-op backward runs
+
+
+def _mods():
+    from sota_imagenet_amd import item_plan, ops
+
+    return ops, item_plan
+
+
+def _np_same(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(b).view(np.int32))
+
+
+def _tables(mats, dev):
+    ops, ip = _mods()
+    cut = ip.ortho_loss_cut(mats, ops.OL_TILE, ops.OL_KSLAB)
+    fields = dict(mats=ip.ORTHO_LOSS_FIELDS, tiles=ip.OL_TILE_FIELDS, items=ip.OL_ITEM_FIELDS, gitems=ip.OL_TILE_FIELDS)
+    return {k: ip.pack_records(cut[k], dev, fields[k]) for k in fields}, cut
+
+
+def _scratch(cut, n_gram, dev):
+    ops, _ = _mods()
+    sc = ops.ortho_loss_scratch(n_gram, len(cut["mats"]), len(cut["tiles"]), len(cut["items"]), dev)
+    for t in sc.values():
+        t.fill_(float("nan"))
+    return sc
+
+
+def _run(flat, mats, n_gram, min_norm, dev, s=S_UP):
+    """forward, then the backward onto NaN (accumulate off) and onto a prefill (accumulate on): numpy gram, stats, loss, dw_off, dw_on, prefill"""
+    ops, _ = _mods()
+    tables, cut = _tables(mats, dev)
+    sc = _scratch(cut, n_gram, dev)
+    w = torch.from_numpy(flat).to(dev)
+    loss = ops.ortho_loss_fwd(w, tables, sc, min_norm)
+    sd = torch.tensor([s], dtype=torch.float32, device=dev)
+    dw_off = torch.full_like(w, float("nan"))
+    ops.ortho_loss_bwd(w, dw_off, tables, sc, sd, accumulate=False)
+    pre = torch.from_numpy(np.random.default_rng(9).standard_normal(flat.size).astype(np.float32)).to(dev)
+    pre[~torch.from_numpy(C.mat_mask(flat.size, mats)).to(dev)] = float("nan")
+    dw_on = pre.clone()
+    ops.ortho_loss_bwd(w, dw_on, tables, sc, sd, accumulate=True)
+    torch.cuda.synchronize()
+    assert _np_same(w.cpu().numpy(), flat), "the source is read only"
+    return dict(gram=sc["gram"].cpu().numpy(), stats=sc["stats"].cpu().numpy(), loss=float(loss.cpu()), dw_off=dw_off.cpu().numpy(),
+                dw_on=dw_on.cpu().numpy(), pre=pre.cpu().numpy())
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(scope="module")
+def case(dev):
+    _, ip = _mods()
+    flat, table = C.make_case()
+    mats, n_gram = ip.ortho_loss_mats(table, 1)
+    assert len(mats) == len(C.SHAPES)  # the tall record never reaches a kernel
+    runs = [_run(flat, mats, n_gram, C.MIN_NORM, dev) for _ in range(2)]
+    return dict(flat=flat, mats=mats, n_gram=n_gram, runs=runs, mask=C.mat_mask(flat.size, mats))
+
+
+def _G(c, run, k):
+    _, _, R, g0 = c["mats"][k]
+    return run["gram"][g0: g0 + R * R].reshape(R, R)
+
+
+def test_gram_norm_gate_and_total(case):
+    c, run = case, case["runs"][0]
+    worst = dict(G=0.0, F=0.0, ratio=0.0, coef=0.0)
+    gates = []
+    for k, rec in enumerate(c["mats"]):
+        W, G = C.mat_of(c["flat"], rec), _G(c, run, k)
+        F, ratio, gate, coef = run["stats"][k]
+        ref, b = C.gram64(W)
+        worst["G"] = max(worst["G"], C.worst(G, ref, b))
+        assert _np_same(G, G.T.copy()), f"matrix {k}: the mirror"
+        Fr, bF = C.frob64(G)
+        worst["F"] = max(worst["F"], abs(float(F) - Fr) / bF if bF else float(F != Fr))
+        worst["ratio"] = max(worst["ratio"], abs(float(ratio) - float(F) / W.shape[0]) / (C.U * float(F) / W.shape[0]) if F else float(ratio != 0))
+        g64 = C.gate64(C.ortho_loss64([W], C.MIN_NORM)[2][0], W.shape[0], C.MIN_NORM)
+        assert bool(gate) == g64 and gate in (0.0, 1.0), f"matrix {k}: gate {gate}"
+        gates.append(g64)
+        cr, bc = C.coef64(F, g64)
+        worst["coef"] = max(worst["coef"], abs(float(coef) - cr) / bc if bc else float(coef != 0))
+    print("worst error / bound:", worst)
+    assert max(worst.values()) <= 1.0, worst
+    assert [k for k, g in enumerate(gates) if not g] == [C.ORTHO, C.NEAR]
+    assert (_G(c, run, C.ORTHO) == 0).all() and tuple(run["stats"][C.ORTHO]) == (0.0, 0.0, 0.0, 0.0)  # G = 0: F = 0, closed, no NaN
+    assert run["stats"][C.ZERO][0] == np.float32(np.sqrt(8.0)) and (_G(c, run, C.ZERO) == -np.eye(8, dtype=np.float32)).all()
+    tr, bt = C.total64(run["stats"][:, 0], gates)
+    assert abs(run["loss"] - tr) <= bt, (run["loss"], tr, bt)
+    # unused entries of the Gram storage stay as they were
+    used = sum(r[2] ** 2 for r in c["mats"])
+    assert used == c["n_gram"] and np.isfinite(run["gram"]).all()
+
+
+@pytest.mark.parametrize("mode", ["dw_off", "dw_on"])
+def test_gradient_pass(case, mode):
+    c, run = case, case["runs"][0]
+    got = run[mode]
+    assert np.isnan(got[~c["mask"]]).all(), "elements outside the matrices are not written"
+    worst = 0.0
+    for k, rec in enumerate(c["mats"]):
+        W = C.mat_of(c["flat"], rec)
+        F, ratio, gate, coef = run["stats"][k]
+        old = C.mat_of(run["pre"], rec) if mode == "dw_on" else None
+        ref, b = C.grad64(W, _G(c, run, k), coef, S_UP, old)
+        g = C.mat_of(got, rec)
+        worst = max(worst, C.worst(g, ref, b))
+        if not gate:
+            assert _np_same(g, old if old is not None else np.zeros_like(g)), f"matrix {k}: a closed gate contributes nothing"
+    print("dw worst error / bound:", worst)
+    assert worst <= 1.0
+    assert (C.mat_of(run["dw_off"], c["mats"][C.ZERO]) == 0).all()  # G = -I on zero weights: exactly 0
+    assert np.abs(C.mat_of(run["dw_off"], c["mats"][C.LARGEST])).max() > 0
+
+
+def test_open_gates_at_min_norm_zero(case, dev):
+    """min_norm = 0 opens every gate but the exactly orthonormal matrix's, whose F is 0"""
+    ops, _ = _mods()
+    c = case
+    tables, cut = _tables(c["mats"], dev)
+    sc = _scratch(cut, c["n_gram"], dev)
+    loss = ops.ortho_loss_fwd(torch.from_numpy(c["flat"]).to(dev), tables, sc, 0.0)
+    stats = sc["stats"].cpu().numpy()
+    assert [k for k in range(len(c["mats"])) if not stats[k, 2]] == [C.ORTHO]
+    tr, bt = C.total64(stats[:, 0], stats[:, 2] != 0)
+    assert abs(float(loss.cpu()) - tr) <= bt
+    assert _np_same(stats[:, 0], c["runs"][0]["stats"][:, 0])
+
+
+def test_two_runs_agree_bit_for_bit(case):
+    a, b = case["runs"]
+    for k in ("gram", "stats", "dw_off", "dw_on"):
+        assert _np_same(a[k], b[k]), k
+    assert a["loss"] == b["loss"]
+
+
+def test_integer_weights_give_the_exact_gram_matrix(dev):
+    """weights in {-2 .. 2}: every product and partial sum is exact in float32, so G equals the integer Gram matrix bit for bit — tiles, mirror, slabs"""
+    _, ip = _mods()
+    flat, table = C.integer_case()
+    mats, n_gram = ip.ortho_loss_mats(table, 1)
+    run = _run(flat, mats, n_gram, 0.0, dev, s=1.0)
+    for rec in mats:
+        _, _, R, g0 = rec
+        W = C.mat_of(flat, rec).astype(np.float64)
+        ref = (W @ W.T - np.eye(R)).astype(np.float32)
+        assert _np_same(run["gram"][g0: g0 + R * R].reshape(R, R), ref), (R, rec[1])
+
+
+def test_item_that_does_not_name_its_tile_is_skipped(case, dev):
+    """a foreign item table: one item of the ragged matrix's tile (1, 0) names another slab.  Its workgroup writes no partial, so the finish pass
+    must not sum that tile: its entries of G and their mirror stay as they were and the tile counts 0 in F"""
+    ops, ip = _mods()
+    c = case
+    tables, cut = _tables(c["mats"], dev)
+    t = cut["mats"][C.RAGGED][4] + 1  # tile (1, 0)
+    assert cut["tiles"][t][:2] == (C.RAGGED, 1)
+    items = list(cut["items"])
+    items[cut["tiles"][t][2] + 1] = (t, 0)
+    tables["items"] = ip.pack_records(items, dev, ip.OL_ITEM_FIELDS)
+    sc = _scratch(cut, c["n_gram"], dev)
+    ops.ortho_loss_fwd(torch.from_numpy(c["flat"]).to(dev), tables, sc, C.MIN_NORM)
+    torch.cuda.synchronize()
+    _, _, R, g0 = c["mats"][C.RAGGED]
+    G = sc["gram"].cpu().numpy()[g0: g0 + R * R].reshape(R, R)
+    good = _G(c, c["runs"][0], C.RAGGED)
+    hole = np.zeros((R, R), dtype=bool)
+    hole[64:128, :64] = hole[:64, 64:128] = True
+    assert np.isnan(G[hole]).all() and _np_same(G[~hole], good[~hole])
+    F = float(sc["stats"].cpu().numpy()[C.RAGGED, 0])
+    ref = float(np.sqrt((good[~hole].astype(np.float64) ** 2).sum()))
+    assert abs(F - ref) <= (C.U + (R * R + 4) * C.D) * ref
+    others = [k for k in range(len(c["mats"])) if k != C.RAGGED]
+    assert _np_same(sc["stats"].cpu().numpy()[others], c["runs"][0]["stats"][others])
+
+
+# ---- NormLoss -----------------------------------------------------------------------------------------------------------------------------------------
+def test_norm_loss_per_op(dev):
+    ops, ip = _mods()
+    flat, table = C.norm_case()
+    rows = ip.norm_loss_rows(table)
+    names = [t[0] for t in table if (t[2], t[3][0], int(np.prod(t[3])) // t[3][0]) in rows]
+    assert names == ["conv.weight", "bn.weight", "fc.weight", "long.weight", "wide.weight"]
+    items, tensors = ip.norm_loss_items(rows, 1024)  # several items per tensor
+    assert len(items) > len(tensors)
+    mask = C.mat_mask(flat.size, [(o, L, R) for o, R, L in rows])
+    w = torch.from_numpy(flat).to(dev)
+    idev, tdev = ip.pack_records(items, dev), ip.pack_records(tensors, dev)
+    Ws = [flat[o: o + R * L].reshape(R, L) for o, R, L in rows]
+    outs = []
+    for _ in range(2):
+        sc = ops.norm_loss_scratch(len(items), len(tensors), dev)
+        loss = ops.norm_loss_fwd(w, idev, tdev, sc)
+        sd = torch.tensor([S_UP], dtype=torch.float32, device=dev)
+        dw_off = torch.full_like(w, float("nan"))
+        ops.norm_loss_bwd(w, dw_off, idev, tdev, sd, accumulate=False)
+        pre = torch.from_numpy(np.random.default_rng(4).standard_normal(flat.size).astype(np.float32)).to(dev)
+        pre[~torch.from_numpy(mask).to(dev)] = float("nan")
+        dw_on = pre.clone()
+        ops.norm_loss_bwd(w, dw_on, idev, tdev, sd, accumulate=True)
+        torch.cuda.synchronize()
+        outs.append((float(loss.cpu()), sc["tensor_loss"].cpu().numpy(), dw_off.cpu().numpy(), dw_on.cpu().numpy()))
+    assert _np_same(w.cpu().numpy(), flat)
+    loss, per_tensor, dw_off, dw_on = outs[0]
+    ref, bound, means = C.norm_loss64(Ws)
+    print("norm loss", loss, ref, bound)
+    assert abs(loss - ref) <= bound
+    assert np.abs(per_tensor - np.array(means)).max() <= bound
+    pre = pre.cpu().numpy()
+    for got, old in ((dw_off, None), (dw_on, pre)):
+        assert np.isnan(got[~mask]).all()
+        for (o, R, L), W in zip(rows, Ws):
+            r, b = C.norm_grad64(W, S_UP, None if old is None else old[o: o + R * L].reshape(R, L))
+            assert C.worst(got[o: o + R * L].reshape(R, L), r, b) <= 1.0, (R, L)
+    fc = rows[names.index("fc.weight")]
+    assert (dw_off[fc[0] + 3 * 37: fc[0] + 4 * 37] == 0).all()  # the zero row: n_r = 0 gives 0, not NaN
+    bn = rows[names.index("bn.weight")]
+    assert dw_off[bn[0] + 7] == 0 and np.isfinite(dw_off[bn[0]: bn[0] + 64]).all()
+    assert outs[0][0] == outs[1][0] and all(_np_same(a.astype(np.float32), b.astype(np.float32)) for a, b in zip(outs[0][1:], outs[1][1:]))
+
+
+# ---- the reference's record ---------------------------------------------------------------------------------------------------------------------------
+def test_against_the_reference_record(dev):
+    ops, ip = _mods()
+    z = np.load(os.path.join(HERE, "golden", "ortho_loss_ref.npz"))
+    names = json.loads(str(z["names"]))
+    table, off = [], 4
+    for n in names:
+        table.append((f"{n}.weight", 0, off, tuple(z[f"w/{n}"].shape)))
+        off += z[f"w/{n}"].size + (-z[f"w/{n}"].size) % 4 + 1  # torch's (O, I, kh, kw) order: the rule does not depend on the order of the columns
+    flat = np.full(off + 3, np.nan, dtype=np.float32)
+    for (_, _, o, shape), n in zip(table, names):
+        flat[o: o + z[f"w/{n}"].size] = z[f"w/{n}"].reshape(-1)
+    by_off = {t[2]: t[0][: -len(".weight")] for t in table}
+    for k in (0, 1):
+        st = json.loads(str(z[f"ortho/{k}/setting"]))
+        mats, n_gram = ip.ortho_loss_mats(table, st["min_filters"])
+        run = _run(flat, mats, n_gram, st["min_norm"], dev, s=1.0)
+        Fs = json.loads(str(z[f"ortho/{k}/F"]))
+        contributed = json.loads(str(z[f"ortho/{k}/contributed"]))
+        b_loss = 0.0
+        for i, rec in enumerate(mats):
+            n = by_off[rec[0]]
+            W = C.mat_of(flat, rec)
+            bF, bg = C.whole_rule_bounds(W, Fs[n], n in contributed)
+            b_loss += bF if n in contributed else 0.0
+            assert bool(run["stats"][i][2]) == (n in contributed), n
+            assert abs(float(run["stats"][i][0]) - Fs[n]) <= bF, n
+            assert C.worst(C.mat_of(run["dw_off"], rec), z[f"ortho/{k}/g/{n}"].reshape(W.shape), bg) <= 1.0, n
+        assert abs(run["loss"] - float(z[f"ortho/{k}/loss"])) <= b_loss
+    rows = ip.norm_loss_rows(table)
+    sel = [by_off[r[0]] for r in rows]
+    assert sel == json.loads(str(z["norm/contributed"]))
+    items, tensors = ip.norm_loss_items(rows, ops.NL_ITEM_ELEMS)
+    w = torch.from_numpy(flat).to(dev)
+    idev, tdev = ip.pack_records(items, dev), ip.pack_records(tensors, dev)
+    sc = ops.norm_loss_scratch(len(items), len(tensors), dev)
+    loss = ops.norm_loss_fwd(w, idev, tdev, sc)
+    dw = torch.zeros_like(w)
+    ops.norm_loss_bwd(w, dw, idev, tdev, torch.ones(1, device=dev), accumulate=False)
+    Ws = [flat[o: o + R * L].reshape(R, L) for o, R, L in rows]
+    ref, bound, _ = C.norm_loss64(Ws)
+    assert abs(ref - float(z["norm/loss"])) <= 1e-12 * ref and abs(float(loss.cpu()) - float(z["norm/loss"])) <= bound
+    dw = dw.cpu().numpy()
+    for (o, R, L), n, W in zip(rows, sel, Ws):
+        assert C.worst(dw[o: o + R * L].reshape(R, L), z[f"norm/g/{n}"].reshape(R, L), C.norm_grad64(W, 1.0)[1]) <= 1.0, n
+
+
+# ---- on the executor ----------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def net(dev):
+    from sota_imagenet_amd.models import resnet50
+    from sota_imagenet_amd.synth import synthetic_batch
+
+    m = resnet50(dtype="fp32").cuda()
+    data, target = synthetic_batch(4, 64, seed=3, index=0)
+    return m, data.cuda(), target.cuda()
+
+
+def _penalty_alone(pen, m, weight):
+    """weight * d penalty / d parameters by the op alone, into zeros"""
+    ops, _ = _mods()
+    pen._plan()
+    pen._launch_forward()
+    g = torch.zeros_like(m.flat_grads)
+    ops.ortho_loss_bwd(m.flat_params.detach(), g, pen._tables, pen._scratch, torch.tensor([weight], dtype=torch.float32, device=g.device), accumulate=True)
+    return g
+
+
+def test_penalty_gradient_adds_to_the_native_gradient_in_any_state(net):
+    """flat_grads after criterion(model(x), t).backward() = the plain criterion's gradient + the penalty's, whether the gradients were clean (the
+    executor overwrites), dirty (the second micro-step) or cleaned by optimizer.zero_grad() before a second backward (SAM's second pass).  The
+    accumulating executor adds the value it finds inside its own float32 reductions, a handful of partial sums of the order of the tensor's
+    largest gradient: per tensor, |got - expected| <= 16 U (max |native| + max |penalty|), decades below either term."""
+    from sota_imagenet_amd.losses import CrossEntropyLoss, OrthoLoss
+    from sota_imagenet_amd.optim import SGD
+
+    m, x, t = net
+    m.train()
+    weight = 0.25
+    ce = CrossEntropyLoss(smoothing=0.1)
+    pen = OrthoLoss(m, min_filters=64, min_norm=0)
+    crit = ce + pen * weight
+    opt = SGD([{"params": list(m.parameters())}], lr=0.0, momentum=0.0, weight_decay=0.0)
+    opt.attach_model(m)
+    m.mark_grads_clean()
+    ce(m(x), t).backward()
+    g_plain = m.flat_grads.double().clone()
+    g_pen = _penalty_alone(pen, m, weight).double()
+    assert g_pen.abs().max() > 1e-3 * g_plain.abs().max(), "the penalty must be visible next to the native gradient"
+
+    def check(expected, tag):
+        got = m.flat_grads.double()
+        worst = 0.0
+        for name, kind, off, shape in m._table:
+            if kind != 0:
+                continue
+            n = int(np.prod(shape))
+            sl = slice(off, off + n)
+            bound = 16 * C.U * (g_plain[sl].abs().max() + g_pen[sl].abs().max()) * (2 if tag == "dirty" else 1)
+            worst = max(worst, float((got[sl] - expected[sl]).abs().max() / bound))
+        print(tag, "worst error / bound:", worst)
+        assert worst <= 1.0, tag
+
+    m.mark_grads_clean()
+    crit(m(x), t).backward()
+    check(g_plain + g_pen, "clean")
+    crit(m(x), t).backward()  # dirty: the second micro-step accumulates
+    check(2 * (g_plain + g_pen), "dirty")
+    opt.zero_grad()
+    crit(m(x), t).backward()  # SAM's second pass
+    check(g_plain + g_pen, "after zero_grad")
+    stale = pen(None, None)  # a second forward of the term before the backward of the first: the scratch has moved on
+    fresh = pen(None, None)
+    with pytest.raises(RuntimeError, match="one backward per forward"):
+        stale.backward()
+    fresh.backward()
+    m.mark_grads_clean()  # the other order of the terms
+    (pen * weight + ce)(m(x), t).backward()
+    check(g_plain + g_pen, "penalty first")
+
+
+def test_evaluation_carries_the_penalty_and_writes_no_gradient(net):
+    from sota_imagenet_amd.losses import CrossEntropyLoss, NormLoss, OrthoLoss
+
+    m, x, t = net
+    m.eval()
+    ce, pen, nl = CrossEntropyLoss(smoothing=0.1), OrthoLoss(m, min_filters=64, min_norm=0), NormLoss(m)
+    before = m.flat_grads.clone()
+    dirty = m._grads_dirty
+    with torch.no_grad():
+        out = m(x)
+        total, a, b, c = (ce + pen * 0.5 + nl * 0.25)(out, t), ce(out, t), pen(out, t), nl(out, t)
+    assert total.dim() == 0 and total.dtype == torch.float32 and total.is_cuda and not total.requires_grad
+    assert abs(float(total) - (float(a) + 0.5 * float(b) + 0.25 * float(c))) <= 4 * C.U * abs(float(total))
+    assert float(b) > 0 and float(c) > 0
+    assert torch.equal(m.flat_grads, before) and m._grads_dirty == dirty
+    # against float64 on the flat parameters
+    _, ip = _mods()
+    flat = m.flat_params.detach().cpu().numpy()
+    Ws = [C.mat_of(flat, r) for r in pen.mats]
+    ref, _, Fs, gates = C.ortho_loss64(Ws, 0.0)
+    assert abs(float(b) - ref) <= sum(C.whole_rule_bounds(W, F, g)[0] for W, F, g in zip(Ws, Fs, gates)) + C.U * ref
+    ref, bound, _ = C.norm_loss64([flat[o: o + R * L].reshape(R, L) for o, R, L in nl.records])
+    assert abs(float(c) - ref) <= bound
+    m.train()
+
+
+def test_norm_loss_gradient_through_autograd(net):
+    from sota_imagenet_amd.losses import NormLoss
+
+    m, x, t = net
+    nl = NormLoss(m)
+    m.mark_grads_clean()
+    (nl * 0.5)(None, None).backward()
+    flat = m.flat_params.detach().cpu().numpy()
+    got = m.flat_grads.cpu().numpy()
+    mask = np.zeros(flat.size, dtype=bool)
+    for o, R, L in nl.records:
+        W = flat[o: o + R * L].reshape(R, L)
+        r, b = C.norm_grad64(W, 0.5)
+        assert C.worst(got[o: o + R * L].reshape(R, L), r, b) <= 1.0
+        mask[o: o + R * L] = True
+    assert (got[~mask] == 0).all() and m._grads_dirty
+    m.mark_grads_clean()
+
+
+def test_three_steps_through_runner_fit(dev):
+    from sota_imagenet_amd import callbacks
+    from sota_imagenet_amd.data import SyntheticLoader
+    from sota_imagenet_amd.fit_wrapper import Callback, Runner
+    from sota_imagenet_amd.losses import CrossEntropyLoss
+    from sota_imagenet_amd.models import resnet50
+    from sota_imagenet_amd.optim import SGD
+
+    def fit(with_penalty, ortho_init=True, weight=0.01):
+        m = resnet50(dtype="fp32", num_classes=10).cuda()
+        opt = SGD([{"params": list(m.parameters())}], lr=0.01, momentum=0.9, weight_decay=3e-5)
+        opt.attach_model(m)
+        seen = {}
+
+        class Spy(Callback):
+            def on_begin(self):
+                seen["p0"] = m.flat_params.detach().cpu().numpy().copy()
+
+            def on_batch_end(self):
+                if "loss" not in seen:
+                    seen["loss"] = float(self.state.loss_meter.val)
+                    with torch.no_grad():
+                        seen["ce"] = float(CrossEntropyLoss(smoothing=0.1)(self.state.output.detach(), self.state.input[1]))
+
+        cbs = ([callbacks.OrthoInitClb()] if ortho_init else []) + [callbacks.ForwardSpectralNorm()]
+        clb = callbacks.OrthoLossClb(weight=weight, min_filters=64, min_norm=0)
+        r = Runner(m, opt, CrossEntropyLoss(smoothing=0.1), callbacks=cbs + ([clb] if with_penalty else []) + [Spy()])
+        r.fit(SyntheticLoader(dict(batch_size=8, image_size=64, num_classes=10), size=24, seed=0, device="cuda", pool=2), steps_per_epoch=3, epochs=1)
+        torch.cuda.synchronize()
+        return m, clb, seen
+
+    m, clb, seen = fit(True)
+    Ws = [C.mat_of(seen["p0"], r) for r in clb.term.mats]
+    assert len(Ws) == 33
+    ref, _, Fs, gates = C.ortho_loss64(Ws, 0.0)
+    bound = clb.weight * sum(C.whole_rule_bounds(W, F, True)[0] for W, F in zip(Ws, Fs)) + 4 * C.U * abs(seen["loss"])
+    print("meter", seen["loss"], "ce", seen["ce"], "weight * penalty", clb.weight * ref, "bound", bound)
+    assert abs(seen["loss"] - seen["ce"] - clb.weight * ref) <= bound
+    # after OrthoInitClb the penalty is rounding noise and the identity above holds for a criterion without it; from the default initialisation
+    # the term is far above its bound, so there the meter must show it
+    _, clb2, seen2 = fit(True, ortho_init=False, weight=0.5)
+    Ws = [C.mat_of(seen2["p0"], r) for r in clb2.term.mats]
+    ref, _, Fs, gates = C.ortho_loss64(Ws, 0.0)
+    bound = clb2.weight * sum(C.whole_rule_bounds(W, F, True)[0] for W, F in zip(Ws, Fs)) + 4 * C.U * abs(seen2["loss"])
+    print("default init: meter", seen2["loss"], "ce", seen2["ce"], "weight * penalty", clb2.weight * ref, "bound", bound)
+    assert all(gates) and clb2.weight * ref > 10 * bound
+    assert abs(seen2["loss"] - seen2["ce"] - clb2.weight * ref) <= bound
+    m0, _, seen0 = fit(False)
+    assert np.array_equal(seen0["p0"], seen["p0"]), "both runs start from the same orthogonal initialisation"
+    assert torch.isfinite(m.flat_params).all() and not torch.equal(m.flat_params, m0.flat_params)
