@@ -7,22 +7,16 @@ native AdamP is against that restatement and is unpinned against the package its
 include/mi355rn.h and csrc/optim_adamp.hip document for the kernels: float32 element operations, one rounding each, coefficients formed in double
 and rounded once, the sums of the decision in double, s = sum(p*u)/d."""
 import importlib.util
-import json
 import math
 import os
 
-import numpy as np
 import torch
+
+from optim_harness import TrajectoryFixture
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "adamp_ref_trajectories.npz")
 CASES = ["adamp_recipe51", "adamp_alt"]
-U = 2.0 ** -24
-FACTOR = 1.5  # the rule of tests/layerwise_common.py: err <= FACTOR * yard + 4 * U * max |ref|
-
-
-def _js(a):
-    return json.loads(bytes(a).decode())
 
 
 def recorder():
@@ -36,38 +30,28 @@ GEN = recorder()
 DEFAULTS = GEN.DEFAULTS
 
 
-class Fixture:
+class Fixture(TrajectoryFixture):
+    """four steps; param groups, inputs and gradients per case; the yardstick is the restatement's float32 run; state4: its float32 moments"""
+
+    GOLDEN = GOLDEN
+    YARD_NAME = "restated fp32"
+
     def __init__(self, case):
-        z = np.load(GOLDEN)
-        self.case = case
-        self.shapes = [tuple(s) for s in _js(z["shapes"])]
-        self.sizes = [int(np.prod(s)) for s in self.shapes]
-        self.offs = np.cumsum([0] + self.sizes)
-        self.hyper, self.groups = _js(z[f"{case}/hyper"]), _js(z[f"{case}/groups"])
+        super().__init__(case)
+        self.shapes = [tuple(s) for s in self.shapes]
         if "betas" in self.hyper:
             self.hyper["betas"] = tuple(self.hyper["betas"])
-        self.wds, self.lrs = [float(x) for x in z[f"{case}/wds"]], [float(x) for x in z[f"{case}/lrs"]]
-        self.p0, self.grads = torch.from_numpy(z[f"{case}/p0"]), torch.from_numpy(z[f"{case}/grads"])
-        self.p64, self.yard, self.modes = torch.from_numpy(z[f"{case}/p64"]), z[f"{case}/yard"], z[f"{case}/modes"]
-        self.margins, self.effect = z[f"{case}/margins"], z[f"{case}/effect"]
-        self.state4 = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith(f"{case}/state4/")}
+        self.wds, self.grads = [float(x) for x in self.rec("wds")], torch.from_numpy(self.rec("grads"))
+        self.modes, self.margins, self.effect = self.rec("modes"), self.rec("margins"), self.rec("effect")
+        self.state4 = self.states("state4")
         self.group_of = [next(gi for gi, idx in enumerate(self.groups) if i in idx) for i in range(len(self.shapes))]
         self.order = [i for idx in self.groups for i in idx]  # param-group order -> fixture tensor
 
     def split(self, flat):
-        return [flat[self.offs[i]:self.offs[i + 1]].view(self.shapes[i]) for i in range(len(self.shapes))]
+        return [t.view(shape) for t, shape in zip(super().split(flat), self.shapes)]
 
-    def check(self, k, got, what):
-        """got: the native parameters after step k + 1 as a list in the fixture's tensor order"""
-        ratios = []
-        for i, (g, ref) in enumerate(zip(got, self.split(self.p64[k]))):
-            err = (g.detach().double().cpu() - ref).abs().max().item()
-            floor = 4 * U * ref.abs().max().item()
-            ratios.append(err / self.yard[k, i])
-            print(f"{what} step {k + 1} tensor {i} {self.shapes[i]}: native {err:.3e}  restated fp32 {self.yard[k, i]:.3e}  ratio {ratios[-1]:.2f}  "
-                  f"floor {floor:.2e}")
-            assert err <= FACTOR * self.yard[k, i] + floor, f"{what} step {k + 1} tensor {i}: native {err:.3e} vs restated fp32 {self.yard[k, i]:.3e}"
-        return max(ratios)
+    def tensor_label(self, i):
+        return f"tensor {i} {self.shapes[i]}"
 
 
 def f32(x):

@@ -2,21 +2,16 @@
 AdamLayerwise and MyAdai (tests/golden/layerwise_ref_trajectories.npz, written by tests/golden/make_layerwise_golden.py) and the four update rules
 as this project documents them (include/mi355rn.h), restated in torch on the CPU in a chosen dtype."""
 import importlib.util
-import json
 import os
 
 import numpy as np
 import torch
 
+from optim_harness import TrajectoryFixture
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "layerwise_ref_trajectories.npz")
 CASES = ["nov_recipe", "mynov_recipe", "adamlw_recipe", "myadai_recipe", "adamlw_alt", "nov_alt", "myadai_alt"]
-U = 2.0 ** -24
-FACTOR = 1.5
-
-
-def _js(a):
-    return json.loads(bytes(a).decode())
 
 
 def _generator():
@@ -39,37 +34,17 @@ def problem_grads():
     return _PROBLEM[1]
 
 
-class Fixture:
+class Fixture(TrajectoryFixture):
+    """the gradients are rebuilt from their seeds; MyAdai's momentum coefficients and second moments where the case records them"""
+
+    GOLDEN = GOLDEN
+
     def __init__(self, case):
-        z = np.load(GOLDEN)
-        self.case = case
-        self.shapes, self.groups = _js(z["shapes"]), _js(z["groups"])
-        self.sizes = [int(np.prod(s)) for s in self.shapes]
-        self.offs = np.cumsum([0] + self.sizes)
-        self.p0, self.grads = torch.from_numpy(z["p0"]), problem_grads()
+        super().__init__(case)
+        self.grads = problem_grads()
         assert torch.equal(self.p0, _PROBLEM[0])  # the seeds rebuild the recorded inputs bit for bit
-        self.hyper = _js(z[f"{case}/hyper"])
-        self.cls = self.hyper.pop("cls")
-        self.lrs = [float(x) for x in z[f"{case}/lrs"]]
-        self.p64, self.yard = torch.from_numpy(z[f"{case}/p64"]), z[f"{case}/yard"]
-        self.state_keys, self.state_shapes = _js(z[f"{case}/state_keys"]), _js(z[f"{case}/state_shapes"])
-        self.state5 = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith(f"{case}/state5/")}
-        self.beta1 = z[f"{case}/beta1"] if f"{case}/beta1" in z.files else None
-        self.v0 = z[f"{case}/v0"] if f"{case}/v0" in z.files else None
-
-    def split(self, flat):
-        return [flat[self.offs[i]:self.offs[i + 1]] for i in range(len(self.shapes))]
-
-    def check(self, k, got_flat, what):
-        """got_flat: the native parameters after step k + 1, in the fixture's tensor order; the rule of test_madgrad_adais_gpu.py"""
-        ratios = []
-        for i, (got, ref) in enumerate(zip(self.split(got_flat.detach().double().cpu()), self.split(self.p64[k]))):
-            err = (got - ref).abs().max().item()
-            floor = 4 * U * ref.abs().max().item()
-            ratios.append(err / self.yard[k, i])
-            print(f"{what} step {k + 1} tensor {i}: native {err:.3e}  reference fp32 {self.yard[k, i]:.3e}  ratio {ratios[-1]:.2f}  floor {floor:.2e}")
-            assert err <= FACTOR * self.yard[k, i] + floor, f"{what} step {k + 1} tensor {i}: native {err:.3e} vs reference fp32 {self.yard[k, i]:.3e}"
-        return max(ratios)
+        self.beta1 = self.rec("beta1") if self.has("beta1") else None
+        self.v0 = self.rec("v0") if self.has("v0") else None
 
 
 class Restated:

@@ -3,10 +3,9 @@ NovogradApex with unitwise_norm=True (tests/golden/layerwise_unit_ref_trajectori
 the unit-wise rule as this project documents it (include/mi355rn.h), restated in torch on the CPU in a chosen dtype."""
 import os
 
-import numpy as np
 import torch
 
-from layerwise_common import HERE, Fixture, _js, problem_grads
+from layerwise_common import HERE, Fixture
 
 GOLDEN = os.path.join(HERE, "golden", "layerwise_unit_ref_trajectories.npz")
 CASES = ["mynov_unit_recipe", "nov_unit", "nov_unit_alt"]
@@ -15,22 +14,13 @@ M_KEY = {"MyNovograd": "ema_grad", "NovogradApex": "exp_avg"}
 
 
 class UnitFixture(Fixture):
-    """the layout of layerwise_common.Fixture (its split and check apply as they are) over the unit-wise file"""
+    """layerwise_common.Fixture over the unit-wise file, with the float32 second moment after step 5 and its spread"""
+
+    GOLDEN = GOLDEN
 
     def __init__(self, case):
-        z = np.load(GOLDEN)
-        self.case = case
-        self.shapes, self.groups = _js(z["shapes"]), _js(z["groups"])
-        self.sizes = [int(np.prod(s)) for s in self.shapes]
-        self.offs = np.cumsum([0] + self.sizes)
-        self.p0, self.grads = torch.from_numpy(z["p0"]), problem_grads()
-        self.hyper = _js(z[f"{case}/hyper"])
-        self.cls = self.hyper.pop("cls")
-        self.lrs = [float(x) for x in z[f"{case}/lrs"]]
-        self.p64, self.yard = torch.from_numpy(z[f"{case}/p64"]), z[f"{case}/yard"]
-        self.state_keys, self.state_shapes = _js(z[f"{case}/state_keys"]), _js(z[f"{case}/state_shapes"])
-        self.state5 = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith(f"{case}/state5/")}
-        self.v32_5, self.spread, self.vs_layerwise = torch.from_numpy(z[f"{case}/v32_5"]), z[f"{case}/spread"], float(z[f"{case}/vs_layerwise"])
+        super().__init__(case)
+        self.v32_5, self.spread, self.vs_layerwise = torch.from_numpy(self.rec("v32_5")), self.rec("spread"), float(self.rec("vs_layerwise"))
         self.v_key, self.m_key = V_KEY[self.cls], M_KEY[self.cls]
 
 

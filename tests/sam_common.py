@@ -2,60 +2,53 @@
 (tests/golden/sam_ref_trajectories.npz, written by tests/golden/make_sam_golden.py), the rules of the callback as this project documents them
 (include/mi355rn.h) restated in torch on the CPU in a chosen dtype, and the quadratic problem of the fixture."""
 import importlib.util
-import json
 import os
 
-import numpy as np
 import torch
+
+from optim_harness import TrajectoryFixture, _js
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "sam_ref_trajectories.npz")
 CASES = ["sgd", "adamlw_recipe", "clamp"]
-U = 2.0 ** -24
-FACTOR = 1.5
 NORM_FLOOR = 2e-5
 
-_GEN = None
+
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, "golden", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
-def generator():
-    """tests/golden/make_sam_golden.py as a module: the problem (shapes, groups, seeds, the quadratic module) is stated there once"""
-    global _GEN
-    if _GEN is None:
-        spec = importlib.util.spec_from_file_location("make_sam_golden", os.path.join(HERE, "golden", "make_sam_golden.py"))
-        _GEN = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(_GEN)
-    return _GEN
+_GEN = {}
 
 
-def _js(a):
-    return json.loads(bytes(a).decode())
+def generator(name="make_sam_golden"):
+    """tests/golden/<name>.py as a module: the problem (shapes, groups, seeds, the quadratic module) is stated there once"""
+    if name not in _GEN:
+        _GEN[name] = _load(name)
+    return _GEN[name]
 
 
-class Fixture:
+class CallbackFixture(TrajectoryFixture):
+    """a callback's trajectory: per step the reference's float64 eps, the parameters at the second forward (p + eps) and the parameters after
+    the optimizer step, each with the yardstick of the reference's float32 run"""
+
+    GENERATOR = None  # the subclass's recorder, tests/golden/<GENERATOR>.py
+
     def __init__(self, case):
-        z = np.load(GOLDEN)
-        gen = generator()
-        self.case = case
-        self.shapes, self.groups, self.steps = _js(z["shapes"]), _js(z["groups"]), _js(z["steps"])
-        self.sizes = [int(np.prod(s)) for s in self.shapes]
-        self.offs = np.cumsum([0] + self.sizes)
-        self.p0 = torch.from_numpy(z["p0"])
+        super().__init__(case)
+        gen = generator(self.GENERATOR)
         assert torch.equal(self.p0, gen.flat(gen.params0()))  # the seeds rebuild the recorded inputs bit for bit
-        h = _js(z[f"{case}/hyper"])
-        self.cls, self.kw, self.rho, self.eta = h["cls"], h["kw"], h["rho"], h["eta"]
-        self.a = [float(x) for x in z[f"{case}/a"]]
-        self.lrs = [float(x) for x in z[f"{case}/lrs"]]
-        self.norm = z[f"{case}/norm"]
-        self.forwards = [int(x) for x in z[f"{case}/forwards"]]
-        self.eps, self.p_step = torch.from_numpy(z[f"{case}/eps"]), torch.from_numpy(z[f"{case}/p_step"])
-        self.yard = {k: z[f"{case}/yard_{k}"] for k in ("eps", "pert", "step")}
+        self.steps, self.kw, self.rho = _js(self.rec("steps")), self.hyper["kw"], self.hyper["rho"]
+        self.a = [float(x) for x in self.rec("a")]
+        self.forwards = [int(x) for x in self.rec("forwards")]
+        self.eps, self.p_step = torch.from_numpy(self.rec("eps")), torch.from_numpy(self.rec("p_step"))
+        self.yard = {k: self.rec(f"yard_{k}") for k in ("eps", "pert", "step")}
 
     def targets(self, k):
-        return generator().targets(k)
-
-    def split(self, flat):
-        return [flat[self.offs[i]:self.offs[i + 1]] for i in range(len(self.shapes))]
+        return generator(self.GENERATOR).targets(k)
 
     def pert(self, k):
         """the float64 run's parameters at the second forward of step k: the parameters before the step plus eps (exact in float64, asserted by
@@ -63,18 +56,18 @@ class Fixture:
         return (self.p0.double() if k == 0 else self.p_step[k - 1]) + self.eps[k]
 
     def check(self, k, got_flat, what):
-        """got_flat: the native values of step k + 1 (what: "eps", "pert" or "step") in the fixture's tensor order, against the float64 run; the
-        rule and floor of layerwise_common.Fixture.check"""
+        """got_flat: the native values of step k + 1 (what: "eps", "pert" or "step") in the fixture's tensor order, against the float64 run"""
         ref_flat = {"eps": self.eps[k], "pert": self.pert(k), "step": self.p_step[k]}[what]
-        ratios = []
-        for i, (got, ref) in enumerate(zip(self.split(got_flat.detach().double().cpu()), self.split(ref_flat))):
-            err = (got - ref).abs().max().item()
-            yard = float(self.yard[what][k, i])
-            floor = 4 * U * ref.abs().max().item()
-            ratios.append(err / max(yard, floor))
-            print(f"{self.case} {what} step {k + 1} tensor {i}: native {err:.3e}  reference fp32 {yard:.3e}  floor {floor:.2e}")
-            assert err <= FACTOR * yard + floor, f"{self.case} {what} step {k + 1} tensor {i}: native {err:.3e} vs reference fp32 {yard:.3e}"
-        return max(ratios)
+        return self.check_tensors(got_flat, ref_flat, [float(y) for y in self.yard[what][k]], f"{self.case} {what} step {k + 1}", floor_in_ratio=True)
+
+
+class Fixture(CallbackFixture):
+    GOLDEN = GOLDEN
+    GENERATOR = "make_sam_golden"
+
+    def __init__(self, case):
+        super().__init__(case)
+        self.eta, self.norm = self.hyper["eta"], self.rec("norm")
 
 
 def sam_norm(ps, gs, eta):

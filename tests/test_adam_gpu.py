@@ -4,7 +4,7 @@ Yardstick: the native result may be no further from a float64 run of torch.optim
 distance of the same torch optimizer in float32 on the CPU (one intra-op thread), plus a floor of 1e-7 * lr for the parameters
 and one fp32 rounding of the largest value per step for the moments — the form of test_resnet_gpu's fp32 gradient yardstick."""
 import copy
-import glob
+import functools
 import math
 import os
 import sys
@@ -12,9 +12,13 @@ import sys
 import pytest
 import torch
 
+import optim_harness as H
+from optim_harness import U
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -24
+_grads_for = functools.partial(H.grads_for, pad=0.0)  # zero in the padding: what a backward leaves there
+_flat_steps = functools.partial(H.flat_steps, lr=1e-3, pad=0.0)
 
 
 @pytest.fixture(autouse=True)
@@ -102,15 +106,6 @@ def test_adam_step_with_the_moving_average_in_the_same_pass(dev):
         assert ((ema - ema_ref).abs().max() / ema_ref.abs().max()).item() < 1e-6 and not torch.equal(ema, pe)
 
 
-def _grads_for(m, seed):
-    """one flat gradient for every parameter of a flat model, zero in the padding (what a backward leaves there)"""
-    g = torch.zeros_like(m.flat_grads)
-    for i, (name, p) in enumerate(m.named_parameters()):
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        g[off: off + p.numel()] = rnd((p.numel(),), seed * 1000 + i, 1e-2).to(g.device)
-    return g
-
-
 def _sgd_plan_ranges(m, groups):
     from sota_imagenet_amd.optim import SGD
 
@@ -178,17 +173,6 @@ def test_adamw_model_level_teacher_forced(dev):
     o2.attach_model(m2)
     o2.step()
     assert [len(segs) for segs in o2._plans] == [1]
-
-
-def _flat_steps(m, opt, seeds, lr=1e-3):
-    for s in seeds:
-        m.flat_grads.copy_(_grads_for(m, s))
-        for g in opt.param_groups:
-            g["lr"] = lr
-        if hasattr(opt, "attach_model"):  # (a stock torch optimizer's zero_grad would unbind the flat gradient views)
-            opt.zero_grad()
-        opt.step()
-    torch.cuda.synchronize()
 
 
 def test_adamw_resume_continues_bitwise(dev):
@@ -291,43 +275,10 @@ def test_adamw_state_dict_moves_both_ways_with_torch(dev):
 def test_model_ema_inside_the_adamw_kernel_matches_the_callback(dev):
     """ModelEma (train.py:111-112) under the native AdamW: the average advanced by the step kernel (attach_ema) equals the
     callback's own lerp after every batch"""
-    from sota_imagenet_amd import fit_wrapper as fw
-    from sota_imagenet_amd.losses import CrossEntropyLoss
-    from sota_imagenet_amd.models import resnet50
-    from sota_imagenet_amd.optim import AdamW
-    from sota_imagenet_amd.synth import synthetic_batch
-
-    class Loader:
-        batch_size = 4
-
-        def __len__(self):
-            return 3
-
-        def __iter__(self):
-            return iter([synthetic_batch(4, 64, seed=6, index=i, device="cuda") for i in range(3)])
-
-    res = []
-    for fused in (True, False):
-        m = resnet50(dtype="fp32").cuda()
-        opt = AdamW([{"params": list(m.parameters())}], lr=0.0, weight_decay=5e-2)
-        opt.attach_model(m)
-        ema = fw.ModelEma(m, 0.9)
-        if not fused:
-            ema.on_begin = lambda: None
-        runner = fw.Runner(m, opt, CrossEntropyLoss(smoothing=0.1), callbacks=[fw.PhasesScheduler([dict(ep=(0, 1), lr=(1e-3, 2e-3))]), ema])
-        runner.fit(Loader(), val_loader=Loader(), epochs=1)
-        assert ema._fused == fused and not ema._swapped
-        res.append((m.flat_params.clone(), ema.ema[0].clone(), ema.ema[1].clone()))
-    (p_a, e_a, b_a), (p_b, e_b, b_b) = res
-    assert torch.equal(p_a, p_b) and torch.equal(b_a, b_b)
-    assert not torch.equal(e_a, p_a)
-    assert ((e_a - e_b).abs().max() / e_b.abs().max()).item() < 1e-6
+    H.ema_matches_callback(lambda: H.model_opt("AdamW", dict(weight_decay=5e-2), 0.0), 1e-3)
 
 
 def test_train_py_runs_the_adamw_smoke_config(dev, tmp_path, monkeypatch):
-    sys.path.insert(0, ROOT)
-    import train
-
     from sota_imagenet_amd import optim
 
     made = []
@@ -338,19 +289,11 @@ def test_train_py_runs_the_adamw_smoke_config(dev, tmp_path, monkeypatch):
         return build(self)
 
     monkeypatch.setattr(optim.Adam, "_build_plans", spy)
-    logdir = os.path.relpath(str(tmp_path), ROOT)
-    val_loss, metrics = train.main(["+hydra_exp=adamw_test", f"log.dir={logdir}", "run.fp16=false", "random_seed=0",
-                                    "data.pool=2", "log.save_optim=true"])
+    _, _, run, losses = H.run_smoke_config("adamw_test", tmp_path, ["run.fp16=false", "random_seed=0", "data.pool=2", "log.save_optim=true"],
+                                           resume_eval=True)
     assert made and all(type(o) is optim.AdamW for o in made)
-    assert math.isfinite(val_loss) and 0.0 <= metrics["Acc@1"].avg <= 100.0
-    run = glob.glob(os.path.join(str(tmp_path), "*_adamw_test", "*"))[0]
-    logs = open(os.path.join(run, "logs.txt")).read()
-    losses = [float(x) for x in __import__("re").findall(r"Train loss: ([0-9.]+)", logs)]
     assert losses and all(math.isfinite(x) for x in losses)
     ck = torch.load(os.path.join(run, "model.chpn"), map_location="cpu")
     st = ck["optimizer"]["state"]
     assert st and all({"step", "exp_avg", "exp_avg_sq"} <= set(s) for s in st.values())
     assert ck["optimizer"]["param_groups"][0]["decoupled_weight_decay"] is True
-    loss2, m2 = train.main(["+hydra_exp=adamw_test", f"log.dir={logdir}", f"run.resume={os.path.join(run, 'model.chpn')}",
-                            "run.evaluate=true", "data.pool=2"])
-    assert math.isfinite(loss2) and 0.0 <= m2["Acc@1"].avg <= 100.0

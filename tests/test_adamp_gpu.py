@@ -2,60 +2,31 @@
 fixture tests/golden/adamp_ref_trajectories.npz recorded from it on the CPU).  The `adamp` package is not available to this project: the rule is
 written down from memory of the public package and parity is unpinned against the package itself.
 
-Yardstick, stored in the fixture and never computed from the code under test: the rule of tests/layerwise_common.py — FACTOR = 1.5 times the
-restatement's own float32 error plus a floor of 4 * 2^-24 of the largest parameter magnitude.  At model scale the same rule with the restatement's
+Yardstick, stored in the fixture and never computed from the code under test: the rule of this family (tests/optim_harness.py, within_yardstick)
+— FACTOR = 1.5 times the restatement's own float32 error plus a floor of 4 * 2^-24 of the largest parameter magnitude.  At model scale the same rule with the restatement's
 float32 run as the yardstick.  The update kernel alone is compared bit for bit with the float32 restatement that is handed the device's own
 coefficients."""
 import copy
 import ctypes
-import glob
 import math
 import os
-import re
 import sys
 
 import pytest
 import torch
 
-from adamp_common import CASES, FACTOR, U, Fixture, Restated, slot_rows
-from plan_common import layout as _layout
+import optim_harness as H
+from adamp_common import CASES, Fixture, Restated, slot_rows
+from optim_harness import NAN, U
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAN = float("nan")
-
-
-def _flat_params(shapes, values, dev, order=None):
-    """parameters as views of one flat parameter / gradient buffer under the 64-element alignment rule: zero gaps in p, NaN in every gap of g"""
-    sizes = [math.prod(s) for s in shapes]
-    offs, n = _layout(sizes, order)
-    fp, fg = torch.zeros(n, device=dev), torch.full((n,), NAN, device=dev)
-    ps = []
-    for o, s, shape, val in zip(offs, sizes, shapes, values):
-        fp[o:o + s] = val.to(dev).reshape(-1)
-        p = torch.nn.Parameter(fp[o:o + s].view(shape))
-        p.grad = fg[o:o + s].view(shape)
-        ps.append(p)
-    return ps, fp, fg
-
-
-def _set_grads(ps, grads, mult=1.0):
-    for p, g in zip(ps, grads):
-        p.grad.copy_((g * mult).view(p.shape))
-
-
-def _gaps(ps, fp):
-    mask = torch.ones_like(fp, dtype=torch.bool)
-    for p in ps:
-        o = (p.data_ptr() - fp.data_ptr()) // 4
-        mask[o:o + p.numel()] = False
-    return mask
 
 
 def _fixture_opt(fx, dev, values=None):
     from sota_imagenet_amd import optim
 
-    ps, fp, fg = _flat_params(fx.shapes, fx.split(fx.p0) if values is None else values, dev, fx.order)
+    ps, fp, fg, _ = H.flat_params(fx.sizes, fx.shapes, fx.split(fx.p0) if values is None else values, dev, fx.order)
     groups = [{"params": [ps[i] for i in idx], "weight_decay": wd} for idx, wd in zip(fx.groups, fx.wds)]
     return optim.AdamP(groups, lr=fx.lrs[0], **fx.hyper), ps, fp, fg
 
@@ -65,7 +36,7 @@ def _fixture_steps(fx, opt, ps, steps, grad_scale=1.0, each=None):
     for k in steps:
         for g in opt.param_groups:
             g["lr"] = fx.lrs[k]
-        _set_grads(ps, fx.split(fx.grads[k]), 1.0 / grad_scale)  # (exact: a power of two)
+        H.set_grads(ps, fx.split(fx.grads[k]), 1.0 / grad_scale)  # (exact: a power of two)
         opt.step()
         if each:
             each(k)
@@ -90,7 +61,7 @@ def test_steps_follow_the_restated_trajectory(dev, case):
             worst = max(worst, fx.check(k, [p.detach() for p in ps], f"{case} grad_scale={gs}"))
 
         _fixture_steps(fx, opt, ps, range(4), gs, each)
-        gaps = _gaps(ps, fp)
+        gaps = H.gaps(ps, fp)
         assert gaps.any() and (fp[gaps] == 0).all() and torch.isnan(fg[gaps]).all() and torch.isfinite(fp).all()
         assert all(opt.state[p]["step"] == 4 and type(opt.state[p]["step"]) is int for p in ps)
         assert [c for _, c in opt.slot_ranges] == [slot_rows(ps[i]).shape[0] for i in fx.order]
@@ -113,7 +84,7 @@ def _small_problem(dev, seed):
 
     gen = torch.Generator().manual_seed(seed)
     vals = [torch.randn(s, generator=gen) * (0.02 * 2.0 ** (i % 3)) for i, s in enumerate(SMALL)]
-    ps, fp, fg = _flat_params(SMALL, vals, dev)
+    ps, fp, fg, _ = H.flat_params([math.prod(s) for s in SMALL], SMALL, vals, dev)
     kinds = {1: "channel", 2: "layer", 0: "none"}
 
     def grads(k):
@@ -141,9 +112,9 @@ def test_unit_sums_equal_the_float64_sums(dev):
     h = dict(betas=(0.8, 0.95), eps=1e-5, nesterov=True)
     opt = optim.AdamP(ps, lr=1e-3, weight_decay=1e-2, **h)
     opt.grad_scale = 0.5
-    _set_grads(ps, grads(0))
+    H.set_grads(ps, grads(0))
     opt.step()
-    _set_grads(ps, grads(1))
+    H.set_grads(ps, grads(1))
     torch.cuda.synchronize()
     seg, = opt._segs
     before = [t.clone() for t in (seg.p, seg.g, seg.m, seg.v)]
@@ -193,7 +164,7 @@ def test_update_equals_the_float32_restatement_bit_for_bit(dev, nesterov, ema):
     for k, lr in enumerate((1e-3, 3e-3)):
         opt.param_groups[0]["lr"] = lr
         gk = grads(k)
-        _set_grads(ps, gk)
+        H.set_grads(ps, gk)
         opt.step()
         torch.cuda.synchronize()
         modes = [int(x) for x in opt.projection_modes.cpu()]
@@ -212,7 +183,7 @@ def test_update_equals_the_float32_restatement_bit_for_bit(dev, nesterov, ema):
             if ema:
                 o = (p.data_ptr() - fp.data_ptr()) // 4
                 assert torch.equal(fe[o:o + p.numel()].cpu().view(p.shape), r.ema[i]), f"{what}: moving average"
-    gaps = _gaps(ps, fp)
+    gaps = H.gaps(ps, fp)
     assert (fp[gaps] == 0).all() and torch.isnan(fg[gaps]).all()
     if ema:
         assert (fe[gaps] == 0).all()
@@ -288,45 +259,12 @@ def test_state_dict_round_trip_continues_bit_for_bit(dev):
 
 
 # ---- 6. the whole model ---------------------------------------------------------------------------------------------------------------------------
-def _grads_for(m, seed, scale=1e-2):
-    g = torch.full_like(m.flat_grads, NAN)
-    for i, (name, p) in enumerate(m.named_parameters()):
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        gen = torch.Generator().manual_seed(seed * 1000 + i)
-        g[off: off + p.numel()] = (torch.randn((p.numel(),), generator=gen) * scale).to(g.device)
-    return g
-
-
-def _padding_mask(m):
-    mask = torch.ones(m.flat_params.numel(), dtype=torch.bool, device=m.flat_params.device)
-    for p in m.parameters():
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        mask[off: off + p.numel()] = False
-    return mask
-
-
-def _count_launches(monkeypatch):
-    from sota_imagenet_amd import ops
-
-    calls = []
-    for name in ("adamp_unit_sums", "adamp_coef", "adamp_update"):
-        fn = getattr(ops, name)
-        monkeypatch.setattr(ops, name, (lambda f, n: lambda *a, **k: (calls.append(n), f(*a, **k))[1])(fn, name))
-    return calls
-
-
+STAGES = ["adamp_unit_sums", "adamp_coef", "adamp_update"]
 KW = dict(weight_decay=1e-2, eps=1e-8)
 
 
 def _model_opt(groups_of=None):
-    from sota_imagenet_amd import optim
-    from sota_imagenet_amd.models import resnet50
-
-    m = resnet50(dtype="fp32").cuda()
-    groups = groups_of(m) if groups_of else [{"params": list(m.parameters())}]
-    opt = optim.AdamP(groups, lr=1e-3, **KW)
-    opt.attach_model(m)
-    return m, opt
+    return H.model_opt("AdamP", KW, 1e-3, groups_of)
 
 
 def test_two_steps_at_model_scale(dev, monkeypatch):
@@ -339,10 +277,10 @@ def test_two_steps_at_model_scale(dev, monkeypatch):
     p0 = [p.detach().cpu().clone() for p in params]
     r64 = Restated(KW, p0, [0] * 161, [KW["weight_decay"]], torch.float64)
     r32 = Restated(KW, p0, [0] * 161, [KW["weight_decay"]], torch.float32)
-    calls = _count_launches(monkeypatch)
+    calls = H.count_launches(monkeypatch, STAGES)
     worst = 0.0
     for k, lr in enumerate((1e-3, 2e-3)):
-        m.flat_grads.copy_(_grads_for(m, 41 + k))
+        m.flat_grads.copy_(H.grads_for(m, 41 + k))
         opt.param_groups[0]["lr"] = lr
         opt.zero_grad()
         del calls[:]
@@ -355,14 +293,11 @@ def test_two_steps_at_model_scale(dev, monkeypatch):
         modes = [int(x) for x in opt.projection_modes.cpu()]
         assert modes == r64.modes, f"step {k + 1}: modes"
         for i, p in enumerate(params):
-            ref = r64.p[i]
-            err = (p.detach().cpu().double() - ref).abs().max().item()
-            yard = (r32.p[i].double() - ref).abs().max().item()
-            floor = 4 * U * ref.abs().max().item()
-            worst = max(worst, err / max(yard, floor))
-            assert err <= FACTOR * yard + floor, f"step {k + 1} tensor {i} {tuple(p.shape)} mode {modes[i]}: native {err:.3e} vs restated fp32 {yard:.3e} (floor {floor:.2e})"
+            yard = (r32.p[i].double() - r64.p[i]).abs().max().item()
+            worst = max(worst, H.within_yardstick(p, r64.p[i], yard, f"step {k + 1} tensor {i} {tuple(p.shape)} mode {modes[i]}", floor_in_ratio=True,
+                                                  yard_name="restated fp32"))
     print(f"model scale: worst native error / max(restated-fp32 error, floor) {worst:.2f}; modes 0/1/2: {[modes.count(x) for x in (0, 1, 2)]}")
-    mask = _padding_mask(m)
+    mask = H.padding_mask(m)
     assert mask.any() and (m.flat_params[mask] == 0).all() and torch.isnan(m.flat_grads[mask]).all() and torch.isfinite(m.flat_params).all()
     assert all((p.detach().cpu() != q).any() for p, q in zip(params, p0))
     # the recipe's two groups
@@ -370,45 +305,20 @@ def test_two_steps_at_model_scale(dev, monkeypatch):
     import train
 
     m2, opt2 = _model_opt(lambda mm: train.filter_from_weight_decay(mm, ["bn", "bias"]))
-    m2.flat_grads.copy_(_grads_for(m2, 43))
+    m2.flat_grads.copy_(H.grads_for(m2, 43))
     del calls[:]
     opt2.zero_grad()
     opt2.step()
     torch.cuda.synchronize()
     assert len(calls) <= 5 and calls == ["adamp_unit_sums", "adamp_coef", "adamp_coef", "adamp_update", "adamp_update"]
-    assert (m2.flat_params[_padding_mask(m2)] == 0).all() and torch.isfinite(m2.flat_params).all()
+    assert (m2.flat_params[H.padding_mask(m2)] == 0).all() and torch.isfinite(m2.flat_params).all()
     assert all(opt2.state[p]["step"] == 1 for p in m2.parameters())
 
 
 def test_model_ema_inside_the_step_kernel_matches_the_callback(dev):
     """ModelEma (train.py:111-112) under AdamP: the average advanced by the update kernel (attach_ema) equals the callback's own lerp after
     every batch within the rule of this file, and the parameters are the same bits either way"""
-    from sota_imagenet_amd import fit_wrapper as fw
-    from sota_imagenet_amd.losses import CrossEntropyLoss
-    from sota_imagenet_amd.synth import synthetic_batch
-
-    class Loader:
-        batch_size = 4
-
-        def __len__(self):
-            return 3
-
-        def __iter__(self):
-            return iter([synthetic_batch(4, 64, seed=6, index=i, device="cuda") for i in range(3)])
-
-    res = []
-    for fused in (True, False):
-        m, opt = _model_opt()
-        ema = fw.ModelEma(m, 0.9)
-        if not fused:
-            ema.on_begin = lambda: None
-        runner = fw.Runner(m, opt, CrossEntropyLoss(smoothing=0.1), callbacks=[fw.PhasesScheduler([dict(ep=(0, 1), lr=(1e-4, 2e-4))]), ema])
-        runner.fit(Loader(), val_loader=Loader(), epochs=1)
-        assert ema._fused == fused and not ema._swapped
-        res.append((m.flat_params.clone(), ema.ema[0].clone(), ema.ema[1].clone()))
-    (p_a, e_a, b_a), (p_b, e_b, b_b) = res
-    assert torch.equal(p_a, p_b) and torch.equal(b_a, b_b)
-    assert not torch.equal(e_a, p_a) and torch.isfinite(e_a).all()
+    e_a, e_b = H.ema_matches_callback(_model_opt, 1e-4)
     # the callback's lerp may fuse ema + w*(p - ema) into one rounding where the kernel makes two: at most one ulp of the average, 2 * 2^-24 of
     # its magnitude, in each of the 3 steps
     assert (e_a - e_b).abs().max().item() <= 3 * 2 * U * e_b.abs().max().item()
@@ -475,9 +385,6 @@ def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch):
     """train.py on adamp_test: the native class is built and stepped, the two epochs' losses are finite and decreasing over the run, and the
     log shows how many tensors took mode 0 / 1 / 2 at the last step (printed, not asserted: which mode a bf16 BatchNorm net's convolutions
     take is not known until it is run)"""
-    sys.path.insert(0, ROOT)
-    import train
-
     from sota_imagenet_amd import optim
 
     made = []
@@ -488,14 +395,8 @@ def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch):
         return build(self)
 
     monkeypatch.setattr(optim.AdamP, "_build_plans", spy)
-    logdir = os.path.relpath(str(tmp_path), ROOT)
-    val_loss, metrics = train.main(["+hydra_exp=adamp_test", f"log.dir={logdir}", "run.fp16=false", "random_seed=0", "data.pool=2",
-                                    "log.save_optim=true"])
+    _, _, run, losses = H.run_smoke_config("adamp_test", tmp_path, ["run.fp16=false", "random_seed=0", "data.pool=2", "log.save_optim=true"])
     assert made and all(type(o) is optim.AdamP for o in made)
-    assert math.isfinite(val_loss) and 0.0 <= metrics["Acc@1"].avg <= 100.0
-    run = glob.glob(os.path.join(str(tmp_path), "*_adamp_test", "*"))[0]
-    logs = open(os.path.join(run, "logs.txt")).read()
-    losses = [float(x) for x in re.findall(r"Train loss: ([0-9.]+)", logs)]
     modes = [int(x) for x in made[-1].projection_modes.cpu()]
     print("adamp_test train losses:", losses, "| tensors in mode 0 / 1 / 2 at the last step:", [modes.count(x) for x in (0, 1, 2)])
     assert len(losses) == 2 and all(math.isfinite(x) for x in losses) and losses[-1] < losses[0]

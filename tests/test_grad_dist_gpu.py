@@ -15,9 +15,9 @@ sys.path.insert(0, HERE)
 import flat_layout  # noqa: E402
 import grad_dist_common as G  # noqa: E402
 from flat_layout import _ops  # noqa: E402
+from optim_harness import NAN, grads_for  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-NAN = float("nan")
 GAP = 7.0e3  # fills everything between the records; no record below holds a value of its bin, which must stay empty
 
 
@@ -250,16 +250,6 @@ class _Capture:
                                step=global_step))
 
 
-def _grads_for(m, seed, scale=1e-2):
-    """one flat gradient for every parameter of a flat model, NaN in the padding"""
-    g = torch.full_like(m.flat_grads, NAN)
-    for i, (name, p) in enumerate(m.named_parameters()):
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        gen = torch.Generator().manual_seed(seed * 1000 + i)
-        g[off: off + p.numel()] = (torch.randn((p.numel(),), generator=gen) * scale).to(g.device)
-    return g
-
-
 CASES = {
     "adamw": ("AdamW", dict(lr=1e-3, weight_decay=2e-2)),
     "nov": ("NovogradApex", dict(lr=1e-2, betas=(0.9, 0.99), weight_decay=0.002, wd_eps=0.01)),
@@ -280,7 +270,7 @@ def test_callback_on_resnet50(dev, case):
     m = resnet50(dtype="fp32").cuda()
     opt = getattr(optim, cls)([{"params": list(m.parameters())}], **kw)
     opt.attach_model(m)
-    m.flat_grads.copy_(_grads_for(m, 3))
+    m.flat_grads.copy_(grads_for(m, 3))
     opt.zero_grad()
     opt.step()
     s = 10

@@ -2,88 +2,38 @@
 from the reference's own classes (tests/golden/layerwise_unit_ref_trajectories.npz, written by tests/golden/make_layerwise_unit_golden.py on
 the CPU).
 
-Yardstick, stored in the fixture and never computed from the code under test: the rule of test_layerwise_gpu.py (layerwise_common.Fixture.check:
-FACTOR = 1.5 times the reference's own float32 error plus a floor of 4 * 2^-24 of the largest parameter magnitude).  At model scale the same rule
+Yardstick, stored in the fixture and never computed from the code under test: the rule of this family (tests/optim_harness.py, within_yardstick:
+1.5 times the reference's own float32 error plus a floor of 4 * 2^-24 of the largest parameter magnitude).  At model scale the same rule
 with the float32 run of the restated rule (tests/layerwise_unit_common.py) as the yardstick.  The update kernel alone is compared bit for bit
 with the float32 restatement that is handed the native denominators."""
 import copy
 import ctypes
-import glob
 import math
 import os
-import re
 import sys
 
 import pytest
 import torch
 
-from layerwise_common import FACTOR, U
+import optim_harness as H
 from layerwise_unit_common import CASES, UnitFixture, UnitRestated, slot_rows
-from plan_common import layout as _layout
+from optim_harness import U
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAN = float("nan")
-
-
-def _flat_params(sizes, shapes, values, dev, order=None, separate=False):
-    """parameters as views of one flat parameter / gradient buffer (zero gaps in p, NaN in every gap of g), or each in its own allocation"""
-    offs, n = _layout(sizes, order)
-    fp, fg = torch.zeros(n, device=dev), torch.full((n,), NAN, device=dev)
-    ps = []
-    for i, (o, s, shape) in enumerate(zip(offs, sizes, shapes)):
-        if separate:
-            p = torch.nn.Parameter(values[i].to(dev).clone().view(shape))
-            p.grad = torch.zeros(s, device=dev).view(shape)
-        else:
-            fp[o:o + s] = values[i].to(dev).reshape(-1)
-            p = torch.nn.Parameter(fp[o:o + s].view(shape))
-            p.grad = fg[o:o + s].view(shape)
-        ps.append(p)
-    return ps, fp, fg, offs
-
-
-def _fixture_problem(fx, dev, p_flat0=None, separate=False):
-    order = [i for idx in fx.groups for i in idx]
-    ps, fp, fg, offs = _flat_params(fx.sizes, fx.shapes, fx.split(fx.p0 if p_flat0 is None else p_flat0), dev, order, separate)
-    groups = [{"params": [ps[i] for i in fx.groups[0]]}, {"params": [ps[i] for i in fx.groups[1]], "weight_decay": 0}]
-    return ps, groups, fp, fg, offs
-
-
-def _make(fx, groups, lr):
-    from sota_imagenet_amd import optim
-
-    return getattr(optim, fx.cls)(groups, lr=lr, **fx.hyper)
-
-
-def _set_grads(ps, grads, mult=1.0):
-    for p, g in zip(ps, grads):
-        p.grad.copy_((g * mult).view(p.shape))
-
-
-def _gather(ps):
-    return torch.cat([p.detach().reshape(-1) for p in ps])
-
-
-def _gaps(ps, fp):
-    mask = torch.ones_like(fp, dtype=torch.bool)
-    for p in ps:
-        o = (p.data_ptr() - fp.data_ptr()) // 4
-        mask[o:o + p.numel()] = False
-    return mask
 
 
 def _run(fx, dev, grad_scale=1.0, steps=6, separate=False):
-    ps, groups, fp, fg, offs = _fixture_problem(fx, dev, separate=separate)
-    opt = _make(fx, groups, fx.lrs[0])
+    ps, groups, fp, fg, offs = H.fixture_problem(fx, dev, separate=separate)
+    opt = H.make_opt(fx, groups, fx.lrs[0])
     opt.grad_scale = grad_scale
     traj = []
     for k in range(steps):
         for g in opt.param_groups:
             g["lr"] = fx.lrs[k]
-        _set_grads(ps, fx.split(fx.grads[k]), 1.0 / grad_scale)  # (exact: a power of two)
+        H.set_grads(ps, fx.split(fx.grads[k]), 1.0 / grad_scale)  # (exact: a power of two)
         opt.step()
-        traj.append(_gather(ps).clone())
+        traj.append(H.gather(ps).clone())
     torch.cuda.synchronize()
     return traj, opt, ps, fp, fg
 
@@ -100,7 +50,7 @@ def test_steps_follow_the_reference_trajectory(dev, case):
         traj, opt, ps, fp, fg = _run(fx, dev, grad_scale=gs)
         for k, got in enumerate(traj):
             worst = max(worst, fx.check(k, got, f"{case} grad_scale={gs}"))
-        gaps = _gaps(ps, fp)
+        gaps = H.gaps(ps, fp)
         assert gaps.any() and (fp[gaps] == 0).all() and torch.isnan(fg[gaps]).all() and torch.isfinite(fp).all()
         assert all(opt.state[p]["step"] == 6 and type(opt.state[p]["step"]) is int for p in ps)
     print(f"{case}: worst native / reference-fp32 error ratio {worst:.2f}")
@@ -131,7 +81,7 @@ def _small_problem(dev, separate=False, seed=11):
     vals = [(torch.randn(s, generator=gen) * (10.0 ** (i % 3 - 1))).view(shape) for i, (s, shape) in enumerate(zip(sizes, shapes))]
     grads = [[(torch.randn(s, generator=gen) * (10.0 ** ((i + k) % 3 - 2))).view(shape) for i, (s, shape) in enumerate(zip(sizes, shapes))]
              for k in range(2)]
-    ps, fp, fg, offs = _flat_params(sizes, shapes, vals, dev, separate=separate)
+    ps, fp, fg, offs = H.flat_params(sizes, shapes, vals, dev, separate=separate)
     return W, shapes, vals, grads, ps, fp, fg
 
 
@@ -150,7 +100,7 @@ def test_per_slot_sums_equal_the_float64_sums(dev, source):
     from sota_imagenet_amd import optim
 
     W, shapes, vals, grads, ps, fp, fg = _small_problem(dev)
-    _set_grads(ps, grads[0])
+    H.set_grads(ps, grads[0])
     if source == "gradient":
         opt, scale, src = optim.NovogradApex(ps, lr=1e-3, betas=(0.9, 0.99), unitwise_norm=True), 0.5, grads[0]
     else:
@@ -167,7 +117,7 @@ def test_per_slot_sums_equal_the_float64_sums(dev, source):
     assert opt._pieces.shape[0] == 85 and opt._whole.shape[0] == 5 and opt._partial.numel() == 90
     for t in (opt._sums, opt._partial, opt._den, opt._v, fp, *[opt.state[p][opt._m_key] for p in ps]):
         assert torch.isfinite(t).all()
-    gaps = _gaps(ps, fp)
+    gaps = H.gaps(ps, fp)
     assert (fp[gaps] == 0).all() and torch.isnan(fg[gaps]).all()
     assert all((p.detach().cpu() != v).any() for p, v in zip(ps, vals))  # every tensor was updated
     # the second moment follows the NORM, sqrt(S), from ema_norm_init, and the views show one value per slot in the parameter's shape
@@ -203,7 +153,7 @@ def test_update_equals_the_float32_restatement_bit_for_bit(dev, cls, wd_eps, ema
         r.ema = [v.clone() for v in vals]
     for k, lr in enumerate((1e-2, 3e-2)):
         opt.param_groups[0]["lr"] = lr
-        _set_grads(ps, grads[k])
+        H.set_grads(ps, grads[k])
         opt.step()
         torch.cuda.synchronize()
         den = _per_slot(opt, opt._den)
@@ -215,7 +165,7 @@ def test_update_equals_the_float32_restatement_bit_for_bit(dev, cls, wd_eps, ema
             if ema:
                 o = (p.data_ptr() - fp.data_ptr()) // 4
                 assert torch.equal(fe[o:o + p.numel()].cpu().view(p.shape), r.ema[i]), f"{cls} step {k + 1} tensor {i}: moving average"
-    gaps = _gaps(ps, fp)
+    gaps = H.gaps(ps, fp)
     assert (fp[gaps] == 0).all() and torch.isnan(fg[gaps]).all()
     if ema:
         assert (fe[gaps] == 0).all()
@@ -233,9 +183,9 @@ def test_placement_and_replay_are_bitwise(dev, cls):
         opt = getattr(optim, cls)(ps, lr=1e-2, betas=(0.9, 0.99), weight_decay=0.02, unitwise_norm=True)
         out = []
         for k in range(2):
-            _set_grads(ps, grads[k])
+            H.set_grads(ps, grads[k])
             opt.step()
-            out.append(_gather(ps).clone())
+            out.append(H.gather(ps).clone())
         torch.cuda.synchronize()
         return out, opt
 
@@ -249,26 +199,6 @@ def test_placement_and_replay_are_bitwise(dev, cls):
 
 
 # ---- 5. one step at model scale ---------------------------------------------------------------------------------------------------------------
-def _grads_for(m, seed, scale=1e-2):
-    """one flat gradient for every parameter of a flat model, NaN in the padding"""
-    g = torch.full_like(m.flat_grads, NAN)
-    for i, (name, p) in enumerate(m.named_parameters()):
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        gen = torch.Generator().manual_seed(seed * 1000 + i)
-        g[off: off + p.numel()] = (torch.randn((p.numel(),), generator=gen) * scale).to(g.device)
-    return g
-
-
-def _flat_steps(m, opt, seeds, lr):
-    for s in seeds:
-        m.flat_grads.copy_(_grads_for(m, s))
-        for g in opt.param_groups:
-            g["lr"] = lr
-        opt.zero_grad()
-        opt.step()
-    torch.cuda.synchronize()
-
-
 KINDS = {
     "nov_unit": ("NovogradApex", dict(betas=(0.9, 0.99), weight_decay=0.002, wd_eps=0.01, unitwise_norm=True), 1e-2),
     "mynov_unit": ("MyNovograd", dict(betas=(0.9, 0.99), weight_decay=0.0002, unitwise_norm=True), 1e-2),
@@ -276,33 +206,10 @@ KINDS = {
 
 
 def _model_opt(kind, groups_of=None):
-    from sota_imagenet_amd import optim
-    from sota_imagenet_amd.models import resnet50
-
-    cls, kw, lr = KINDS[kind]
-    m = resnet50(dtype="fp32").cuda()
-    groups = groups_of(m) if groups_of else [{"params": list(m.parameters())}]
-    opt = getattr(optim, cls)(groups, lr=lr, **kw)
-    opt.attach_model(m)
-    return m, opt
+    return H.model_opt(*KINDS[kind], groups_of)
 
 
-def _padding_mask(m):
-    mask = torch.ones(m.flat_params.numel(), dtype=torch.bool, device=m.flat_params.device)
-    for p in m.parameters():
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        mask[off: off + p.numel()] = False
-    return mask
-
-
-def _count_launches(monkeypatch):
-    from sota_imagenet_amd import ops
-
-    calls = []
-    for name in ("lw_sumsq", "lw_coef", "lw_update", "lw_unit_sumsq", "lw_unit_coef", "lw_unit_update"):
-        fn = getattr(ops, name)
-        monkeypatch.setattr(ops, name, (lambda f, n: lambda *a, **k: (calls.append(n), f(*a, **k))[1])(fn, name))
-    return calls
+STAGES = ["lw_sumsq", "lw_coef", "lw_update", "lw_unit_sumsq", "lw_unit_coef", "lw_unit_update"]
 
 
 @pytest.mark.parametrize("kind", sorted(KINDS))
@@ -315,11 +222,11 @@ def test_one_step_at_model_scale(dev, monkeypatch, kind):
     params = list(m.parameters())
     assert len(params) == 161
     p0 = [p.detach().cpu().clone() for p in params]
-    calls = _count_launches(monkeypatch)
-    _flat_steps(m, opt, [31], lr)
+    calls = H.count_launches(monkeypatch, STAGES)
+    H.flat_steps(m, opt, [31], lr)
     assert calls == ["lw_unit_sumsq", "lw_sumsq", "lw_unit_coef", "lw_unit_update"]
     assert opt._den.numel() == 27667 and opt._whole.shape[0] == 107
-    mask = _padding_mask(m)
+    mask = H.padding_mask(m)
     assert mask.any() and (m.flat_params[mask] == 0).all() and torch.isnan(m.flat_grads[mask]).all() and torch.isfinite(m.flat_params).all()
     grads = [p.grad.detach().cpu().clone() for p in params]
     wd = kw["weight_decay"]
@@ -329,13 +236,9 @@ def test_one_step_at_model_scale(dev, monkeypatch, kind):
     r32.step(grads, [lr])
     worst, moved = 0.0, 0
     for i, p in enumerate(params):
-        ref = r64.p[i]
-        err = (p.detach().cpu().double() - ref).abs().max().item()
-        yard = (r32.p[i].double() - ref).abs().max().item()
-        floor = 4 * U * ref.abs().max().item()
-        worst = max(worst, err / max(yard, floor))
+        yard = (r32.p[i].double() - r64.p[i]).abs().max().item()
+        worst = max(worst, H.within_yardstick(p, r64.p[i], yard, f"{kind} tensor {i} {tuple(p.shape)}", floor_in_ratio=True, yard_name="restated fp32"))
         moved += int((p.detach().cpu() != p0[i]).any())
-        assert err <= FACTOR * yard + floor, f"{kind} tensor {i} {tuple(p.shape)}: native {err:.3e} vs restated fp32 {yard:.3e} (floor {floor:.2e})"
     print(f"{kind}: worst native error / max(restated-fp32 error, floor) over 161 tensors {worst:.2f}")
     assert moved == 161
     # the recipe's two groups
@@ -344,9 +247,9 @@ def test_one_step_at_model_scale(dev, monkeypatch, kind):
 
     m2, opt2 = _model_opt(kind, lambda mm: train.filter_from_weight_decay(mm, ["bn", "bias"]))
     del calls[:]
-    _flat_steps(m2, opt2, [32], lr)
+    H.flat_steps(m2, opt2, [32], lr)
     assert calls == ["lw_unit_sumsq", "lw_sumsq", "lw_unit_coef", "lw_unit_coef", "lw_unit_update", "lw_unit_update"]
-    assert (m2.flat_params[_padding_mask(m2)] == 0).all() and torch.isfinite(m2.flat_params).all()
+    assert (m2.flat_params[H.padding_mask(m2)] == 0).all() and torch.isfinite(m2.flat_params).all()
     assert all(opt2.state[p]["step"] == 1 for p in m2.parameters())
 
 
@@ -376,23 +279,23 @@ def test_state_layout_resume_and_the_load_tolerance(dev, case):
         for k in range(3, 6):
             for g in o.param_groups:
                 g["lr"] = fx.lrs[k]
-            _set_grads(pp, fx.split(fx.grads[k]))
+            H.set_grads(pp, fx.split(fx.grads[k]))
             o.step()
         torch.cuda.synchronize()
-        return _gather(pp).clone()
+        return H.gather(pp).clone()
 
     want = three_more(opt, ps)
-    ps2, groups2, _, _, _ = _fixture_problem(fx, dev, p_flat0=traj[2].cpu())
-    opt2 = _make(fx, groups2, fx.lrs[3])
+    ps2, groups2, _, _, _ = H.fixture_problem(fx, dev, p_flat0=traj[2].cpu())
+    opt2 = H.make_opt(fx, groups2, fx.lrs[3])
     opt2.load_state_dict(copy.deepcopy(sd))
     assert torch.equal(three_more(opt2, ps2), want) and all(opt2.state[p]["step"] == 6 for p in ps2)
-    ps3, groups3, _, _, _ = _fixture_problem(fx, dev, p_flat0=traj[2].cpu())  # without the state the steps differ
-    assert not torch.equal(three_more(_make(fx, groups3, fx.lrs[3]), ps3), want)
+    ps3, groups3, _, _, _ = H.fixture_problem(fx, dev, p_flat0=traj[2].cpu())  # without the state the steps differ
+    assert not torch.equal(three_more(H.make_opt(fx, groups3, fx.lrs[3]), ps3), want)
 
     # the reference's own state after five steps
     def from_reference(mutate=None):
-        ps4, groups4, _, _, _ = _fixture_problem(fx, dev, p_flat0=fx.p64[4].float())
-        opt4 = _make(fx, groups4, fx.lrs[5])
+        ps4, groups4, _, _, _ = H.fixture_problem(fx, dev, p_flat0=fx.p64[4].float())
+        opt4 = H.make_opt(fx, groups4, fx.lrs[5])
         state = {}
         for j, i in enumerate(order):
             state[j] = {key: fx.split(t)[i].view(fx.shapes[i]).clone() for key, t in fx.state5.items()}
@@ -403,10 +306,10 @@ def test_state_layout_resume_and_the_load_tolerance(dev, case):
         opt4.load_state_dict({"state": state, "param_groups": pg})
         for g in opt4.param_groups:
             g["lr"] = fx.lrs[5]
-        _set_grads(ps4, fx.split(fx.grads[5]))
+        H.set_grads(ps4, fx.split(fx.grads[5]))
         opt4.step()
         torch.cuda.synchronize()
-        return _gather(ps4), opt4, ps4
+        return H.gather(ps4), opt4, ps4
 
     got, opt4, ps4 = from_reference()
     fx.check(5, got, f"{case} step 6 from the reference's state")
@@ -440,34 +343,7 @@ def test_state_layout_resume_and_the_load_tolerance(dev, case):
 def test_model_ema_inside_the_step_kernel_matches_the_callback(dev, kind):
     """ModelEma (train.py:111-112) under the unit-wise optimizers: the average advanced by the update kernel (attach_ema) equals the
     callback's own lerp after every batch, and the parameters are the same bits either way"""
-    from sota_imagenet_amd import fit_wrapper as fw
-    from sota_imagenet_amd.losses import CrossEntropyLoss
-    from sota_imagenet_amd.synth import synthetic_batch
-
-    class Loader:
-        batch_size = 4
-
-        def __len__(self):
-            return 3
-
-        def __iter__(self):
-            return iter([synthetic_batch(4, 64, seed=6, index=i, device="cuda") for i in range(3)])
-
-    res = []
-    lr = KINDS[kind][2] * 0.1
-    for fused in (True, False):
-        m, opt = _model_opt(kind)
-        ema = fw.ModelEma(m, 0.9)
-        if not fused:
-            ema.on_begin = lambda: None
-        runner = fw.Runner(m, opt, CrossEntropyLoss(smoothing=0.1), callbacks=[fw.PhasesScheduler([dict(ep=(0, 1), lr=(lr, 2 * lr))]), ema])
-        runner.fit(Loader(), val_loader=Loader(), epochs=1)
-        assert ema._fused == fused and not ema._swapped
-        res.append((m.flat_params.clone(), ema.ema[0].clone(), ema.ema[1].clone()))
-    (p_a, e_a, b_a), (p_b, e_b, b_b) = res
-    assert torch.equal(p_a, p_b) and torch.equal(b_a, b_b)
-    assert not torch.equal(e_a, p_a) and torch.isfinite(e_a).all()
-    assert ((e_a - e_b).abs().max() / e_b.abs().max()).item() < 1e-6
+    H.ema_matches_callback(lambda: _model_opt(kind), KINDS[kind][2] * 0.1)
 
 
 # ---- 8. entry points --------------------------------------------------------------------------------------------------------------------------
@@ -525,9 +401,6 @@ def test_entry_points_refuse_bad_arguments_before_any_launch(dev):
 def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch):
     """train.py on my-nov-unit_test: the native class is built with unitwise_norm and planned, the losses are finite, the checkpoint carries
     the reference's state layout and evaluates after a resume"""
-    sys.path.insert(0, ROOT)
-    import train
-
     from sota_imagenet_amd import optim
 
     name, cls, keys = "my-nov-unit_test", optim.MyNovograd, {"step", "ema_grad", "ema_norm"}
@@ -539,20 +412,12 @@ def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch):
         return build(self, entries)
 
     monkeypatch.setattr(cls, "_build_unit_plans", spy)
-    logdir = os.path.relpath(str(tmp_path), ROOT)
-    val_loss, metrics = train.main([f"+hydra_exp={name}", f"log.dir={logdir}", "run.fp16=false", "random_seed=0", "data.pool=2",
-                                    "log.save_optim=true"])
+    _, _, run, losses = H.run_smoke_config(name, tmp_path, ["run.fp16=false", "random_seed=0", "data.pool=2", "log.save_optim=true"],
+                                           resume_eval=True)
     assert made and all(type(o) is cls and o.unitwise_norm is True for o in made)
-    assert math.isfinite(val_loss) and 0.0 <= metrics["Acc@1"].avg <= 100.0
-    run = glob.glob(os.path.join(str(tmp_path), f"*_{name}", "*"))[0]
-    logs = open(os.path.join(run, "logs.txt")).read()
-    losses = [float(x) for x in re.findall(r"Train loss: ([0-9.]+)", logs)]
     print(name, "train losses:", losses)
     assert losses and all(math.isfinite(x) for x in losses)
     ck = torch.load(os.path.join(run, "model.chpn"), map_location="cpu")
     per_param = list(ck["optimizer"]["state"].values())
     assert len(per_param) == 161 and all(set(s) == keys and s["step"] > 0 for s in per_param)
     assert all(s["ema_norm"].shape == s["ema_grad"].shape and s["ema_norm"].is_contiguous() for s in per_param)
-    loss2, m2 = train.main([f"+hydra_exp={name}", f"log.dir={logdir}", f"run.resume={os.path.join(run, 'model.chpn')}", "run.evaluate=true",
-                            "data.pool=2"])
-    assert math.isfinite(loss2) and 0.0 <= m2["Acc@1"].avg <= 100.0

@@ -8,105 +8,39 @@ it, plus a floor of 4 * 2^-24 (two float32 ulps) of the largest parameter magnit
 the worst native / reference-float32 ratios are 2.42, 1.68 (MADGRAD) and 1.22, 1.18 (AdaiS), and every ratio above 1.5 is an error
 below the floor itself (<= 8.4e-8 against 9.8e-8)."""
 import copy
-import glob
-import json
+import functools
 import math
 import os
-import re
 import sys
 
-import numpy as np
 import pytest
 import torch
 
+import optim_harness as H
+from madgrad_adais_common import CASES, Fixture
+from optim_harness import U
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "optim_ref_trajectories.npz")
-U = 2.0 ** -24
-FACTOR = 1.5
-CASES = ["madgrad_recipe", "madgrad_alt", "adais_recipe", "adais_alt"]
-
-
-def _js(a):
-    return json.loads(bytes(a).decode())
-
-
-class Fixture:
-    def __init__(self, case):
-        z = np.load(GOLDEN)
-        self.shapes, self.groups = _js(z["shapes"]), _js(z["groups"])
-        self.sizes = [int(np.prod(s)) for s in self.shapes]
-        self.offs = np.cumsum([0] + self.sizes)
-        self.p0, self.grads = torch.from_numpy(z["p0"]), torch.from_numpy(z["grads"])
-        self.hyper = _js(z[f"{case}/hyper"])
-        self.cls = self.hyper.pop("cls")
-        self.lrs = [float(x) for x in z[f"{case}/lrs"]]
-        self.p64, self.yard = torch.from_numpy(z[f"{case}/p64"]), z[f"{case}/yard"]
-        self.state_keys, self.state_shapes = _js(z[f"{case}/state_keys"]), _js(z[f"{case}/state_shapes"])
-        self.state5 = {k.split("/")[-1]: torch.from_numpy(z[k]) for k in z.files if k.startswith(f"{case}/state5/")}
-        if self.cls == "AdaiS":
-            self.mean64, self.mean32 = z[f"{case}/mean64"], z[f"{case}/mean32"]
-
-    def split(self, flat):
-        return [flat[self.offs[i]:self.offs[i + 1]] for i in range(len(self.shapes))]
-
-    def check(self, k, got_flat, what):
-        """got_flat: the native parameters after step k + 1, in the fixture's tensor order"""
-        ratios = []
-        for i, (got, ref) in enumerate(zip(self.split(got_flat.detach().double().cpu()), self.split(self.p64[k]))):
-            err = (got - ref).abs().max().item()
-            floor = 4 * U * ref.abs().max().item()
-            ratios.append(err / self.yard[k, i])
-            print(f"{what} step {k + 1} tensor {i}: native {err:.3e}  reference fp32 {self.yard[k, i]:.3e}  ratio {ratios[-1]:.2f}  floor {floor:.2e}")
-            assert err <= FACTOR * self.yard[k, i] + floor, f"{what} step {k + 1} tensor {i}: native {err:.3e} vs reference fp32 {self.yard[k, i]:.3e}"
-        return max(ratios)
 
 
 def _flat_problem(fx, dev, p_flat0=None):
-    """the fixture's tensors as views of one flat parameter and one flat gradient buffer, 64-element aligned with zero gaps (the layout
-    of the flat models); returns (params in tensor order, param groups, flat p, flat g, element offsets)"""
-    offs, n = [0] * len(fx.sizes), 0
-    for i in [i for idx in fx.groups for i in idx]:  # group by group, so that each group is one range with bridged gaps
-        offs[i] = n
-        n += (fx.sizes[i] + 63) // 64 * 64
-    fp, fg = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-    ps = []
-    src = fx.split(fx.p0 if p_flat0 is None else p_flat0)
-    for i, (o, s, shape) in enumerate(zip(offs, fx.sizes, fx.shapes)):
-        fp[o:o + s] = src[i].to(dev)
-        p = torch.nn.Parameter(fp[o:o + s].view(shape))
-        p.grad = fg[o:o + s].view(shape)
-        ps.append(p)
-    groups = [{"params": [ps[i] for i in fx.groups[0]]}, {"params": [ps[i] for i in fx.groups[1]], "weight_decay": 0}]
-    return ps, groups, fp, fg, offs
-
-
-def _make(fx, groups, lr):
-    from sota_imagenet_amd import optim
-
-    return getattr(optim, fx.cls)(groups, lr=lr, **fx.hyper)
-
-
-def _set_grads(fx, fg, offs, k, mult=1.0):
-    for o, s, g in zip(offs, fx.sizes, fx.split(fx.grads[k])):
-        fg[o:o + s] = (g * mult).to(fg.device)
-
-
-def _gather(ps):
-    return torch.cat([p.detach().reshape(-1) for p in ps])
+    """the fixture's tensors in the layout of the flat models, group by group, so that each group is one range with bridged gaps: zero in
+    the gaps of the gradient too, which these launches sweep"""
+    return H.fixture_problem(fx, dev, p_flat0, grad_fill=0.0)
 
 
 def _run(fx, dev, grad_scale=1.0, steps=6):
     ps, groups, fp, fg, offs = _flat_problem(fx, dev)
-    opt = _make(fx, groups, fx.lrs[0])
+    opt = H.make_opt(fx, groups, fx.lrs[0])
     opt.grad_scale = grad_scale
     traj, means = [], []
     for k in range(steps):
         for g in opt.param_groups:
             g["lr"] = fx.lrs[k]
-        _set_grads(fx, fg, offs, k, 1.0 / grad_scale)  # (exact: a power of two)
+        H.set_grads(ps, fx.split(fx.grads[k]), 1.0 / grad_scale)  # (exact: a power of two)
         opt.step()
-        traj.append(_gather(ps).clone())
+        traj.append(H.gather(ps).clone())
         if fx.cls == "AdaiS":
             means.append(opt.exp_avg_sq_hat_mean.clone())
     torch.cuda.synchronize()
@@ -124,10 +58,7 @@ def test_steps_follow_the_reference_trajectory(dev, case):
         for k, got in enumerate(traj):
             worst = max(worst, fx.check(k, got, f"{case} grad_scale={gs}"))
         # the alignment gaps of the flat buffer were bridged into the launches and stayed zero
-        mask = torch.ones_like(fp, dtype=torch.bool)
-        for p in ps:
-            o = (p.data_ptr() - fp.data_ptr()) // 4
-            mask[o:o + p.numel()] = False
+        mask = H.gaps(ps, fp)
         assert mask.any() and (fp[mask] == 0).all() and [len(segs) for segs in opt._plans] == [1, 1]
     print(f"{case}: worst native / reference-fp32 error ratio {worst:.2f}")
     # the steps really moved the parameters (a no-op would sit far from the trajectory, but make it explicit)
@@ -146,53 +77,19 @@ def test_adais_mean_matches_the_reference_and_replays_bitwise(dev, case):
         rel = abs(got - fx.mean64[k]) / fx.mean64[k]
         yard = abs(fx.mean32[k] - fx.mean64[k]) / fx.mean64[k]
         print(f"{case} step {k + 1}: mean {got:.9g} (reference fp64 {fx.mean64[k]:.12g})  rel {rel:.3e}  reference fp32 rel {yard:.3e}")
-        assert rel <= FACTOR * yard + 4 * U
+        assert rel <= H.bound(yard, 1.0)
         assert torch.equal(means_a[k], means_b[k]) and torch.equal(traj_a[k], traj_b[k])
 
 
-def _grads_for(m, seed, scale=1e-2):
-    """one flat gradient for every parameter of a flat model, zero in the padding (what a backward leaves there)"""
-    g = torch.zeros_like(m.flat_grads)
-    for i, (name, p) in enumerate(m.named_parameters()):
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        gen = torch.Generator().manual_seed(seed * 1000 + i)
-        g[off: off + p.numel()] = (torch.randn((p.numel(),), generator=gen) * scale).to(g.device)
-    return g
-
-
-def _flat_steps(m, opt, seeds, lr):
-    for s in seeds:
-        m.flat_grads.copy_(_grads_for(m, s))
-        for g in opt.param_groups:
-            g["lr"] = lr
-        opt.zero_grad()
-        opt.step()
-    torch.cuda.synchronize()
+KINDS = {"madgrad": ("MADGRAD", dict(momentum=0.9, weight_decay=1e-4), 1e-3), "adais": ("AdaiS", dict(betas=(0.1, 0.99), weight_decay=1e-3), 1e-2)}
+LR = {kind: lr for kind, (_, _, lr) in KINDS.items()}
 
 
 def _model_opt(kind, groups_of=None):
-    from sota_imagenet_amd import optim
-    from sota_imagenet_amd.models import resnet50
-
-    m = resnet50(dtype="fp32").cuda()
-    groups = groups_of(m) if groups_of else [{"params": list(m.parameters())}]
-    if kind == "madgrad":
-        opt = optim.MADGRAD(groups, lr=1e-3, momentum=0.9, weight_decay=1e-4)
-    else:
-        opt = optim.AdaiS(groups, lr=1e-2, betas=(0.1, 0.99), weight_decay=1e-3)
-    opt.attach_model(m)
-    return m, opt
+    return H.model_opt(*KINDS[kind], groups_of)
 
 
-LR = {"madgrad": 1e-3, "adais": 1e-2}
-
-
-def _padding_mask(m):
-    mask = torch.ones(m.flat_params.numel(), dtype=torch.bool, device=m.flat_params.device)
-    for p in m.parameters():
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        mask[off: off + p.numel()] = False
-    return mask
+_flat_steps = functools.partial(H.flat_steps, pad=0.0)  # zero in the padding: what a backward leaves there
 
 
 @pytest.mark.parametrize("kind", ["madgrad", "adais"])
@@ -201,7 +98,7 @@ def test_padding_stays_zero_and_the_step_is_the_planned_launches(dev, kind):
     for AdaiS; after three steps the padding of p and of every state array is exactly 0, and the AdaiS mean (16384 partial sums)
     equals the mean over the real elements only"""
     m, opt = _model_opt(kind)
-    mask = _padding_mask(m)
+    mask = H.padding_mask(m)
     assert mask.any()
     _flat_steps(m, opt, [21, 22, 23], LR[kind])
     segs = [seg for segs in opt._plans for seg in segs]
@@ -237,7 +134,7 @@ def test_padding_stays_zero_and_the_step_is_the_planned_launches(dev, kind):
     s = SGD(train.filter_from_weight_decay(m2, ["bn", "bias"]), lr=0.0)
     s.attach_model(m2)
     assert [len(x) for x in opt2._plans] == [sum(1 for r in s._merged_ranges() if r[5] == gi) for gi in range(2)]
-    assert (m2.flat_params[_padding_mask(m2)] == 0).all() and torch.isfinite(m2.flat_params).all()
+    assert (m2.flat_params[H.padding_mask(m2)] == 0).all() and torch.isfinite(m2.flat_params).all()
     if kind == "adais":
         v = torch.cat([opt2.state[p]["exp_avg_sq"].reshape(-1) for p in m2.parameters()])
         want = ((v / (1 - 0.99)).double().sum() / v.numel()).item()
@@ -248,34 +145,7 @@ def test_padding_stays_zero_and_the_step_is_the_planned_launches(dev, kind):
 def test_model_ema_inside_the_step_kernel_matches_the_callback(dev, kind):
     """ModelEma (train.py:111-112) under the native MADGRAD / AdaiS: the average advanced by the step kernel (attach_ema) equals the
     callback's own lerp after every batch, and the parameters are the same bits either way"""
-    from sota_imagenet_amd import fit_wrapper as fw
-    from sota_imagenet_amd.losses import CrossEntropyLoss
-    from sota_imagenet_amd.synth import synthetic_batch
-
-    class Loader:
-        batch_size = 4
-
-        def __len__(self):
-            return 3
-
-        def __iter__(self):
-            return iter([synthetic_batch(4, 64, seed=6, index=i, device="cuda") for i in range(3)])
-
-    res = []
-    for fused in (True, False):
-        m, opt = _model_opt(kind)
-        ema = fw.ModelEma(m, 0.9)
-        if not fused:
-            ema.on_begin = lambda: None
-        lr = LR[kind]
-        runner = fw.Runner(m, opt, CrossEntropyLoss(smoothing=0.1), callbacks=[fw.PhasesScheduler([dict(ep=(0, 1), lr=(lr, 2 * lr))]), ema])
-        runner.fit(Loader(), val_loader=Loader(), epochs=1)
-        assert ema._fused == fused and not ema._swapped
-        res.append((m.flat_params.clone(), ema.ema[0].clone(), ema.ema[1].clone()))
-    (p_a, e_a, b_a), (p_b, e_b, b_b) = res
-    assert torch.equal(p_a, p_b) and torch.equal(b_a, b_b)
-    assert not torch.equal(e_a, p_a)
-    assert ((e_a - e_b).abs().max() / e_b.abs().max()).item() < 1e-6
+    H.ema_matches_callback(lambda: _model_opt(kind), LR[kind])
 
 
 @pytest.mark.parametrize("kind", ["madgrad", "adais"])
@@ -328,7 +198,7 @@ def test_state_dict_has_the_references_layout_and_loads_its_state(dev, case):
         assert set(sd["param_groups"][0]) == {"lr", "betas", "eps", "weight_decay", "params"}
     # reference state after step 5 -> native, then step 6
     ps2, groups2, fp2, fg2, offs2 = _flat_problem(fx, dev, p_flat0=fx.p64[4].float())
-    opt2 = _make(fx, groups2, fx.lrs[5])
+    opt2 = H.make_opt(fx, groups2, fx.lrs[5])
     state = {}
     for j, i in enumerate(order):
         state[j] = {key: fx.split(t)[i].view(fx.shapes[i]).clone() for key, t in fx.state5.items()}
@@ -340,10 +210,10 @@ def test_state_dict_has_the_references_layout_and_loads_its_state(dev, case):
     opt2.load_state_dict({"state": state, "param_groups": pg})
     for g in opt2.param_groups:
         g["lr"] = fx.lrs[5]
-    _set_grads(fx, fg2, offs2, 5)
+    H.set_grads(ps2, fx.split(fx.grads[5]))
     opt2.step()
     torch.cuda.synchronize()
-    fx.check(5, _gather(ps2), f"{case} step 6 from the reference's state")
+    fx.check(5, H.gather(ps2), f"{case} step 6 from the reference's state")
 
 
 @pytest.mark.parametrize("name,cls_name,keys", [("madgrad_test", "MADGRAD", {"grad_sum_sq", "s", "x0"}),
@@ -352,9 +222,6 @@ def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch, name, cls_na
     """train.py on madgrad_test.yaml / adais_test.yaml: the native class is built and planned, the loss is finite and decreasing or
     stable (the last epoch's training loss at most 10 % above the first's: a diverging step rule multiplies it), the checkpoint carries
     the reference's state layout and evaluates after a resume"""
-    sys.path.insert(0, ROOT)
-    import train
-
     from sota_imagenet_amd import optim
 
     cls = getattr(optim, cls_name)
@@ -366,14 +233,9 @@ def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch, name, cls_na
         return build(self)
 
     monkeypatch.setattr(cls, "_build_plans", spy)
-    logdir = os.path.relpath(str(tmp_path), ROOT)
-    val_loss, metrics = train.main([f"+hydra_exp={name}", f"log.dir={logdir}", "run.fp16=false", "random_seed=0", "data.pool=2",
-                                    "log.save_optim=true"])
+    _, _, run, losses = H.run_smoke_config(name, tmp_path, ["run.fp16=false", "random_seed=0", "data.pool=2", "log.save_optim=true"],
+                                           resume_eval=True)
     assert made and all(type(o) is cls for o in made)
-    assert math.isfinite(val_loss) and 0.0 <= metrics["Acc@1"].avg <= 100.0
-    run = glob.glob(os.path.join(str(tmp_path), f"*_{name}", "*"))[0]
-    logs = open(os.path.join(run, "logs.txt")).read()
-    losses = [float(x) for x in re.findall(r"Train loss: ([0-9.]+)", logs)]
     print(name, "train losses:", losses)
     assert losses and all(math.isfinite(x) for x in losses) and losses[-1] <= 1.1 * losses[0]
     ck = torch.load(os.path.join(run, "model.chpn"), map_location="cpu")
@@ -382,6 +244,3 @@ def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch, name, cls_na
     assert per_param and all(set(s) == keys for s in per_param)
     if cls_name == "MADGRAD":
         assert int(st["k"].item()) > 0
-    loss2, m2 = train.main([f"+hydra_exp={name}", f"log.dir={logdir}", f"run.resume={os.path.join(run, 'model.chpn')}", "run.evaluate=true",
-                            "data.pool=2"])
-    assert math.isfinite(loss2) and 0.0 <= m2["Acc@1"].avg <= 100.0

@@ -3,21 +3,15 @@ entries refuse bad arguments before any launch, the constructors keep the refere
 project documents them (include/mi355rn.h) reproduce — restated here in float64 torch — the trajectories that the
 reference's own program recorded in tests/golden/optim_ref_trajectories.npz (tests/golden/make_optim_golden.py)."""
 import ctypes
-import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from madgrad_adais_common import CASES, GOLDEN, Fixture
 from sota_imagenet_amd import config as C
 from sota_imagenet_amd import native
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "optim_ref_trajectories.npz")
-
-
-def _js(a):
-    return json.loads(bytes(a).decode())
 
 
 def test_madgrad_adais_targets_resolve_to_the_native_classes():
@@ -179,37 +173,33 @@ def _adais_step_rule(p, g, st, vhat, mean, lr, beta0, eps, weight_decay):
     return p - lr * st["m"] / (1 - st["b1prod"])
 
 
-@pytest.mark.parametrize("case", ["madgrad_recipe", "madgrad_alt", "adais_recipe", "adais_alt"])
+@pytest.mark.parametrize("case", CASES)
 def test_documented_rules_reproduce_the_reference_fp64_trajectory(case):
-    z = np.load(GOLDEN)
-    shapes, groups = _js(z["shapes"]), _js(z["groups"])
-    sizes = [int(np.prod(s)) for s in shapes]
-    offs = np.cumsum([0] + sizes)
-    hyper = _js(z[f"{case}/hyper"])
-    cls = hyper.pop("cls")
-    wd_of = {i: (hyper["weight_decay"] if gi == 0 else 0.0) for gi, idx in enumerate(groups) for i in idx}
-    p = [torch.from_numpy(z["p0"][offs[i]:offs[i + 1]]).double() for i in range(len(shapes))]
-    grads, lrs, want = torch.from_numpy(z["grads"]).double(), z[f"{case}/lrs"], torch.from_numpy(z[f"{case}/p64"])
-    if cls == "MADGRAD":
+    fx = Fixture(case)
+    hyper, n = fx.hyper, len(fx.shapes)
+    wd_of = {i: (hyper["weight_decay"] if gi == 0 else 0.0) for gi, idx in enumerate(fx.groups) for i in idx}
+    p = [t.double() for t in fx.split(fx.p0)]
+    grads = fx.grads.double()
+    if fx.cls == "MADGRAD":
         st = [dict(gss=torch.zeros_like(q), s=torch.zeros_like(q), x0=q.clone()) for q in p]
     else:
         st = [dict(v=torch.full_like(q, hyper.get("ema_norm_init", 1e-3)), m=torch.zeros_like(q), b1prod=torch.ones_like(q)) for q in p]
     for k in range(grads.shape[0]):
-        gs = [grads[k, offs[i]:offs[i + 1]] for i in range(len(shapes))]
-        if cls == "MADGRAD":
-            p = [_madgrad_rule(p[i], gs[i], st[i], k, float(lrs[k]), hyper["momentum"], wd_of[i], hyper["eps"]) for i in range(len(p))]
+        gs = fx.split(grads[k])
+        if fx.cls == "MADGRAD":
+            p = [_madgrad_rule(p[i], gs[i], st[i], k, fx.lrs[k], hyper["momentum"], wd_of[i], hyper["eps"]) for i in range(n)]
         else:
             beta0, beta2 = hyper["betas"]
-            vhat = [_adais_moments_rule(gs[i], st[i], k + 1, beta2) for i in range(len(p))]
-            mean = sum(h.sum() for h in vhat) / sum(sizes)
-            assert abs(float(mean) - float(z[f"{case}/mean64"][k])) <= 1e-12 * abs(float(mean))
-            p = [_adais_step_rule(p[i], gs[i], st[i], vhat[i], mean, float(lrs[k]), beta0, hyper["eps"], wd_of[i]) for i in range(len(p))]
+            vhat = [_adais_moments_rule(gs[i], st[i], k + 1, beta2) for i in range(n)]
+            mean = sum(h.sum() for h in vhat) / sum(fx.sizes)
+            assert abs(float(mean) - float(fx.mean64[k])) <= 1e-12 * abs(float(mean))
+            p = [_adais_step_rule(p[i], gs[i], st[i], vhat[i], mean, fx.lrs[k], beta0, hyper["eps"], wd_of[i]) for i in range(n)]
         got = torch.cat(p)
-        rel = ((got - want[k]).abs().max() / want[k].abs().max()).item()
+        rel = ((got - fx.p64[k]).abs().max() / fx.p64[k].abs().max()).item()
         assert rel <= 1e-12, f"{case} step {k + 1}: {rel:.3e}"
     # the trajectory moves (a no-op rule would not pass by accident) and the recorded float32 run is a usable yardstick
-    assert (want[-1] - torch.from_numpy(z["p0"]).double()).abs().max().item() > 1e-3
-    assert (z[f"{case}/yard"] > 0).all() and z[f"{case}/yard"].max() < 1e-4
+    assert (fx.p64[-1] - fx.p0.double()).abs().max().item() > 1e-3
+    assert (fx.yard > 0).all() and fx.yard.max() < 1e-4
 
 
 def test_fixture_records_both_ends_of_the_adais_clamp():

@@ -7,25 +7,14 @@ import numpy as np
 import pytest
 import torch
 
+import exec_gpu_common as E
 from sota_imagenet_amd import config as C
 from sota_imagenet_amd import item_plan, native
 from sota_imagenet_amd.fit_wrapper import RunnerState
 
 
-def _resnet50():
-    from sota_imagenet_amd.models import resnet50
-
-    return resnet50()
-
-
-def _bresnet50():
-    from sota_imagenet_amd.models import resnet50
-
-    return resnet50(stem_type="deep", antialias=True, attn_type="eca", norm_layer="inplaceabn", norm_act="leaky_relu")
-
-
 def test_records_of_the_resnet50_table():
-    m = _resnet50()
+    m = E.resnet50()
     recs = item_plan.ortho_records(m._table)
     by_name = {name: (kind, off, shape) for name, kind, off, shape in m._table}
     assert len(recs) == 54  # 53 convolutions and the FC
@@ -44,7 +33,7 @@ def test_records_of_the_resnet50_table():
 
 
 def test_records_of_the_bresnet50_table():
-    m = _bresnet50()
+    m = E.bresnet50()
     recs = item_plan.ortho_records(m._table)
     shapes = {off: (name, shape) for name, kind, off, shape in m._table if kind == 0}
     assert any(len(sh) == 3 for _, sh in shapes.values())  # the ECA weights exist ...
@@ -125,7 +114,7 @@ def test_recipe_53_and_its_smoke_config():
 def test_a_cpu_model_is_refused():
     from sota_imagenet_amd.callbacks import OrthoInitClb
 
-    for model in (_resnet50(), torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.Linear(8, 4))):
+    for model in (E.resnet50(), torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.Linear(8, 4))):
         before = [p.detach().clone() for p in model.parameters()]
         cb = OrthoInitClb()
         cb.set_state(RunnerState(model=model))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import exec_gpu_common as E
 import ortho_loss_common as C
 
 pytestmark = pytest.mark.gpu
@@ -15,25 +16,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 S_UP = 0.37  # the upstream scalar of the per-op backward runs
 
 
-def _mods():
-    from sota_imagenet_amd import item_plan, ops
-
-    return ops, item_plan
-
-
-def _np_same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(b).view(np.int32))
-
-
 def _tables(mats, dev):
-    ops, ip = _mods()
+    ops, ip = E.mods()
     cut = ip.ortho_loss_cut(mats, ops.OL_TILE, ops.OL_KSLAB)
     fields = dict(mats=ip.ORTHO_LOSS_FIELDS, tiles=ip.OL_TILE_FIELDS, items=ip.OL_ITEM_FIELDS, gitems=ip.OL_TILE_FIELDS)
     return {k: ip.pack_records(cut[k], dev, fields[k]) for k in fields}, cut
 
 
 def _scratch(cut, n_gram, dev):
-    ops, _ = _mods()
+    ops, _ = E.mods()
     sc = ops.ortho_loss_scratch(n_gram, len(cut["mats"]), len(cut["tiles"]), len(cut["items"]), dev)
     for t in sc.values():
         t.fill_(float("nan"))
@@ -42,7 +33,7 @@ def _scratch(cut, n_gram, dev):
 
 def _run(flat, mats, n_gram, min_norm, dev, s=S_UP):
     """forward, then the backward onto NaN (accumulate off) and onto a prefill (accumulate on): numpy gram, stats, loss, dw_off, dw_on, prefill"""
-    ops, _ = _mods()
+    ops, _ = E.mods()
     tables, cut = _tables(mats, dev)
     sc = _scratch(cut, n_gram, dev)
     w = torch.from_numpy(flat).to(dev)
@@ -55,7 +46,7 @@ def _run(flat, mats, n_gram, min_norm, dev, s=S_UP):
     dw_on = pre.clone()
     ops.ortho_loss_bwd(w, dw_on, tables, sc, sd, accumulate=True)
     torch.cuda.synchronize()
-    assert _np_same(w.cpu().numpy(), flat), "the source is read only"
+    assert E.np_same(w.cpu().numpy(), flat), "the source is read only"
     return dict(gram=sc["gram"].cpu().numpy(), stats=sc["stats"].cpu().numpy(), loss=float(loss.cpu()), dw_off=dw_off.cpu().numpy(),
                 dw_on=dw_on.cpu().numpy(), pre=pre.cpu().numpy())
 
@@ -68,7 +59,7 @@ def dev():
 
 @pytest.fixture(scope="module")
 def case(dev):
-    _, ip = _mods()
+    _, ip = E.mods()
     flat, table = C.make_case()
     mats, n_gram = ip.ortho_loss_mats(table, 1)
     assert len(mats) == len(C.SHAPES)  # the tall record never reaches a kernel
@@ -90,7 +81,7 @@ def test_gram_norm_gate_and_total(case):
         F, ratio, gate, coef = run["stats"][k]
         ref, b = C.gram64(W)
         worst["G"] = max(worst["G"], C.worst(G, ref, b))
-        assert _np_same(G, G.T.copy()), f"matrix {k}: the mirror"
+        assert E.np_same(G, G.T.copy()), f"matrix {k}: the mirror"
         Fr, bF = C.frob64(G)
         worst["F"] = max(worst["F"], abs(float(F) - Fr) / bF if bF else float(F != Fr))
         worst["ratio"] = max(worst["ratio"], abs(float(ratio) - float(F) / W.shape[0]) / (C.U * float(F) / W.shape[0]) if F else float(ratio != 0))
@@ -125,7 +116,7 @@ def test_gradient_pass(case, mode):
         g = C.mat_of(got, rec)
         worst = max(worst, C.worst(g, ref, b))
         if not gate:
-            assert _np_same(g, old if old is not None else np.zeros_like(g)), f"matrix {k}: a closed gate contributes nothing"
+            assert E.np_same(g, old if old is not None else np.zeros_like(g)), f"matrix {k}: a closed gate contributes nothing"
     print("dw worst error / bound:", worst)
     assert worst <= 1.0
     assert (C.mat_of(run["dw_off"], c["mats"][C.ZERO]) == 0).all()  # G = -I on zero weights: exactly 0
@@ -134,7 +125,7 @@ def test_gradient_pass(case, mode):
 
 def test_open_gates_at_min_norm_zero(case, dev):
     """min_norm = 0 opens every gate but the exactly orthonormal matrix's, whose F is 0"""
-    ops, _ = _mods()
+    ops, _ = E.mods()
     c = case
     tables, cut = _tables(c["mats"], dev)
     sc = _scratch(cut, c["n_gram"], dev)
@@ -143,19 +134,19 @@ def test_open_gates_at_min_norm_zero(case, dev):
     assert [k for k in range(len(c["mats"])) if not stats[k, 2]] == [C.ORTHO]
     tr, bt = C.total64(stats[:, 0], stats[:, 2] != 0)
     assert abs(float(loss.cpu()) - tr) <= bt
-    assert _np_same(stats[:, 0], c["runs"][0]["stats"][:, 0])
+    assert E.np_same(stats[:, 0], c["runs"][0]["stats"][:, 0])
 
 
 def test_two_runs_agree_bit_for_bit(case):
     a, b = case["runs"]
     for k in ("gram", "stats", "dw_off", "dw_on"):
-        assert _np_same(a[k], b[k]), k
+        assert E.np_same(a[k], b[k]), k
     assert a["loss"] == b["loss"]
 
 
 def test_integer_weights_give_the_exact_gram_matrix(dev):
     """weights in {-2 .. 2}: every product and partial sum is exact in float32, so G equals the integer Gram matrix bit for bit — tiles, mirror, slabs"""
-    _, ip = _mods()
+    _, ip = E.mods()
     flat, table = C.integer_case()
     mats, n_gram = ip.ortho_loss_mats(table, 1)
     run = _run(flat, mats, n_gram, 0.0, dev, s=1.0)
@@ -163,13 +154,13 @@ def test_integer_weights_give_the_exact_gram_matrix(dev):
         _, _, R, g0 = rec
         W = C.mat_of(flat, rec).astype(np.float64)
         ref = (W @ W.T - np.eye(R)).astype(np.float32)
-        assert _np_same(run["gram"][g0: g0 + R * R].reshape(R, R), ref), (R, rec[1])
+        assert E.np_same(run["gram"][g0: g0 + R * R].reshape(R, R), ref), (R, rec[1])
 
 
 def test_item_that_does_not_name_its_tile_is_skipped(case, dev):
     """a foreign item table: one item of the ragged matrix's tile (1, 0) names another slab.  Its workgroup writes no partial, so the finish pass
     must not sum that tile: its entries of G and their mirror stay as they were and the tile counts 0 in F"""
-    ops, ip = _mods()
+    ops, ip = E.mods()
     c = case
     tables, cut = _tables(c["mats"], dev)
     t = cut["mats"][C.RAGGED][4] + 1  # tile (1, 0)
@@ -185,17 +176,17 @@ def test_item_that_does_not_name_its_tile_is_skipped(case, dev):
     good = _G(c, c["runs"][0], C.RAGGED)
     hole = np.zeros((R, R), dtype=bool)
     hole[64:128, :64] = hole[:64, 64:128] = True
-    assert np.isnan(G[hole]).all() and _np_same(G[~hole], good[~hole])
+    assert np.isnan(G[hole]).all() and E.np_same(G[~hole], good[~hole])
     F = float(sc["stats"].cpu().numpy()[C.RAGGED, 0])
     ref = float(np.sqrt((good[~hole].astype(np.float64) ** 2).sum()))
     assert abs(F - ref) <= (C.U + (R * R + 4) * C.D) * ref
     others = [k for k in range(len(c["mats"])) if k != C.RAGGED]
-    assert _np_same(sc["stats"].cpu().numpy()[others], c["runs"][0]["stats"][others])
+    assert E.np_same(sc["stats"].cpu().numpy()[others], c["runs"][0]["stats"][others])
 
 
 # ---- NormLoss -----------------------------------------------------------------------------------------------------------------------------------------
 def test_norm_loss_per_op(dev):
-    ops, ip = _mods()
+    ops, ip = E.mods()
     flat, table = C.norm_case()
     rows = ip.norm_loss_rows(table)
     names = [t[0] for t in table if (t[2], t[3][0], int(np.prod(t[3])) // t[3][0]) in rows]
@@ -219,7 +210,7 @@ def test_norm_loss_per_op(dev):
         ops.norm_loss_bwd(w, dw_on, idev, tdev, sd, accumulate=True)
         torch.cuda.synchronize()
         outs.append((float(loss.cpu()), sc["tensor_loss"].cpu().numpy(), dw_off.cpu().numpy(), dw_on.cpu().numpy()))
-    assert _np_same(w.cpu().numpy(), flat)
+    assert E.np_same(w.cpu().numpy(), flat)
     loss, per_tensor, dw_off, dw_on = outs[0]
     ref, bound, means = C.norm_loss64(Ws)
     print("norm loss", loss, ref, bound)
@@ -235,12 +226,12 @@ def test_norm_loss_per_op(dev):
     assert (dw_off[fc[0] + 3 * 37: fc[0] + 4 * 37] == 0).all()  # the zero row: n_r = 0 gives 0, not NaN
     bn = rows[names.index("bn.weight")]
     assert dw_off[bn[0] + 7] == 0 and np.isfinite(dw_off[bn[0]: bn[0] + 64]).all()
-    assert outs[0][0] == outs[1][0] and all(_np_same(a.astype(np.float32), b.astype(np.float32)) for a, b in zip(outs[0][1:], outs[1][1:]))
+    assert outs[0][0] == outs[1][0] and all(E.np_same(a.astype(np.float32), b.astype(np.float32)) for a, b in zip(outs[0][1:], outs[1][1:]))
 
 
 # ---- the reference's record ---------------------------------------------------------------------------------------------------------------------------
 def test_against_the_reference_record(dev):
-    ops, ip = _mods()
+    ops, ip = E.mods()
     z = np.load(os.path.join(HERE, "golden", "ortho_loss_ref.npz"))
     names = json.loads(str(z["names"]))
     table, off = [], 4
@@ -298,7 +289,7 @@ def net(dev):
 
 def _penalty_alone(pen, m, weight):
     """weight * d penalty / d parameters by the op alone, into zeros"""
-    ops, _ = _mods()
+    ops, _ = E.mods()
     pen._plan()
     pen._launch_forward()
     g = torch.zeros_like(m.flat_grads)
@@ -375,7 +366,7 @@ def test_evaluation_carries_the_penalty_and_writes_no_gradient(net):
     assert float(b) > 0 and float(c) > 0
     assert torch.equal(m.flat_grads, before) and m._grads_dirty == dirty
     # against float64 on the flat parameters
-    _, ip = _mods()
+    _, ip = E.mods()
     flat = m.flat_params.detach().cpu().numpy()
     Ws = [C.mat_of(flat, r) for r in pen.mats]
     ref, _, Fs, gates = C.ortho_loss64(Ws, 0.0)

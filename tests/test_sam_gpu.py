@@ -1,11 +1,9 @@
 """Native SAMOriginal (csrc/optim_sam.hip, callbacks.SAMOriginal) on the MI355X: the four kernels against torch on the same arrays (the norm to
 the summation bound, the elementwise stages bit for bit), the callback over the native optimizers against the trajectories recorded from the
-reference's own callback (tests/golden/sam_ref_trajectories.npz, the yardstick rule of test_layerwise_gpu.py), and the callback inside Runner on
+reference's own callback (tests/golden/sam_ref_trajectories.npz, the yardstick rule of tests/optim_harness.py), and the callback inside Runner on
 the real models: what the second forward sees, what the optimizer steps on, what it leaves behind."""
-import glob
 import math
 import os
-import re
 import subprocess
 import sys
 
@@ -13,13 +11,14 @@ import numpy as np
 import pytest
 import torch
 
+import optim_harness as H
+from optim_harness import NAN, U
 from plan_common import layout as _layout
 from plan_common import table
-from sam_common import CASES, NORM_FLOOR, U, Fixture, generator
+from sam_common import CASES, NORM_FLOOR, Fixture, generator
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAN = float("nan")
 SENTINEL = 123.0
 RHO, ETA = 0.5, 0.01
 
@@ -355,29 +354,6 @@ def _model(kind):
     return resnet50(dtype=kind.split("-")[1]).cuda()
 
 
-def _padding_mask(m):
-    mask = torch.ones(m.flat_params.numel(), dtype=torch.bool, device=m.flat_params.device)
-    for p in m.parameters():
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        mask[off: off + p.numel()] = False
-    return mask
-
-
-class _Loader:
-    batch_size = 4
-
-    def __init__(self, n=3, seed=6):
-        from sota_imagenet_amd.synth import synthetic_batch
-
-        self.batches = [synthetic_batch(4, 64, seed=seed, index=i, device="cuda") for i in range(n)]
-
-    def __len__(self):
-        return len(self.batches)
-
-    def __iter__(self):
-        return iter(self.batches)
-
-
 @pytest.mark.parametrize("kind", ["resnet50-fp32", "resnet50-bf16", "bresnet50-bf16"])
 def test_three_runner_steps_on_the_real_model(dev, kind):
     """N = 4 at 64 px, AdamLayerwise with recipe 49's values, a spy before and one after SAMOriginal: num_batches_tracked reads 1, 3, 5; the
@@ -394,7 +370,7 @@ def test_three_runner_steps_on_the_real_model(dev, kind):
     crit = CrossEntropyLoss(smoothing=0.1)
     opt = optim.AdamLayerwise([{"params": list(m.parameters())}], lr=1e-3, betas=(0.9, 0.995), weight_decay=2e-2)
     sam = SAMOriginal()
-    pad = _padding_mask(m)
+    pad = H.padding_mask(m)
     pad0 = m.flat_params[pad].clone()
     nbt = next(b for n, b in m.named_buffers() if n.endswith("num_batches_tracked"))
     log = dict(seen=[], p0=[], g1=[], after=[], g_cb=[], eps=[], norm=[], nbt=[], finite=[])
@@ -416,7 +392,7 @@ def test_three_runner_steps_on_the_real_model(dev, kind):
             log["nbt"].append(int(nbt))
             log["finite"].append(bool(torch.isfinite(m.flat_params).all()) and bool(torch.isfinite(self.state.loss_meter.val)))
 
-    loader = _Loader()
+    loader = H.Loader()
     runner = fw.Runner(m, opt, crit, callbacks=[Before(), sam, After()])
     runner.fit(loader, epochs=1)
     torch.cuda.synchronize()
@@ -457,52 +433,32 @@ def test_three_runner_steps_on_the_real_model(dev, kind):
 def test_model_ema_inside_the_step_kernel_matches_the_callback(dev):
     """ModelEma under AdamLayerwise + SAMOriginal: the average advanced by the optimizer's update kernel (attach_ema) equals the callback's own lerp
     after every batch, the parameters are the same bits either way, and the perturbed parameters never enter the average"""
-    from sota_imagenet_amd import fit_wrapper as fw
     from sota_imagenet_amd import optim
     from sota_imagenet_amd.callbacks import SAMOriginal
-    from sota_imagenet_amd.losses import CrossEntropyLoss
 
-    res = []
-    for fused in (True, False):
+    def make():
         m = _model("resnet50-fp32")
-        opt = optim.AdamLayerwise([{"params": list(m.parameters())}], lr=1e-4, betas=(0.9, 0.995), weight_decay=2e-2)
-        ema = fw.ModelEma(m, 0.9)
-        if not fused:
-            ema.on_begin = lambda: None
-        sam = SAMOriginal()
-        runner = fw.Runner(m, opt, CrossEntropyLoss(smoothing=0.1), callbacks=[fw.PhasesScheduler([dict(ep=(0, 1), lr=(1e-4, 2e-4))]), ema, sam])
-        runner.fit(_Loader(), val_loader=_Loader(2, seed=8), epochs=1)
-        assert ema._fused == fused and not ema._swapped and sam.forwards == 2
-        res.append((m.flat_params.clone(), ema.ema[0].clone(), ema.ema[1].clone()))
-    (p_a, e_a, b_a), (p_b, e_b, b_b) = res
-    assert torch.equal(p_a, p_b) and torch.equal(b_a, b_b)
-    assert not torch.equal(e_a, p_a) and torch.isfinite(e_a).all()
-    assert ((e_a - e_b).abs().max() / e_b.abs().max()).item() < 1e-6
+        return m, optim.AdamLayerwise([{"params": list(m.parameters())}], lr=1e-4, betas=(0.9, 0.995), weight_decay=2e-2)
+
+    def two_forwards(sam):
+        assert sam.forwards == 2
+
+    H.ema_matches_callback(make, 1e-4, callbacks=(SAMOriginal,), val_loader=H.Loader(2, seed=8), after_fit=two_forwards)
 
 
 # ---- smoke: train.py and the data-parallel wrapper --------------------------------------------------------------------------------------------
 def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch):
     """train.py on nov-adam_sam_test: the native callback is built from the reference's target, perturbs in every step but the first, and the losses
     are finite"""
-    sys.path.insert(0, ROOT)
-    import train
+    from sota_imagenet_amd import callbacks
 
-    from sota_imagenet_amd import callbacks, ops
-
-    made, calls = [], []
+    made = []
     init = callbacks.SAMOriginal.__init__
     monkeypatch.setattr(callbacks.SAMOriginal, "__init__", lambda self, *a, **k: (made.append(self), init(self, *a, **k))[1])
-    for name in ("sam_sumsq", "sam_scale", "sam_perturb", "sam_restore"):
-        fn = getattr(ops, name)
-        monkeypatch.setattr(ops, name, (lambda f, n: lambda *a, **k: (calls.append(n), f(*a, **k))[1])(fn, name))
-    logdir = os.path.relpath(str(tmp_path), ROOT)
-    val_loss, metrics = train.main(["+hydra_exp=nov-adam_sam_test", f"log.dir={logdir}", "run.fp16=false", "random_seed=0", "data.pool=2"])
+    calls = H.count_launches(monkeypatch, ["sam_sumsq", "sam_scale", "sam_perturb", "sam_restore"])
+    _, _, _, losses = H.run_smoke_config("nov-adam_sam_test", tmp_path, ["run.fp16=false", "random_seed=0", "data.pool=2"])
     assert len(made) == 1 and (made[0].rho, made[0].eta) == (0.5, 0.01) and made[0].forwards > 0
     assert calls[:4] == ["sam_sumsq", "sam_scale", "sam_perturb", "sam_restore"] and len(calls) == 4 * made[0].forwards  # four launches a step
-    assert math.isfinite(val_loss) and 0.0 <= metrics["Acc@1"].avg <= 100.0
-    run = glob.glob(os.path.join(str(tmp_path), "*_nov-adam_sam_test", "*"))[0]
-    logs = open(os.path.join(run, "logs.txt")).read()
-    losses = [float(x) for x in re.findall(r"Train loss: ([0-9.]+)", logs)]
     print("nov-adam_sam_test train losses:", losses, " SAM steps:", made[0].forwards, " last norm:", float(made[0].norm))
     assert losses and all(math.isfinite(x) for x in losses) and math.isfinite(float(made[0].norm))
 

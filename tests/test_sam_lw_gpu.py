@@ -1,11 +1,9 @@
 """Native SAM (csrc/optim_sam_lw.hip, callbacks.SAM) on the MI355X: the kernels against torch on the same arrays (the norms to the summation
 bound, the elementwise stages bit for bit), the callback over the native optimizers against the trajectories recorded from the reference's own
-callback (tests/golden/sam_lw_ref_trajectories.npz, the yardstick rule of test_sam_gpu.py), and the callback inside Runner on the real models:
+callback (tests/golden/sam_lw_ref_trajectories.npz, the yardstick rule of tests/optim_harness.py), and the callback inside Runner on the real models:
 what the second forward sees, what it leaves behind, how many launches a step makes."""
-import glob
 import math
 import os
-import re
 import subprocess
 import sys
 
@@ -13,12 +11,13 @@ import numpy as np
 import pytest
 import torch
 
+import optim_harness as H
+from optim_harness import NAN, U
 from plan_common import layout, table
-from sam_lw_common import CASES, U, Fixture, generator
+from sam_lw_common import CASES, Fixture, generator
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAN = float("nan")
 SENTINEL = 123.0
 RHO = 0.01
 GN_FLOOR, WN_FLOOR = float(np.float32(1e-5)), float(np.float32(1e-3))
@@ -388,38 +387,10 @@ def _model(kind):
     return resnet50(dtype=kind.split("-")[1]).cuda()
 
 
-def _padding_mask(m):
-    mask = torch.ones(m.flat_params.numel(), dtype=torch.bool, device=m.flat_params.device)
-    for p in m.parameters():
-        off = (p.data_ptr() - m.flat_params.data_ptr()) // 4
-        mask[off: off + p.numel()] = False
-    return mask
-
-
-class _Loader:
-    batch_size = 4
-
-    def __init__(self, n=3, seed=6):
-        from sota_imagenet_amd.synth import synthetic_batch
-
-        self.batches = [synthetic_batch(4, 64, seed=seed, index=i, device="cuda") for i in range(n)]
-
-    def __len__(self):
-        return len(self.batches)
-
-    def __iter__(self):
-        return iter(self.batches)
-
-
 _STAGES = ("sam_unit_sumsq", "sam_lw_sumsq", "sam_lw_coef", "sam_lw_perturb", "sam_restore")
 
 
-def _count_launches(monkeypatch, calls):
-    from sota_imagenet_amd import ops
-
-    for name in _STAGES + ("sam_sumsq", "sam_scale", "sam_perturb"):
-        fn = getattr(ops, name)
-        monkeypatch.setattr(ops, name, (lambda f, n: lambda *a, **k: (calls.append(n), f(*a, **k))[1])(fn, name))
+_COUNTED = _STAGES + ("sam_sumsq", "sam_scale", "sam_perturb")
 
 
 @pytest.mark.parametrize("unitwise", [False, True])
@@ -434,13 +405,12 @@ def test_three_runner_steps_on_the_real_model(dev, kind, unitwise, monkeypatch):
     from sota_imagenet_amd.callbacks import SAM
     from sota_imagenet_amd.losses import CrossEntropyLoss
 
-    calls = []
-    _count_launches(monkeypatch, calls)
+    calls = H.count_launches(monkeypatch, _COUNTED)
     m = _model(kind)
     params = list(m.parameters())
     opt = optim.AdamLayerwise([{"params": params}], lr=1e-3, betas=(0.9, 0.995), weight_decay=2e-2)
     sam = SAM(unitwise=unitwise, rho=0.001)
-    pad = _padding_mask(m)
+    pad = H.padding_mask(m)
     pad0 = m.flat_params[pad].clone()
     nbt = next(b for n, b in m.named_buffers() if n.endswith("num_batches_tracked"))
     log = dict(seen=[], p0=[], g1=[], after=[], g_cb=[], eps=[], coef=[], nbt=[], finite=[])
@@ -463,7 +433,7 @@ def test_three_runner_steps_on_the_real_model(dev, kind, unitwise, monkeypatch):
             log["finite"].append(bool(torch.isfinite(m.flat_params).all()) and bool(torch.isfinite(self.state.loss_meter.val)))
 
     runner = fw.Runner(m, opt, CrossEntropyLoss(smoothing=0.1), callbacks=[Before(), sam, After()])
-    runner.fit(_Loader(), epochs=1)
+    runner.fit(H.Loader(), epochs=1)
     torch.cuda.synchronize()
     assert log["nbt"] == [2, 4, 6] and all(log["finite"]) and math.isfinite(runner.state.loss_meter.avg)
     assert len(log["seen"]) == 6 and sam.forwards == 3 and len(sam._segs) == 1
@@ -504,23 +474,15 @@ def test_three_runner_steps_on_the_real_model(dev, kind, unitwise, monkeypatch):
 def test_train_py_runs_the_smoke_config(dev, tmp_path, monkeypatch):
     """train.py on nov-adam_sam-unit_test: the native callback is built from the reference's target, perturbs in every step with five launches,
     and the losses are finite"""
-    sys.path.insert(0, ROOT)
-    import train
-
     from sota_imagenet_amd import callbacks
 
-    made, calls = [], []
+    made = []
     init = callbacks.SAM.__init__
     monkeypatch.setattr(callbacks.SAM, "__init__", lambda self, *a, **k: (made.append(self), init(self, *a, **k))[1])
-    _count_launches(monkeypatch, calls)
-    logdir = os.path.relpath(str(tmp_path), ROOT)
-    val_loss, metrics = train.main(["+hydra_exp=nov-adam_sam-unit_test", f"log.dir={logdir}", "run.fp16=false", "random_seed=0", "data.pool=2"])
+    calls = H.count_launches(monkeypatch, _COUNTED)
+    _, _, _, losses = H.run_smoke_config("nov-adam_sam-unit_test", tmp_path, ["run.fp16=false", "random_seed=0", "data.pool=2"])
     assert len(made) == 1 and (made[0].rho, made[0].unitwise) == (0.001, True) and made[0].forwards > 0
     assert calls[:5] == list(_STAGES) and len(calls) == 5 * made[0].forwards
-    assert math.isfinite(val_loss) and 0.0 <= metrics["Acc@1"].avg <= 100.0
-    run = glob.glob(os.path.join(str(tmp_path), "*_nov-adam_sam-unit_test", "*"))[0]
-    logs = open(os.path.join(run, "logs.txt")).read()
-    losses = [float(x) for x in re.findall(r"Train loss: ([0-9.]+)", logs)]
     print("nov-adam_sam-unit_test train losses:", losses, " SAM steps:", made[0].forwards)
     assert losses and all(math.isfinite(x) for x in losses) and torch.isfinite(made[0].coef).all()
 

@@ -2,29 +2,19 @@
 warm start on planted spectra, torch's own spectral_norm, the executor's wiring against a plain model fed w_hat, the whole step against the
 parametrised torch oracle, and the ForwardSpectralNorm callback.  The bounds are those of tests/spectral_common.py; the wiring and callback tests
 run at N=2, 64 px, 10 classes, the oracle step at N=8."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import exec_gpu_common as E
 import spectral_common as SN
 
 pytestmark = pytest.mark.gpu
 N, S, NC = 2, 64, 10
+_model = functools.partial(E.model, num_classes=NC)
 SENT = -7.0
-
-
-def _mods():
-    from sota_imagenet_amd import item_plan, ops
-
-    return ops, item_plan
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def _np_same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(b).view(np.int32))
 
 
 @pytest.fixture(scope="module")
@@ -36,7 +26,7 @@ def case():
 
 def _forward(flat, mats, u, v, iters, dev, dest="out"):
     """one ops.spectral_fwd: dest "out" (w_hat into NaN), "in" (w_hat is w) or None (no division) -> numpy (w_hat or None, u, v, sigma)"""
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     w = torch.from_numpy(flat).to(dev)
     w_hat = {"out": torch.full_like(w, float("nan")), "in": w, None: None}[dest]
     ud, vd = torch.from_numpy(u).to(dev), torch.from_numpy(v).to(dev)
@@ -44,7 +34,7 @@ def _forward(flat, mats, u, v, iters, dev, dest="out"):
     ops.spectral_fwd(w, w_hat, ud, vd, sigma, ops.spectral_scratch(ud, vd), item_plan.pack_records(mats, dev, item_plan.SPECTRAL_FIELDS), iters)
     torch.cuda.synchronize()
     if dest != "in":
-        assert _np_same(w.cpu().numpy(), flat), "the source is read only"
+        assert E.np_same(w.cpu().numpy(), flat), "the source is read only"
     return (None if w_hat is None else w_hat.cpu().numpy()), ud.cpu().numpy(), vd.cpu().numpy(), sigma.cpu().numpy()
 
 
@@ -82,7 +72,7 @@ def _check_untouched(c, before, got):
     o, L, R, u0, v0 = c["mats"][c["zero"]]
     assert sigma[c["zero"]] == 0.0 and (u[u0: u0 + R] == 0).all() and (v[v0: v0 + L] == 0).all(), "a zero matrix: zero vectors, sigma 0"
     o2, L2, R2, u2, v2 = c["mats"][c["bad"]]
-    assert sigma[c["bad"]] == SENT and _np_same(u[u2: u2 + R2], before[0][u2: u2 + R2]) and _np_same(v[v2: v2 + L2], before[1][v2: v2 + L2])
+    assert sigma[c["bad"]] == SENT and E.np_same(u[u2: u2 + R2], before[0][u2: u2 + R2]) and E.np_same(v[v2: v2 + L2], before[1][v2: v2 + L2])
     if w_hat is not None:
         assert np.isnan(w_hat[o: o + R * L]).all(), "0 / 0, as torch"
         assert np.isnan(w_hat[~c["mask"]]).all(), "gaps (the skipped record's among them) are neither read into a matrix nor written"
@@ -102,10 +92,10 @@ def test_training_iteration_against_float64(dev, case):
     assert R == 1 and abs(got[1][u0]) == 1.0, "one row: u = +-1"
     # bit for bit on a second run; in place (the bake) gives the bits of out of place, gaps untouched
     again = _forward(c["flat"], c["mats"], c["u"], c["v"], 1, dev)
-    assert _np_same(again[0][c["mask"]], got[0][c["mask"]]) and all(_np_same(a, b) for a, b in zip(again[1:], got[1:]))
+    assert E.np_same(again[0][c["mask"]], got[0][c["mask"]]) and all(E.np_same(a, b) for a, b in zip(again[1:], got[1:]))
     ip = _forward(c["flat"], c["mats"], c["u"], c["v"], 1, dev, dest="in")
-    assert _np_same(ip[0][c["mask"]], got[0][c["mask"]]) and np.isnan(ip[0][~c["mask"]]).all()
-    assert all(_np_same(a, b) for a, b in zip(ip[1:], got[1:]))
+    assert E.np_same(ip[0][c["mask"]], got[0][c["mask"]]) and np.isnan(ip[0][~c["mask"]]).all()
+    assert all(E.np_same(a, b) for a, b in zip(ip[1:], got[1:]))
 
 
 def test_two_iterations_are_one_after_the_other(dev, case):
@@ -114,7 +104,7 @@ def test_two_iterations_are_one_after_the_other(dev, case):
     second = _forward(c["flat"], c["mats"], first[1], first[2], 1, dev)
     _check_iteration(c, first[2], second, "second of two")
     both = _forward(c["flat"], c["mats"], c["u"], c["v"], 2, dev)
-    assert _np_same(both[0][c["mask"]], second[0][c["mask"]]) and all(_np_same(a, b) for a, b in zip(both[1:], second[1:]))
+    assert E.np_same(both[0][c["mask"]], second[0][c["mask"]]) and all(E.np_same(a, b) for a, b in zip(both[1:], second[1:]))
     _check_untouched(c, (c["u"], c["v"]), both)
 
 
@@ -123,7 +113,7 @@ def test_eval_rule_leaves_the_vectors_alone(dev, case):
     _, u1, v1, _ = _forward(c["flat"], c["mats"], c["u"], c["v"], 1, dev, dest=None)
     got = _forward(c["flat"], c["mats"], u1, v1, 0, dev)
     w_hat, u, v, sigma = got
-    assert _np_same(u, u1) and _np_same(v, v1), "eval: u and v bit-unchanged"
+    assert E.np_same(u, u1) and E.np_same(v, v1), "eval: u and v bit-unchanged"
     worst = 0.0
     for i, rec in enumerate(c["mats"]):
         o, L, R, u0, v0 = rec
@@ -138,7 +128,7 @@ def test_eval_rule_leaves_the_vectors_alone(dev, case):
         worst = max(worst, rs, rw)
     _check_untouched(c, (u1, v1), got)
     ip = _forward(c["flat"], c["mats"], u1, v1, 0, dev, dest="in")
-    assert _np_same(ip[0][c["mask"]], w_hat[c["mask"]]) and np.isnan(ip[0][~c["mask"]]).all() and _np_same(ip[3], sigma)
+    assert E.np_same(ip[0][c["mask"]], w_hat[c["mask"]]) and np.isnan(ip[0][~c["mask"]]).all() and E.np_same(ip[3], sigma)
 
 
 # ---- 2. matrices, backward -----------------------------------------------------------------------------------------------------------------
@@ -162,7 +152,7 @@ def forwarded(dev, case):
 
 
 def _backward(c, f, dw0, beta, dev, rows=None):
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     w_hat, u, v, sigma, g, _ = f
     t = [torch.from_numpy(x).to(dev) for x in (g, w_hat, u, v, sigma)]
     dw = torch.from_numpy(dw0).to(dev)
@@ -199,8 +189,8 @@ def test_backward_against_float64(dev, case, forwarded, beta):
         if i == c["bad"]:
             continue
         sl = slice(o, o + R * L)
-        assert _np_same(part[sl], got[sl] if 1 <= i < 4 else start[sl]), i
-    assert _np_same(_backward(c, f, start, beta, dev)[c["mask"]], got[c["mask"]]), "two runs, the same bits"
+        assert E.np_same(part[sl], got[sl] if 1 <= i < 4 else start[sl]), i
+    assert E.np_same(_backward(c, f, start, beta, dev)[c["mask"]], got[c["mask"]]), "two runs, the same bits"
 
 
 # ---- 3. warm start ------------------------------------------------------------------------------------------------------------------------
@@ -269,32 +259,10 @@ def test_one_iteration_against_torch_spectral_norm(dev, case, which):
 
 
 # ---- the model tests -----------------------------------------------------------------------------------------------------------------------
-def _model(dtype, **kw):
-    from sota_imagenet_amd.models import resnet50
-
-    return resnet50(num_classes=NC, dtype=dtype, **kw)
-
-
 def _batch(index=0, n=N):
     from sota_imagenet_amd.synth import synthetic_batch
 
     return synthetic_batch(n, S, num_classes=NC, seed=3, index=index)
-
-
-def _step(m, data, target, zero=True):
-    from sota_imagenet_amd.losses import CrossEntropyLoss
-
-    m.train()
-    if zero:
-        m.zero_grad()
-    out = m(data.cuda())
-    CrossEntropyLoss(smoothing=0.1)(out, target.cuda()).backward()
-    torch.cuda.synchronize()
-    return out.detach().clone(), {k: p.grad.detach().clone() for k, p in m.named_parameters()}
-
-
-def _conv_names(m):
-    return [k for k, p in m.named_parameters() if p.dim() == 4]
 
 
 def _rows(t):
@@ -326,10 +294,10 @@ def test_executor_wiring_is_exact(dev, dtype):
     a = _model(dtype).cuda()
     a.set_spectral_norm(True)
     assert a.spectral_norm and a.weight_transform == 0 and a.spectral_u.numel() == 26560 and a.spectral_v.numel() == 52883
-    convs = _conv_names(a)
+    convs = E.conv_names(a)
     pa = dict(a.named_parameters())
     state0 = a.spectral_state()
-    out_a, ga = _step(a, data, target)
+    out_a, ga = E.step(a, data, target)
     w_hat, u, v, sigma = _debug(a, (N, S, S), convs)
     state1 = a.spectral_state()
     # what the executor reads is the model's own state, in torch's layout, and one iteration of the kernels' rule from the warmed state
@@ -351,42 +319,42 @@ def test_executor_wiring_is_exact(dev, dtype):
     with torch.no_grad():
         for k, p in b.named_parameters():
             p.copy_(w_hat[k].permute(0, 3, 1, 2) if k in w_hat else pa[k])
-    out_b, gb = _step(b, data, target)
-    assert _same_bits(out_a, out_b), "the logits of A are those of a plain model on w_hat"
+    out_b, gb = E.step(b, data, target)
+    assert E.same_bits(out_a, out_b), "the logits of A are those of a plain model on w_hat"
     for k in ga:
         if k not in w_hat:
-            assert _same_bits(ga[k], gb[k]), f"{k}: BatchNorm / FC gradients do not see the parametrisation"
+            assert E.same_bits(ga[k], gb[k]), f"{k}: BatchNorm / FC gradients do not see the parametrisation"
     _check_conv_grads(ga, gb, w_hat, u, v, sigma, convs, f"{dtype} step 1")
 
     # a second step without zero_grad: u, v advance once more, so the rule is applied again, on top of the first step's gradients
-    out_a2, ga2 = _step(a, data, target, zero=False)
+    out_a2, ga2 = E.step(a, data, target, zero=False)
     w_hat2, u2, v2, sigma2 = _debug(a, (N, S, S), convs)
     assert any(not np.array_equal(u2[k], u[k]) for k in convs), "a training forward advances the state"
     with torch.no_grad():
         for k in convs:
             dict(b.named_parameters())[k].copy_(w_hat2[k].permute(0, 3, 1, 2))
-    out_b2, gb2 = _step(b, data, target)
-    assert _same_bits(out_a2, out_b2)
+    out_b2, gb2 = E.step(b, data, target)
+    assert E.same_bits(out_a2, out_b2)
     _check_conv_grads(ga2, gb2, w_hat2, u2, v2, sigma2, convs, f"{dtype} step 2 (accumulated)", prev=ga)
     for k in ga:
         if k not in w_hat:
-            assert _same_bits(ga2[k], ga[k] + gb2[k]), f"{k}: accumulated gradient"
+            assert E.same_bits(ga2[k], ga[k] + gb2[k]), f"{k}: accumulated gradient"
 
     # the backward in two segment calls (what the DDP hook does) gives the bits of one call: from the same state, by teacher forcing
     a.load_spectral_state(state1)
-    out_r, gr = _step(a, data, target)
+    out_r, gr = E.step(a, data, target)
     nseg = len(a.grad_segments)
     seen = []
     a.load_spectral_state(state1)
     a._grad_sync = lambda seg, lo, hi: seen.append(seg)
     a._grad_sync_points = {nseg // 2}
     try:
-        out_s, gs = _step(a, data, target)
+        out_s, gs = E.step(a, data, target)
     finally:
         a._grad_sync = a._grad_sync_points = None
-    assert seen == list(range(nseg)) and _same_bits(out_s, out_r) and _same_bits(out_r, out_a2)
+    assert seen == list(range(nseg)) and E.same_bits(out_s, out_r) and E.same_bits(out_r, out_a2)
     for k in ga:
-        assert _same_bits(gs[k], gr[k]), f"{k}: segmented backward"
+        assert E.same_bits(gs[k], gr[k]), f"{k}: segmented backward"
 
     # a second context of another batch shape continues the same u, v; an eval forward leaves them alone
     before = a.spectral_state()
@@ -397,7 +365,7 @@ def test_executor_wiring_is_exact(dev, dtype):
     torch.cuda.synchronize()
     mid = a.spectral_state()
     assert all(torch.equal(before[k][0], mid[k][0]) and torch.equal(before[k][1], mid[k][1]) for k in before), "eval: no iteration"
-    _step(a, d3, t3)
+    E.step(a, d3, t3)
     after = a.spectral_state()
     u3 = a.debug_tensor((3, S, S), "conv1.sn_u").cpu().numpy()
     assert np.array_equal(u3, after["conv1"][0].cpu().numpy()) and not torch.equal(after["conv1"][0], before["conv1"][0])
@@ -417,9 +385,9 @@ def test_executor_wiring_is_exact(dev, dtype):
     a.set_spectral_norm(False)
     assert not a.spectral_norm
     c = _model(dtype).cuda()
-    out_off, g_off = _step(a, data, target)
-    out_c, g_c = _step(c, data, target)
-    assert _same_bits(out_off, out_c) and all(_same_bits(g_off[k], g_c[k]) for k in g_c)
+    out_off, g_off = E.step(a, data, target)
+    out_c, g_c = E.step(c, data, target)
+    assert E.same_bits(out_off, out_c) and all(E.same_bits(g_off[k], g_c[k]) for k in g_c)
     ws = _model(dtype, weight_standardization=True).cuda()
     ctx = ws._ctx(N, S, S)
     p = a.flat_params.data_ptr()
@@ -427,17 +395,6 @@ def test_executor_wiring_is_exact(dev, dtype):
 
 
 # ---- 6. against the oracle ---------------------------------------------------------------------------------------------------------------------
-def _nerr(got, ref):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    assert got.shape == ref.shape and torch.isfinite(got).all()
-    return ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
-
-
-def _l2err(got, ref):
-    assert torch.isfinite(got).all()
-    return ((got - ref).norm() / ref.norm().clamp_min(1e-30)).item()
-
-
 def test_fp32_step_matches_the_torch_spectral_norm_oracle(dev):
     """one fp32 training step at N=8 (at N=2 the gradient rule is batch luck: tests/test_weight_std_gpu.py) against oracle.resnet50_ref with
     torch's spectral_norm on every Conv2d; the native model is teacher-forced with the float32 oracle's _u, _v after registration, and so is
@@ -457,12 +414,12 @@ def test_fp32_step_matches_the_torch_spectral_norm_oracle(dev):
     o64, g64, s64 = SN.oracle_step(sd, data, target, NC, True, state)
     m.set_spectral_norm(True)
     m.load_spectral_state(state)
-    out, g = _step(m, data, target)
+    out, g = E.step(m, data, target)
     names = [k for k, _ in m.named_parameters()]
     assert set(names) == set(g64)
-    e32, e64 = _nerr(out, o32), _nerr(out, o64)
-    yard = _l2err(WS.flat_grads(names, g32), WS.flat_grads(names, g64))
-    got = _l2err(WS.flat_grads(names, g), WS.flat_grads(names, g64))
+    e32, e64 = E.nerr(out, o32), E.nerr(out, o64)
+    yard = E.l2err(WS.flat_grads(names, g32), WS.flat_grads(names, g64))
+    got = E.l2err(WS.flat_grads(names, g), WS.flat_grads(names, g64))
     print(f"logits vs fp32 {e32:.3e}, vs fp64 {e64:.3e}; grad rel-L2 vs fp64: native {got:.3e}, torch-cpu fp32 {yard:.3e}")
     assert e32 < 1e-3 and e64 < 1e-3
     assert got < 1.5 * yard + 1e-3, f"grad rel-L2 vs fp64: native {got:.3e}, torch-cpu fp32 {yard:.3e}"
@@ -500,24 +457,24 @@ def test_forward_spectral_norm_callback(dev):
     with pytest.raises(RuntimeError):
         other.on_begin()
     data, target = _batch(index=2)
-    _step(m, data, target)
+    E.step(m, data, target)
     opt.step()
     torch.cuda.synchronize()
     stepped = {k: p.detach().clone() for k, p in m.named_parameters()}
     m.eval()
     with torch.no_grad():
         before = m(data.cuda()).clone()
-    convs = _conv_names(m)
+    convs = E.conv_names(m)
     sigma = {k: m.debug_tensor((N, S, S), k[: -len(".weight")] + ".sn_sigma").item() for k in convs}
     cb.on_end()
     assert not m.spectral_norm
     with torch.no_grad():
         after = m(data.cuda()).clone()
     torch.cuda.synchronize()
-    assert _same_bits(before, after), "on_end leaves w / sigma behind: the same forward"
+    assert E.same_bits(before, after), "on_end leaves w / sigma behind: the same forward"
     for k, p in m.named_parameters():
         if p.dim() != 4:
-            assert _same_bits(p.detach(), stepped[k]), k
+            assert E.same_bits(p.detach(), stepped[k]), k
             continue
         ref = _rows(stepped[k]).astype(np.float64) / sigma[k]
         assert SN.worst(_rows(p), ref, 2 * SN.U1 * np.abs(ref)) <= 1.0, k

@@ -9,29 +9,22 @@ import sys
 import pytest
 import torch
 
+from optim_harness import run_smoke_config
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_train_py_runs_the_smoke_config(dev, tmp_path):
-    sys.path.insert(0, ROOT)
-    import train
-
-    logdir = os.path.relpath(str(tmp_path), ROOT)
-    val_loss, metrics = train.main(["+hydra_exp=test", f"log.dir={logdir}", "run.fp16=false", "random_seed=0",
-                                    "data.pool=2", "log.save_optim=true"])
-    assert val_loss == val_loss and 0.0 <= metrics["Acc@1"].avg <= 100.0 and metrics["Acc@5"].avg >= metrics["Acc@1"].avg
-    run = glob.glob(os.path.join(str(tmp_path), "*_test", "*"))[0]
+    # (with resume_eval: evaluate-only from the checkpoint, train.py:158-162, in bf16 this time)
+    _, metrics, run, _ = run_smoke_config("test", tmp_path, ["run.fp16=false", "random_seed=0", "data.pool=2", "log.save_optim=true"], resume_eval=True)
+    assert metrics["Acc@5"].avg >= metrics["Acc@1"].avg
     logs = open(os.path.join(run, "logs.txt")).read()
     assert "Train loss:" in logs and "Acc@1:" in logs and "Model params: 25.56M" in logs  # line formats of the reference
     ck = torch.load(os.path.join(run, "model.chpn"), map_location="cpu")
     assert {"epoch", "state_dict", "optimizer"} <= set(ck) and "layer4.2.bn3.running_var" in ck["state_dict"]
     last = torch.load(os.path.join(run, "model_last.chpn"), map_location="cpu")
     assert last["conv1.weight"].shape == (64, 3, 7, 7)
-    # evaluate-only from the checkpoint (train.py:158-162) in bf16 this time
-    loss2, m2 = train.main(["+hydra_exp=test", f"log.dir={logdir}", f"run.resume={os.path.join(run, 'model.chpn')}",
-                            "run.evaluate=true", "data.pool=2"])
-    assert loss2 == loss2 and 0.0 <= m2["Acc@1"].avg <= 100.0
 
 
 def test_train_py_runs_progressive_resize_with_fp8_convs(dev, tmp_path):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import exec_gpu_common as E
 import weight_norm_common as WN
 
 pytestmark = pytest.mark.gpu
@@ -25,14 +26,8 @@ ROOT = os.path.dirname(HERE)
 SENTINEL = 0x7FC0DEAD  # a NaN bit pattern: a gap that is read poisons what reads it
 
 
-def _mods():
-    from sota_imagenet_amd import item_plan, ops
-
-    return ops, item_plan
-
-
 def _launch(flat, items):
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     st = ops.weight_norm_rows_(flat, items, item_plan.pack_records(items, flat.device))
     torch.cuda.synchronize()
     return st
@@ -40,7 +35,7 @@ def _launch(flat, items):
 
 def _shapes():
     """(skew of the first element against a 64-element boundary, rows, row_len)"""
-    ops, _ = _mods()
+    ops, _ = E.mods()
     T, W = ops.WNORM_WAVE_ROW_MAX, ops.WNORM_ITEM_ELEMS
     return [(3, 5, 147), (0, 4, 64), (1, 3, 65), (2, 1, 4608), (1, 2, T - 1), (0, 2, T), (3, 2, T + 1), (1, 1, 20011), (2, 130, 2),
             (0, W // 64 + 1, 64)]
@@ -53,7 +48,7 @@ def _rows(rows, L, mean, sd, seed):
 
 def run_kernel(dev):
     """ONE launch over every shape at every (mean, sd) of the grid, plus a record whose middle row is constant; the float64 rule of every row"""
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     recs, data, off = [], [], 64
     for g, (mean, sd) in enumerate(WN.GRID):
         for s, (skew, rows, L) in enumerate(_shapes()):
@@ -89,7 +84,7 @@ def _planned(k):
 
 # ---- 1. the kernel against the float64 rule ------------------------------------------------------------------------------------------------------
 def test_the_layout_sits_on_the_boundaries(kernel_run):
-    ops, _ = _mods()
+    ops, _ = E.mods()
     k = kernel_run
     T, W = ops.WNORM_WAVE_ROW_MAX, ops.WNORM_ITEM_ELEMS
     assert k["n"] < 400_000 and len(k["recs"]) == 4 * 10 + 1
@@ -130,7 +125,7 @@ def test_a_second_run_gives_the_same_bits(kernel_run, dev):
     assert torch.equal(again.cpu().view(torch.int32), k["out"].view(torch.int32))
     # ... and so does another cut of the same rows into items: a row's result does not depend on the item or the workgroup that took it,
     # as long as its length keeps it on the same side of WNORM_WAVE_ROW_MAX
-    _, item_plan = _mods()
+    _, item_plan = E.mods()
     other = k["host"].to(dev)
     items = item_plan.wnorm_items(k["recs"], 1000)
     assert len(items) > len(k["items"]) and _launch(other, items).tolist() == [0] * len(items)
@@ -206,7 +201,7 @@ def test_items_that_do_not_fit_are_refused_and_their_memory_untouched(dev):
 
 
 def test_overlapping_items_are_refused_by_the_wrapper(dev):
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     flat = torch.ones(256, device=dev)
     items = [(0, 16, 4), (32, 8, 2)]
     with pytest.raises(ValueError, match="overlaps"):
@@ -222,7 +217,7 @@ def test_against_the_reference_fixture(dev):
     memory order), planned by item_plan.wnorm_records: within the native bound plus the reference bound of what the reference's own callback
     left; what the planner does not select — biases, the Conv1d, both BatchNorm weights — keeps its bits, where the reference turned the
     64-channel BatchNorm weight into NaN"""
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     z = np.load(os.path.join(HERE, "golden", "weight_norm_ref.npz"))
     names = json.loads(bytes(z["names"]))
     for d in range(2):

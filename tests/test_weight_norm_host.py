@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import exec_gpu_common as E
 import weight_norm_common as WN
 from plan_common import resnet50_table
 from sota_imagenet_amd import config as C
@@ -17,18 +18,6 @@ from sota_imagenet_amd.fit_wrapper import RunnerState
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROW_LENS = {64, 128, 147, 256, 512, 576, 1024, 1152, 2048, 2304, 4608}
-
-
-def _resnet50():
-    from sota_imagenet_amd.models import resnet50
-
-    return resnet50()
-
-
-def _bresnet50():
-    from sota_imagenet_amd.models import resnet50
-
-    return resnet50(stem_type="deep", antialias=True, attn_type="eca", norm_layer="inplaceabn", norm_act="leaky_relu")
 
 
 # ---- the planner -----------------------------------------------------------------------------------------------------------------------------------
@@ -59,7 +48,7 @@ def test_records_of_the_recorded_resnet50_layout():
 
 
 def test_records_of_the_resnet50_model():
-    m = _resnet50()
+    m = E.resnet50()
     recs = item_plan.wnorm_records(m._table)
     _check_resnet50_records(recs, m._table)
     off = {name: off for name, kind, off, _ in m._table if kind == 0}["fc.weight"]
@@ -67,7 +56,7 @@ def test_records_of_the_resnet50_model():
 
 
 def test_records_of_the_bresnet50_model_hold_no_conv1d():
-    m = _bresnet50()
+    m = E.bresnet50()
     recs = item_plan.wnorm_records(m._table)
     shapes = {off: shape for _, kind, off, shape in m._table if kind == 0}
     eca = [sh for sh in shapes.values() if len(sh) == 3]
@@ -226,7 +215,7 @@ def test_the_stale_keys_of_the_recipe_raise():
 def test_a_cpu_model_is_refused():
     from sota_imagenet_amd.callbacks import WeightNorm
 
-    for model in (_resnet50(), torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.Linear(8, 4))):
+    for model in (E.resnet50(), torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.Linear(8, 4))):
         before = [p.detach().clone() for p in model.parameters()]
         cb = WeightNorm()
         cb.set_state(RunnerState(model=model))

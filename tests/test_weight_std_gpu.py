@@ -1,21 +1,19 @@
 """The per-filter forward weight transform on the GPU: the row kernels of csrc/weight_std.hip against float64 on synthetic rows, the executor's
 wiring against a plain model fed the transformed weights, the whole step against the parametrised torch oracle, and the ForwardWeightNorm callback.
 The bounds are those of tests/weight_std_common.py; the model tests run at N=2, 64 px, 10 classes."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import exec_gpu_common as E
 import weight_std_common as WS
 
 pytestmark = pytest.mark.gpu
 N, S, NC = 2, 64, 10
+_model = functools.partial(E.model, num_classes=NC)
 MODE_IDS = sorted(WS.MODES)
-
-
-def _mods():
-    from sota_imagenet_amd import item_plan, ops
-
-    return ops, item_plan
 
 
 @pytest.fixture(scope="module")
@@ -24,12 +22,8 @@ def rows_case():
     return flat, rows, const, WS.row_mask(flat.size, rows)
 
 
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 def _forward_rows(flat, rows, mode, dev):
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     w = torch.from_numpy(flat).to(dev)
     w_hat = torch.full_like(w, float("nan"))
     invstd = torch.full((len(rows),), float("nan"), device=dev)
@@ -61,8 +55,8 @@ def test_rows_forward_against_float64(dev, rows_case, mode_name):
         assert (inv == 1.0).all()
     # bit for bit on a second run, and in place (the bake): the same bits as out of place, gaps untouched
     _, again, inv2 = _forward_rows(flat, rows, mode, dev)
-    assert _same_bits(again[torch.from_numpy(mask).to(dev)], w_hat[torch.from_numpy(mask).to(dev)]) and _same_bits(inv2, invstd)
-    ops, item_plan = _mods()
+    assert E.same_bits(again[torch.from_numpy(mask).to(dev)], w_hat[torch.from_numpy(mask).to(dev)]) and E.same_bits(inv2, invstd)
+    ops, item_plan = E.mods()
     inplace = torch.from_numpy(flat).to(dev)
     ops.weight_std_rows_fwd(inplace, inplace, inv2, item_plan.pack_records(rows, dev), mode)
     torch.cuda.synchronize()
@@ -72,7 +66,7 @@ def test_rows_forward_against_float64(dev, rows_case, mode_name):
 
 def test_rows_that_do_not_fit_are_skipped(dev, rows_case):
     flat, rows, _, mask = rows_case
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     n = flat.size
     bad = [(-1, 64), (n - 10, 64), (0, 0), (n, 1), (5, n + 1)]
     w = torch.from_numpy(flat).to(dev)
@@ -96,7 +90,7 @@ def test_rows_that_do_not_fit_are_skipped(dev, rows_case):
 def test_rows_backward_against_float64(dev, rows_case, mode_name, beta):
     flat, rows, _, mask = rows_case
     mode = WS.MODES[mode_name]
-    ops, item_plan = _mods()
+    ops, item_plan = E.mods()
     _, w_hat, invstd = _forward_rows(flat, rows, mode, dev)
     rng = np.random.default_rng(7)
     g = np.full(flat.size, np.nan, dtype=np.float32)
@@ -129,7 +123,7 @@ def test_rows_backward_against_float64(dev, rows_case, mode_name, beta):
     ops.weight_std_rows_bwd(gd, w_hat, invstd, again, tab, mode, beta=beta)
     torch.cuda.synchronize()
     m = torch.from_numpy(mask).to(dev)
-    assert _same_bits(again[m], dw[m])
+    assert E.same_bits(again[m], dw[m])
 
 
 # ---- the recorded bits ---------------------------------------------------------------------------------------------------------------------------
@@ -175,32 +169,10 @@ def test_rows_backward_gives_the_recorded_bits(recorded, mode_name, beta):
 
 
 # ---- the model tests -----------------------------------------------------------------------------------------------------------------------------
-def _model(dtype, **kw):
-    from sota_imagenet_amd.models import resnet50
-
-    return resnet50(num_classes=NC, dtype=dtype, **kw)
-
-
 def _batch(index=0):
     from sota_imagenet_amd.synth import synthetic_batch
 
     return synthetic_batch(N, S, num_classes=NC, seed=3, index=index)
-
-
-def _step(m, data, target, zero=True):
-    from sota_imagenet_amd.losses import CrossEntropyLoss
-
-    m.train()
-    if zero:
-        m.zero_grad()
-    out = m(data.cuda())
-    CrossEntropyLoss(smoothing=0.1)(out, target.cuda()).backward()
-    torch.cuda.synchronize()
-    return out.detach().clone(), {k: p.grad.detach().clone() for k, p in m.named_parameters()}
-
-
-def _conv_names(m):
-    return [k for k, p in m.named_parameters() if p.dim() == 4]
 
 
 # ---- 3. the executor wiring, exactly -----------------------------------------------------------------------------------------------------------
@@ -211,8 +183,8 @@ def test_executor_wiring_is_exact(dev, dtype, mode_name):
     data, target = _batch()
     a = _model(dtype).cuda()
     a.set_weight_transform(mode_name)
-    out_a, ga = _step(a, data, target)
-    convs = _conv_names(a)
+    out_a, ga = E.step(a, data, target)
+    convs = E.conv_names(a)
     w_hat = {k: a.debug_tensor((N, S, S), k[: -len(".weight")] + ".w_hat") for k in convs}       # [Cout, K, K, Cin]
     invstd = {k: a.debug_tensor((N, S, S), k[: -len(".weight")] + ".ws_invstd") for k in convs}  # [Cout]
 
@@ -230,11 +202,11 @@ def test_executor_wiring_is_exact(dev, dtype, mode_name):
     with torch.no_grad():
         for k, p in b.named_parameters():
             p.copy_(w_hat[k].permute(0, 3, 1, 2) if k in w_hat else pa[k])
-    out_b, gb = _step(b, data, target)
-    assert _same_bits(out_a, out_b), "the logits of A are those of a plain model on w_hat"
+    out_b, gb = E.step(b, data, target)
+    assert E.same_bits(out_a, out_b), "the logits of A are those of a plain model on w_hat"
     for k in ga:
         if k not in w_hat:
-            assert _same_bits(ga[k], gb[k]), f"{k}: BatchNorm / FC gradients do not see the transform"
+            assert E.same_bits(ga[k], gb[k]), f"{k}: BatchNorm / FC gradients do not see the transform"
     worst = 0.0
     for k in convs:
         co = ga[k].shape[0]
@@ -250,9 +222,9 @@ def test_executor_wiring_is_exact(dev, dtype, mode_name):
     print(f"{dtype} {mode_name}: conv gradients, worst error / bound {worst:.3f}")
 
     # accumulation: a second identical step without zero_grad leaves exactly twice the gradients
-    _, g2 = _step(a, data, target, zero=False)
+    _, g2 = E.step(a, data, target, zero=False)
     for k in ga:
-        assert _same_bits(g2[k], 2 * ga[k]), f"{k}: accumulated gradient"
+        assert E.same_bits(g2[k], 2 * ga[k]), f"{k}: accumulated gradient"
 
     # the backward in two segment calls (what the DDP hook does) gives the bits of one call
     nseg = len(a.grad_segments)
@@ -260,34 +232,23 @@ def test_executor_wiring_is_exact(dev, dtype, mode_name):
     a._grad_sync = lambda seg, lo, hi: seen.append(seg)
     a._grad_sync_points = {nseg // 2}
     try:
-        out_s, gs = _step(a, data, target)
+        out_s, gs = E.step(a, data, target)
     finally:
         a._grad_sync = a._grad_sync_points = None
     assert seen == list(range(nseg))
-    assert _same_bits(out_s, out_a)
+    assert E.same_bits(out_s, out_a)
     for k in ga:
-        assert _same_bits(gs[k], ga[k]), f"{k}: segmented backward"
+        assert E.same_bits(gs[k], ga[k]), f"{k}: segmented backward"
 
     # off again: the plain model's bits on the raw weights
     a.set_weight_transform("off")
     c = _model(dtype).cuda()
-    out_off, g_off = _step(a, data, target)
-    out_c, g_c = _step(c, data, target)
-    assert _same_bits(out_off, out_c) and all(_same_bits(g_off[k], g_c[k]) for k in g_c)
+    out_off, g_off = E.step(a, data, target)
+    out_c, g_c = E.step(c, data, target)
+    assert E.same_bits(out_off, out_c) and all(E.same_bits(g_off[k], g_c[k]) for k in g_c)
 
 
 # ---- 4. against the oracle ---------------------------------------------------------------------------------------------------------------------
-def _nerr(got, ref):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    assert got.shape == ref.shape and torch.isfinite(got).all()
-    return ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item()
-
-
-def _l2err(got, ref):
-    assert torch.isfinite(got).all()
-    return ((got - ref).norm() / ref.norm().clamp_min(1e-30)).item()
-
-
 def test_fp32_standardised_step_matches_the_parametrised_oracle(dev):
     """The rule of test_resnet_gpu.test_fp32_forward_backward_matches_cpu on that test's own batch (synthetic_batch seed 0, index 3), at N=2, 64 px,
     10 classes.  Both distances are samples of the same rounding noise, amplified by BatchNorm over as few as 8 values per channel, and at this
@@ -304,12 +265,12 @@ def test_fp32_standardised_step_matches_the_parametrised_oracle(dev):
     data, target = synthetic_batch(N, S, num_classes=NC, seed=0, index=3)
     o32, g32 = WS.oracle_step(sd, data, target, WS.STANDARDISE, NC, double=False)
     o64, g64 = WS.oracle_step(sd, data, target, WS.STANDARDISE, NC, double=True)
-    out, g = _step(m, data, target)
+    out, g = E.step(m, data, target)
     names = [k for k, _ in m.named_parameters()]
     assert set(names) == set(g64)
-    e32, e64 = _nerr(out, o32), _nerr(out, o64)
-    yard = _l2err(WS.flat_grads(names, g32), WS.flat_grads(names, g64))
-    got = _l2err(WS.flat_grads(names, g), WS.flat_grads(names, g64))
+    e32, e64 = E.nerr(out, o32), E.nerr(out, o64)
+    yard = E.l2err(WS.flat_grads(names, g32), WS.flat_grads(names, g64))
+    got = E.l2err(WS.flat_grads(names, g), WS.flat_grads(names, g64))
     print(f"logits vs fp32 {e32:.3e}, vs fp64 {e64:.3e}; grad rel-L2 vs fp64: native {got:.3e}, torch-cpu fp32 {yard:.3e}")
     assert e32 < 1e-3 and e64 < 1e-3
     assert got < 1.5 * yard + 1e-3, f"grad rel-L2 vs fp64: native {got:.3e}, torch-cpu fp32 {yard:.3e}"
@@ -331,7 +292,7 @@ def test_forward_weight_norm_callback(dev):
     cb.on_begin()
     assert m.weight_transform == WS.CENTRE
     data, target = _batch(index=2)
-    _step(m, data, target)
+    E.step(m, data, target)
     opt.step()
     torch.cuda.synchronize()
     stepped = {k: p.detach().clone() for k, p in m.named_parameters()}
@@ -343,10 +304,10 @@ def test_forward_weight_norm_callback(dev):
     with torch.no_grad():
         after = m(data.cuda()).clone()
     torch.cuda.synchronize()
-    assert _same_bits(before, after), "on_end leaves the parametrised weights behind: the same forward"
+    assert E.same_bits(before, after), "on_end leaves the parametrised weights behind: the same forward"
     for k, p in m.named_parameters():
         if p.dim() != 4:
-            assert _same_bits(p.detach(), stepped[k]), k
+            assert E.same_bits(p.detach(), stepped[k]), k
             continue
         co = p.shape[0]
         w = stepped[k].permute(0, 2, 3, 1).reshape(co, -1).cpu().numpy()
