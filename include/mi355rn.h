@@ -56,7 +56,9 @@ int mi355_device_count(void);
 
 /* ---- per-op entry points (unit parity tests; the executor below calls the same kernels) ----------
  * All pointers are device pointers.  `ws`/`ws_bytes` is caller-provided scratch; query the need with
- * mi355_conv2d_workspace_bytes().                                                                   */
+ * mi355_conv2d_workspace_bytes().  Where a scratch or table size is stated below as a need (">="), the library takes
+ * a larger buffer; the Python wrappers (sota_imagenet_amd/ops.py) allocate the scratch themselves or take EXACTLY the size
+ * their *_scratch / sizing helper gives (xpad, the spectral scratch, the ortho-loss partial / tile_ss).                */
 
 /* scratch needed by dgrad (transposed weights) / wgrad (split-K partials) for one conv geometry */
 size_t mi355_conv2d_workspace_bytes(int dtype, int N, int H, int W, int Cin, int Cout, int KH, int KW,
@@ -93,7 +95,8 @@ int mi355_conv2d_fwd_bn_in(int dtype, const void* y_in, const float* scale_shift
  *   dx = conv_transpose(dy, w) + (addend under addend_bits — the shortcut gradient under the block output's ReLU bit mask; bits null: plain)
  * and, when `partial` is non-null, the BN-backward sums of the layer whose post-ReLU activation dx is the gradient of, as partial
  * rows [*nblk][2][Cin] floats: sum dz and sum dz * xhat, dz = dx (as stored) under bn_bits, xhat = (bn_y - bn_mean) * bn_invstd
- * (bn_y laid out like dx, masks one byte per 16-byte vector).  *nblk = 0 when the launch shape cannot produce them.
+ * (bn_y laid out like dx, bn_mean / bn_invstd [Cin] floats, masks [N][H][W][Cin / V] with one byte per 16-byte vector, V = 16 /
+ * sizeof(element); addend_bits masks the addend).  *nblk = 0 when the launch shape cannot produce them.
  * partial: >= 768 * 2 * Cin floats.  dx may alias addend.
  * addend_sub2 = 1: `addend` is [N][H/2][W/2][Cin] and stands for the full-resolution tensor that is zero at odd rows / columns — the
  * data gradient of the stride-2 1x1 downsample convolution of a stage's first block, which the executor then never writes at full size
@@ -181,7 +184,8 @@ size_t mi355_stem_workspace_bytes(int dtype, int N, int H, int W);
  *   running = (1-momentum)*running + momentum*batch.   Outputs save_mean/save_invstd [C] for backward.
  *   out = act(x_hat*gamma + beta (+ residual)),   act by `relu`: 0 identity, 1 ReLU, 2 leaky ReLU (slope 0.01 — the
  *   `norm_act: leaky_relu` of the BResNet-50 configs, BResNet50_encoder.yaml:49-50; same codes in mi355_bn_bwd).
- *   ws: >= mi355_bn_workspace_bytes(C) bytes.
+ *   ws: >= mi355_bn_workspace_bytes(C) bytes.  gamma, beta, the running statistics and every other per-channel vector of the
+ *   mi355_bn_* calls: [C] floats; residual, out, dout, dz_out, dx: laid out like x.
  * replaces cuDNN BatchNormalizationForwardTraining + ATen relu/add — callbacks.py:316 (K3,K4);
  * momentum semantics: train.py:76 / arg_parser.py:132                                              */
 size_t mi355_bn_workspace_bytes(int C);
@@ -225,7 +229,8 @@ int mi355_bn_bwd_bits(int dtype, const void* g, const uint8_t* bits, const void*
                       const float* invstd, void* dx, void* dz_out, float* dgamma, float* dbeta, float beta_acc, int M, int C, int relu,
                       const float* partial, int nblk, void* ws, size_t ws_bytes, void* stream);
 
-/* MaxPool 3x3 stride 2 pad 1 on NHWC; idx[N,Ho,Wo,C] uint8 = window position of the first maximum.
+/* MaxPool 3x3 stride 2 pad 1 on NHWC; idx[N,Ho,Wo,C] uint8 = window position of the first maximum.  H, W even: Ho = H/2, Wo = W/2,
+ * y and dy [N,Ho,Wo,C] like idx.
  * replaces ATen max_pool2d_with_indices fwd/bwd — callbacks.py:316-317 (K5)                         */
 int mi355_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C,
                       void* stream);
@@ -263,7 +268,7 @@ int mi355_gap_bwd(int dtype, const float* dpooled, void* dx, int N, int HW, int 
 /* label-smoothed softmax cross-entropy on float (one-hot or soft) targets, reduction = mean:
  *   loss = mean_n[ (1-s) * -(sum_c y*logp) + s * -(mean_c logp) ],  logp = log_softmax(logits)
  *   dlogits = d loss / d logits (already divided by N) times grad_scale.
- * loss: 1 float on device.  row_loss: N floats of scratch.  dlogits may be NULL (evaluation).
+ * logits, target, dlogits: [N][C] floats.  loss: 1 float on device.  row_loss: N floats of scratch.  dlogits may be NULL (evaluation).
  * replaces pytorch_tools.losses.smooth.CrossEntropyLoss — arg_parser.py:140-142, callbacks.py:316 (K7)*/
 int mi355_ce_loss(const float* logits, const float* target, float smoothing, float grad_scale,
                   float* loss, float* row_loss, float* dlogits, int N, int C, void* stream);
@@ -704,14 +709,16 @@ int mi355_norm_loss_bwd(const float* w, float* dw, size_t n, const float* s, con
  * norm_layer="inplaceabn", norm_act="leaky_relu", drop_rate=0.2, drop_connect_rate=0.2) —
  * configs/_old_configs/_first_attempts/BResNet50_encoder.yaml:41-51 — and wraps every conv in weight standardisation
  * (train.py:66-67).  Convolutions and BN reuse the entry points above; these are the additional ops, all NHWC.
- *   blurpool    3x3 binomial [1,2,1]x[1,2,1]/16, stride 2, reflect padding 1 (anti-aliased down-sampling); H, W even
+ *   blurpool    3x3 binomial [1,2,1]x[1,2,1]/16, stride 2, reflect padding 1 (anti-aliased down-sampling); H, W even; y, dy [N][H/2][W/2][C]
+ *               (as for avgpool2)
  *   avgpool2    2x2 average, stride 2 (the anti-aliased shortcut of a stride-2 block)
- *   maxpool3s1  3x3 max, stride 1, pad 1 + u8 argmax (first maximum in window scan order): the anti-aliased stem pool
+ *   maxpool3s1  3x3 max, stride 1, pad 1 + u8 argmax (first maximum in window scan order): the anti-aliased stem pool; y, idx, dy like x
  *   eca         y = x * sigmoid(conv1d_k(GAP(x)))[n][c]; k odd <= 9, zero padded over the channel axis.  pooled / gate
  *               [N][C] fp32 are outputs kept for backward; eca_bwd returns dx and the k conv-weight gradients
  *               (beta = 0 overwrite / 1 accumulate), ws = 2*N*C + 1152 floats of scratch
  *   weight_std  w_hat[o] = (w[o] - mean_o) * rsqrt(var_o + eps) over the K = KH*KW*Cin weights of output channel o
- *               (biased variance) and its backward dw = invstd * (g - mean(g) - w_hat * mean(g * w_hat))
+ *               (biased variance) and its backward dw = invstd * (g - mean(g) - w_hat * mean(g * w_hat)); mean, invstd: [Cout] floats,
+ *               w_hat, dw_hat, dw: [Cout][K] like w
  *   residual_act  out = act(branch * scale_n[n] + shortcut): drop-connect keep/scale per sample (scale_n may be NULL),
  *               shortcut add (may be NULL), activation code as in mi355_bn_fwd_train; backward from `out`
  *   keep_scale  keep[i] = u_i >= p ? 1/(1-p) : 0 from a counter-based generator (seed, counter): the drop-connect
