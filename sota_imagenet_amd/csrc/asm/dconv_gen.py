@@ -31,13 +31,13 @@ Structure (one workgroup = 4 waves = one wave per SIMD, one tile per workgroup):
 """
 import functools
 import os
-import re
 import sys
 from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_common  # noqa: E402
-from asm_common import LEAKY_BITS, Emitter, R, merge, resolve_waits  # noqa: E402
+from asm_common import (Emitter, R, acc_pair_read, bn_bwd_acc, bn_relu_bits16, desc, desc_addr, desc_tail, dpp_row_sum, dz_xhat_finish,  # noqa: E402
+                        exec_lane15, merge, mfma, pack4, spread, stats_acc, unpack8, vm)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -455,11 +455,7 @@ class Gen(Emitter):
         else:
             # this wave's piece table: 64 words at kernarg + 128 + (parity*4 + w)*256, word i into lane i (one vector load; the
             # kernarg pointer is in s[0:1] from the start, so this does not wait for the scalar loads above)
-            e("s_add_u32 %s, s0, 128" % R("s", self.srdK))
-            e("s_addc_u32 %s, s1, 0" % R("s", self.srdK + 1))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdK + 1), R("s", self.srdK + 1)))
-            e("s_mov_b32 %s, %d" % (R("s", self.srdK + 2), NCLS * 1024 * (2 if c.bnin else 1)))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdK + 3))
+            self.put(desc(self.srdK, 0, 1, "128", records="%d" % (NCLS * 1024 * (2 if c.bnin else 1))))
             # tile -> image (s_img), row tile t inside it (s_par), class (first 0 / middle 1 / last 2)
             if c.TPI == 1:
                 e("s_mov_b32 %s, %s" % (R("s", self.s_img), R("s", self.s_tile)))
@@ -539,19 +535,11 @@ class Gen(Emitter):
             tile_in = c.IPT * c.H * rowb
             e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_tile), tile_in))
             e("s_mul_hi_u32 %s, %s, %d" % (R("s", t1), R("s", self.s_tile), tile_in))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdA), R("s", ka + 0), R("s", t0)))
-        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdA + 1), R("s", ka + 1), R("s", t1)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdA + 1), R("s", self.srdA + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdA + 2), tile_in))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdA + 3))
+        self.put(desc(self.srdA, ka, ka + 1, R("s", t0), R("s", t1), "%d" % tile_in))
         if c.bnin:
             # a out: the same window on the other tensor; its ReLU bits: 1 byte per 16 bytes of it (the window's offset / 16: rowb is a multiple of 16);
             # scale / shift: [2][Cin] floats
-            e("s_add_u32 %s, %s, %s" % (R("s", self.srdA1), R("s", ka + 8), R("s", t0)))
-            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdA1 + 1), R("s", ka + 9), R("s", t1)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdA1 + 1), R("s", self.srdA1 + 1)))
-            e("s_mov_b32 %s, %d" % (R("s", self.srdA1 + 2), tile_in))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdA1 + 3))
+            self.put(desc(self.srdA1, ka + 8, ka + 9, R("s", t0), R("s", t1), "%d" % tile_in))
             assert rowb % 16 == 0 and tile_in % 16 == 0
             if c.ROWS_T:
                 e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_tile), c.ROWS_T * rowb // 16))
@@ -561,15 +549,8 @@ class Gen(Emitter):
             else:
                 e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_tile), tile_in // 16))
                 e("s_mul_hi_u32 %s, %s, %d" % (R("s", t1), R("s", self.s_tile), tile_in // 16))
-            e("s_add_u32 %s, %s, %s" % (R("s", self.srdBt), R("s", ka + 10), R("s", t0)))
-            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdBt + 1), R("s", ka + 11), R("s", t1)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdBt + 1), R("s", self.srdBt + 1)))
-            e("s_mov_b32 %s, %d" % (R("s", self.srdBt + 2), tile_in // 16))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdBt + 3))
-            e("s_mov_b32 %s, %s" % (R("s", self.srdSS), R("s", ka + 12)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdSS + 1), R("s", ka + 13)))
-            e("s_mov_b32 %s, %d" % (R("s", self.srdSS + 2), 2 * c.Cin * 4))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdSS + 3))
+            self.put(desc(self.srdBt, ka + 10, ka + 11, R("s", t0), R("s", t1), "%d" % (tile_in // 16)))
+            self.put(desc(self.srdSS, ka + 12, ka + 13, records="%d" % (2 * c.Cin * 4)))
             e("s_mov_b32 %s, 0" % R("s", self.s_last))
             e("s_mov_b32 %s, 0x00010001" % R("s", self.s_k1))
         self.b_descriptor()
@@ -710,11 +691,7 @@ class Gen(Emitter):
         """srdB = weight rows nt*BN .. + BN"""
         c, e, ka, t0 = self.c, self.e, self.s_ka, self.s_t0
         e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * c.w_row))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdB), R("s", ka + 2), R("s", t0)))
-        e("s_addc_u32 %s, %s, 0" % (R("s", self.srdB + 1), R("s", ka + 3)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdB + 1), R("s", self.srdB + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdB + 2), c.BN * c.w_row))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdB + 3))
+        self.put(desc(self.srdB, ka + 2, ka + 3, R("s", t0), records="%d" % (c.BN * c.w_row)))
 
     def out_descriptors(self, tile_out):
         """the output window of this tile and column tile (tile_out bytes per tile), the statistics rows; stats >= 2: the y and ReLU-mask
@@ -726,40 +703,23 @@ class Gen(Emitter):
         e("s_mul_i32 %s, %s, %d" % (R("s", self.s_stg), R("s", self.s_nt), c.BN * 2))
         e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
         e("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdO), R("s", ka + 4), R("s", t0)))
-        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdO + 1), R("s", ka + 5), R("s", t1)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdO + 1), R("s", self.srdO + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdO + 2), tile_out))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdO + 3))
+        self.put(desc(self.srdO, ka + 4, ka + 5, R("s", t0), R("s", t1), "%d" % tile_out))
         # (the O window starts at this tile's column offset: num_records covers exactly what may be stored)
         e("s_sub_u32 %s, %s, %s" % (R("s", self.srdO + 2), R("s", self.srdO + 2), R("s", self.s_stg)))
-        e("s_mov_b32 %s, %s" % (R("s", self.srdX), R("s", ka + 6)), "statistics rows")
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdX + 1), R("s", ka + 7)))
-        e("s_mov_b32 %s, 0x7fffffff" % R("s", self.srdX + 2))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdX + 3))
+        self.put(desc(self.srdX, ka + 6, ka + 7, records="0x7fffffff", comment="statistics rows"))
         if c.stats >= 2:
             # y: laid out like the output (same window); mask bytes: 1/16 of it; mean / invstd: this column tile's 256 floats
-            e("s_add_u32 %s, %s, %s" % (R("s", self.srdY), R("s", ka + 8), R("s", t0)))
-            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdY + 1), R("s", ka + 9), R("s", t1)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdY + 1), R("s", self.srdY + 1)))
-            e("s_mov_b32 %s, %s" % (R("s", self.srdY + 2), R("s", self.srdO + 2)))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdY + 3))
+            self.put(desc(self.srdY, ka + 8, ka + 9, R("s", t0), R("s", t1), R("s", self.srdO + 2)))
             e("s_lshr_b32 %s, %s, 4" % (R("s", t0), R("s", t0)))
             e("s_lshl_b32 %s, %s, 28" % (R("s", self.s_stg), R("s", t1)))
             e("s_or_b32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
             e("s_lshr_b32 %s, %s, 4" % (R("s", t1), R("s", t1)))
-            e("s_add_u32 %s, %s, %s" % (R("s", self.srdM), R("s", ka + 10), R("s", t0)))
-            e("s_addc_u32 %s, %s, %s" % (R("s", self.srdM + 1), R("s", ka + 11), R("s", t1)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdM + 1), R("s", self.srdM + 1)))
+            self.put(desc_addr(self.srdM, ka + 10, ka + 11, R("s", t0), R("s", t1)))
             e("s_lshr_b32 %s, %s, 4" % (R("s", self.srdM + 2), R("s", self.srdO + 2)))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdM + 3))
+            self.put(desc_tail(self.srdM))
             e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_nt), c.BN * 4))
             for srd, k0 in ((self.srdMu, 12), (self.srdIs, 14)):
-                e("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", ka + k0), R("s", t0)))
-                e("s_addc_u32 %s, %s, 0" % (R("s", srd + 1), R("s", ka + k0 + 1)))
-                e("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
-                e("s_mov_b32 %s, %d" % (R("s", srd + 2), c.BN * 4))
-                e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
+                self.put(desc(srd, ka + k0, ka + k0 + 1, R("s", t0), records="%d" % (c.BN * 4)))
 
     def bn_backward_first_loads(self):
         """stats >= 2: the BN-backward inputs of tile pairs 0 and 1, requested before the first loads of the main loop (the oldest vector-memory
@@ -818,55 +778,30 @@ class Gen(Emitter):
             e("v_add_u32 %s, %s, %s" % (R("v", v[9]), R("s", t0), R("v", v[8])))
             e("ds_write_b128 %s, %s" % (R("v", v[9]), R("v", z, 4)))
 
-    VMTAG = "\t;vm:"   # main-loop bookkeeping (stripped before the text is returned): tags a vector-memory operation for the counted waits
-
     def a_piece_insts(self, k, buf, s_chunk, tag=""):
-        """A piece slot k (table entries k and NPA + k of this wave) of the chunk at byte offset s_chunk into A buffer `buf`"""
+        """A piece slot k (table entries k and NPA + k of this wave) of the chunk at byte offset s_chunk into A buffer `buf`; tag: the main loop's, for its
+        counted waits (asm_common.vm)"""
         c = self.c
         var = a_slots(c)[k][0]
-        tag = self.VMTAG + tag if tag else ""
+        load = vm(tag, "buffer_load_dwordx4 %s, %s, %s offen lds" % (R("v", self.vA_dma[var]), R("s", self.srdA, 4), R("s", self.s_t1)))
         if self.tab_sgpr:
             return ["s_add_u32 m0, %s, %d" % (R("s", self.s_tbl + k), c.ABASE + buf * c.ASTRIDE),
-                    "s_add_u32 %s, %s, %s" % (R("s", self.s_t1), R("s", s_chunk), R("s", self.s_tbl + self.NPA + k)),
-                    "buffer_load_dwordx4 %s, %s, %s offen lds" % (R("v", self.vA_dma[var]), R("s", self.srdA, 4), R("s", self.s_t1)) + tag]
+                    "s_add_u32 %s, %s, %s" % (R("s", self.s_t1), R("s", s_chunk), R("s", self.s_tbl + self.NPA + k)), load]
         return ["v_readlane_b32 %s, %s, %d" % (R("s", self.s_a), R("v", self.v_tab), k),
                 "v_readlane_b32 %s, %s, %d" % (R("s", self.s_b), R("v", self.v_tab), self.NPA + k),
                 "s_add_u32 m0, %s, %d" % (R("s", self.s_a), c.ABASE + buf * c.ASTRIDE),
-                "s_add_u32 %s, %s, %s" % (R("s", self.s_t1), R("s", s_chunk), R("s", self.s_b)),
-                "buffer_load_dwordx4 %s, %s, %s offen lds" % (R("v", self.vA_dma[var]), R("s", self.srdA, 4), R("s", self.s_t1)) + tag]
+                "s_add_u32 %s, %s, %s" % (R("s", self.s_t1), R("s", s_chunk), R("s", self.s_b)), load]
 
     def b_piece_insts(self, i, bp, s_stage, tag=""):
         """weight piece i into ring stage bp; s_stage holds (wtap*Cin + chunk*64)*2"""
         c = self.c
-        tag = self.VMTAG + tag if tag else ""
+        load = vm(tag, "buffer_load_dwordx4 %s, %s, %s offen lds" % (R("v", self.vB_dma[i & 1]), R("s", self.srdB, 4), R("s", self.s_t0)))
         if self.tab_sgpr:
             return ["s_add_u32 m0, %s, %d" % (R("s", self.s_ldsBw), c.BBASE + bp * c.BSTAGE + i * 1024),
-                    "s_add_u32 %s, %s, %s" % (R("s", self.s_t0), R("s", s_stage), R("s", self.s_tbl + 2 * self.NPA + i)),
-                    "buffer_load_dwordx4 %s, %s, %s offen lds" % (R("v", self.vB_dma[i & 1]), R("s", self.srdB, 4), R("s", self.s_t0)) + tag]
+                    "s_add_u32 %s, %s, %s" % (R("s", self.s_t0), R("s", s_stage), R("s", self.s_tbl + 2 * self.NPA + i)), load]
         return ["v_readlane_b32 %s, %s, %d" % (R("s", self.s_b), R("v", self.v_tab), 2 * self.NPA + i),
                 "s_add_u32 m0, %s, %d" % (R("s", self.s_ldsBw), c.BBASE + bp * c.BSTAGE + i * 1024),
-                "s_add_u32 %s, %s, %s" % (R("s", self.s_t0), R("s", s_stage), R("s", self.s_b)),
-                "buffer_load_dwordx4 %s, %s, %s offen lds" % (R("v", self.vB_dma[i & 1]), R("s", self.srdB, 4), R("s", self.s_t0)) + tag]
-
-    def patch_waits(self, start):
-        """the stage-barrier waits of the main-loop trip emitted since self.out[start]: a wait line carries `@need:<tags>@`, a vector-memory
-        operation its tag; the counts are resolve_waits' (every buffer_ instruction of the trip must be tagged)"""
-        events = []
-        for i in range(start, len(self.out)):
-            line = self.out[i]
-            m = re.search(r";vm:(\S+)", line)
-            if m:
-                events.append(("op", m.group(1), False))
-            elif re.match(r"\tbuffer_", line):
-                raise AssertionError("untagged vector-memory operation in the main loop: " + line)
-            w = re.search(r"@need:([^@]*)@", line)
-            if w:
-                events.append(("wait", i, w.group(1).split(",")))
-        for i, cnt in resolve_waits(events).items():
-            assert 0 <= cnt <= 63
-            self.out[i] = re.sub(r"vmcnt\(@need:[^@]*@\)", "vmcnt(%d)" % cnt, self.out[i])
-        for i in range(start, len(self.out)):
-            self.out[i] = re.sub(r"\t;vm:\S+", "", self.out[i])
+                "s_add_u32 %s, %s, %s" % (R("s", self.s_t0), R("s", s_stage), R("s", self.s_b)), load]
 
     def first_stage_issue(self, st):
         """prologue: the weight pieces of the workgroup's stage st (< NB) into ring stage st.  One class: tap st of chunk 0.  Several classes
@@ -931,26 +866,7 @@ class Gen(Emitter):
     def mfmas(self, fset):
         c = self.c
         fa, fb = self.F[fset]
-        out = []
-        for n in range(c.NT):
-            for m in range(c.MFR):
-                acc = (m * c.NT + n) * 4
-                out.append("v_mfma_f32_16x16x32_bf16 %s, %s, %s, %s" % (R("a", acc, 4), R("v", fb + 4 * n, 4), R("v", fa + 4 * m, 4), R("a", acc, 4)))
-        return out
-
-    def interleave(self, mf, others, first=1):
-        """place the instruction groups `others` (lists) between the MFMAs, evenly, starting after MFMA `first`"""
-        n, k = len(mf), len(others)
-        slots = {}
-        if k:
-            span = n - first - 1
-            for j, grp in enumerate(others):
-                pos = first + (j * span) // k
-                slots.setdefault(pos, []).extend(grp)
-        for i, m in enumerate(mf):
-            self.e(m)
-            for ins in slots.get(i, []):
-                self.e(ins)
+        return [mfma((m * c.NT + n) * 4, fb + 4 * n, fa + 4 * m) for n in range(c.NT) for m in range(c.MFR)]
 
     def skew(self):
         c, e = self.c, self.e
@@ -1037,7 +953,7 @@ class Gen(Emitter):
         var = a_slots(c)[k][0]
         d, f = r["d"], r["f"]
         inv = self.tr_inv_mask(var)
-        tag = (self.VMTAG + "S") if tagged else ""
+        tag = "S" if tagged else ""
         g = []
         g.append(["v_readlane_b32 %s, %s, %d" % (R("s", self.s_tb), R("v", self.v_tab2), self.NPA + k),
                   "s_or_b32 %s, %s, %s" % (R("s", self.s_tb), R("s", self.s_tb), R("s", self.s_last))])
@@ -1051,41 +967,23 @@ class Gen(Emitter):
             g.append(["s_or_b32 %s, %s, 0x%x" % (R("s", self.s_sel + 1), R("s", self.s_sel + 1), inv >> 32)])
         g.append(["v_or_b32 %s, %s, %s" % (R("v", r["o"]), R("s", self.s_dead), R("v", self.vA_dma[var])),
                   "s_lshr_b32 %s, %s, 4" % (R("s", self.s_tb2), R("s", self.s_tb))])
-        for j in range(4):
-            g.append(["v_lshlrev_b32 %s, 16, %s" % (R("v", f + 2 * j), R("v", d + j)),
-                      "v_and_b32 %s, 0xffff0000, %s" % (R("v", f + 2 * j + 1), R("v", d + j))])
-        for j in range(4):
-            g.append(["v_fma_f32 %s, %s, %s, %s" % (R("v", f + 2 * j + q), R("v", f + 2 * j + q), R("v", self.v_sc + 2 * j + q), R("v", self.v_sh + 2 * j + q)) for q in range(2)])
-        # round to bf16 first, ReLU on the packed pairs as signed 16-bit integers (a negative bf16, -0 included, is a negative int16): the same values as
-        # ReLU in fp32 followed by the rounding, in 4 instead of 8 instructions
-        for j in range(0, 4, 2):
-            g.append(["v_cvt_pk_bf16_f32 %s, %s, %s" % (R("v", f + j + q), R("v", f + 2 * (j + q)), R("v", f + 2 * (j + q) + 1)) for q in range(2)])
-        for j in range(0, 4, 2):
-            g.append(["v_pk_max_i16 %s, %s, 0" % (R("v", f + j + q), R("v", f + j + q)) for q in range(2)])
-        # ReLU bits = (a != 0) of the eight stored values (bn_apply_kernel tests the fp32 value: the same bit unless a positive fp32 value rounds to a
-        # bf16 zero, below 2^-134): 0 / 1 per half, gathered to bit 2j + half of one byte
-        t = f + 4
-        for j in range(0, 4, 2):
-            g.append(["v_pk_min_u16 %s, %s, %s" % (R("v", t + j + q), R("v", f + j + q), R("s", self.s_k1)) for q in range(2)])
-        g.append(["v_lshl_or_b32 %s, %s, 2, %s" % (R("v", t), R("v", t + 1), R("v", t)), "v_lshl_or_b32 %s, %s, 2, %s" % (R("v", t + 2), R("v", t + 3), R("v", t + 2))])
-        g.append(["v_lshl_or_b32 %s, %s, 4, %s" % (R("v", t), R("v", t + 2), R("v", t)), "v_lshrrev_b32 %s, 4, %s" % (R("v", r["o2"]), R("v", r["o"]))])
-        g.append(["v_lshrrev_b32 %s, 15, %s" % (R("v", t + 1), R("v", t)), "v_and_b32 %s, 0x55, %s" % (R("v", t), R("v", t))])
-        g.append(["v_and_b32 %s, 0xaa, %s" % (R("v", t + 1), R("v", t + 1)), "v_or_b32 %s, %s, %s" % (R("v", r["bits"]), R("v", t + 1), R("v", t))])
+        work = bn_relu_bits16(d, f, self.v_sc, self.v_sh, self.s_k1, r["bits"], r["o"], r["o2"])
+        g += [work[i:i + 2] for i in range(0, len(work), 2)]
         # (one group: nothing else runs under the partial EXEC)
         g.append(["s_andn2_b64 exec, exec, %s" % R("s", self.s_sel, 2), "ds_write_b128 %s, %s" % (R("v", r["ta"]), R("v", f, 4)), "s_mov_b64 exec, -1"])
-        g.append(["buffer_store_dwordx4 %s, %s, %s, %s offen" % (R("v", f, 4), R("v", r["o"]), R("s", self.srdA1, 4), R("s", self.s_tb)) + tag])
-        g.append(["buffer_store_byte %s, %s, %s, %s offen" % (R("v", r["bits"]), R("v", r["o2"]), R("s", self.srdBt, 4), R("s", self.s_tb2)) + tag])
+        g.append([vm(tag, "buffer_store_dwordx4 %s, %s, %s, %s offen" % (R("v", f, 4), R("v", r["o"]), R("s", self.srdA1, 4), R("s", self.s_tb)))])
+        g.append([vm(tag, "buffer_store_byte %s, %s, %s, %s offen" % (R("v", r["bits"]), R("v", r["o2"]), R("s", self.srdBt, 4), R("s", self.s_tb2)))])
         return g
 
     def ss_loads(self, s_chunk, tagged=True):
         """scale / shift of this lane's 8 channels of the chunk at byte offset s_chunk (64 channels = 128 bytes of a pixel = 256 bytes of floats)"""
-        tag = (self.VMTAG + "C") if tagged else ""
+        tag = "C" if tagged else ""
         out = ["s_lshl_b32 %s, %s, 1" % (R("s", self.s_tb), R("s", s_chunk))]
         for h in range(2):
-            out.append("buffer_load_dwordx4 %s, %s, %s, %s offen offset:%d" % (R("v", self.v_sc + 4 * h, 4), R("v", self.v_ssoff), R("s", self.srdSS, 4), R("s", self.s_tb), 16 * h) + tag)
+            out.append(vm(tag, "buffer_load_dwordx4 %s, %s, %s, %s offen offset:%d" % (R("v", self.v_sc + 4 * h, 4), R("v", self.v_ssoff), R("s", self.srdSS, 4), R("s", self.s_tb), 16 * h)))
         out.append("s_add_u32 %s, %s, %d" % (R("s", self.s_tb), R("s", self.s_tb), self.c.Cin * 4))
         for h in range(2):
-            out.append("buffer_load_dwordx4 %s, %s, %s, %s offen offset:%d" % (R("v", self.v_sh + 4 * h, 4), R("v", self.v_ssoff), R("s", self.srdSS, 4), R("s", self.s_tb), 16 * h) + tag)
+            out.append(vm(tag, "buffer_load_dwordx4 %s, %s, %s, %s offen offset:%d" % (R("v", self.v_sh + 4 * h, 4), R("v", self.v_ssoff), R("s", self.srdSS, 4), R("s", self.s_tb), 16 * h)))
         return out
 
     def mainloop(self):
@@ -1120,8 +1018,7 @@ class Gen(Emitter):
 
     def mfma8_col(self, n, aset):
         c = self.c
-        return ["v_mfma_f32_16x16x128_f8f6f4 %s, %s, %s, %s" % (R("a", (m * c.NT + n) * 4, 4), R("v", self.B8[n % 4], 8), R("v", self.A8[aset] + 8 * m, 8), R("a", (m * c.NT + n) * 4, 4))
-                for m in range(c.MFR)]
+        return [mfma((m * c.NT + n) * 4, self.B8[n % 4], self.A8[aset] + 8 * m, f8=True) for m in range(c.MFR)]
 
     def mainloop_fp8(self, stages):
         """e4m3 operands: a stage = one tap of a 128-channel chunk = NT columns of MFR v_mfma_f32_16x16x128_f8f6f4.  Weight ring of THREE stages: stage t
@@ -1136,7 +1033,7 @@ class Gen(Emitter):
         self.comment("---- main loop (e4m3): chunks (2 per trip) x %d taps x %d columns of %d MFMAs" % (T, NT, c.MFR))
         top, done = self.newlabel("loop"), self.newlabel("done")
         self.label(top)
-        body = len(self.out)
+        self.trip_open()
         aset = 0
         for cp in range(c.NA):
             if c.NA == 1:
@@ -1156,14 +1053,14 @@ class Gen(Emitter):
                 # vector-memory requests of the stage, in its first columns: next chunk's A pieces, then the weight pieces of stage t + 2
                 t3 = (t + 2) % T
                 s_ch = self.s_cC if t + 2 < T else self.s_cN
-                vm = [self.a_piece_insts(k, cp ^ 1, self.s_cN, "A") for k in range(t * aps, min((t + 1) * aps, self.NPA))] if (c.NA == 2 and t < ntap_a) else []
+                vmem = [self.a_piece_insts(k, cp ^ 1, self.s_cN, "A") for k in range(t * aps, min((t + 1) * aps, self.NPA))] if (c.NA == 2 and t < ntap_a) else []
                 for i in range(c.NPB):
                     g = self.b_piece_insts(i, bp2, self.s_stg, "B%d" % ((q + 2) % L))
                     if i == 0:
                         g = ["s_add_u32 %s, %s, %s" % (R("s", self.s_stg), R("s", self.s_wt + stages[t3][1]), R("s", s_ch))] + g
-                    vm.append(g)
+                    vmem.append(g)
                 if c.probe & 1:
-                    vm = []
+                    vmem = []
                 # the next tap's pixel fragments: before the barrier within a chunk, behind it at a chunk switch
                 a_next = [[r] for r in self.a8_reads(aset ^ 1, stages[t1][0])]
                 pre = NT - 2
@@ -1171,8 +1068,7 @@ class Gen(Emitter):
                     self.comment("chunk parity %d tap %d column %d" % (cp, t, n))
                     e("s_waitcnt lgkmcnt(0)")
                     if n == pre:
-                        need = ["B%d" % ((q + 1) % L)] + (["A"] if switch else [])
-                        e("s_waitcnt vmcnt(@need:%s@)" % ",".join(need))
+                        self.wait_vm(["B%d" % ((q + 1) % L)] + (["A"] if switch else []))
                         if not c.probe & 4:
                             e("s_barrier")
                         if switch:
@@ -1194,11 +1090,11 @@ class Gen(Emitter):
                         per = -(-len(a_next) // pre)
                         groups += a_next[n * per:(n + 1) * per]
                     if n < pre:
-                        per = -(-len(vm) // pre)
-                        groups = merge(groups, vm[n * per:(n + 1) * per])
+                        per = -(-len(vmem) // pre)
+                        groups = merge(groups, vmem[n * per:(n + 1) * per])
                     if c.probe & 2:
                         groups = [g for g in groups if not g[0].startswith("ds_read")]
-                    self.interleave(self.mfma8_col(n, aset), groups, first=0)
+                    self.put(spread(self.mfma8_col(n, aset), groups, first=0))
                 aset ^= 1
             if c.NA == 1:
                 break
@@ -1210,7 +1106,7 @@ class Gen(Emitter):
             else:
                 e("s_cbranch_scc0 %s" % top)
         assert c.NA == 1 or aset == 0 or (c.NA * T) % 2 == 0
-        self.patch_waits(body)
+        self.trip_close()
         self.label(done)
 
     def mainloop_of(self, stages):
@@ -1234,7 +1130,7 @@ class Gen(Emitter):
         self.comment("---- main loop: chunks (2 per trip: the A buffer and the weight-stage parity alternate) x %d taps x 2 substeps" % T)
         top, done = self.newlabel("loop"), self.newlabel("done")
         self.label(top)
-        body = len(self.out)
+        self.trip_open()
         for cp in range(c.NA):
             if c.NA == 1:
                 e("s_mov_b32 %s, 0" % R("s", self.s_cN), "one chunk: the weight stages past the last tap re-load chunk 0 (never used)")
@@ -1271,13 +1167,12 @@ class Gen(Emitter):
                 groups = merge(groups, pieces)
                 if bn:
                     groups = self.tr_groups(groups, read_at.get((t, 0), []), work_at.get((t, 0), []), cp ^ 1)
-                self.interleave(mf, groups)
+                self.put(spread(mf, groups))
                 # ---- the stage barrier: stage t+1's weights (and after the last tap the next A tile) have landed for every wave
                 self.comment("chunk parity %d tap %d substep 1" % (cp, t))
                 # younger than stage t+1's pieces: the weight groups of stages t+2 .. t+NB-1 and the A pieces issued since; at the last tap
-                # the A pieces must have landed too (patch_waits counts them)
-                need = ["B%d" % ((q + 1) % L)] + (["A"] if (t == T - 1 and c.NA == 2) else [])
-                e("s_waitcnt vmcnt(@need:%s@)" % ",".join(need))
+                # the A pieces must have landed too (trip_close counts them)
+                self.wait_vm(["B%d" % ((q + 1) % L)] + (["A"] if (t == T - 1 and c.NA == 2) else []))
                 e("s_waitcnt lgkmcnt(0)")
                 if not c.probe & 4:
                     e("s_barrier")
@@ -1307,7 +1202,7 @@ class Gen(Emitter):
                 groups = merge(groups, pieces)
                 if bn:
                     groups = self.tr_groups(groups, read_at.get((t, 1), []), work_at.get((t, 1), []), cp ^ 1)
-                self.interleave(mf, groups)
+                self.put(spread(mf, groups))
             if c.NA == 1:
                 break
             # next chunk
@@ -1318,7 +1213,7 @@ class Gen(Emitter):
                 e("s_cbranch_scc1 %s" % done)
             else:
                 e("s_cbranch_scc0 %s" % top)
-        self.patch_waits(body)
+        self.trip_close()
         self.label(done)
 
     def tr_groups(self, groups, reads, works, buf):
@@ -1531,62 +1426,31 @@ class Gen(Emitter):
                         e(ins)
                 self.emit_frag(m)
                 d = dsets[m % 4]
-                for i in range(4):
-                    e("v_accvgpr_read_b32 %s, a%d" % (R("v", tv[i]), (m * c.NT + 2 * p) * 4 + i))
-                    e("v_accvgpr_read_b32 %s, a%d" % (R("v", tv[4 + i]), (m * c.NT + 2 * p + 1) * 4 + i))
+                self.put(acc_pair_read(tv, (m * c.NT + 2 * p) * 4, (m * c.NT + 2 * p + 1) * 4))
                 if c.fp8:
                     for i in range(8):
                         e("v_mul_f32 %s, %s, %s" % (R("v", tv[i]), R("v", self.v_osc), R("v", tv[i])))
-                for i in range(4):
-                    e("v_cvt_pk_bf16_f32 %s, %s, %s" % (R("v", d + i), R("v", tv[2 * i]), R("v", tv[2 * i + 1])))
+                self.put(pack4(d, tv))
                 if not (c.probe & 32):
                     e("buffer_store_dwordx4 %s, %s, %s, %s offen offset:%d" % (R("v", d, 4), R("v", self.v_out), R("s", self.srdO, 4), R("s", self.s_t0), p * 64))
                 else:
                     e("s_nop 0")
                 if c.stats and not (c.probe & 16):
-                    for i in range(4):
-                        e("v_lshlrev_b32 %s, 16, %s" % (R("v", xr[2 * i]), R("v", d + i)))
-                        e("v_and_b32 %s, 0xffff0000, %s" % (R("v", xr[2 * i + 1]), R("v", d + i)))
+                    self.put(unpack8(xr, d))
                 if c.stats == 1 and not (c.probe & 16):
-                    for i in range(8):
-                        e("v_add_f32 %s, %s, %s" % (R("v", s1[i]), R("v", s1[i]), R("v", xr[i])))
-                        e("v_fma_f32 %s, %s, %s, %s" % (R("v", s2[i]), R("v", xr[i]), R("v", xr[i]), R("v", s2[i])))
+                    self.put(stats_acc(s1, s2, xr))
                 if c.stats >= 2 and not (c.probe & 16):
-                    yr, br = ysets[p & 1][m], self.v_mb
-                    for i in range(8):
-                        t = tv[i]  # (the accumulator copies are dead after the conversion)
-                        e("v_bfe_i32 %s, %s, %d, 1" % (R("v", t), R("v", br), i), "0 / -1: ReLU mask bit of element %d" % i)
-                        if c.stats == 3:   # leaky: dz = bit ? dx : dx * 0.01 (the fp32 product of the rounded value, as bn_reduce_kernel<MASK = 3>)
-                            t2 = tv[(i + 1) % 8]
-                            e("v_mul_f32 %s, 0x%08x, %s" % (R("v", t2), LEAKY_BITS, R("v", xr[i])))
-                            e("v_bfi_b32 %s, %s, %s, %s" % (R("v", xr[i]), R("v", t), R("v", xr[i]), R("v", t2)), "dz")
-                        else:
-                            e("v_and_b32 %s, %s, %s" % (R("v", xr[i]), R("v", xr[i]), R("v", t)), "dz")
-                        if i & 1:
-                            e("v_and_b32 %s, 0xffff0000, %s" % (R("v", yv[1]), R("v", yr + i // 2)))
-                        else:
-                            e("v_lshlrev_b32 %s, 16, %s" % (R("v", yv[0]), R("v", yr + i // 2)))
-                        e("v_add_f32 %s, %s, %s" % (R("v", s1[i]), R("v", s1[i]), R("v", xr[i])))
-                        e("v_fma_f32 %s, %s, %s, %s" % (R("v", s2[i]), R("v", xr[i]), R("v", yv[i & 1]), R("v", s2[i])), "sum dz*y")
+                    # (mask and leaky temporaries: the accumulator copies, dead after the conversion)
+                    self.put(bn_bwd_acc(s1, s2, xr, ysets[p & 1][m], self.v_mb, tv, yv, leaky=tv[1:] + tv[:1] if c.stats == 3 else None))
             if c.stats:
                 e("s_mov_b64 exec, -1")
                 e("s_nop 1")
-                for sh in (1, 2, 4, 8):
-                    for arr in (s1, s2):
-                        for i in range(8):
-                            rr = R("v", arr[i])
-                            e("v_add_f32_dpp %s, %s, %s row_shr:%d row_mask:0xf bank_mask:0xf bound_ctrl:1" % (rr, rr, rr, sh))
+                self.put(dpp_row_sum(s1 + s2))
                 if c.stats >= 2:
-                    # sum dz*xhat = invstd * (sum dz*y - mean * sum dz)
-                    mu, isd = msets[p & 1], msets[p & 1] + 8
-                    for i in range(8):
-                        e("v_mul_f32 %s, %s, %s" % (R("v", tv[i]), R("v", mu + i), R("v", s1[i])))
-                    for i in range(8):
-                        e("v_sub_f32 %s, %s, %s" % (R("v", s2[i]), R("v", s2[i]), R("v", tv[i])))
-                    for i in range(8):
-                        e("v_mul_f32 %s, %s, %s" % (R("v", s2[i]), R("v", isd + i), R("v", s2[i])))
+                    mu = msets[p & 1]
+                    self.put(dz_xhat_finish(s1, s2, range(mu, mu + 8), range(mu + 8, mu + 16), tv))
                 # lanes 15 of every row write their 8 channel slots: [channel][2]
-                self.set_exec(0x8000800080008000)
+                self.put(exec_lane15())
                 for i in range(8):
                     e("ds_write_b32 %s, %s offset:%d" % (R("v", vst), R("v", s1[i]), p * 32 * 8 + i * 8))
                     e("ds_write_b32 %s, %s offset:%d" % (R("v", vst), R("v", s2[i]), p * 32 * 8 + i * 8 + 4))

@@ -23,7 +23,7 @@ from dataclasses import dataclass
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_common  # noqa: E402
 import dconv_gen  # noqa: E402
-from asm_common import R, merge  # noqa: E402
+from asm_common import R, desc_addr, desc_tail, merge, spread  # noqa: E402
 
 
 @dataclass
@@ -212,11 +212,10 @@ class Gen(dconv_gen.Gen):
         tile_out = c.W * c.NCOLS * 2
         e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_tile), tile_in))
         e("s_mul_hi_u32 %s, %s, %d" % (R("s", t1), R("s", self.s_tile), tile_in))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdA), R("s", ka + 0), R("s", t0)))
-        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdA + 1), R("s", ka + 1), R("s", t1)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdA + 1), R("s", self.srdA + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdA + 2), tile_in), "pixels past the tile read zeros")
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdA + 3))
+        self.put(desc_addr(self.srdA, ka, ka + 1, R("s", t0), R("s", t1)))
+        records, flags = desc_tail(self.srdA, "%d" % tile_in)
+        e(records, "pixels past the tile read zeros")
+        e(flags)
         self.b_descriptor()
         e("s_mov_b32 %s, %s" % (R("s", self.s_nch), R("s", kb)))
         e("s_sub_u32 %s, %s, 1" % (R("s", self.s_clast), R("s", self.s_nch)))
@@ -309,7 +308,7 @@ class Gen(dconv_gen.Gen):
             pieces[-1] = pieces[-1] + self.adv_insts(self.s_cA, self.s_srcAw)
             if c.probe & 1:
                 pieces = []
-            self.interleave(self.mfmas(0), merge(groups, pieces))
+            self.put(spread(self.mfmas(0), merge(groups, pieces)))
             # ---- substep 1: the stage barrier (chunk + 1 has landed for every wave; this chunk's fragments are all read), compute on
             # set 1, read (chunk + 1, kk 0), request the weight slab of chunk + NB into the stage just released
             self.comment("chunk %d substep 1" % ch)
@@ -322,7 +321,7 @@ class Gen(dconv_gen.Gen):
             pieces[-1] = pieces[-1] + self.adv_insts(self.s_cB, self.s_srcBw)
             if c.probe & 1:
                 pieces = []
-            self.interleave(self.mfmas(1), merge(groups, pieces))
+            self.put(spread(self.mfmas(1), merge(groups, pieces)))
             e("s_sub_u32 %s, %s, 1" % (R("s", self.s_cnt), R("s", self.s_cnt)))
             e("s_cmp_eq_u32 %s, 0" % R("s", self.s_cnt))
             if ch < trip - 1:

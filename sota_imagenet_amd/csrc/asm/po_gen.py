@@ -34,7 +34,8 @@ from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_common  # noqa: E402
-from asm_common import LEAKY_BITS, Emitter, R, merge  # noqa: E402
+from asm_common import (Emitter, R, acc_pair_read, bn_bwd_acc, bn_relu_bits16, desc, desc_addr, desc_adv, desc_tail, dpp_row_sum, dz_xhat_finish, exec_lane15, merge,  # noqa: E402
+                        mfma, pack4, spread, stats_acc, unpack8)
 
 
 @dataclass
@@ -121,6 +122,11 @@ class PoCfg:
     @property
     def FULL(self):   # full-line stores: a wave owns 128 bytes of every pixel row (two tile pairs), a store instruction writes 8 pixels x 128 bytes
         return self.NT == 4
+
+
+def regs8(r):
+    """the 8 registers of a block allocated at r"""
+    return range(r, r + 8)
 
 
 class Gen(Emitter):
@@ -230,17 +236,7 @@ class Gen(Emitter):
     # -----------------------------------------------------------------------------------------------------------------
     def desc_from(self, srd, ptr_lo, off_lo, off_hi, total, comment=None):
         """srd = raw buffer at ptr + (off_hi:off_lo) with num_records = total - off_lo (total, off: SGPRs; total < 2^32 bytes)"""
-        e = self.e
-        e("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", ptr_lo), R("s", off_lo)), comment)
-        e("s_addc_u32 %s, %s, %s" % (R("s", srd + 1), R("s", ptr_lo + 1), R("s", off_hi) if off_hi is not None else "0"))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
-        e("s_sub_u32 %s, %s, %s" % (R("s", srd + 2), R("s", total), R("s", off_lo)))
-        e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
-
-    def desc_adv(self, srd, inc):
-        return ["s_add_u32 %s, %s, %s" % (R("s", srd), R("s", srd), R("s", inc)),
-                "s_addc_u32 %s, %s, 0" % (R("s", srd + 1), R("s", srd + 1)),
-                "s_sub_u32 %s, %s, %s" % (R("s", srd + 2), R("s", srd + 2), R("s", inc))]
+        self.put(desc(srd, ptr_lo, ptr_lo + 1, R("s", off_lo), R("s", off_hi), R("s", total), minus=R("s", off_lo), comment=comment))
 
     def a_piece(self, j, buf):
         """A piece j of this wave: 8-pixel block 4 * (j % (RB / 4)) + w of plane j // (RB / 4), RB = blocks per plane"""
@@ -411,10 +407,7 @@ class Gen(Emitter):
             e("s_lshr_b32 %s, %s, 4" % (R("s", t1), R("s", t1)))
             e("s_lshr_b32 %s, %s, 4" % (R("s", t2), R("s", t2)))
             self.desc_from(self.srdBt, ka + 10, t0, t1, t2, "its ReLU bits")
-            e("s_mov_b32 %s, %s" % (R("s", self.srdSS), R("s", ka + 12)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdSS + 1), R("s", ka + 13)))
-            e("s_mov_b32 %s, %d" % (R("s", self.srdSS + 2), 2 * c.K * 4))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdSS + 3))
+            self.put(desc(self.srdSS, ka + 12, ka + 13, records="%d" % (2 * c.K * 4)))
             e("s_mov_b32 %s, 0x00010001" % R("s", self.s_k1))
             # only the workgroups of column tile 0 store a and its bits (every column tile transforms its own LDS copy)
             e("s_cmp_eq_u32 %s, 0" % R("s", self.s_ct))
@@ -423,11 +416,7 @@ class Gen(Emitter):
         e("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_ct), c.BN * c.K * 2))
         e("s_mul_i32 %s, %s, %d" % (R("s", t1), R("s", self.s_wn), c.NT * 16 * c.K * 2))
         e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", t1)))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdB), R("s", ka + 2), R("s", t0)))
-        e("s_addc_u32 %s, %s, 0" % (R("s", self.srdB + 1), R("s", ka + 3)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdB + 1), R("s", self.srdB + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdB + 2), c.NT * 16 * c.K * 2))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdB + 3))
+        self.put(desc(self.srdB, ka + 2, ka + 3, R("s", t0), records="%d" % (c.NT * 16 * c.K * 2)))
         # B lane offsets: tile n = 2p + odd, MFMA row rho = lane & 15 -> channel p*32 + (rho >> 2)*8 + odd*4 + (rho & 3); k bytes kg*16
         vb = [v[4], v[5]]
         e("v_lshrrev_b32 %s, 2, %s" % (R("v", v[6]), R("v", r)))
@@ -487,12 +476,9 @@ class Gen(Emitter):
         if c.add == 3:
             # the whole half-resolution tensor from this column tile's first column on: npix / 4 pixels
             e("s_mul_i32 %s, %s, %d" % (R("s", t3), R("s", self.s_ct), c.BN * 2))
-            e("s_add_u32 %s, %s, %s" % (R("s", self.srdAD), R("s", ka + 16), R("s", t3)))
-            e("s_addc_u32 %s, %s, 0" % (R("s", self.srdAD + 1), R("s", ka + 17)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdAD + 1), R("s", self.srdAD + 1)))
+            self.put(desc_addr(self.srdAD, ka + 16, ka + 17, R("s", t3)))
             e("s_lshr_b32 %s, %s, 2" % (R("s", self.srdAD + 2), R("s", t2)))
-            e("s_sub_u32 %s, %s, %s" % (R("s", self.srdAD + 2), R("s", self.srdAD + 2), R("s", t3)))
-            e("s_mov_b32 %s, 0x00020000" % R("s", self.srdAD + 3))
+            self.put(desc_tail(self.srdAD, R("s", self.srdAD + 2), minus=R("s", t3)))
             e("s_mul_i32 %s, %s, %d" % (R("s", self.s_qpf), R("s", S_first), c.TP))
         elif c.add:
             self.desc_from(self.srdAD, ka + 16, t0, t1, t2, "addend")
@@ -594,28 +580,13 @@ class Gen(Emitter):
         c, r = self.c, self.tr[i]
         rb4 = c.TP // 8 // 4
         blk4, plane = j % rb4, j // rb4
-        d, f, t = r["d"], r["f"], r["f"] + 4
-        sc, sh = self.v_sc[plane], self.v_sh[plane]
-        g = ["v_add_u32 %s, %d, %s" % (R("v", r["o"]), blk4 * 32 * c.K * 2 + plane * 128, R("v", self.vA_dma)),
-             "v_or_b32 %s, %s, %s" % (R("v", r["o"]), R("s", self.s_trflag), R("v", r["o"]))]
-        for q in range(4):
-            g += ["v_lshlrev_b32 %s, 16, %s" % (R("v", f + 2 * q), R("v", d + q)), "v_and_b32 %s, 0xffff0000, %s" % (R("v", f + 2 * q + 1), R("v", d + q))]
-        for q in range(8):
-            g.append("v_fma_f32 %s, %s, %s, %s" % (R("v", f + q), R("v", f + q), R("v", sc + q), R("v", sh + q)))
-        for q in range(4):   # round first, ReLU on the packed pairs as signed 16-bit integers: the values of ReLU in fp32 followed by the rounding
-            g.append("v_cvt_pk_bf16_f32 %s, %s, %s" % (R("v", f + q), R("v", f + 2 * q), R("v", f + 2 * q + 1)))
-        for q in range(4):
-            g.append("v_pk_max_i16 %s, %s, 0" % (R("v", f + q), R("v", f + q)))
-        for q in range(4):   # ReLU bits = (a != 0): 0 / 1 per half, gathered to bit 2q + half of one byte
-            g.append("v_pk_min_u16 %s, %s, %s" % (R("v", t + q), R("v", f + q), R("s", self.s_k1)))
-        g += ["v_lshl_or_b32 %s, %s, 2, %s" % (R("v", t), R("v", t + 1), R("v", t)), "v_lshl_or_b32 %s, %s, 2, %s" % (R("v", t + 2), R("v", t + 3), R("v", t + 2)),
-              "v_lshl_or_b32 %s, %s, 4, %s" % (R("v", t), R("v", t + 2), R("v", t)), "v_lshrrev_b32 %s, 4, %s" % (R("v", r["o2"]), R("v", r["o"])),
-              "v_lshrrev_b32 %s, 15, %s" % (R("v", t + 1), R("v", t)), "v_and_b32 %s, 0x55, %s" % (R("v", t), R("v", t)),
-              "v_and_b32 %s, 0xaa, %s" % (R("v", t + 1), R("v", t + 1)), "v_or_b32 %s, %s, %s" % (R("v", r["bits"]), R("v", t + 1), R("v", t)),
-              "ds_write_b128 %s, %s" % (R("v", r["ta"]), R("v", f, 4)),
-              "buffer_store_dwordx4 %s, %s, %s, 0 offen" % (R("v", f, 4), R("v", r["o"]), R("s", self.srdA2, 4)),
-              "buffer_store_byte %s, %s, %s, 0 offen" % (R("v", r["bits"]), R("v", r["o2"]), R("s", self.srdBt, 4))]
-        return g
+        f = r["f"]
+        return (["v_add_u32 %s, %d, %s" % (R("v", r["o"]), blk4 * 32 * c.K * 2 + plane * 128, R("v", self.vA_dma)),
+                 "v_or_b32 %s, %s, %s" % (R("v", r["o"]), R("s", self.s_trflag), R("v", r["o"]))]
+                + bn_relu_bits16(r["d"], f, self.v_sc[plane], self.v_sh[plane], self.s_k1, r["bits"], r["o"], r["o2"])
+                + ["ds_write_b128 %s, %s" % (R("v", r["ta"]), R("v", f, 4)),
+                   "buffer_store_dwordx4 %s, %s, %s, 0 offen" % (R("v", f, 4), R("v", r["o"]), R("s", self.srdA2, 4)),
+                   "buffer_store_byte %s, %s, %s, 0 offen" % (R("v", r["bits"]), R("v", r["o2"]), R("s", self.srdBt, 4))])
 
     def transform_tile(self, buf, first):
         """this wave's NPW pieces of the tile in A buffer `buf` (they have landed: the caller waited for this wave's own LDS-DMA), the next piece's
@@ -639,7 +610,7 @@ class Gen(Emitter):
         e("s_cmp_gt_u32 %s, %d" % (R("s", self.s_trleft), 0 if first else 1))
         e("s_cselect_b32 %s, %d, 0" % (R("s", self.s_tinc), c.TP * c.K * 2))
         e("s_cselect_b32 %s, %d, 0" % (R("s", self.s_tincb), c.TP * c.K * 2 // 16))
-        for ins in self.desc_adv(self.srdA2, self.s_tinc) + self.desc_adv(self.srdBt, self.s_tincb):
+        for ins in desc_adv(self.srdA2, self.s_tinc) + desc_adv(self.srdBt, self.s_tincb):
             e(ins)
         if not first:
             e("s_cmp_gt_u32 %s, 0" % R("s", self.s_trleft))
@@ -653,7 +624,7 @@ class Gen(Emitter):
         return ["s_cmp_gt_u32 %s, 0" % R("s", self.s_pfa),
                 "s_cselect_b32 %s, %d, 0" % (R("s", self.s_ia), c.TP * c.K * 2),
                 "s_cselect_b32 %s, 1, 0" % R("s", self.s_t3),
-                "s_sub_u32 %s, %s, %s" % (R("s", self.s_pfa), R("s", self.s_pfa), R("s", self.s_t3))] + self.desc_adv(self.srdA, self.s_ia)
+                "s_sub_u32 %s, %s, %s" % (R("s", self.s_pfa), R("s", self.s_pfa), R("s", self.s_t3))] + desc_adv(self.srdA, self.s_ia)
 
     def prefetch_advance(self):
         """the prefetch descriptors of the epilogue operands (y, addend, masks) move to the next tile while one is left, else stay"""
@@ -669,29 +640,14 @@ class Gen(Emitter):
             out += ["s_mul_i32 %s, %s, %d" % (R("s", self.s_t3), R("s", self.s_t3), c.TP),
                     "s_add_u32 %s, %s, %s" % (R("s", self.s_qpf), R("s", self.s_qpf), R("s", self.s_t3))]
         if c.stats >= 2:
-            out += self.desc_adv(self.srdY, self.s_io) + self.desc_adv(self.srdM, self.s_ib)
+            out += desc_adv(self.srdY, self.s_io) + desc_adv(self.srdM, self.s_ib)
         if c.add in (1, 2):
-            out += self.desc_adv(self.srdAD, self.s_io)
+            out += desc_adv(self.srdAD, self.s_io)
         if c.add == 2:
-            out += self.desc_adv(self.srdAB, self.s_ib)
+            out += desc_adv(self.srdAB, self.s_ib)
         return out
 
     # -----------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def spread(mf, others, first=1):
-        """MFMA list with the instruction groups `others` placed evenly between them"""
-        n, k = len(mf), len(others)
-        slots = {}
-        if k:
-            span = max(1, n - first - 1)
-            for j, grp in enumerate(others):
-                slots.setdefault(min(n - 1, first + (j * span) // k), []).extend(grp)
-        out = []
-        for i, m in enumerate(mf):
-            out.append(m)
-            out.extend(slots.get(i, []))
-        return out
-
     def capture(self, fn, *args):
         """the instructions fn(*args) emits, as a list"""
         keep, self.out = self.out, []
@@ -707,17 +663,11 @@ class Gen(Emitter):
         for ks in range(c.KS):
             e("s_waitcnt lgkmcnt(0)")
             fs = self.F[ks & 1]
-            mf = []
-            for n in range(c.NT):
-                for m in range(c.MFRW):
-                    a = self.acc(m, n, aset)
-                    csrc = "0" if ks == 0 else R("a", a, 4)
-                    mf.append("v_mfma_f32_16x16x32_bf16 %s, %s, %s, %s" % (R("a", a, 4), R("a", self.breg(n, ks), 4), R("v", fs + 4 * m, 4), csrc))
+            mf = [mfma(self.acc(m, n, aset), self.breg(n, ks), fs + 4 * m, zero=(ks == 0), afile="a") for n in range(c.NT) for m in range(c.MFRW)]
             if c.probe & 1:
                 mf = mf[:c.MFRW] if ks == 0 else []
             nxt = [[r] for r in self.frag_reads((ks + 1) & 1, ks + 1, buf)] if ks + 1 < c.KS else []
-            for ins in (self.spread(mf, nxt) if mf else [x for g in nxt for x in g]):
-                e(ins)
+            self.put(spread(mf, nxt, clamp=True) if mf else [x for g in nxt for x in g])
 
     def epilogue_tile(self, CW):
         c = self.c
@@ -799,7 +749,7 @@ class Gen(Emitter):
                 e("s_nop 7")
                 self.epilogue_tile(CW)
             # ---- next tile
-            for ins in self.desc_adv(self.srdO, self.s_tout):
+            for ins in desc_adv(self.srdO, self.s_tout):
                 e(ins)
             for ins in self.prefetch_advance():
                 e(ins)
@@ -811,14 +761,12 @@ class Gen(Emitter):
                 e("s_cbranch_scc0 %s" % top)
         self.label(done)
 
-    def pair_math(self, i, m, p, ds):
-        """accumulators of (fragment m, tile pair p) -> + addend -> bf16 in ds; statistics of the pair"""
+    def pair_math(self, i, m, p, ds, store=()):
+        """accumulators of (fragment m, tile pair p) -> + addend -> bf16 in ds -> `store` (item(): the pair's own 16-byte store) -> statistics of the pair"""
         c, e = self.c, self.e
         d = self.it[i]
         tv, xr, yv, vm = self.tv, self.xr, self.yv, self.v_m
-        for k in range(4):
-            e("v_accvgpr_read_b32 %s, a%d" % (R("v", tv + k), self.acc(m, 2 * p) + k))
-            e("v_accvgpr_read_b32 %s, a%d" % (R("v", tv + 4 + k), self.acc(m, 2 * p + 1) + k))
+        self.put(acc_pair_read(regs8(tv), self.acc(m, 2 * p), self.acc(m, 2 * p + 1)))
         if c.add and not (c.probe & 2):
             for k in range(8):
                 src = R("v", d["ad"] + k // 2)
@@ -830,31 +778,15 @@ class Gen(Emitter):
                     e("v_bfe_i32 %s, %s, %d, 1" % (R("v", vm), R("v", d["ab"]), k), "0 / -1: ReLU bit of addend element %d" % k)
                     e("v_and_b32 %s, %s, %s" % (R("v", xr + k), R("v", xr + k), R("v", vm)))
                 e("v_add_f32 %s, %s, %s" % (R("v", tv + k), R("v", tv + k), R("v", xr + k)))
-        for k in range(4):
-            e("v_cvt_pk_bf16_f32 %s, %s, %s" % (R("v", ds + k), R("v", tv + 2 * k), R("v", tv + 2 * k + 1)))
+        self.put(pack4(ds, regs8(tv)))
+        self.put(store)
         if c.stats and not (c.probe & 2):
-            s1, s2 = self.s1[p], self.s2[p]
-            for k in range(4):
-                e("v_lshlrev_b32 %s, 16, %s" % (R("v", xr + 2 * k), R("v", ds + k)))
-                e("v_and_b32 %s, 0xffff0000, %s" % (R("v", xr + 2 * k + 1), R("v", ds + k)))
+            s1, s2 = regs8(self.s1[p]), regs8(self.s2[p])
+            self.put(unpack8(regs8(xr), ds))
             if c.stats == 1:
-                for k in range(8):
-                    e("v_add_f32 %s, %s, %s" % (R("v", s1 + k), R("v", s1 + k), R("v", xr + k)))
-                    e("v_fma_f32 %s, %s, %s, %s" % (R("v", s2 + k), R("v", xr + k), R("v", xr + k), R("v", s2 + k)))
-            else:
-                for k in range(8):
-                    e("v_bfe_i32 %s, %s, %d, 1" % (R("v", vm), R("v", d["yb"]), k), "0 / -1: ReLU bit of element %d" % k)
-                    if c.stats == 3:   # leaky mask: dz = bit ? dx : dx * 0.01 (asm_common.LEAKY_BITS; tv + k is dead after the conversion)
-                        e("v_mul_f32 %s, 0x%08x, %s" % (R("v", tv + k), LEAKY_BITS, R("v", xr + k)))
-                        e("v_bfi_b32 %s, %s, %s, %s" % (R("v", xr + k), R("v", vm), R("v", xr + k), R("v", tv + k)), "dz")
-                    else:
-                        e("v_and_b32 %s, %s, %s" % (R("v", xr + k), R("v", xr + k), R("v", vm)), "dz")
-                    if k & 1:
-                        e("v_and_b32 %s, 0xffff0000, %s" % (R("v", yv + 1), R("v", d["y"] + k // 2)))
-                    else:
-                        e("v_lshlrev_b32 %s, 16, %s" % (R("v", yv), R("v", d["y"] + k // 2)))
-                    e("v_add_f32 %s, %s, %s" % (R("v", s1 + k), R("v", s1 + k), R("v", xr + k)))
-                    e("v_fma_f32 %s, %s, %s, %s" % (R("v", s2 + k), R("v", xr + k), R("v", yv + (k & 1)), R("v", s2 + k)), "sum dz*y")
+                self.put(stats_acc(s1, s2, regs8(xr)))
+            else:   # (leaky temporaries: the accumulator copies, dead after the conversion)
+                self.put(bn_bwd_acc(s1, s2, regs8(xr), d["y"], d["yb"], [vm] * 8, (yv, yv + 1), leaky=regs8(tv) if c.stats == 3 else None, what="ReLU bit"))
 
     def unit(self, m, CW):
         """fragment m, both tile pairs: a lane ends with the two 16-byte chunks (pair 0, pair 1) of pixel r; lanes r and r + 8 of a row
@@ -888,8 +820,6 @@ class Gen(Emitter):
 
     def item(self, i, m, p, CW):
         c, e = self.c, self.e
-        d = self.it[i]
-        tv, xr, yv, vm = self.tv, self.xr, self.yv, self.v_m
         ds = self.dsets[i % 4]
         self.comment("item %d: fragment %d, tile pair %d" % (i, m, p))
         if (c.L or c.NMT) and not (c.probe & 4):
@@ -897,47 +827,8 @@ class Gen(Emitter):
         if p == 0:
             for ins in self.mask_fetch(m, self.mbuf):
                 e(ins)
-        for k in range(4):
-            e("v_accvgpr_read_b32 %s, a%d" % (R("v", tv + k), self.acc(m, 2 * p) + k))
-            e("v_accvgpr_read_b32 %s, a%d" % (R("v", tv + 4 + k), self.acc(m, 2 * p + 1) + k))
-        if c.add and not (c.probe & 2):
-            for k in range(8):
-                src = R("v", d["ad"] + k // 2)
-                if k & 1:
-                    e("v_and_b32 %s, 0xffff0000, %s" % (R("v", xr + k), src))
-                else:
-                    e("v_lshlrev_b32 %s, 16, %s" % (R("v", xr + k), src))
-                if c.add == 2:
-                    e("v_bfe_i32 %s, %s, %d, 1" % (R("v", vm), R("v", d["ab"]), k), "0 / -1: ReLU bit of addend element %d" % k)
-                    e("v_and_b32 %s, %s, %s" % (R("v", xr + k), R("v", xr + k), R("v", vm)))
-                e("v_add_f32 %s, %s, %s" % (R("v", tv + k), R("v", tv + k), R("v", xr + k)))
-        for k in range(4):
-            e("v_cvt_pk_bf16_f32 %s, %s, %s" % (R("v", ds + k), R("v", tv + 2 * k), R("v", tv + 2 * k + 1)))
-        if not (c.probe & 8):
-            e("buffer_store_dwordx4 %s, %s, %s, 0 offen offset:%d" % (R("v", ds, 4), R("v", self.v_out_m[m]), R("s", self.srdO, 4), p * 64))
-        if c.stats and not (c.probe & 2):
-            s1, s2 = self.s1[p], self.s2[p]
-            for k in range(4):
-                e("v_lshlrev_b32 %s, 16, %s" % (R("v", xr + 2 * k), R("v", ds + k)))
-                e("v_and_b32 %s, 0xffff0000, %s" % (R("v", xr + 2 * k + 1), R("v", ds + k)))
-            if c.stats == 1:
-                for k in range(8):
-                    e("v_add_f32 %s, %s, %s" % (R("v", s1 + k), R("v", s1 + k), R("v", xr + k)))
-                    e("v_fma_f32 %s, %s, %s, %s" % (R("v", s2 + k), R("v", xr + k), R("v", xr + k), R("v", s2 + k)))
-            else:
-                for k in range(8):
-                    e("v_bfe_i32 %s, %s, %d, 1" % (R("v", vm), R("v", d["yb"]), k), "0 / -1: ReLU bit of element %d" % k)
-                    if c.stats == 3:   # leaky mask: dz = bit ? dx : dx * 0.01 (asm_common.LEAKY_BITS; tv + k is dead after the conversion)
-                        e("v_mul_f32 %s, 0x%08x, %s" % (R("v", tv + k), LEAKY_BITS, R("v", xr + k)))
-                        e("v_bfi_b32 %s, %s, %s, %s" % (R("v", xr + k), R("v", vm), R("v", xr + k), R("v", tv + k)), "dz")
-                    else:
-                        e("v_and_b32 %s, %s, %s" % (R("v", xr + k), R("v", xr + k), R("v", vm)), "dz")
-                    if k & 1:
-                        e("v_and_b32 %s, 0xffff0000, %s" % (R("v", yv + 1), R("v", d["y"] + k // 2)))
-                    else:
-                        e("v_lshlrev_b32 %s, 16, %s" % (R("v", yv), R("v", d["y"] + k // 2)))
-                    e("v_add_f32 %s, %s, %s" % (R("v", s1 + k), R("v", s1 + k), R("v", xr + k)))
-                    e("v_fma_f32 %s, %s, %s, %s" % (R("v", s2 + k), R("v", xr + k), R("v", yv + (k & 1)), R("v", s2 + k)), "sum dz*y")
+        store = ["buffer_store_dwordx4 %s, %s, %s, 0 offen offset:%d" % (R("v", ds, 4), R("v", self.v_out_m[m]), R("s", self.srdO, 4), p * 64)]
+        self.pair_math(i, m, p, ds, store if not (c.probe & 8) else ())
         for ins in (self.sub2_addr(m) if p == 0 else []) + self.item_loads(i):   # rolling refill: the same vectors of the NEXT tile
             e(ins)
 
@@ -961,11 +852,7 @@ class Gen(Emitter):
             # mean / invstd of this lane's 8 channels per pair (the fragment registers are free)
             for name, k0 in (("mu", 12), ("is", 14)):
                 srd = self.srdY if name == "mu" else self.srdM
-                e("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", ka + k0), R("s", t0)))
-                e("s_addc_u32 %s, %s, 0" % (R("s", srd + 1), R("s", ka + k0 + 1)))
-                e("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
-                e("s_mov_b32 %s, %d" % (R("s", srd + 2), c.NT * 16 * 4))
-                e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
+                self.put(desc(srd, ka + k0, ka + k0 + 1, R("s", t0), records="%d" % (c.NT * 16 * 4)))
             # registers: the (now dead) y vectors of the first items hold mean, the packed-output sets hold invstd, 4 floats per block
             mu = [[self.it[2 * p + h]["y"] + k for h in range(2) for k in range(4)] for p in range(npair)]
             isd = [[self.dsets[2 * p + h] + k for h in range(2) for k in range(4)] for p in range(npair)]
@@ -983,30 +870,15 @@ class Gen(Emitter):
             e("s_mul_i32 %s, %s, %s" % (R("s", t1), R("s", self.s_g), R("s", self.s_n4)))
         e("s_lshl_b32 %s, %s, 1" % (R("s", t1), R("s", t1)))
         e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", t1)))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdX), R("s", ka + 6), R("s", t0)))
-        e("s_addc_u32 %s, %s, 0" % (R("s", self.srdX + 1), R("s", ka + 7)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdX + 1), R("s", self.srdX + 1)))
-        e("s_mov_b32 %s, 0x7fffffff" % R("s", self.srdX + 2))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdX + 3))
-        for sh in (1, 2, 4, 8):
-            for p in range(npair):
-                for arr in (self.s1[p], self.s2[p]):
-                    for k in range(8):
-                        rr = R("v", arr + k)
-                        e("v_add_f32_dpp %s, %s, %s row_shr:%d row_mask:0xf bank_mask:0xf bound_ctrl:1" % (rr, rr, rr, sh))
+        self.put(desc(self.srdX, ka + 6, ka + 7, R("s", t0), records="0x7fffffff"))
+        self.put(dpp_row_sum([arr + k for p in range(npair) for arr in (self.s1[p], self.s2[p]) for k in range(8)]))
         if c.stats >= 2:
             e("s_waitcnt vmcnt(0)")
-            tv = self.tv
             for p in range(npair):
-                # sum dz*xhat = invstd * (sum dz*y - mean * sum dz)
-                for k in range(8):
-                    e("v_mul_f32 %s, %s, %s" % (R("v", tv + k), R("v", mu[p][k]), R("v", self.s1[p] + k)))
-                for k in range(8):
-                    e("v_sub_f32 %s, %s, %s" % (R("v", self.s2[p] + k), R("v", self.s2[p] + k), R("v", tv + k)))
-                for k in range(8):
-                    e("v_mul_f32 %s, %s, %s" % (R("v", self.s2[p] + k), R("v", isd[p][k]), R("v", self.s2[p] + k)))
-        e("s_mov_b32 exec_lo, 0x80008000", "lanes 15 of every row hold the row sums")
-        e("s_mov_b32 exec_hi, 0x80008000")
+                self.put(dz_xhat_finish(regs8(self.s1[p]), regs8(self.s2[p]), mu[p], isd[p], regs8(self.tv)))
+        lo, hi = exec_lane15()
+        e(lo, "lanes 15 of every row hold the row sums")
+        e(hi)
         for p in range(npair):
             for h in range(2):
                 e("buffer_store_dwordx4 %s, %s, %s, 0 offen offset:%d" % (R("v", self.s1[p] + 4 * h, 4), R("v", self.v_chan), R("s", self.srdX, 4), p * 128 + 16 * h))

@@ -31,7 +31,7 @@ from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_common  # noqa: E402
-from asm_common import Emitter, R, merge, resolve_waits  # noqa: E402
+from asm_common import Emitter, R, acc_pair_read, desc, desc_addr, desc_tail, dpp_row_sum, exec_lane15, merge, mfma, pack4, spread, stats_acc, unpack8, vm  # noqa: E402
 
 
 @dataclass
@@ -115,11 +115,6 @@ def tables(c):
 class Gen(Emitter):
     KA = dict(in_=0, wt=8, out=16, stat=24, units=80, upw=84, mtiles=88, table=128, size=640)
 
-    def __init__(self, c: PwCfg):
-        super().__init__(c)
-        self.events = []   # the vector-memory operations and counted waits of one loop trip, in program order (resolve_waits)
-        self.nwaits = 0
-
     # -----------------------------------------------------------------------------------------------------------------
     def gen(self):
         c, S, V = self.c, self.S, self.V
@@ -169,12 +164,7 @@ class Gen(Emitter):
             self.UB += 2
         self.prologue()
         self.loop()
-        text = self.finish(c.LDS, self.KA["size"], 10, [self.KA["size"] - 80])
-        # resolve the counted waits
-        for slot, n in resolve_waits(self.events).items():
-            text = text.replace("@VM%d@" % slot, str(min(n, 63)))
-        assert "@VM" not in text
-        return text
+        return self.finish(c.LDS, self.KA["size"], 10, [self.KA["size"] - 80])
 
     # -----------------------------------------------------------------------------------------------------------------
     def a_slot_insts(self, k, plane):
@@ -197,9 +187,7 @@ class Gen(Emitter):
         tb = c.ROWS * c.K * 2
         e("s_mul_i32 %s, %s, %d" % (R("s", self.s_t0), R("s", s_mt_reg), tb))
         e("s_mul_hi_u32 %s, %s, %d" % (R("s", self.s_t1), R("s", s_mt_reg), tb))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdA), R("s", self.s_alo), R("s", self.s_t0)))
-        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdA + 1), R("s", self.s_ahi), R("s", self.s_t1)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdA + 1), R("s", self.srdA + 1)))
+        self.put(desc_addr(self.srdA, self.s_alo, self.s_ahi, R("s", self.s_t0), R("s", self.s_t1)))
 
     def unit_scalars(self):
         """after s_mt / s_nt of the CURRENT unit are set: next column tile, last flag, weight row offsets, refill tile"""
@@ -302,21 +290,11 @@ class Gen(Emitter):
         e("s_lshr_b32 %s, %s, %d" % (R("s", self.s_mt), R("s", self.s_u), lg))
         e("s_and_b32 %s, %s, %d" % (R("s", self.s_nt), R("s", self.s_u), c.NTN - 1))
         # descriptors
-        e("s_mov_b32 %s, %d" % (R("s", self.srdA + 2), c.ROWS * c.K * 2))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdA + 3))
-        e("s_mov_b32 %s, %s" % (R("s", self.srdB), R("s", ka + 2)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdB + 1), R("s", ka + 3)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdB + 2), c.N * c.w_row))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdB + 3))
-        e("s_mov_b32 %s, %s" % (R("s", self.srdX), R("s", ka + 6)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdX + 1), R("s", ka + 7)))
-        e("s_mov_b32 %s, 0x7fffffff" % R("s", self.srdX + 2))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdX + 3))
+        self.put(desc_tail(self.srdA, "%d" % (c.ROWS * c.K * 2)))   # (its address words: set_srdA)
+        self.put(desc(self.srdB, ka + 2, ka + 3, records="%d" % (c.N * c.w_row)))
+        self.put(desc(self.srdX, ka + 6, ka + 7, records="0x7fffffff"))
         # previous unit: none -> a null output window (stores dropped), its accumulator set zeroed below
-        e("s_mov_b32 %s, %s" % (R("s", self.srdOp), R("s", self.s_outlo)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdOp + 1), R("s", self.s_outhi)))
-        e("s_mov_b32 %s, 0" % R("s", self.srdOp + 2))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdOp + 3))
+        self.put(desc(self.srdOp, self.s_outlo, self.s_outhi, records="0"))
         e("s_lshl_b32 %s, %s, 9" % (R("s", t0), R("s", self.s_w)))
         e("s_add_u32 %s, %s, %d" % (R("s", t0), R("s", t0), c.SBASE))
         e("v_lshl_add_u32 %s, %s, 6, %s" % (R("v", self.v_st), R("v", self.v_kg), R("s", t0)), "(the first unit's idle epilogue adds zeros here)")
@@ -375,15 +353,8 @@ class Gen(Emitter):
         return out
 
     def mfmas(self, fset, ap, zero_c):
-        c = self.c
         fa, fb = self.F[fset]
-        out = []
-        for n in range(4):
-            for m in range(c.MT):
-                acc = ap * self.nacc + (m * 4 + n) * 4
-                src = "0" if zero_c else R("a", acc, 4)
-                out.append("v_mfma_f32_16x16x32_bf16 %s, %s, %s, %s" % (R("a", acc, 4), R("v", fb + 4 * n, 4), R("v", fa + 4 * m, 4), src))
-        return out
+        return [mfma(ap * self.nacc + (m * 4 + n) * 4, fb + 4 * n, fa + 4 * m, zero=zero_c) for n in range(4) for m in range(self.c.MT)]
 
     # ---- epilogue of one accumulator set, as a list of instruction groups --------------------------------------------------
     def epi_item(self, ap, p, m, k):
@@ -391,43 +362,29 @@ class Gen(Emitter):
         c = self.c
         tv, xr, s1, s2 = self.tv, self.xr, self.s1, self.s2
         d = self.dsets[k % 4]
-        g = []
-        for i in range(4):
-            if c.probe & 32:
-                break
-            g.append("v_accvgpr_read_b32 %s, a%d" % (R("v", tv[i]), ap * self.nacc + (m * 4 + 2 * p) * 4 + i))
-            g.append("v_accvgpr_read_b32 %s, a%d" % (R("v", tv[4 + i]), ap * self.nacc + (m * 4 + 2 * p + 1) * 4 + i))
+        a0 = ap * self.nacc + (m * 4 + 2 * p) * 4
+        g = acc_pair_read(tv, a0, a0 + 4) if not (c.probe & 32) else []
         if c.probe & 16:
             return g
-        for i in range(4):
-            g.append("v_cvt_pk_bf16_f32 %s, %s, %s" % (R("v", d + i), R("v", tv[2 * i]), R("v", tv[2 * i + 1])))
+        g += pack4(d, tv)
         g.append("s_mov_b32 %s, %d" % (R("s", self.s_t1), m * 16 * c.N * 2))
         if not (c.probe & 2):
-            g.append(("vm", "store", "buffer_store_dwordx4 %s, %s, %s, %s offen offset:%d" % (R("v", d, 4), R("v", self.v_out), R("s", self.srdOp, 4), R("s", self.s_t1), p * 64)))
+            g.append(vm("store", "buffer_store_dwordx4 %s, %s, %s, %s offen offset:%d" % (R("v", d, 4), R("v", self.v_out), R("s", self.srdOp, 4), R("s", self.s_t1), p * 64)))
         if c.stats:
-            for i in range(4):
-                g.append("v_lshlrev_b32 %s, 16, %s" % (R("v", xr[2 * i]), R("v", d + i)))
-                g.append("v_and_b32 %s, 0xffff0000, %s" % (R("v", xr[2 * i + 1]), R("v", d + i)))
-            for i in range(8):
-                if m == 0:  # first fragment of the pair: start the sums
+            g += unpack8(xr, d)
+            if m == 0:  # first fragment of the pair: start the sums
+                for i in range(8):
                     g.append("v_mov_b32 %s, %s" % (R("v", s1[i]), R("v", xr[i])))
                     g.append("v_mul_f32 %s, %s, %s" % (R("v", s2[i]), R("v", xr[i]), R("v", xr[i])))
-                else:
-                    g.append("v_add_f32 %s, %s, %s" % (R("v", s1[i]), R("v", s1[i]), R("v", xr[i])))
-                    g.append("v_fma_f32 %s, %s, %s, %s" % (R("v", s2[i]), R("v", xr[i]), R("v", xr[i]), R("v", s2[i])))
+            else:
+                g += stats_acc(s1, s2, xr)
         return g
 
     def epi_stat_finish(self, p):
         """row sums of the pair's 16 statistics registers, then lanes 15 add them into the workgroup's LDS rows (one contiguous
         group: EXEC is narrowed inside it)"""
-        c = self.c
-        g = []
-        for sh in (1, 2, 4, 8):
-            for arr in (self.s1, self.s2):
-                for i in range(8):
-                    rr = R("v", arr[i])
-                    g.append("v_add_f32_dpp %s, %s, %s row_shr:%d row_mask:0xf bank_mask:0xf bound_ctrl:1" % (rr, rr, rr, sh))
-        tail = ["s_mov_b32 exec_lo, 0x80008000", "s_mov_b32 exec_hi, 0x80008000"]
+        g = dpp_row_sum(self.s1 + self.s2)
+        tail = exec_lane15()
         for i in range(8):
             tail.append("ds_add_f32 %s, %s offset:%d" % (R("v", self.v_st), R("v", self.s1[i]), p * 32 * 8 + i * 8))
             tail.append("ds_add_f32 %s, %s offset:%d" % (R("v", self.v_st), R("v", self.s2[i]), p * 32 * 8 + i * 8 + 4))
@@ -449,31 +406,14 @@ class Gen(Emitter):
                 items.append(("block", tail))
         return items
 
-    def interleave(self, mf, groups, skip=None):
-        """groups: list of instruction lists kept together; spread evenly between the MFMAs.  skip: groups (by identity) left out
-        WITHOUT moving the others (the two copies of a substep must issue their common instructions in the same order)"""
-        n, k = len(mf), len(groups)
-        slots = {}
-        for j, grp in enumerate(groups):
-            pos = (j * n) // k if k else 0
-            slots.setdefault(pos, []).append(grp)
-        skip_ids = {id(g) for g in (skip or [])}
-        for i, m in enumerate(mf):
-            self.e(m)
-            for grp in slots.get(i, []):
-                if id(grp) not in skip_ids:
-                    self.emit_group(grp)
+    def interleave(self, mf, groups, skip=(), count=True):
+        """groups: list of instruction lists kept together, spread evenly between the MFMAs from the first one on (asm_common.spread, pw_gen's rule)"""
+        self.put(spread(mf, groups, first=0, tail=0, skip=skip), count)
 
     @staticmethod
     def chop(entries, size):
         """split a flat instruction list into groups of `size`"""
         return [entries[i:i + size] for i in range(0, len(entries), size)]
-
-    def wait_vm(self, required):
-        slot = self.nwaits
-        self.nwaits += 1
-        self.events.append(("wait", slot, required))
-        self.e("s_waitcnt vmcnt(@VM%d@)" % slot)
 
     # -----------------------------------------------------------------------------------------------------------------
     def unit_body(self, ub):
@@ -522,9 +462,9 @@ class Gen(Emitter):
             gt = (g + c.NB) % (self.UB * c.NCH)
             for i in range(8):
                 ins = self.b_piece_insts(i, self.s_fillw, self.s_stg)
-                dma.append(ins[:2] + [("vm", ("B", gt), ins[2])])
+                dma.append(ins[:2] + [vm(("B", gt), ins[2])])
             if c.probe & 4:
-                dma = [[("vm", ("B", gt), "s_nop 0")] for i in range(8)]
+                dma = [[vm(("B", gt), "s_nop 0")] for i in range(8)]
             mf = self.mfmas(1, ap, zero_c=False)
             # A refill of plane ch with the NEXT pixel tile — only during the last column tile of this pixel tile: two copies of
             # the substep, selected by a scalar branch (same MFMAs / reads / weight pieces in both)
@@ -534,29 +474,16 @@ class Gen(Emitter):
             adma = []
             for k in range(len(a_slots(c))):
                 ins = self.a_slot_insts(k, ch)
-                adma.append(ins[:2] + [("vm", ("A", ch, (ub + 1) % self.UB), ins[2], True)])
-            saved = list(self.events)
+                adma.append(ins[:2] + [vm(("A", ch, (ub + 1) % self.UB), ins[2], True)])
             allg = merge(merge(per[2 * ch + 1], groups), merge(dma, adma))
             self.interleave(mf, allg)
             e("s_branch %s" % lab_end)
             self.label(lab_no)
-            # (the tracker follows the refill path: its extra instructions are flagged conditional; the other path is the same
-            # stream without them)
-            ev_refill = self.events
-            self.events = list(saved)
-            self.interleave(mf, allg, skip=adma)
-            self.events = ev_refill
+            # (the counted waits follow the refill path: its extra instructions are flagged conditional; the other path is the same
+            # stream without them, emitted and not counted a second time)
+            self.interleave(mf, allg, skip=adma, count=False)
             self.label(lab_end)
             e("s_mov_b32 %s, %s" % (R("s", self.s_bcur), R("s", self.s_bnext)))
-
-    def emit_group(self, entries):  # (redefined: conditional flag support)
-        for ins in entries:
-            if isinstance(ins, tuple):
-                tag, text = ins[1], ins[2]
-                self.events.append(("op", tag, len(ins) > 3 and ins[3]))
-                self.e(text)
-            else:
-                self.e(ins)
 
     def unit_switch(self, ap, lab_exit):
         """the unit that just ran becomes the previous one; advance to the next unit or leave the loop"""
@@ -569,9 +496,7 @@ class Gen(Emitter):
         e("s_lshl_b32 %s, %s, 9" % (R("s", self.s_stg), R("s", self.s_nt)))
         e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_stg)))
         e("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdOp), R("s", self.s_outlo), R("s", t0)))
-        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdOp + 1), R("s", self.s_outhi), R("s", t1)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdOp + 1), R("s", self.srdOp + 1)))
+        self.put(desc_addr(self.srdOp, self.s_outlo, self.s_outhi, R("s", t0), R("s", t1)))
         e("s_sub_u32 %s, %d, %s" % (R("s", self.srdOp + 2), tb, R("s", self.s_stg)))
         # statistics rows of the previous unit's column tile: this lane's slot = SBASE + (pnt*256 + 64w + kg*8)*8
         e("s_lshl_b32 %s, %s, 11" % (R("s", t0), R("s", self.s_nt)))
@@ -594,20 +519,19 @@ class Gen(Emitter):
         exits = [self.newlabel("exit0"), self.newlabel("exit1")]
         done = self.newlabel("done")
         self.label(top)
+        self.trip_open()
         for ub in range(self.UB):
             self.unit_body(ub)
             self.unit_switch(ub & 1, exits[ub & 1])
         e("s_branch %s" % top)
+        self.trip_close(clamp=True)
         # ---- the last unit's epilogue, not interleaved
         for ap in range(2):
             self.label(exits[ap])
             e("s_nop 15")
             e("s_nop 15")
-            saved = self.events
-            self.events = []
             for kind, g in self.epi_groups(ap):
-                self.emit_group(g)
-            self.events = saved
+                self.put(g)
             if ap == 0:
                 e("s_branch %s" % done)
         self.label(done)

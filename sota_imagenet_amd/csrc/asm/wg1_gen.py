@@ -28,7 +28,7 @@ from dataclasses import dataclass
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_common  # noqa: E402
 import wg_gen  # noqa: E402
-from asm_common import R, merge  # noqa: E402
+from asm_common import R, desc, desc_addr, desc_tail, merge, mfma  # noqa: E402
 
 
 @dataclass
@@ -138,12 +138,7 @@ class Gen(wg_gen.Gen):
 
     def mfmas(self, fset):
         fd, fx = self.F[fset]
-        out = []
-        for j in range(self.NX):
-            for n in range(self.NF):
-                acc = (j * self.NF + n) * 4
-                out.append("v_mfma_f32_16x16x32_bf16 %s, %s, %s, %s" % (R("a", acc, 4), R("v", fx + 4 * j, 4), R("v", fd + 4 * n, 4), R("a", acc, 4)))
-        return out
+        return [mfma((j * self.NF + n) * 4, fx + 4 * j, fd + 4 * n) for j in range(self.NX) for n in range(self.NF)]
 
     # -----------------------------------------------------------------------------------------------------------------
     def prologue(self):
@@ -184,23 +179,16 @@ class Gen(wg_gen.Gen):
         e("s_add_u32 %s, %s, %s" % (R("s", self.s_t2), R("s", self.s_t2), R("s", self.s_t3)))
         e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_t2)))
         e("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdP), R("s", ka + 4), R("s", t0)))
-        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdP + 1), R("s", ka + 5), R("s", t1)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdP + 1), R("s", self.srdP + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdP + 2), c.DP * 64 * c.C * 4))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdP + 3))
+        self.put(desc(self.srdP, ka + 4, ka + 5, R("s", t0), R("s", t1), "%d" % (c.DP * 64 * c.C * 4)))
         e("s_mul_i32 %s, %s, %d" % (R("s", self.s_outw), R("s", self.s_w), 16 * c.DP * c.C * 4), "this wave's output channels in the slab")
         # channel tile byte offsets into the pixel rows
         e("s_mul_i32 %s, %s, %d" % (R("s", self.s_ci), R("s", self.s_ci), c.XP * 128))
         e("s_mul_i32 %s, %s, %d" % (R("s", self.s_co), R("s", self.s_co), c.DP * 128))
         for k, chn, ptr, tile_ch in (("d", c.CO, 0, self.s_co), ("x", c.C, 2, self.s_ci)):
             srd = self.srd[k]
-            e("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", ka + ptr), R("s", tile_ch)))
-            e("s_addc_u32 %s, %s, 0" % (R("s", srd + 1), R("s", ka + ptr + 1)))
-            e("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
+            self.put(desc_addr(srd, ka + ptr, ka + ptr + 1, R("s", tile_ch)))
             e("s_mul_i32 %s, %s, %d" % (R("s", srd + 2), R("s", ka + 8), chn * 2), "tensor bytes (< 4 GiB)")
-            e("s_sub_u32 %s, %s, %s" % (R("s", srd + 2), R("s", srd + 2), R("s", tile_ch)))
-            e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
+            self.put(desc_tail(srd, R("s", srd + 2), minus=R("s", tile_ch)))
         e("s_mul_i32 %s, %s, %s" % (R("s", self.s_tile), R("s", self.s_split), R("s", ka + 6)))
         e("s_add_u32 %s, %s, %s" % (R("s", self.s_tend), R("s", self.s_tile), R("s", ka + 6)))
         e("s_min_u32 %s, %s, %s" % (R("s", self.s_tend), R("s", self.s_tend), R("s", ka + 7)))

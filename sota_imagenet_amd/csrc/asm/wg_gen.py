@@ -31,7 +31,7 @@ from dataclasses import dataclass
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_common  # noqa: E402
-from asm_common import Emitter, R, merge  # noqa: E402
+from asm_common import Emitter, R, desc, desc_addr, desc_tail, merge, mfma, spread  # noqa: E402
 
 
 @dataclass
@@ -269,9 +269,7 @@ class Gen(Emitter):
             a("s_mul_hi_u32 %s, %s, %d" % (R("s", t1), R("s", t2), win))
             a("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", tile_ch)))
             a("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
-            a("s_add_u32 %s, %s, %s" % (R("s", srd), R("s", self.s_ka + ptr), R("s", t0)))
-            a("s_addc_u32 %s, %s, %s" % (R("s", srd + 1), R("s", self.s_ka + ptr + 1), R("s", t1)))
-            a("s_and_b32 %s, %s, 0xffff" % (R("s", srd + 1), R("s", srd + 1)))
+            out += desc_addr(srd, self.s_ka + ptr, self.s_ka + ptr + 1, R("s", t0), R("s", t1))   # (num_records and flags: the prologue's)
             if tpw > 1:
                 a("s_mul_i32 %s, %s, %d" % (R("s", t0), R("s", self.s_t3), c.DR * c.W * ch * 2))
                 a("s_add_u32 %s, %s, %s" % (R("s", self.s_tsrc[k]), R("s", self.s_srcw[k]), R("s", t0)))
@@ -335,23 +333,12 @@ class Gen(Emitter):
         for t in range(9):
             ky, kx = divmod(t, 3)
             xr = self.XW[buf][kx] + 2 * (2 * step + ky * self.HS) if self.xwin else fx + 4 * t
-            for n in range(4):
-                acc = (t * 4 + n) * 4
-                out.append("v_mfma_f32_16x16x32_bf16 %s, %s, %s, %s" % (R("a", acc, 4), R("v", xr, 4), R("v", fd + 4 * n, 4), R("a", acc, 4)))
+            out += [mfma((t * 4 + n) * 4, xr, fd + 4 * n) for n in range(4)]
         return out
 
-    def interleave(self, mf, groups, first=1):
-        n, k = len(mf), len(groups)
-        slots = {}
-        if k:
-            span = int((n - first) * getattr(self.c, "rspan", 100) / 100)  # (tuning knob: issue everything within the first rspan % of the MFMAs)
-            for j, grp in enumerate(groups):
-                pos = first + (j * span) // k
-                slots.setdefault(pos, []).extend(grp)
-        for i, m in enumerate(mf):
-            self.e(m)
-            for ins in slots.get(i, []):
-                self.e(ins)
+    def interleave(self, mf, groups):
+        """asm_common.spread under this kernel's rule (tuning knob: everything is issued within the first rspan % of the MFMAs)"""
+        self.put(spread(mf, groups, tail=0, percent=getattr(self.c, "rspan", 100)))
 
     # -----------------------------------------------------------------------------------------------------------------
     def prologue(self):
@@ -425,18 +412,15 @@ class Gen(Emitter):
         e("s_add_u32 %s, %s, %s" % (R("s", self.s_t2), R("s", self.s_t2), R("s", self.s_t3)))
         e("s_add_u32 %s, %s, %s" % (R("s", t0), R("s", t0), R("s", self.s_t2)))
         e("s_addc_u32 %s, %s, 0" % (R("s", t1), R("s", t1)))
-        e("s_add_u32 %s, %s, %s" % (R("s", self.srdP), R("s", ka + 4), R("s", t0)))
-        e("s_addc_u32 %s, %s, %s" % (R("s", self.srdP + 1), R("s", ka + 5), R("s", t1)))
-        e("s_and_b32 %s, %s, 0xffff" % (R("s", self.srdP + 1), R("s", self.srdP + 1)))
-        e("s_mov_b32 %s, %d" % (R("s", self.srdP + 2), 64 * 9 * c.C * 4))
-        e("s_mov_b32 %s, 0x00020000" % R("s", self.srdP + 3))
+        self.put(desc(self.srdP, ka + 4, ka + 5, R("s", t0), R("s", t1), "%d" % (64 * 9 * c.C * 4)))
         # channel tile byte offsets (added to the descriptor bases)
         e("s_lshl_b32 %s, %s, 7" % (R("s", self.s_ci), R("s", self.s_ci)))
         e("s_lshl_b32 %s, %s, 7" % (R("s", self.s_co), R("s", self.s_co)))
         for k, chn in (("d", c.CO), ("x", c.C)):
             srd = self.srd[k]
-            e("s_sub_u32 %s, %d, %s" % (R("s", srd + 2), c.WIN_PIX * chn * 2, R("s", self.s_co if k == "d" else self.s_ci)), "window bytes behind the channel tile offset")
-            e("s_mov_b32 %s, 0x00020000" % R("s", srd + 3))
+            records, flags = desc_tail(srd, "%d" % (c.WIN_PIX * chn * 2), minus=R("s", self.s_co if k == "d" else self.s_ci))   # (the address words: tile_setup)
+            e(records, "window bytes behind the channel tile offset")
+            e(flags)
         # first tile of this split, last tile
         e("s_mul_i32 %s, %s, %s" % (R("s", self.s_tile), R("s", self.s_split), R("s", ka + 6)))
         e("s_add_u32 %s, %s, %s" % (R("s", self.s_tend), R("s", self.s_tile), R("s", ka + 6)))
